@@ -94,6 +94,8 @@ def parse():
     ap.add_argument("--no-fallback", action="store_true", help="N>1: do not try the other multi-GPU form when this one fails")
     ap.add_argument("--per-process", action="store_true",
                     help="N>1: insist on the one-process-per-GPU form (must be started by torch.distributed.run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -887,6 +889,29 @@ def timed_steps(idx, step, fence, warmup: int, steps: int, world: int):
     return dt, st
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <name>.npy -- ids and counts in
+    float64 (exact below 2^53), scores and distances in float32 -- so that two builds can be compared output for output.
+    Above DUMP_MAX_BYTES in all, a fixed seeded sample of the query rows is written, with their row numbers in rows.npy."""
+    outs = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        outs[name] = x.astype(np.float64 if x.dtype.kind in "iu" else np.float32)
+    rows = next(iter(outs.values())).shape[0]
+    per_row = sum(x[:1].nbytes for x in outs.values()) + 8
+    budget = DUMP_MAX_BYTES - 4096  # the .npy headers
+    if rows * per_row > budget:
+        keep = np.sort(np.random.default_rng(0).choice(rows, budget // per_row, replace=False))
+        outs = {name: x[keep] for name, x in outs.items()}
+        outs["rows"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, x in outs.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def scan_of(st) -> str:
     """What the index's scan streams now (mx_index_stats.filter_kind): the library chooses unless told."""
     return {0: "f32", 2: "i8", 3: "bf16"}[int(st.filter_kind)]
@@ -1079,6 +1104,9 @@ def run(a):
 
     dt, st = timed_steps(idx, step, fence, a.warmup, a.steps, world)
     lap("headline (build + timed steps)")
+    if a.dump_outputs and rank == 0:  # before the legs below reuse bufs
+        dump_outputs(a.dump_outputs, {"ids": m_ids, "scores": m_scores, "dists": m_dists} if world > 1 else
+                     {"ids": bufs.ids, "scores": bufs.scores, "dists": bufs.dists, "n_found": bufs.nf})
     settle_steps = getattr(timed_steps, "last_settle", 0)
     ids_main = bufs.ids.clone()
     exchange = idx.exchange
