@@ -107,7 +107,8 @@ struct Scratch {
 };
 
 // The lane buffers of the scan (records of the collect launch: 64 per lane x 68 B, 0.57 GB per set at 256 workgroups x 512
-// lanes; twice that for a 512-query pass of the int8 scan, which numbers 1024 lanes per workgroup) are
+// lanes; twice that for a 512-query pass of the int8 scan, which numbers 1024 lanes per workgroup, and for its two-workgroup
+// form, 512 workgroups x 512 lanes) are
 // only live inside one search_batch call, which returns host-synchronised.  They are therefore leased from a pool per
 // device instead of owned by every index: a process with many resident collections holds as many sets as it has
 // searches in flight on a device at the same time, not one per collection.  The pool is freed when the last index
@@ -117,7 +118,8 @@ struct LaneBufs {
     uint32_t *tile = nullptr, *cnt = nullptr;
     float *max = nullptr;
     int nwg = 0;
-    int groups = 1;  // query groups per wave the set is sized for (2: a 512-query pass)
+    int groups = 1;  // query groups per wave the set is sized for (2: a 512-query pass, or the int8 scan's two-workgroup form:
+                     // twice the workgroups with half the waves, the same 1024 lanes per CU)
 };
 constexpr int kMaxDevices = 64;
 struct LanePool {
@@ -214,7 +216,8 @@ struct mx_index {
     uint64_t n_wild = 0;            // ... how many; more than kWildCap -> EXACT path
     int mode = MX_SEARCH_AUTO;
     bool profiling = false;
-    int n_cu = 0, nwg = 0;
+    int n_cu = 0, nwg = 0;       // nwg: workgroups of the one-per-CU scans (min(CUs, kMaxScanCUs))
+    bool scan8_pair = true;      // plain int8 copy, 129-256 queries: the two-workgroup form (Scan8Geom::kPair, 2 x nwg workgroups)
     Scratch s;
     mx_index_stats stats{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wait = nullptr;
@@ -861,6 +864,10 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     // (a centred int8 copy runs passes of 256: the two-group variant has no register left for the per-row epilogue)
     const bool centred8 = idx->centred && filt8 && idx->amean && idx->mean && idx->kc <= kMaxKC;
     const bool x2 = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch;
+    // 129-256 queries on a plain int8 copy up to 512 dims: two 4-wave workgroups per CU with two query groups per wave
+    // (DESIGN.md section 3.2e).  Smaller batches stay on the 8-wave form, whose idle waves skip their MFMAs.
+    const bool pair = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch / 2 && B <= kPassBatch && idx->scan8_pair;
+    const int nwg = pair ? 2 * idx->nwg : idx->nwg;  // workgroups of the scan launches; finish_kernel and theta_kernel follow
     if (B > kPassBatch && !x2 && !(fast && wide)) {
         rc = search_batch(idx, d_q, kPassBatch, k, d_ids, d_scores, d_dists, d_nfound);
         if (rc != MX_OK) return rc;
@@ -878,7 +885,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     // the bf16 copy of this index is centred on its rows' mean direction (build_filter_copy): queries are split the same way
     const bool centred = centred8 || (idx->centred && idx->xh && !filt8 && !wide && !idx->compressed && idx->amean && idx->mean && idx->kc <= kMaxKC);
     LaneLease lease;  // every return below is host-synchronised with the kernels that used the lane buffers
-    if ((rc = lease.take(idx, x2 ? 2 : 1)) != MX_OK) return rc;
+    if ((rc = lease.take(idx, x2 || pair ? 2 : 1)) != MX_OK) return rc;  // pair: 2 x nwg workgroups x 512 lanes, the 512-query set
     MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
                                idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
                                centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
@@ -893,7 +900,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     FinishParams fp;
     fp.k = k;
     fp.ds = idx->ds;
-    fp.nwg = idx->nwg;
+    fp.nwg = nwg;
     fp.x = idx->compressed ? nullptr : idx->x;
     fp.xh = idx->xh;
     fp.scale = idx->scale;
@@ -1014,7 +1021,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         p.amean = centred ? idx->amean : nullptr;
         p.qmean = s.qmean;
         auto scan = [&](bool collect) {
-            if (filt8) return launch_scan8(st, idx->kc, collect, idx->nwg, p, x2);
+            if (filt8) return launch_scan8(st, idx->kc, collect, nwg, p, pair ? Scan8Geom::kPair : x2 ? Scan8Geom::k512 : Scan8Geom::k256);
             if (wide) return launch_scan16w(st, idx->kc, collect, idx->nwg, p);
             return idx->xh ? launch_scan16(st, idx->kc, collect, idx->nwg, p) : launch_scan(st, idx->kc, collect, idx->nwg, p);
         };
@@ -1036,13 +1043,13 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
             return MX_OK;
         };
         // a lane holds 16 scores per tile of its workgroup: up to 2 tiles per workgroup everything fits
-        // in the lane buffers and no threshold is needed
+        // in the lane buffers and no threshold is needed (counted per CU: the two-workgroup form samples the same corpora)
         if (tiles > 2ull * idx->nwg) {
             p.tile_begin = 0;
             p.tile_end = (uint32_t)full;
-            p.tile_stride = sample_stride(full, idx->nwg, k, filt8, idx->ds, centred8);
+            p.tile_stride = sample_stride(full, nwg, k, filt8, idx->ds, centred8);
             MX_HIP(scan(false));
-            MX_HIP(launch_theta(st, B, k, idx->nwg, s.lane_max, s.qa, !filt8, s.theta));
+            MX_HIP(launch_theta(st, B, k, nwg, s.lane_max, s.qa, !filt8, s.theta));
         }
         if ((rc = collect(true)) != MX_OK) return rc;
         if ((rc = finish_and_wait()) != MX_OK) return rc;
@@ -1615,7 +1622,11 @@ int open_plain(const std::string &k, int dim, int device, mx_index **out) {
     hipDeviceProp_t prop;
     MX_HIP(hipGetDeviceProperties(&prop, device));
     idx->n_cu = prop.multiProcessorCount;
-    idx->nwg = std::max(1, std::min(idx->n_cu, kMaxScanWGs));
+    idx->nwg = std::max(1, std::min(idx->n_cu, kMaxScanCUs));
+    {   // MEMEX_HIP_SCAN8_PAIR=0: the int8 scan keeps one 8-wave workgroup per CU for 129-256 queries (A/B runs)
+        const char *pv = getenv("MEMEX_HIP_SCAN8_PAIR");
+        idx->scan8_pair = !(pv && pv[0] == '0');
+    }
     MX_HIP(hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking));
     MX_HIP(hipEventCreate(&idx->ev0));
     MX_HIP(hipEventCreate(&idx->ev1));

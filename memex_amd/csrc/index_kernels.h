@@ -38,7 +38,8 @@ constexpr int kMaxBatch = 512;     // queries per pipeline batch: a pass of the 
                                    // 512 dims) serves 512; everything else splits a batch into passes of 256 (128: scan16w)
 constexpr int kMaxKC8x2 = 4;       // ... up to this many 128-dim slots per row
 constexpr int kRecCap = 64;        // lane-private records per collect launch: one record = the lane's 16 scores of a tile
-constexpr int kMaxScanWGs = 256;   // persistent workgroups (<= CUs)
+constexpr int kMaxScanCUs = 256;   // CUs a scan spreads over: persistent workgroups, one per CU
+constexpr int kMaxScanWGs = 2 * kMaxScanCUs;  // ... two per CU in the int8 scan's two-workgroup form (Scan8Geom::kPair)
 constexpr int kCandCap = 16384;    // candidates finish_kernel holds per query (LDS); more = rescan with a tight threshold
 constexpr int kZeroCap = 1024;     // zero-norm rows an index tracks in its list (more: EXACT path)
 constexpr int kWildCap = 64;       // rows with a norm outside [1e-15, 1e15] an f32 index lists (more: EXACT path)
@@ -114,8 +115,23 @@ constexpr float kMinStep8 = 1.0f / 32768.0f;  // smallest quantisation step of a
 constexpr int kScaleRing8 = 32;  // tiles whose scales can be in flight (15 slots ahead at one slot per tile, + the tile being multiplied)
 constexpr int kScale8Entry = 512;  // per tile: [0, 16) the steps and residual bounds of its halves | [256, 512) a_c of its 64 rows (centred copy)
 constexpr int kScan8LdsBytes = kRing16 * kSlot16Bytes + kScaleRing8 * kScale8Entry + 256;  // ... | 256 B that absorb the empty a_c operations
+// Two-workgroup form of the plain int8 scan (256 queries, up to kMaxKC8x2 slots): 4-wave workgroups, two resident per CU,
+// each wave holding two query groups, each workgroup with its own 8-slot ring (7 in flight) and a 16-tile scale ring of
+// 256-byte entries (the scales' DMA operation writes 64 lanes x 4 B): 72 KiB, so two fit in the CU's 160 KiB.  The two
+// workgroups of a CU meet at separate barriers -- one's tile epilogue and DMA waits can run under the other's MFMAs.
+constexpr int kScan8PairWaves = 4;
+constexpr int kScan8PairRing = 8;
+constexpr int kScan8PairScaleRing = 16;
+constexpr int kScan8PairEntry = 256;
+constexpr int kScan8PairLdsBytes = kScan8PairRing * kSlot16Bytes + kScan8PairScaleRing * kScan8PairEntry;
+static_assert(2 * kScan8PairLdsBytes <= 160 * 1024, "two workgroups of the pair form must fit one CU's LDS");
+enum class Scan8Geom {
+    k256,   // one 8-wave workgroup per CU, 256 queries (every batch size; idle waves skip their MFMAs)
+    k512,   // one 8-wave workgroup per CU, two query groups per wave: 512 queries (up to kMaxKC8x2 slots)
+    kPair,  // two 4-wave workgroups per CU, two query groups per wave: 256 queries (up to kMaxKC8x2 slots); nwg = 2 x CUs
+};
 hipError_t scan8_setup();
-hipError_t launch_scan8(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p, bool two_groups = false);
+hipError_t launch_scan8(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p, Scan8Geom geom = Scan8Geom::k256);
 // (re)build half tiles [half0, half1) (32 rows each) of the 8-bit filter copy from the padded f32 store: per half
 // tile one quantisation step = max |c_i/|c|| / 127 over its rows below row_hi (rows at or above row_hi, and zero-norm
 // rows, are stored as zeros) and one residual bound = 1.01 * max_rows |c/|c| - step * c8| + 1e-6; both go to

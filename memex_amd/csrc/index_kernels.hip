@@ -448,6 +448,8 @@ hipError_t launch_mean_dir(hipStream_t s, const float *x, const float *scale, ui
 // k-th best cosine, a row of the top-k has score + (qa + qb * residual) >= L_k, and the scan tests
 // score >= theta - qb * residual with theta = L_k - qa.  `raw` = 1: lane maxima are plain scores, theta = a_k - 2*qa
 // (qa = e1 there).
+// PER values per thread: 2 up to 256 workgroups, 4 up to 512 (the int8 scan's two-workgroup form)
+template <int PER>
 __global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float *__restrict__ lane_max,
                                                     const float *__restrict__ qa, int raw, float *__restrict__ theta) {
     __shared__ uint32_t s_hist[256];
@@ -455,12 +457,12 @@ __global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float 
     __shared__ uint32_t s_nvalid[4];
     const int q = blockIdx.x;
     const int tid = threadIdx.x;
-    const int n = 2 * nwg;  // <= 512: two values per thread
+    const int n = 2 * nwg;  // <= 256 * PER
     const uint32_t t0 = (uint32_t)(q >> 5) * 64 + (uint32_t)(q & 31);
-    uint32_t key[2];
-    bool valid[2];
+    uint32_t key[PER];
+    bool valid[PER];
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
+    for (int e = 0; e < PER; ++e) {
         const int i = e * 256 + tid;
         float v = -INFINITY;
         if (i < n) {
@@ -470,18 +472,24 @@ __global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float 
         valid[e] = v > -INFINITY;  // a lane that saw no row keeps -inf
         key[e] = f32_key(v);
     }
-    uint32_t nv = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[0])) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[1]));
+    uint32_t nv = 0;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) nv += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[e]));
     if ((tid & 63) == 0) s_nvalid[tid >> 6] = nv;
     __syncthreads();
     nv = s_nvalid[0] + s_nvalid[1] + s_nvalid[2] + s_nvalid[3];
     float kth = -INFINITY;  // fewer than k lanes saw a row: no threshold
-    if (nv >= (uint32_t)k && k > 0) kth = key_f32(block_kth_largest<2>(key, valid, (uint32_t)k, s_hist, s_pick));
+    if (nv >= (uint32_t)k && k > 0) kth = key_f32(block_kth_largest<PER>(key, valid, (uint32_t)k, s_hist, s_pick));
     if (tid == 0 && theta[q] != INFINITY) theta[q] = kth - (raw ? 2.0f : 1.0f) * qa[q];
 }
 
 hipError_t launch_theta(hipStream_t s, int B, int k, int nwg, const float *lane_max, const float *qa, bool raw, float *theta) {
     if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(theta_kernel, dim3(B), dim3(256), 0, s, k, nwg, lane_max, qa, raw ? 1 : 0, theta);
+    if (nwg > kMaxScanWGs) return hipErrorInvalidValue;
+    if (nwg <= 256)
+        hipLaunchKernelGGL(theta_kernel<2>, dim3(B), dim3(256), 0, s, k, nwg, lane_max, qa, raw ? 1 : 0, theta);
+    else
+        hipLaunchKernelGGL(theta_kernel<4>, dim3(B), dim3(256), 0, s, k, nwg, lane_max, qa, raw ? 1 : 0, theta);
     return hipGetLastError();
 }
 
@@ -671,7 +679,8 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     }
     uint32_t R;
     const uint32_t roff = block_scan_1024(nrec, s_w, &R);
-    if (tid <= 2 * nwg) s_off[tid] = tid < 2 * nwg ? roff : R;
+    if (tid < 2 * nwg) s_off[tid] = roff;
+    if (tid == 0) s_off[2 * nwg] = R;  // (2 * nwg = kFinThreads with the int8 scan's two-workgroup form)
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     // (b) one record per thread and trip (all of a query's records are in flight together): find its
@@ -1053,6 +1062,7 @@ hipError_t finish_setup() {
 
 hipError_t launch_finish(hipStream_t s, int B, const FinishParams &p) {
     if (B <= 0) return hipSuccess;
+    if (p.nwg > kMaxScanWGs || 2 * p.nwg > kFinThreads) return hipErrorInvalidValue;  // one lane buffer per thread
     const size_t lds = sizeof(Cand) * (size_t)kCandCap + sizeof(float) * (size_t)p.ds + kFinishTailBytes;  // candidates | query | staged row ids | record offsets
     if (p.x) hipLaunchKernelGGL(finish_kernel<false>, dim3(B), dim3(kFinThreads), lds, s, p);
     else hipLaunchKernelGGL(finish_kernel<true>, dim3(B), dim3(kFinThreads), lds, s, p);  // compressed corpus: rows come from xh

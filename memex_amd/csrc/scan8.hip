@@ -32,7 +32,8 @@
 // being waited for: 13 slots plus the per-tile operations among them, a compile-time constant per position in the
 // tile), 8 MFMAs per slot each followed by the ds_read_b128 that refills the fragment register it consumed.
 // The query fragments take dim_pad/8 VGPRs (48 at 384 dims, 192 at 1536), so one launch serves 256 queries at
-// every supported width -- 512 up to 512 dims, with two query groups per wave (QG = 2).  A wave none of whose
+// every supported width -- 512 up to 512 dims, with two query groups per wave (QG = 2); 129-256 queries up to 512 dims run
+// on two 4-wave workgroups per CU, each with an 8-slot ring (NW = 4, RING = 8).  A wave none of whose
 // queries is wanted (small batches, retry passes: ScanParams::wave_mask) skips its MFMAs.
 // Tile epilogue, per half: integer max over the lane's 16 sums, one conversion, two multiplications (s_h, s_q),
 // one FMA (theta - qb * e_h), one compare; a passing lane stores its 16 scores as floats -- the record format of
@@ -52,8 +53,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 #define MX_LDS_DMA16(rsrc, ldsptr, voff, soff, aux) \
     __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lds_void *)(ldsptr), 16, (voff), (soff), 0, (aux))
 
-static_assert(kRing16 == 16, "waits below assume a 16-slot ring with 15 slots in flight");
-
 // Ablation switch for scripts/scan8_ubench.hip only (0 = production kernel): 1 = tile scales are constants (no LDS read),
 // 2 = every second fragment read dropped
 #ifndef MX_SCAN8_ABLATE
@@ -70,30 +69,45 @@ __device__ __forceinline__ void static_for(F &&f) {
         static_for<B + 1, E>(f);
     }
 }
-// DMA operations a wave has issued after the one of slot j+1 when it waits for that slot at position kc of a
-// tile: the 13 slots j+2 .. j+14, plus the TWO per-tile operations (scales; a_c of the centred copy, issued with
-// num_records = 0 for a plain one: the kernel has one wait schedule) of every tile that starts among them
-template <int KC>
+// DMA operations a wave has issued after the last one of slot j+1 when it waits for that slot at position kc of a
+// tile: the RING - 3 slots j+2 .. j+RING-2 (13 with the 16-slot ring), DPS operations each (a wave's share of a slot's
+// eight 1-KiB pieces), plus the TOPS per-tile operations of every tile that starts among them (scales; with 8 waves also
+// a_c of the centred copy, issued with num_records = 0 for a plain one: the kernel has one wait schedule)
+template <int KC, int DPS = 1, int TOPS = 2>
 constexpr int ops_after(int lo, int hi) {  // slots lo .. hi relative to the tile start
     int n = 0;
-    for (int i = lo; i <= hi; ++i) n += 1 + (i % KC == 0 ? 2 : 0);
+    for (int i = lo; i <= hi; ++i) n += DPS + (i % KC == 0 ? TOPS : 0);
     return n;
 }
 // 384 dims (3 slots per tile): after slot j+1 come 13 slots and the per-tile operations of the tiles that start at
 // relative slots 3, 6, 9, 12 (position 0 and 2) or 3 .. 15 (position 1); before the loop, after slot 0: 14 + 2 x 4.
 static_assert(ops_after<3>(2, 14) == 21 && ops_after<3>(3, 15) == 23 && ops_after<3>(4, 16) == 21 && ops_after<3>(1, 14) == 22, "");
 static_assert(ops_after<1>(2, 14) == 39 && ops_after<12>(2, 14) == 15 && ops_after<12>(13, 25) == 15 && ops_after<6>(5, 17) == 17, "");
+// two-workgroup form (8-slot ring, 2 slot operations and 1 per-tile operation per wave): at most 5 x 3 = 15 < 64 (vmcnt)
+static_assert(ops_after<3, 2, 1>(2, 6) == 12 && ops_after<3, 2, 1>(4, 8) == 11 && ops_after<1, 2, 1>(2, 6) == 15, "");
 }  // namespace
 
 // QG = query groups (of 32) per wave: 1 = a pass of 256 queries (the kernel every batch size up to 256 runs);
 // 2 = a pass of 512 (each fragment read feeds two MFMAs; wave w holds the "virtual waves" 2w and 2w+1 of
 // theta_kernel's / finish_kernel's lane numbering; up to 512 dims)
 // CEN = the centred copy (KC <= kMaxKC, one query group): see below
-template <int KC, int MODE, int QG, bool CEN>
-__global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams p) {
+// NW = waves per workgroup, RING = slots of the workgroup's LDS ring (RING - 1 in flight).  8 / 16: one workgroup per CU.
+// 4 / 8: the two-workgroup form (Scan8Geom::kPair, two query groups per wave, plain copy only): a wave issues two of a
+// slot's eight 1-KiB pieces and only the scales' per-tile operation; wave w holds the virtual waves 2w and 2w+1, so the
+// lane numbering is the 512-query pass's with twice the workgroups and half the waves
+template <int KC, int MODE, int QG, bool CEN, int NW = kScanWaves, int RING = kRing16>
+__global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
     static_assert(!CEN || (KC <= kMaxKC && QG == 1), "the centred form exists up to kMaxKC slots with one query group");
+    static_assert((NW == kScanWaves && RING == kRing16) || (NW == kScan8PairWaves && RING == kScan8PairRing && QG == 2 && !CEN),
+                  "one 8-wave workgroup with a 16-slot ring, or the two-workgroup form");
+    static_assert((RING & (RING - 1)) == 0 && 8 % NW == 0, "");
+    constexpr int DPS = 8 / NW;                                 // DMA operations per wave and slot
+    constexpr int TOPS = NW == kScanWaves ? 2 : 1;              // ... and per tile
+    constexpr int SRING = NW == kScanWaves ? kScaleRing8 : kScan8PairScaleRing;  // per-tile entries
+    constexpr int SENTRY = NW == kScanWaves ? kScale8Entry : kScan8PairEntry;
+    constexpr uint32_t kSbase = RING * kSlot16Bytes;            // per-tile ring behind the slot ring
     constexpr int R = QG == 2 ? (KC <= 3 ? 8 : 4) : KC <= 8 ? 8 : KC <= 10 ? 4 : 2;  // fragment ring: what the 256 VGPRs leave next to qf
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // slot ring | per-tile ring [kScaleRing8] x kScale8Entry B
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // slot ring | per-tile ring [SRING] x SENTRY B
     // Centred copy (ScanParams::amean, section 3.2c of DESIGN.md carried over to int8): the copy holds the quantised
     // r_c = c/|c| - a_c m, amean[row] = a_c, the query fragments the quantised r_q, qmean[q] = a_q; a row's score is
     // a_q a_c + s_h s_q sum.  The a_q a_c term enters as the ACCUMULATOR'S INITIAL VALUE, I = trunc(a_c (a_q / s_q) (1 / s_h)) in
@@ -159,15 +173,16 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams
         const uint32_t tile = t0 + it * tstep;
         const bool live_tile = it < nT;
         __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.tscale + kTscaleFloats * (size_t)tile), 0, live_tile ? (uint32_t)(kTscaleFloats * 4) : 0u, 0x00020000);
-        char *sdst = smem + __builtin_amdgcn_readfirstlane(kRing16 * kSlot16Bytes + (it & (kScaleRing8 - 1)) * kScale8Entry);
+        char *sdst = smem + __builtin_amdgcn_readfirstlane(kSbase + (it & (SRING - 1)) * SENTRY);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(srs, (lds_void *)sdst, 4, lane4, 0, 0, 0);
+        if constexpr (TOPS == 1) return;
         // a_c of the tile's 64 rows: 256 bytes behind the scales, fetched by ONE wave of the eight.  The others, and every wave of a
         // plain copy, issue the same operation on an empty descriptor (one wait schedule, no memory read) -- into a dump area of
         // their own: an out-of-range LDS-DMA lane still WRITES (zeros), and must not land on the values another wave fetched
         const float *abase = centred ? p.amean + (size_t)kTile8Rows * tile : p.tscale;
         const bool mine = live_tile && centred && (int)(it & 7u) == wave;
         __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)abase, 0, mine ? (uint32_t)(kTile8Rows * 4) : 0u, 0x00020000);
-        char *adst = mine ? sdst + 256 : smem + kRing16 * kSlot16Bytes + kScaleRing8 * kScale8Entry;
+        char *adst = mine ? sdst + 256 : smem + kSbase + SRING * SENTRY;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ars, (lds_void *)adst, 4, lane4, 0, 0, 0);
     };
     auto open_tile = [&]() {
@@ -180,8 +195,12 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams
     };
     auto issue = [&](int kci, uint32_t ring_pos) {  // kci is a compile-time constant at every call site
         if (kci == 0) open_tile();
-        char *dst = smem + __builtin_amdgcn_readfirstlane(ring_pos * kSlot16Bytes + wave * 1024);
-        MX_LDS_DMA16(rsrc, dst, lane16, kci * kSlot16Bytes + wave * 1024, 2 /* nt */);
+#pragma unroll
+        for (int d = 0; d < DPS; ++d) {  // the slot's 1-KiB pieces wave, wave + NW, ...
+            const int piece = wave + d * NW;
+            char *dst = smem + __builtin_amdgcn_readfirstlane(ring_pos * kSlot16Bytes + piece * 1024);
+            MX_LDS_DMA16(rsrc, dst, lane16, kci * kSlot16Bytes + piece * 1024, 2 /* nt */);
+        }
     };
 
     auto mylane = [&](int g) { return (uint32_t)((wave * QG + g) * 64 + lane) * gridDim.x + blockIdx.x; };
@@ -192,10 +211,10 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams
 
     tile_ops(0);
 #pragma unroll
-    for (int i = 0; i < kRing16 - 1; ++i) issue(i % KC, (uint32_t)i);
+    for (int i = 0; i < RING - 1; ++i) issue(i % KC, (uint32_t)i);
 
     i32x4 a[R];
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC>(1, kRing16 - 2)) : "memory");  // slot 0 (and its tile's scales) landed
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC, DPS, TOPS>(1, RING - 2)) : "memory");  // slot 0 (and its tile's scales) landed
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int f = 0; f < R; ++f) a[f] = *reinterpret_cast<const i32x4 *>(smem + lane16 + f * 1024);
@@ -212,7 +231,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams
     f32x4 acv[CEN ? 8 : 1];                        // a_c of this lane's rows, group j = half * 4 + (r >> 2): [j][r & 3]
     i32x16 init[CEN ? 2 : 1];                      // [half tile]
     i32x16 acc[QG * 2];                            // [query group][half tile]
-    auto entry_of = [&](uint32_t it) { return (uint32_t)(kRing16 * kSlot16Bytes) + (it & (kScaleRing8 - 1)) * (uint32_t)kScale8Entry; };
+    auto entry_of = [&](uint32_t it) { return kSbase + (it & (SRING - 1)) * (uint32_t)SENTRY; };
     auto group_values = [&](int j) {
         const float ku = kq * ((j >> 2) ? inv_n[1] : inv_n[0]);
 #pragma unroll
@@ -246,11 +265,11 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams
 
         static_for<0, KC>([&](auto kct) __attribute__((always_inline)) {
             constexpr int kc = decltype(kct)::value;
-            const uint32_t rp1 = (rp + 1) & (kRing16 - 1);
-            const uint32_t rpi = (rp + kRing16 - 1) & (kRing16 - 1);
+            const uint32_t rp1 = (rp + 1) & (RING - 1);
+            const uint32_t rpi = (rp + RING - 1) & (RING - 1);
             // slot j+1 landed (the ring reads ahead into it): everything issued after it may still be in flight
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC>(kc + 2, kc + kRing16 - 2)) : "memory");
-            __builtin_amdgcn_s_barrier();  // ... for every wave; slot j-1 is free for slot j+15
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC, DPS, TOPS>(kc + 2, kc + RING - 2)) : "memory");
+            __builtin_amdgcn_s_barrier();  // ... for every wave of the workgroup; slot j-1 is free for slot j+RING-1
             const uint32_t fb0 = rp * kSlot16Bytes + lane16, fb1 = rp1 * kSlot16Bytes + lane16;
             if (live) {
                 static_for<0, 8>([&](auto ft) __attribute__((always_inline)) {
@@ -263,11 +282,11 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams
                     if ((f & 1) == 0)
 #endif
                     a[f % R] = *reinterpret_cast<const i32x4 *>(smem + (f + R < 8 ? fb0 : fb1) + ((f + R) & 7) * 1024);
-                    if (f == 1) issue((kc + kRing16 - 1) % KC, rpi);
+                    if (f == 1) issue((kc + RING - 1) % KC, rpi);
                     __builtin_amdgcn_sched_barrier(0);
                 });
             } else {
-                issue((kc + kRing16 - 1) % KC, rpi);
+                issue((kc + RING - 1) % KC, rpi);
             }
             rp = rp1;
         });
@@ -293,7 +312,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan8_kernel(const ScanParams
                              : "memory");
             }
         } else {
-            const uint32_t sa = kRing16 * kSlot16Bytes + (ti & (kScaleRing8 - 1)) * kScale8Entry;
+            const uint32_t sa = kSbase + (ti & (SRING - 1)) * SENTRY;
             asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(shs) : "v"(sa) : "memory");
         }
 #endif
@@ -497,6 +516,11 @@ static hipError_t setup8_one() {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, QG, CEN>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, kScan8LdsBytes);
 }
+template <int KC, int MODE>
+static hipError_t setup8_pair() {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, 2, false, kScan8PairWaves, kScan8PairRing>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, kScan8PairLdsBytes);
+}
 
 hipError_t scan8_setup() {
     hipError_t e;
@@ -513,6 +537,11 @@ hipError_t scan8_setup() {
     if ((e = setup8_one<KC, 0, 2>()) != hipSuccess) return e;    \
     if ((e = setup8_one<KC, 1, 2>()) != hipSuccess) return e;
     MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4)
+#undef MX_SETUP
+#define MX_SETUP(KC)                                             \
+    if ((e = setup8_pair<KC, 0>()) != hipSuccess) return e;      \
+    if ((e = setup8_pair<KC, 1>()) != hipSuccess) return e;
+    MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4)  // the two-workgroup form
 #undef MX_SETUP
 #define MX_SETUP(KC)                                                   \
     if ((e = setup8_one<KC, 0, 1, true>()) != hipSuccess) return e;    \
@@ -532,8 +561,28 @@ static hipError_t launch8_kc(hipStream_t s, bool collect, int nwg, const ScanPar
     return hipGetLastError();
 }
 
-hipError_t launch_scan8(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p, bool two_groups) {
-    if (two_groups) {  // 512 queries per pass: up to 512 dims (kMaxKC8x2)
+template <int KC>
+static hipError_t launch8_pair(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
+    constexpr int NW = kScan8PairWaves, RING = kScan8PairRing;
+    if (collect)
+        hipLaunchKernelGGL((scan8_kernel<KC, 1, 2, false, NW, RING>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
+    else
+        hipLaunchKernelGGL((scan8_kernel<KC, 0, 2, false, NW, RING>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_scan8(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p, Scan8Geom geom) {
+    if (geom == Scan8Geom::kPair) {  // 256 queries, two 4-wave workgroups per CU: up to 512 dims (kMaxKC8x2), plain copy
+        if (p.amean) return hipErrorInvalidValue;
+        switch (kc) {
+            case 1: return launch8_pair<1>(s, collect, nwg, p);
+            case 2: return launch8_pair<2>(s, collect, nwg, p);
+            case 3: return launch8_pair<3>(s, collect, nwg, p);
+            case 4: return launch8_pair<4>(s, collect, nwg, p);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    if (geom == Scan8Geom::k512) {  // 512 queries per pass: up to 512 dims (kMaxKC8x2)
         if (p.amean) return hipErrorInvalidValue;
         switch (kc) {
             case 1: return launch8_kc<1, 2>(s, collect, nwg, p);
