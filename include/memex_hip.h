@@ -136,6 +136,20 @@ int mx_index_add_device(mx_index *idx, const float *d_rows, uint64_t n, uint64_t
 int mx_index_clear(mx_index *idx);
 
 /*
+ * Remove single rows (HnswStore::delete, storage/local.rs:29-32, which the reference leaves unimplemented).
+ * Tombstones: a removed row keeps its storage and its id and never appears in a search result again; ids
+ * are never reused or renumbered, so mx_index_size still counts every row ever added and
+ * mx_index_get_rows still returns a removed row's stored values.  `ids` are the ids search returns
+ * (id_offset applied).  Every id is checked first: one outside [id_offset + 1, id_offset + size] gives
+ * MX_EINVAL and nothing is removed.  An id already removed, or named twice, is not an error;
+ * *n_removed (may be NULL) counts the rows newly removed.  A search that starts after this call returns
+ * never returns them.  mx_index_clear forgets every removal; mx_index_load replaces them with the ones
+ * saved beside the store (vectors.mxdead); mx_index_save appends the ones made since the last save.
+ */
+int mx_index_remove(mx_index *idx, const uint64_t *ids, uint64_t n, uint64_t *n_removed);
+int mx_index_removed(mx_index *idx, uint64_t *n_removed); /* rows removed so far */
+
+/*
  * Top-k cosine search.  Replaces HnswStore::search (storage/local.rs:71-91) + hnsw_rs DistCosine:
  *   dist  = max(0, 1 - sum_f64(fl32(q_i*c_i)) / sqrt(sum_f64(fl32(q_i^2)) * sum_f64(fl32(c_i^2)))) as f32
  *           (0 when either norm is 0)
@@ -199,7 +213,10 @@ int mx_index_get_rows(mx_index *idx, uint64_t first_row, uint64_t n, float *out)
 
 /*
  * Persistence.  Replaces HnswStore::save / load / has_store (storage/local.rs:110-165).  Files in
- * `dir`: `vectors.mxflat` (header + raw f32 rows).  The string-id map `vectors.meta.json`
+ * `dir`: `vectors.mxflat` (header + raw f32 rows) and, once rows have been removed, `vectors.mxdead`
+ * (magic "MXDEAD01" | u64 count | count x u64 removed rows, 0-based without id offset; entries are
+ * appended and the count patched last; no file = nothing removed; a damaged one fails the load with
+ * MX_EIO and leaves the index as it was).  The string-id map `vectors.meta.json`
  * (local.rs:19,156-163) stays on the Rust side unchanged.
  */
 int mx_index_save(mx_index *idx, const char *dir);

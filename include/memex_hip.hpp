@@ -31,6 +31,7 @@
 #include <functional>
 #include <future>
 #include <map>
+#include <set>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -232,9 +233,42 @@ class HipFlatStore : public VectorStore {
         if (mx_index_remove_files(storage_path.c_str()) != MX_OK) throw VectorStoreError(VectorStoreError::DeleteError, mx_last_error());
         if (idx_ && mx_index_clear(idx_) != MX_OK) throw VectorStoreError(VectorStoreError::DeleteError, mx_last_error());
         _id_map.clear();
+        rows_of_.clear();
+        rows_of_built_ = false;
         meta_known_ = false;
         meta_ids_ = 0;
     }
+
+    // Remove every row whose _id is in `ids` (rows inserted twice under one _id all go) -- what delete_ (local.rs:29-32,
+    // unimplemented!()) lacks.  Tombstones (mx_index_remove): ids stay stable, vectors.meta.json is unchanged, the removals are
+    // saved beside the store (vectors.mxdead) before this returns.  An unknown _id removes nothing.  -> rows newly removed.
+    size_t remove(const std::vector<std::string> &ids) {
+        std::vector<uint64_t> rows;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || _id_map.empty()) return 0;
+            if (!rows_of_built_) {  // once per store: later calls look their _ids up
+                for (auto &kv : _id_map) rows_of_[kv.second].push_back(kv.first);
+                rows_of_built_ = true;
+            }
+            std::set<std::string> seen;
+            for (auto &id : ids) {
+                if (!seen.insert(id).second) continue;
+                auto it = rows_of_.find(id);
+                if (it != rows_of_.end()) rows.insert(rows.end(), it->second.begin(), it->second.end());
+            }
+        }
+        if (rows.empty()) return 0;
+        uint64_t n = 0;
+        if (mx_index_remove(idx_, rows.data(), rows.size(), &n) != MX_OK) throw VectorStoreError(VectorStoreError::DeleteError, mx_last_error());
+        try {
+            save();
+        } catch (const VectorStoreError &e) {
+            throw VectorStoreError(VectorStoreError::DeleteError, e.what());
+        }
+        return (size_t)n;
+    }
+    size_t remove(const std::string &id) { return remove(std::vector<std::string>{id}); }
 
     // local.rs:55-69 semantics (ids in order, store persisted before returning), one transfer and
     // one incremental save instead of a save per vector
@@ -259,7 +293,10 @@ class HipFlatStore : public VectorStore {
         if (rc != MX_OK) throw from_status(rc, VectorStoreError::InsertionError);
         {
             std::lock_guard<std::mutex> lk(mu_);
-            for (size_t i = 0; i < data.size(); ++i) _id_map[(size_t)first + i] = data[i]._id;  // next_id = len + 1 (local.rs:63)
+            for (size_t i = 0; i < data.size(); ++i) {
+                _id_map[(size_t)first + i] = data[i]._id;  // next_id = len + 1 (local.rs:63)
+                if (rows_of_built_) rows_of_[data[i]._id].push_back((size_t)first + i);
+            }
         }
         try {
             save();  // local.rs:67 `let _ = self.save(..)`: errors are ignored there too
@@ -302,6 +339,8 @@ class HipFlatStore : public VectorStore {
     std::pair<long long, long long> meta_sig_{0, 0};
     size_t meta_ids_ = 0;
     bool meta_known_ = false;
+    std::map<std::string, std::vector<size_t>> rows_of_;  // _id -> ids (remove): built by the first remove, kept on insert
+    bool rows_of_built_ = false;
 
     static std::pair<long long, long long> file_sig(const std::string &p) {
         struct stat sb;

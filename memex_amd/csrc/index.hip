@@ -223,6 +223,14 @@ struct mx_index {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wait = nullptr;
     double wait_ema_us[4] = {0.0, 0.0, 0.0, 0.0};  // how long recent batches of <= 32 / 128 / 256 / more queries took from the
                                                    // finish launch to completion (sleeping wait)
+    // removed rows (mx_index_remove): tombstones, ids stay.  A plain index (or shard) keeps one dead-row word per 64-row scan tile
+    // on the device ([cap / 64], allocated at the first removal, grown with the capacity) and its host copy; the scans and
+    // finish_kernel see the device mask only while n_dead > 0, so an index without removals runs the kernels it always ran
+    uint64_t *dead = nullptr;
+    std::vector<uint64_t> dead_h;
+    uint64_t n_dead = 0;            // rows removed (a composite: over its shards)
+    std::vector<uint64_t> dead_log;  // the handle's removals in the order made, global rows without id offset (vectors.mxdead)
+    uint64_t disk_dead = 0;          // ... how many of them vectors.mxdead in disk_dir holds
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -310,7 +318,7 @@ int free_index(mx_index *idx) {
         if (p) (void)hipFree(p);
     };
     F(idx->x); F(idx->scale); F(idx->xh); F(idx->tsc); F(idx->flags); F(idx->xs); F(idx->ss); F(idx->zero_rows); F(idx->wild_list);
-    F(idx->amean); F(idx->mean); F(idx->msum);
+    F(idx->amean); F(idx->mean); F(idx->msum); F(idx->dead);
     Scratch &s = idx->s;
     F(s.qfrag); F(s.qpad); F(s.qnorm2); F(s.theta); F(s.theta_retry); F(s.todo); F(s.dev_flags); F(s.done_ctr);
     if (s.host_flags) (void)hipHostFree(s.host_flags);
@@ -496,10 +504,27 @@ struct DevBuf {
     }
 };
 
+// the dead-row mask covers `cap` rows (one word per 64-row tile); words past the old size start with no row removed
+int grow_dead(mx_index *idx, uint64_t cap) {
+    if (!idx->dead) return MX_OK;  // allocated by the first removal
+    const size_t words = (size_t)(cap / kTile8Rows), have = idx->dead_h.size();
+    if (words <= have) return MX_OK;
+    DevBuf nd;
+    MX_HIP(hipMalloc(&nd.p, words * sizeof(uint64_t)));
+    MX_HIP(hipMemcpyAsync(nd.p, idx->dead, have * sizeof(uint64_t), hipMemcpyDeviceToDevice, idx->stream));
+    MX_HIP(hipMemsetAsync(static_cast<uint64_t *>(nd.p) + have, 0, (words - have) * sizeof(uint64_t), idx->stream));
+    MX_HIP(hipStreamSynchronize(idx->stream));
+    (void)hipFree(idx->dead);
+    idx->dead = static_cast<uint64_t *>(nd.release());
+    idx->dead_h.resize(words, 0);
+    return MX_OK;
+}
+
 int ensure_capacity(mx_index *idx, uint64_t rows) {
     if (rows <= idx->cap) return MX_OK;
     uint64_t want = std::max<uint64_t>(rows, idx->cap + idx->cap / 2);
     want = round_up(std::max<uint64_t>(want, 1024), kTile8Rows);
+    if (int rc = grow_dead(idx, want); rc != MX_OK) return rc;
     if (idx->compressed) {  // the bf16 copy is the corpus: it must grow, there is nothing to fall back to
         DevBuf nh2;
         const size_t hb = (size_t)want * idx->ds * 2;
@@ -765,7 +790,8 @@ int run_exact(mx_index *idx, const std::vector<int> &qs, int k, uint64_t *d_ids,
         grp.n = (int)std::min<size_t>((size_t)gcap, qs.size() - g0);
         for (int j = 0; j < grp.n; ++j) grp.q[j] = qs[g0 + j];
         MX_HIP(launch_exact_group(idx->stream, k, idx->ds, idx->compressed ? nullptr : idx->x, idx->xh, idx->n, idx->idmap, s.qpad,
-                                  s.qnorm2, grp, s.exact_scratch, d_ids, d_scores, d_dists, d_nfound));
+                                  s.qnorm2, grp, s.exact_scratch, d_ids, d_scores, d_dists, d_nfound, idx->n_dead ? idx->dead : nullptr,
+                                  idx->n - idx->n_dead));
     }
     return MX_OK;
 }
@@ -921,6 +947,8 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     fp.n_zero = (uint32_t)std::min<uint64_t>(idx->n_zero, kZeroCap);
     fp.wild_rows = idx->wild_list;
     fp.n_wild = (uint32_t)std::min<uint64_t>(idx->n_wild, kWildCap);
+    fp.dead = idx->n_dead ? idx->dead : nullptr;
+    fp.n_live = trivial ? 0 : idx->n - idx->n_dead;
     fp.overflow = s.overflow;
     fp.todo = nullptr;
     fp.theta_retry = s.theta_retry;
@@ -1020,6 +1048,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         p.qb = s.qb;
         p.amean = centred ? idx->amean : nullptr;
         p.qmean = s.qmean;
+        p.dead = idx->n_dead ? idx->dead : nullptr;  // the masked kernels only for an index with removed rows
         auto scan = [&](bool collect) {
             if (filt8) return launch_scan8(st, idx->kc, collect, nwg, p, pair ? Scan8Geom::kPair : x2 ? Scan8Geom::k512 : Scan8Geom::k256);
             if (wide) return launch_scan16w(st, idx->kc, collect, idx->nwg, p);
@@ -1368,7 +1397,8 @@ int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_i
                             k, d_ids, d_dists ? d_dists : reinterpret_cast<float *>(static_cast<char *>(idx->sh_block[0]) + ids_bytes),
                             d_scores));
     }
-    MX_HIP(launch_fill_nfound(s0->stream, d_nfound, B, (int32_t)std::min<uint64_t>((uint64_t)k, idx->total)));
+    // every shard found min(k, its live rows): the merged lists hold min(k, live rows of the handle) entries
+    MX_HIP(launch_fill_nfound(s0->stream, d_nfound, B, (int32_t)std::min<uint64_t>((uint64_t)k, idx->total - idx->n_dead)));
     MX_HIP(hipStreamSynchronize(s0->stream));
     idx->stats.exchange_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count();
     idx->stats.searches += 1;
@@ -1532,6 +1562,194 @@ void set_raw_ingest(mx_index *idx, bool on) {
     for (mx_index *sh : idx->shards) sh->raw_ingest = on;
 }
 
+// ---- removal (tombstones) --------------------------------------------------------------------------------------
+// Sets the dead bits of local rows `rows` (all < n) of a plain index or shard and copies the changed words to the device on the
+// index's stream -- host-synchronised before it returns, so a search that starts afterwards runs with them.  fresh[i] = 1 when
+// rows[i] was not removed before (a row named twice counts once); *newly = how many.
+int mark_dead_local(mx_index *idx, const std::vector<uint64_t> &rows, std::vector<uint8_t> &fresh, uint64_t *newly) {
+    *newly = 0;
+    fresh.assign(rows.size(), 0);
+    if (rows.empty()) return MX_OK;
+    DeviceGuard dg(idx->device);
+    if (!idx->dead) {
+        const size_t words = (size_t)(idx->cap / kTile8Rows);
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->dead), words * sizeof(uint64_t)));
+        MX_HIP(hipMemsetAsync(idx->dead, 0, words * sizeof(uint64_t), idx->stream));
+        idx->dead_h.assign(words, 0);
+    }
+    size_t w0 = SIZE_MAX, w1 = 0;
+    for (size_t i = 0; i < rows.size(); ++i) {
+        const uint64_t r = rows[i];
+        uint64_t &w = idx->dead_h[r >> 6];
+        const uint64_t bit = 1ull << (r & 63);
+        if (w & bit) continue;
+        w |= bit;
+        fresh[i] = 1;
+        *newly += 1;
+        w0 = std::min<size_t>(w0, r >> 6);
+        w1 = std::max<size_t>(w1, r >> 6);
+    }
+    if (*newly) {
+        MX_HIP(hipMemcpyAsync(idx->dead + w0, idx->dead_h.data() + w0, (w1 - w0 + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, idx->stream));
+        idx->n_dead += *newly;
+        // The side lists (zero-norm rows, rows with an out-of-range norm) keep live rows only, so that the kZeroCap / kWildCap
+        // decisions and later appends count live rows.  A list that overflowed its cap is incomplete (rows past the cap were never
+        // listed) and stays as it is: such an index answers on the EXACT path either way.
+        auto compact = [&](uint32_t *list, uint64_t &cnt, uint64_t cap, int word) -> int {
+            if (cnt == 0 || cnt > cap) return MX_OK;
+            std::vector<uint32_t> z((size_t)cnt);
+            MX_HIP(hipMemcpyAsync(z.data(), list, z.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
+            MX_HIP(hipStreamSynchronize(idx->stream));
+            size_t m = 0;
+            for (uint32_t r : z)
+                if (!((idx->dead_h[r >> 6] >> (r & 63)) & 1ull)) z[m++] = r;  // (ascending order kept)
+            if (m == z.size()) return MX_OK;
+            if (m) MX_HIP(hipMemcpyAsync(list, z.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, idx->stream));
+            const uint32_t c = (uint32_t)m;  // the device count the ingest kernel appends behind
+            MX_HIP(hipMemcpyAsync(idx->flags + word, &c, sizeof(c), hipMemcpyHostToDevice, idx->stream));
+            MX_HIP(hipStreamSynchronize(idx->stream));
+            cnt = m;
+            return MX_OK;
+        };
+        if (int rc = compact(idx->zero_rows, idx->n_zero, kZeroCap, 3); rc != MX_OK) return rc;
+        if (int rc = compact(idx->wild_list, idx->n_wild, kWildCap, 4); rc != MX_OK) return rc;
+    }
+    MX_HIP(hipStreamSynchronize(idx->stream));
+    return MX_OK;
+}
+
+// global rows (0-based, no id offset) of a plain or composite index -> removed.  The rows are < rows_of(idx) (the caller checked).
+// A composite routes row r to the shard that owns its block: block b = r / R, shard b % G, local row (b / G) R + r % R.
+// The rows newly removed join dead_log (what the next save appends to vectors.mxdead).
+int mark_dead(mx_index *idx, const std::vector<uint64_t> &rows, uint64_t *newly) {
+    *newly = 0;
+    std::vector<uint8_t> fresh;
+    if (!idx->composite()) {
+        int rc = mark_dead_local(idx, rows, fresh, newly);
+        for (size_t i = 0; i < rows.size(); ++i)
+            if (fresh[i]) idx->dead_log.push_back(rows[i]);
+        return rc;
+    }
+    const uint64_t R = idx->block_rows, G = idx->shards.size();
+    std::vector<std::vector<uint64_t>> per(G), glob(G);
+    for (uint64_t r : rows) {
+        const uint64_t b = r / R;
+        per[b % G].push_back((b / G) * R + r % R);
+        glob[b % G].push_back(r);
+    }
+    int rc = MX_OK;
+    for (uint64_t g = 0; g < G && rc == MX_OK; ++g) {
+        mx_index *sh = idx->shards[g];
+        std::lock_guard<std::mutex> lk(sh->mu);
+        uint64_t m = 0;
+        rc = mark_dead_local(sh, per[g], fresh, &m);
+        *newly += m;
+        for (size_t i = 0; i < glob[g].size(); ++i)
+            if (fresh[i]) idx->dead_log.push_back(glob[g][i]);
+    }
+    idx->n_dead += *newly;
+    return rc;
+}
+
+// forget every removal (the rows stay): the state mx_index_load starts from before it applies vectors.mxdead
+int reset_dead(mx_index *idx) {
+    for (mx_index *t : idx->composite() ? idx->shards : std::vector<mx_index *>{idx}) {
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        if (t->dead) {
+            DeviceGuard dg(t->device);
+            std::fill(t->dead_h.begin(), t->dead_h.end(), 0);
+            MX_HIP(hipMemsetAsync(t->dead, 0, t->dead_h.size() * sizeof(uint64_t), t->stream));
+            MX_HIP(hipStreamSynchronize(t->stream));
+        }
+        t->n_dead = 0;
+    }
+    idx->n_dead = 0;
+    idx->dead_log.clear();
+    return MX_OK;
+}
+
+// vectors.mxdead: magic[8] | u64 count | count x u64 removed rows (global, without id offset), in the order they were removed.
+// Entries are appended and the count is patched last (the rule of vectors.mxflat); no file = nothing removed.
+const char kDeadMagic[8] = {'M', 'X', 'D', 'E', 'A', 'D', '0', '1'};
+constexpr long kDeadHeaderBytes = 16;
+std::string dead_file(const char *dir) { return std::string(dir) + "/vectors.mxdead"; }
+
+// reads and validates vectors.mxdead of a store of n_rows rows; *present = false when there is none
+int read_dead_file(const char *dir, uint64_t n_rows, std::vector<uint64_t> *rows, bool *present) {
+    rows->clear();
+    *present = false;
+    const std::string path = dead_file(dir);
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) {
+        if (errno == ENOENT) return MX_OK;
+        return fail(MX_EIO, "cannot open %s", path.c_str());
+    }
+    *present = true;
+    char magic[8];
+    uint64_t cnt = 0;
+    struct stat sb;
+    int rc = MX_OK;
+    if (fread(magic, 1, 8, f) != 8 || memcmp(magic, kDeadMagic, 8) != 0 || fread(&cnt, sizeof(cnt), 1, f) != 1 || fstat(fileno(f), &sb) != 0)
+        rc = fail(MX_EIO, "%s: bad header", path.c_str());
+    else if (cnt > ((uint64_t)sb.st_size - kDeadHeaderBytes) / 8)
+        rc = fail(MX_EIO, "%s: truncated (%lld bytes for %llu entries)", path.c_str(), (long long)sb.st_size, (unsigned long long)cnt);
+    if (rc == MX_OK) {
+        rows->resize((size_t)cnt);
+        if (cnt && fread(rows->data(), sizeof(uint64_t), (size_t)cnt, f) != (size_t)cnt) rc = fail(MX_EIO, "%s: read failed", path.c_str());
+    }
+    fclose(f);
+    for (size_t i = 0; rc == MX_OK && i < rows->size(); ++i)
+        if ((*rows)[i] >= n_rows)
+            rc = fail(MX_EIO, "%s: entry %zu names row %llu of a store of %llu rows", path.c_str(), i, (unsigned long long)(*rows)[i],
+                      (unsigned long long)n_rows);
+    if (rc != MX_OK) rows->clear();
+    return rc;
+}
+
+// brings vectors.mxdead in dir up to the handle's removals: appends the ones made since the last save when the file holds exactly
+// the first disk_dead of them, otherwise writes it afresh (temporary file + rename); no removals: no file
+int save_dead_file(mx_index *idx, const char *dir, bool in_sync) {
+    const std::string path = dead_file(dir);
+    const uint64_t total = idx->dead_log.size();
+    struct stat sb;
+    const bool exists = stat(path.c_str(), &sb) == 0;
+    if (total == 0) {
+        if (exists && unlink(path.c_str()) != 0) return fail(MX_EIO, "cannot remove %s", path.c_str());
+        idx->disk_dead = 0;
+        return MX_OK;
+    }
+    if (in_sync && exists && idx->disk_dead <= total && (uint64_t)sb.st_size == (uint64_t)kDeadHeaderBytes + 8 * idx->disk_dead) {
+        if (idx->disk_dead == total) return MX_OK;
+        FILE *f = fopen(path.c_str(), "r+b");
+        if (!f) return fail(MX_EIO, "cannot open %s for appending", path.c_str());
+        const size_t m = (size_t)(total - idx->disk_dead);
+        int rc = fseek(f, kDeadHeaderBytes + (long)(8 * idx->disk_dead), SEEK_SET) == 0 &&
+                         fwrite(idx->dead_log.data() + idx->disk_dead, sizeof(uint64_t), m, f) == m
+                     ? MX_OK : fail(MX_EIO, "write to %s failed", path.c_str());
+        // the count is patched last: a crash before this point leaves the old, consistent file
+        if (rc == MX_OK && (fflush(f) != 0 || fseek(f, 8, SEEK_SET) != 0 || fwrite(&total, sizeof(total), 1, f) != 1))
+            rc = fail(MX_EIO, "write to %s failed", path.c_str());
+        if (fclose(f) != 0 && rc == MX_OK) rc = fail(MX_EIO, "write to %s failed", path.c_str());
+        if (rc == MX_OK) idx->disk_dead = total;
+        return rc;
+    }
+    const std::string tmp = path + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return fail(MX_EIO, "cannot open %s for writing", tmp.c_str());
+    int rc = fwrite(kDeadMagic, 1, 8, f) == 8 && fwrite(&total, sizeof(total), 1, f) == 1 &&
+                     fwrite(idx->dead_log.data(), sizeof(uint64_t), (size_t)total, f) == (size_t)total
+                 ? MX_OK : fail(MX_EIO, "write to %s failed", tmp.c_str());
+    if (fclose(f) != 0 && rc == MX_OK) rc = fail(MX_EIO, "write to %s failed", tmp.c_str());
+    if (rc == MX_OK && rename(tmp.c_str(), path.c_str()) != 0) rc = fail(MX_EIO, "cannot rename %s", tmp.c_str());
+    if (rc != MX_OK) {
+        unlink(tmp.c_str());
+        return rc;
+    }
+    idx->disk_dead = total;
+    return MX_OK;
+}
+
 int clear_locked(mx_index *idx) {
     if (idx->composite()) {
         for (mx_index *sh : idx->shards) {
@@ -1546,12 +1764,20 @@ int clear_locked(mx_index *idx) {
         idx->wild_rows = 0;
         idx->n_zero = 0;
         idx->n_wild = 0;
+        if (idx->dead) {
+            DeviceGuard dg(idx->device);
+            (void)hipMemsetAsync(idx->dead, 0, idx->dead_h.size() * sizeof(uint64_t), idx->stream);
+            std::fill(idx->dead_h.begin(), idx->dead_h.end(), 0);
+        }
         for (double &w : idx->wait_ema_us) w = 0.0;
         if (idx->flags) {
             DeviceGuard dg(idx->device);
             (void)hipMemsetAsync(idx->flags + 2, 0, 4 * sizeof(uint32_t), idx->stream);  // ec_max, zero-row count, listed-row count, rc_max
         }
     }
+    idx->n_dead = 0;
+    idx->dead_log.clear();
+    idx->disk_dead = 0;
     idx->disk_dir.clear();
     return MX_OK;
 }
@@ -1846,6 +2072,35 @@ int mx_index_size(mx_index *idx, uint64_t *n) try {
     if (!idx || !n) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
     *n = rows_of(idx);
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_remove(mx_index *idx, const uint64_t *ids, uint64_t n, uint64_t *n_removed) try {
+    if (n_removed) *n_removed = 0;
+    if (!idx || (!ids && n)) return fail(MX_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    const uint64_t size = rows_of(idx), off = idx->idmap.id_offset;
+    std::vector<uint64_t> rows((size_t)n);
+    for (uint64_t i = 0; i < n; ++i) {  // all ids are checked before anything changes
+        if (ids[i] <= off || ids[i] - off > size)
+            return fail(MX_EINVAL, "id %llu is outside [%llu, %llu]; nothing removed", (unsigned long long)ids[i], (unsigned long long)(off + 1),
+                        (unsigned long long)(off + size));
+        rows[i] = ids[i] - off - 1;
+    }
+    uint64_t m = 0;
+    const int rc = mark_dead(idx, rows, &m);
+    if (n_removed) *n_removed = m;
+    return rc;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_removed(mx_index *idx, uint64_t *n) try {
+    if (!idx || !n) return fail(MX_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    *n = idx->n_dead;
     return MX_OK;
 } catch (...) {
     return guard_exception();
@@ -2281,7 +2536,7 @@ int mx_index_save(mx_index *idx, const char *dir) try {
         return MX_OK;
     };
     if (disk_in_sync(idx, dir) && idx->disk_rows <= n) {
-        if (idx->disk_rows == n) return MX_OK;  // nothing new
+        if (idx->disk_rows == n) return save_dead_file(idx, dir, true);  // no new rows; removals made since the last save, if any
         FILE *f = fopen(path.c_str(), "r+b");
         if (!f) return fail(MX_EIO, "cannot open %s for appending", path.c_str());
         int rc = fseek(f, kHeaderBytes + (long)(idx->disk_rows * (uint64_t)idx->dim * 4), SEEK_SET) == 0 ? MX_OK : fail(MX_EIO, "seek in %s failed", path.c_str());
@@ -2292,6 +2547,7 @@ int mx_index_save(mx_index *idx, const char *dir) try {
         if (fclose(f) != 0 && rc == MX_OK) rc = fail(MX_EIO, "write to %s failed", path.c_str());
         if (rc == MX_OK) remember_disk(idx, dir, n);
         else idx->disk_dir.clear();
+        if (rc == MX_OK) rc = save_dead_file(idx, dir, true);
         return rc;
     }
     const std::string tmp = path + ".tmp";
@@ -2308,7 +2564,7 @@ int mx_index_save(mx_index *idx, const char *dir) try {
         return rc;
     }
     remember_disk(idx, dir, n);
-    return MX_OK;
+    return save_dead_file(idx, dir, false);
 } catch (...) {
     return guard_exception();
 }
@@ -2338,10 +2594,25 @@ int mx_index_load(mx_index *idx, const char *dir) try {
         fclose(f);
         return fail(MX_EIO, "%s: truncated (%lld bytes for %llu rows)", path.c_str(), (long long)sb.st_size, (unsigned long long)n);
     }
+    // the removals beside it (vectors.mxdead), validated before anything changes as well
+    std::vector<uint64_t> file_dead;
+    bool dead_present = false;
+    if (int drc = read_dead_file(dir, n, &file_dead, &dead_present); drc != MX_OK) {
+        fclose(f);
+        return drc;
+    }
     // get_vector_storage loads the store on every request (storage/mod.rs:115-116): when the resident
-    // rows are exactly what this file holds, attaching is O(1)
+    // rows are exactly what this file holds, attaching is O(1) -- the removals are taken from the file unless they are its own
     if (disk_in_sync(idx, dir) && idx->disk_rows == n && rows_of(idx) == n) {
         fclose(f);
+        if (file_dead != idx->dead_log) {
+            uint64_t m = 0;
+            int rc = reset_dead(idx);
+            if (rc == MX_OK) rc = mark_dead(idx, file_dead, &m);
+            if (rc != MX_OK) return rc;
+            idx->dead_log = file_dead;
+        }
+        idx->disk_dead = dead_present ? file_dead.size() : 0;
         return MX_OK;
     }
     clear_locked(idx);
@@ -2417,6 +2688,18 @@ int mx_index_load(mx_index *idx, const char *dir) try {
         last_error_slot() = keep;
         return rc;
     }
+    if (!file_dead.empty()) {
+        uint64_t m = 0;
+        rc = mark_dead(idx, file_dead, &m);
+        if (rc != MX_OK) {
+            const std::string keep = last_error_slot();
+            clear_locked(idx);
+            last_error_slot() = keep;
+            return rc;
+        }
+    }
+    idx->dead_log = file_dead;  // the file's entries as they stand (the next save appends behind them)
+    idx->disk_dead = file_dead.size();
     remember_disk(idx, dir, n);
     return MX_OK;
 } catch (...) {
@@ -2455,6 +2738,8 @@ int mx_index_remove_files(const char *dir) try {
     const std::string p = store_file(dir);
     struct stat sb;
     if (stat(p.c_str(), &sb) == 0 && unlink(p.c_str()) != 0) return fail(MX_EIO, "cannot remove %s", p.c_str());
+    const std::string d = dead_file(dir);  // the removals beside it
+    if (stat(d.c_str(), &sb) == 0 && unlink(d.c_str()) != 0) return fail(MX_EIO, "cannot remove %s", d.c_str());
     return MX_OK;
 } catch (...) {
     return guard_exception();

@@ -100,7 +100,19 @@ struct ScanParams {
     // is a_q a_c + (MFMA sum over r_q r_c).  null: the copy holds c/|c| itself.
     const float *amean = nullptr;   // [cap_rows]
     const float *qmean = nullptr;   // [256]
+    // removed rows (mx_index_remove): bit j of dead[t] = row 64t + j.  null: nothing removed, and the launchers run the kernels
+    // without the mask; otherwise the masked variants score a removed row so low that it passes no test
+    const uint64_t *dead = nullptr;  // [cap_rows / 64]
 };
+
+// The 16 rows an MFMA lane holds of a 32-row half tile are (r & 3) + 8 (r >> 2) + 4h (h = lane >> 5): bit r of the result is
+// bit (r & 3) + 8 (r >> 2) + 4h of `half`, the half tile's 32 dead-row bits
+__device__ __forceinline__ uint32_t lane_dead16(uint32_t half, uint32_t h) {
+    const uint32_t w = half >> (4u * h);
+    return (w & 0xfu) | ((w >> 4) & 0xf0u) | ((w >> 8) & 0xf00u) | ((w >> 12) & 0xf000u);
+}
+// the half tile of 32-row tile t (t / 2 is its 64-row word)
+__device__ __forceinline__ uint32_t dead_half(const uint64_t *dead, uint32_t t) { return (uint32_t)(dead[t >> 1] >> (32u * (t & 1u))); }
 
 // launches ---------------------------------------------------------------------------------
 hipError_t scan_setup();  // one-time function attributes (dynamic LDS size)
@@ -221,6 +233,8 @@ struct FinishParams {
     uint32_t n_zero;
     const uint32_t *wild_rows;  // [kWildCap] rows with a norm outside the f32 stages' range, ascending: stage 3 takes them all
     uint32_t n_wild;
+    const uint64_t *dead;       // removed rows (ScanParams::dead); null: none.  The side lists above hold no removed row.
+    uint64_t n_live;            // rows not removed: a query finds min(k, n_live)
     uint32_t *overflow;         // [256]
     const uint32_t *todo;       // null = every query; else only queries with todo[q] != 0
     float *theta_retry;         // [256]
@@ -254,9 +268,10 @@ struct ExactGroup {
     int q[kExactGroup];
 };
 size_t exact_group_scratch_bytes(uint64_t n_rows, int k, int gcap);  // gcap: queries per pass the dist array holds (<= kExactGroup)
+// dead / n_live: removed rows (ScanParams::dead, null: none) get a distance key that is never selected; min(k, n_live) found
 hipError_t launch_exact_group(hipStream_t s, int k, int ds, const float *x, const void *xh, uint64_t n_rows, const IdMap &idmap,
                               const float *qpad, const double *qnorm2, const ExactGroup &grp, void *scratch, uint64_t *ids,
-                              float *scores, float *dists, int32_t *n_found);
+                              float *scores, float *dists, int32_t *n_found, const uint64_t *dead = nullptr, uint64_t n_live = ~0ull);
 
 hipError_t launch_fill_nfound(hipStream_t s, int32_t *nf, int B, int32_t v);
 hipError_t launch_merge(hipStream_t s, const void *ids, size_t ids_stride, const void *dists, size_t dists_stride,

@@ -614,7 +614,7 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     const int lane = tid & 63, wave = tid >> 6;
     if (p.todo && !p.todo[q]) return;
     const int k = p.k, ds = p.ds;
-    const uint64_t want64 = p.n_rows < (uint64_t)k ? p.n_rows : (uint64_t)k;
+    const uint64_t want64 = p.n_live < (uint64_t)k ? p.n_live : (uint64_t)k;  // removed rows are never found
     const int want = (int)want64;
     uint64_t *oid = p.ids + (size_t)q * k;
     float *osc = p.scores + (size_t)q * k;
@@ -631,11 +631,35 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     if (want == 0) return;
     const double na = p.qnorm2[q];
     if (!(na > 0.0)) {
-        // zero-norm query: DistCosine returns 0 for every row -> ties broken by id (local.rs:63 ids)
-        for (int j = tid; j < want; j += kFinThreads) {
-            oid[j] = p.idmap.id_of((uint32_t)j);
-            osc[j] = 1.0f;
-            if (odi) odi[j] = 0.0f;
+        // zero-norm query: DistCosine returns 0 for every row -> ties broken by id (local.rs:63 ids): the first `want` live rows
+        if (!p.dead) {
+            for (int j = tid; j < want; j += kFinThreads) {
+                oid[j] = p.idmap.id_of((uint32_t)j);
+                osc[j] = 1.0f;
+                if (odi) odi[j] = 0.0f;
+            }
+        } else {
+            // block-wide: 1024 dead-row words per trip, a scan of their live counts places each word's live rows
+            uint32_t found = 0;  // block-uniform
+            for (uint64_t w0 = 0; found < (uint32_t)want && w0 * 64 < p.n_rows; w0 += kFinThreads) {
+                const uint64_t w = w0 + (uint64_t)tid;
+                uint64_t live = 0;
+                if (w * 64 < p.n_rows) {
+                    live = ~p.dead[w];
+                    const uint64_t rem = p.n_rows - w * 64;
+                    if (rem < 64) live &= (1ull << rem) - 1ull;
+                }
+                uint32_t tot;
+                uint32_t j = found + block_scan_1024((uint32_t)__popcll(live), s_w, &tot);
+                for (; live && j < (uint32_t)want; ++j) {
+                    const uint64_t row = w * 64 + (uint64_t)__builtin_ctzll(live);
+                    live &= live - 1;
+                    oid[j] = p.idmap.id_of((uint32_t)row);
+                    osc[j] = 1.0f;
+                    if (odi) odi[j] = 0.0f;
+                }
+                found += tot;
+            }
         }
         return;
     }
@@ -668,6 +692,9 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
         return lo < n && list[lo] == row;
     };
     auto is_zero_row = [&](uint32_t row) { return (nz && in_list(p.zero_rows, nz, row)) || (nw && in_list(p.wild_rows, nw, row)); };
+    // removed rows: the masked scans give them scores no threshold passes, but a half tile of zeros (step 0) scores them 0, and
+    // theta may be -inf; the lists above still name removed rows.  Nothing removed: p.dead is null and this is never asked.
+    auto is_dead = [&](uint32_t row) { return p.dead && ((p.dead[row >> 6] >> (row & 63u)) & 1ull) != 0; };
     // (a) record counts of this query's 2*nwg lane buffers -> exclusive scan in LDS
     uint32_t *s_off = reinterpret_cast<uint32_t *>(qv + ds) + 32;  // [2*kMaxScanWGs + 1], behind the staged-row ids
     uint32_t nrec = 0;
@@ -707,7 +734,10 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
             const uint32_t e = j - s_off[lo], hh = lo / (uint32_t)nwg, w = lo - hh * (uint32_t)nwg;
             const size_t l = (size_t)((uint32_t)(q >> 5) * 64 + (uint32_t)(q & 31) + 32u * hh) * nwg + w;
             const f32x4 *rec = reinterpret_cast<const f32x4 *>(p.lane_rec + l * (kRecCap * 16)) + e * 4;
-            rowb = p.lane_tile[l * kRecCap + e] * kTileRows + 4u * hh;
+            const uint32_t t32 = p.lane_tile[l * kRecCap + e];
+            rowb = t32 * kTileRows + 4u * hh;
+            // removed rows of the record: its 16 rows lie in one half tile, one word loaded beside the scores
+            const uint32_t dm = p.dead ? lane_dead16(dead_half(p.dead, t32), hh) : 0u;
             const f32x4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = a[r], v[4 + r] = b[r], v[8 + r] = c[r], v[12 + r] = d[r];
@@ -716,7 +746,7 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const uint32_t row = rowb + (r & 3) + 8 * (r >> 2);
-                const bool pass = v[r] >= thr && (uint64_t)row < p.n_rows && !(v[r] == 0.0f && (nz | nw) && is_zero_row(row));
+                const bool pass = v[r] >= thr && (uint64_t)row < p.n_rows && !(v[r] == 0.0f && (nz | nw) && is_zero_row(row)) && !((dm >> r) & 1u);
                 mask |= pass ? (1u << r) : 0u;
                 v[r] -= eb;                                // candidates carry the LOWER bound of their cosine
             }
@@ -742,7 +772,7 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     }
     // the zero-norm rows
     for (uint32_t z = tid; z < nz; z += kFinThreads)
-        if ((uint64_t)p.zero_rows[z] < p.n_rows) put(atomicAdd(&s_cnt, 1u), 1.0f, p.zero_rows[z]);
+        if ((uint64_t)p.zero_rows[z] < p.n_rows && !is_dead(p.zero_rows[z])) put(atomicAdd(&s_cnt, 1u), 1.0f, p.zero_rows[z]);
     __syncthreads();
     uint32_t M = s_cnt;
     const bool too_many = M > (uint32_t)kCandCap;  // more than the block can hold: keep what fits (any subset yields a
@@ -962,14 +992,14 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
         __syncthreads();
         if (tid < (int)mt) {
             const float d = exact_dist_row(qv, stage + (size_t)tid * pitch, ds, na, nullptr);
-            keys[tid] = ((uint64_t)__float_as_uint(d) << 32) | srow[tid];
+            keys[tid] = tid >= (int)m2 && is_dead(srow[tid]) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | srow[tid];  // a removed listed row (the candidates are live): last
         }
     } else {
         // (keys[] shares ent[]'s storage, 8 bytes per entry both: thread cI reads ent[cI] and writes keys[cI] itself)
         for (uint32_t cI = tid; cI < mt; cI += kFinThreads) {
             const uint32_t r = cI < m2 ? ent[cI].row : p.wild_rows[cI - m2];
             const float d = exact_dist_stored<CMP>(qv, p.x, p.xh, ds, r, na);
-            keys[cI] = ((uint64_t)__float_as_uint(d) << 32) | r;
+            keys[cI] = cI >= m2 && is_dead(r) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | r;  // a removed listed row (the candidates are live): last
         }
     }
     __syncthreads();
@@ -1095,7 +1125,7 @@ template <bool CMP, int QPT>
 __global__ __launch_bounds__(256) void exact_dist_batch_kernel(int ds, const float *__restrict__ x, const void *__restrict__ xh,
                                                                uint64_t n_rows, const float *__restrict__ qpad,
                                                                const double *__restrict__ qnorm2, ExactGroup grp,
-                                                               uint32_t *__restrict__ dist) {
+                                                               uint32_t *__restrict__ dist, const uint64_t *__restrict__ dead) {
     __shared__ __attribute__((aligned(16))) float s_rows[kXRows * kXPitch];
     __shared__ __attribute__((aligned(16))) float s_q[kExactGroup * kXChunk];
     const int tid = threadIdx.x, lr = tid & 63, qg = tid >> 6;  // local row, query group of the wave (QPT queries)
@@ -1144,9 +1174,12 @@ __global__ __launch_bounds__(256) void exact_dist_batch_kernel(int ds, const flo
             }
         }
         if (r0 + lr < n_rows) {
+            // a removed row: the largest key, which no distance has -- never among the min(k, live rows) selected
+            const bool gone = dead && ((dead[(r0 + lr) >> 6] >> ((r0 + lr) & 63u)) & 1ull) != 0;
 #pragma unroll
             for (int j = 0; j < QPT; ++j)
-                if (qg * QPT + j < nq) dist[(size_t)(qg * QPT + j) * n_rows + r0 + lr] = __float_as_uint(dist_from_sums(dot[j], na[j], nb));
+                if (qg * QPT + j < nq)
+                    dist[(size_t)(qg * QPT + j) * n_rows + r0 + lr] = gone ? 0xffffffffu : __float_as_uint(dist_from_sums(dot[j], na[j], nb));
         }
     }
 }
@@ -1310,9 +1343,10 @@ size_t exact_group_scratch_bytes(uint64_t n_rows, int k, int gcap) {
 
 hipError_t launch_exact_group(hipStream_t s, int k, int ds, const float *x, const void *xh, uint64_t n_rows, const IdMap &idmap,
                               const float *qpad, const double *qnorm2, const ExactGroup &grp, void *scratch, uint64_t *ids,
-                              float *scores, float *dists, int32_t *n_found) {
+                              float *scores, float *dists, int32_t *n_found, const uint64_t *dead, uint64_t n_live) {
     if (grp.n <= 0) return hipSuccess;
-    const uint32_t kk = (uint32_t)(n_rows < (uint64_t)k ? n_rows : (uint64_t)k);
+    const uint64_t live = n_live < n_rows ? n_live : n_rows;
+    const uint32_t kk = (uint32_t)(live < (uint64_t)k ? live : (uint64_t)k);
     char *base = static_cast<char *>(scratch);
     uint32_t *hist = reinterpret_cast<uint32_t *>(base);
     uint32_t *state = hist + (size_t)kExactGroup * kXBins;
@@ -1325,7 +1359,7 @@ hipError_t launch_exact_group(hipStream_t s, int k, int ds, const float *x, cons
         hipLaunchKernelGGL(xsel_init_kernel, dim3(1), dim3(kExactGroup), 0, s, kk, state);
         const uint64_t tiles = (n_rows + kXRows - 1) / kXRows;
         const unsigned blocks = (unsigned)(tiles < 2048 ? tiles : 2048);
-#define MX_XDIST(CMP_, QPT_) hipLaunchKernelGGL((exact_dist_batch_kernel<CMP_, QPT_>), dim3(blocks), dim3(256), 0, s, ds, x, xh, n_rows, qpad, qnorm2, grp, dist)
+#define MX_XDIST(CMP_, QPT_) hipLaunchKernelGGL((exact_dist_batch_kernel<CMP_, QPT_>), dim3(blocks), dim3(256), 0, s, ds, x, xh, n_rows, qpad, qnorm2, grp, dist, dead)
         if (x) {
             if (grp.n <= 4) MX_XDIST(false, 1);
             else if (grp.n <= 8) MX_XDIST(false, 2);

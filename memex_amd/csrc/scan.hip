@@ -48,7 +48,8 @@ constexpr uint32_t kScaleOff = kTileOff + 2 * kTileBytes;  // per-tile 1/|c| rin
 static_assert(kScaleOff + kScaleRing * kTileRows * 4 == kScanLdsBytes, "LDS layout");
 static_assert(kPrefetch == kNumSlots && kNumSlots == 8, "waits below assume an 8-slot ring, all in flight");
 
-template <int KC, int MODE>
+// DEAD: the variant that honours ScanParams::dead (launched only when the index has removed rows)
+template <int KC, int MODE, bool DEAD = false>
 __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -157,6 +158,10 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        // removed rows (DEAD): the 64-row word of this 32-row tile, one SCALAR load issued with the wait for the tile's first slot
+        // (scan8.hip: a plain load would be a vector load outside the ring's counted vmcnt waits, and the compiler's vmcnt(0)
+        // in front of its use would drain the ring once per tile)
+        uint64_t dw = 0;
 
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc, ++j) {
@@ -164,13 +169,21 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
             // the 6 newer slots (12 DMA ops) are outstanding; near the end just drain.
             // lgkmcnt(0): this wave's bf16 tile writes of the previous iteration are done before
             // it arrives at the barrier.
-            if (j + (uint32_t)kNumSlots <= total)
-                asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             // One barrier per slot: tile j&1 (written last iteration) is complete and visible;
             // tile (j+1)&1 (read last iteration) is free to overwrite.
-            __builtin_amdgcn_s_barrier();
+            if (DEAD && kc == 0) {
+                const uint64_t *dp = p.dead + ((t0 + ti * tstep) >> 1);
+                if (j + (uint32_t)kNumSlots <= total)
+                    asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_load_dwordx2 %0, %1, 0x0\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)" : "=s"(dw) : "s"(dp) : "memory");
+                else
+                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_load_dwordx2 %0, %1, 0x0\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)" : "=s"(dw) : "s"(dp) : "memory");
+            } else {
+                if (j + (uint32_t)kNumSlots <= total)
+                    asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
+                else
+                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+            }
             const uint32_t rp1 = (rp + 1 == (uint32_t)kNumSlots) ? 0 : rp + 1;
             const bool more = j + 1 < total;
 
@@ -226,6 +239,15 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
             const f32x4 sv = (r >> 2) == 0 ? s0 : (r >> 2) == 1 ? s1 : (r >> 2) == 2 ? s2 : s3;
             v[r] = acc[r] * sv[r & 3];  // 1/|c| is 0 for a zero-norm row: score 0 (see scan16.hip)
         }
+        if constexpr (DEAD) {  // removed rows (ScanParams::dead): a score no test passes, and no lower bound for the sample
+            const uint32_t hw = (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u)));  // the tile's half of its 64-row word
+            if (hw) {
+                const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
+        #pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((lb >> r) & 1u) v[r] = -INFINITY;
+            }
+        }
         float mx = fmaxf(fmaxf(v[0], v[1]), v[2]);
 #pragma unroll
         for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, v[r]), v[r + 1]);
@@ -259,8 +281,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
 
 template <int KC, int MODE>
 static hipError_t setup_one() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_kernel<KC, MODE>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kScanLdsBytes);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_kernel<KC, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, kScanLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_kernel<KC, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kScanLdsBytes);
 }
 
 hipError_t scan_setup() {
@@ -275,6 +298,11 @@ hipError_t scan_setup() {
 
 template <int KC>
 static hipError_t launch_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
+    if (p.dead) {
+        if (collect) hipLaunchKernelGGL((scan_kernel<KC, 1, true>), dim3(nwg), dim3(kScanThreads), kScanLdsBytes, s, p);
+        else hipLaunchKernelGGL((scan_kernel<KC, 0, true>), dim3(nwg), dim3(kScanThreads), kScanLdsBytes, s, p);
+        return hipGetLastError();
+    }
     if (collect)
         hipLaunchKernelGGL((scan_kernel<KC, 1>), dim3(nwg), dim3(kScanThreads), kScanLdsBytes, s, p);
     else

@@ -88,7 +88,8 @@ static_assert(ops_after16<3>(2, 14) == 17 && ops_after16<6>(5, 17) == 15 && ops_
 #define MX_SCAN16_AUX 2 /* nt */
 #endif
 
-template <int KC, int MODE>
+// DEAD: the variant that honours ScanParams::dead (launched only when the index has removed rows)
+template <int KC, int MODE, bool DEAD = false>
 __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParams p) {
     // Fragment ring: the A fragment of k-step f lives in ring[f % R] and is re-read R k-steps ahead
     // right after the MFMA that consumed it.  8 % R == 0, so the ring index of a k-step does not
@@ -190,6 +191,10 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
         f32x16 acc, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f, acc1[r] = 0.0f;
+        // removed rows (DEAD): the 64-row word of this 32-row tile, one SCALAR load issued with the wait for the tile's first slot
+        // (scan8.hip: a plain load would be a vector load outside the ring's counted vmcnt waits, and the compiler's vmcnt(0)
+        // in front of its use would drain the ring once per tile)
+        uint64_t dw = 0;
 
         static_for16<0, KC>([&](auto kct) __attribute__((always_inline)) {
             constexpr int kc = decltype(kct)::value;
@@ -197,10 +202,17 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
             const uint32_t rpi = (rp + kRing16 - 1) & (kRing16 - 1);  // ring position of slot j+15 = of slot j-1
             // Slot j+1 (the ring reads ahead into it) must have landed; slots 0 .. j+14 are issued ->
             // the 13 newer ones (and the a_c operations of the tiles that start among them) may be in flight.
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after16<KC>(kc + 2, kc + kRing16 - 2)) : "memory");
             // One barrier per slot: every wave's piece of slot j+1 is in LDS, and every wave has
             // consumed (MFMA issued) its fragments of slot j-1, whose ring position is refilled below.
-            __builtin_amdgcn_s_barrier();
+            if constexpr (DEAD && kc == 0) {
+                asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt vmcnt(%2)\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)"
+                             : "=s"(dw)
+                             : "s"(p.dead + ((t0 + ti * tstep) >> 1)), "n"(ops_after16<KC>(kc + 2, kc + kRing16 - 2))
+                             : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after16<KC>(kc + 2, kc + kRing16 - 2)) : "memory");
+                __builtin_amdgcn_s_barrier();
+            }
             const uint32_t fb0 = rp * kSlot16Bytes + lane16, fb1 = rp1 * kSlot16Bytes + lane16;
             if (!live) {
                 issue((kc + kRing16 - 1) % KC, rpi);
@@ -253,6 +265,15 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
                 const f32x4 a4 = am[2 * j];  // rows 8 j + 4 h .. + 3
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[4 * j + e] = __builtin_fmaf(aq, a4[e], v[4 * j + e]);
+            }
+        }
+        if constexpr (DEAD) {  // removed rows (ScanParams::dead): a score no test passes, and no lower bound for the sample
+            const uint32_t hw = (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u)));  // the tile's half of its 64-row word
+            if (hw) {
+                const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
+        #pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((lb >> r) & 1u) v[r] = -INFINITY;
             }
         }
         float mx = fmaxf(fmaxf(v[0], v[1]), v[2]);
@@ -391,8 +412,9 @@ hipError_t launch_shadow(hipStream_t s, const float *x, const float *scale, int 
 
 template <int KC, int MODE>
 static hipError_t setup16_one() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16_kernel<KC, MODE>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kScan16LdsBytes);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16_kernel<KC, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16LdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16_kernel<KC, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16LdsBytes);
 }
 
 hipError_t scan16_setup() {
@@ -407,6 +429,11 @@ hipError_t scan16_setup() {
 
 template <int KC>
 static hipError_t launch16_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
+    if (p.dead) {
+        if (collect) hipLaunchKernelGGL((scan16_kernel<KC, 1, true>), dim3(nwg), dim3(kScanThreads), kScan16LdsBytes, s, p);
+        else hipLaunchKernelGGL((scan16_kernel<KC, 0, true>), dim3(nwg), dim3(kScanThreads), kScan16LdsBytes, s, p);
+        return hipGetLastError();
+    }
     if (collect)
         hipLaunchKernelGGL((scan16_kernel<KC, 1>), dim3(nwg), dim3(kScanThreads), kScan16LdsBytes, s, p);
     else

@@ -36,7 +36,8 @@ typedef __attribute__((address_space(3))) void lds_void;
 
 static_assert(kRing16 == 16, "waits below assume a 16-slot ring with 15 slots in flight");
 
-template <int KC, int MODE>
+// DEAD: the variant that honours ScanParams::dead (launched only when the index has removed rows)
+template <int KC, int MODE, bool DEAD = false>
 __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanParams p) {
     static_assert(KC % 2 == 0 && KC >= 4, "slot parities need an even slot count per tile");
     constexpr int KL = KC / 2;           // slots per tile this wave multiplies
@@ -111,13 +112,24 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
         f32x16 acc, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f, acc1[r] = 0.0f;
+        // removed rows (DEAD): the 64-row word of this 32-row tile, one SCALAR load issued with the wait for the tile's first slot
+        // (scan8.hip: a plain load would be a vector load outside the ring's counted vmcnt waits, and the compiler's vmcnt(0)
+        // in front of its use would drain the ring once per tile)
+        uint64_t dw = 0;
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             const uint32_t rp1 = (rp + 1) & (kRing16 - 1);
             const uint32_t rp2 = (rp + 2) & (kRing16 - 1);
             const uint32_t rpi = (rp + kRing16 - 1) & (kRing16 - 1);
-            asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            if (DEAD && kc == 0) {
+                asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt vmcnt(12)\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)"
+                             : "=s"(dw)
+                             : "s"(p.dead + ((t0 + ti * tstep) >> 1))
+                             : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+            }
             if ((kc & 1) == PAR) {
                 const int c = kc >> 1;  // local chunk
                 const uint32_t fb0 = rp * kSlot16Bytes + lane16, fb2 = rp2 * kSlot16Bytes + lane16;
@@ -155,6 +167,15 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
             const f32x4 o = *reinterpret_cast<const f32x4 *>(smem + xoff + lane16 + i * 1024);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[4 * i + j] += o[j];
+        }
+        if constexpr (DEAD) {  // removed rows (ScanParams::dead): a score no test passes, and no lower bound for the sample
+            const uint32_t hw = (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u)));  // the tile's half of its 64-row word
+            if (hw) {
+                const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
+        #pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((lb >> r) & 1u) acc[r] = -INFINITY;
+            }
         }
         float mx = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
 #pragma unroll
@@ -201,8 +222,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
 
 template <int KC, int MODE>
 static hipError_t setup16w_one() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16w_kernel<KC, MODE>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kScan16WideLdsBytes);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16w_kernel<KC, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16WideLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16w_kernel<KC, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16WideLdsBytes);
 }
 
 hipError_t scan16w_setup() {
@@ -217,6 +239,11 @@ hipError_t scan16w_setup() {
 
 template <int KC>
 static hipError_t launch16w_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
+    if (p.dead) {
+        if (collect) hipLaunchKernelGGL((scan16w_kernel<KC, 1, true>), dim3(nwg), dim3(kScanThreads), kScan16WideLdsBytes, s, p);
+        else hipLaunchKernelGGL((scan16w_kernel<KC, 0, true>), dim3(nwg), dim3(kScanThreads), kScan16WideLdsBytes, s, p);
+        return hipGetLastError();
+    }
     if (collect)
         hipLaunchKernelGGL((scan16w_kernel<KC, 1>), dim3(nwg), dim3(kScanThreads), kScan16WideLdsBytes, s, p);
     else

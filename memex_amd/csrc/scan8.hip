@@ -38,6 +38,7 @@
 // Tile epilogue, per half: integer max over the lane's 16 sums, one conversion, two multiplications (s_h, s_q),
 // one FMA (theta - qb * e_h), one compare; a passing lane stores its 16 scores as floats -- the record format of
 // scan16_kernel with the 32-row tile index 2T + u, so theta_kernel and finish_kernel do not know which scan ran.
+#include <climits>
 #include <type_traits>
 
 #include "index_kernels.h"
@@ -95,7 +96,8 @@ static_assert(ops_after<3, 2, 1>(2, 6) == 12 && ops_after<3, 2, 1>(4, 8) == 11 &
 // 4 / 8: the two-workgroup form (Scan8Geom::kPair, two query groups per wave, plain copy only): a wave issues two of a
 // slot's eight 1-KiB pieces and only the scales' per-tile operation; wave w holds the virtual waves 2w and 2w+1, so the
 // lane numbering is the 512-query pass's with twice the workgroups and half the waves
-template <int KC, int MODE, int QG, bool CEN, int NW = kScanWaves, int RING = kRing16>
+// DEAD = the variant that honours ScanParams::dead (launched only when the index has removed rows)
+template <int KC, int MODE, int QG, bool CEN, int NW = kScanWaves, int RING = kRing16, bool DEAD = false>
 __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
     static_assert(!CEN || (KC <= kMaxKC && QG == 1), "the centred form exists up to kMaxKC slots with one query group");
     static_assert((NW == kScanWaves && RING == kRing16) || (NW == kScan8PairWaves && RING == kScan8PairRing && QG == 2 && !CEN),
@@ -256,6 +258,9 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
 #pragma unroll 1
     for (uint32_t ti = 0; ti < nT; ++ti) {
         const uint32_t tile = t0 + ti * tstep;
+        // removed rows of the tile (DEAD): one SCALAR load, issued with the wait for the tile's first slot below.  (A plain load of
+        // p.dead[tile] becomes a vector load: one more operation on vmcnt that the hand-counted waits of the ring do not know about.)
+        uint64_t dw = 0;
         if constexpr (!CEN) {
 #pragma unroll
             for (int g = 0; g < QG * 2; ++g)
@@ -268,8 +273,17 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
             const uint32_t rp1 = (rp + 1) & (RING - 1);
             const uint32_t rpi = (rp + RING - 1) & (RING - 1);
             // slot j+1 landed (the ring reads ahead into it): everything issued after it may still be in flight
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC, DPS, TOPS>(kc + 2, kc + RING - 2)) : "memory");
-            __builtin_amdgcn_s_barrier();  // ... for every wave of the workgroup; slot j-1 is free for slot j+RING-1
+            if constexpr (DEAD && kc == 0) {
+                // the dead-row word of the tile: its latency hides under the slot wait and the barrier; lgkmcnt(0) behind them, in the same
+                // statement, so that no LDS wait the compiler counts runs while it is in flight
+                asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt vmcnt(%2)\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)"
+                             : "=s"(dw)
+                             : "s"(p.dead + tile), "n"(ops_after<KC, DPS, TOPS>(kc + 2, kc + RING - 2))
+                             : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC, DPS, TOPS>(kc + 2, kc + RING - 2)) : "memory");
+                __builtin_amdgcn_s_barrier();  // ... for every wave of the workgroup; slot j-1 is free for slot j+RING-1
+            }
             const uint32_t fb0 = rp * kSlot16Bytes + lane16, fb1 = rp1 * kSlot16Bytes + lane16;
             if (live) {
                 static_for<0, 8>([&](auto ft) __attribute__((always_inline)) {
@@ -320,15 +334,25 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
         for (int g = 0; g < QG; ++g) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const i32x16 &ac = acc[g * 2 + u];
+                i32x16 &ac = acc[g * 2 + u];
                 const float sh = u ? shs[1] : shs[0], er = u ? shs[3] : shs[2];
+                if constexpr (DEAD) {  // removed rows: the smallest sum (no live row comes near it), then a score no test passes
+                    const uint32_t hw = (uint32_t)(dw >> (32 * u));
+                    if (hw) {
+                        const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if ((lb >> r) & 1u) ac[r] = INT_MIN;
+                    }
+                }
                 int mxi = max(max(ac[0], ac[1]), ac[2]);
 #pragma unroll
                 for (int r = 3; r < 15; r += 2) mxi = max(max(mxi, ac[r]), ac[r + 1]);
                 mxi = max(mxi, ac[15]);
                 // score of a sum: ((float)sum * s_h) * s_q -- monotone in the sum, so the test on the maximum is the
                 // test on "any of the 16 scores" as finish_kernel will see them
-                const float mx = ((float)mxi * sh) * sq[g];
+                float mx = ((float)mxi * sh) * sq[g];
+                if (DEAD && mxi == INT_MIN) mx = -INFINITY;  // every row of the lane removed (also when the step is 0)
                 const float thr = fmaf(-qb[g], er, theta[g]);
                 if (MODE == 0) {
                     best[g] = fmaxf(best[g], mx - fmaf(qb[g], er, qa[g]));  // only full tiles are sampled (index.hip): every row is a real row
@@ -513,12 +537,18 @@ hipError_t launch_shadow8(hipStream_t s, const float *x, const float *scale, int
 
 template <int KC, int MODE, int QG, bool CEN = false>
 static hipError_t setup8_one() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, QG, CEN>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, QG, CEN>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScan8LdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, QG, CEN, kScanWaves, kRing16, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, kScan8LdsBytes);
 }
 template <int KC, int MODE>
 static hipError_t setup8_pair() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, 2, false, kScan8PairWaves, kScan8PairRing>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, 2, false, kScan8PairWaves, kScan8PairRing>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScan8PairLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, 2, false, kScan8PairWaves, kScan8PairRing, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, kScan8PairLdsBytes);
 }
 
@@ -554,6 +584,11 @@ hipError_t scan8_setup() {
 
 template <int KC, int QG, bool CEN = false>
 static hipError_t launch8_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
+    if (p.dead) {
+        if (collect) hipLaunchKernelGGL((scan8_kernel<KC, 1, QG, CEN, kScanWaves, kRing16, true>), dim3(nwg), dim3(kScanThreads), kScan8LdsBytes, s, p);
+        else hipLaunchKernelGGL((scan8_kernel<KC, 0, QG, CEN, kScanWaves, kRing16, true>), dim3(nwg), dim3(kScanThreads), kScan8LdsBytes, s, p);
+        return hipGetLastError();
+    }
     if (collect)
         hipLaunchKernelGGL((scan8_kernel<KC, 1, QG, CEN>), dim3(nwg), dim3(kScanThreads), kScan8LdsBytes, s, p);
     else
@@ -564,6 +599,11 @@ static hipError_t launch8_kc(hipStream_t s, bool collect, int nwg, const ScanPar
 template <int KC>
 static hipError_t launch8_pair(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
     constexpr int NW = kScan8PairWaves, RING = kScan8PairRing;
+    if (p.dead) {
+        if (collect) hipLaunchKernelGGL((scan8_kernel<KC, 1, 2, false, NW, RING, true>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
+        else hipLaunchKernelGGL((scan8_kernel<KC, 0, 2, false, NW, RING, true>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
+        return hipGetLastError();
+    }
     if (collect)
         hipLaunchKernelGGL((scan8_kernel<KC, 1, 2, false, NW, RING>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
     else

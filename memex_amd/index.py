@@ -161,6 +161,21 @@ class FlatIndex:
     def clear(self) -> None:
         check(lib().mx_index_clear(self._h))
 
+    def remove(self, ids) -> int:
+        """Remove rows by the ids search returns (tombstones: ids stay, the rows never appear in a result again).
+        Every id is checked first: one that does not name a row raises and nothing is removed.  -> rows newly removed."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+        n = ctypes.c_uint64(0)
+        check(lib().mx_index_remove(self._h, _ptr(a) if a.size else None, a.size, ctypes.byref(n)))
+        return int(n.value)
+
+    @property
+    def removed(self) -> int:
+        """Rows removed so far (len(self) still counts them)."""
+        n = ctypes.c_uint64(0)
+        check(lib().mx_index_removed(self._h, ctypes.byref(n)))
+        return int(n.value)
+
     # -- search --------------------------------------------------------------------------
     def search(self, queries, k: int):
         """-> (ids u64 [B,k], scores f32 [B,k], dists f32 [B,k], n_found i32 [B])."""

@@ -167,6 +167,7 @@ class HipFlatStore(VectorStore):
     _lock: threading.RLock = field(default_factory=threading.RLock, repr=False, compare=False)
     _meta_sig: tuple | None = None          # (mtime_ns, size) of vectors.meta.json as last written / read
     _meta_ids: int = 0                      # ids that file holds
+    _rows_of: Dict[str, List[int]] | None = field(default=None, repr=False, compare=False)  # _id -> ids (remove): built once, kept on insert
 
     # -- construction (local.rs:95-141) ----------------------------------------------------
     @classmethod
@@ -217,6 +218,7 @@ class HipFlatStore(VectorStore):
             raise SerdeError(str(e)) from e
         store._meta_sig = _file_sig(meta)
         store._meta_ids = len(store._id_map)
+        store._rows_of = None
         if store._id_map:
             try:
                 if not FlatIndex.has_store(store_path):
@@ -310,8 +312,36 @@ class HipFlatStore(VectorStore):
             except _lib.MemexHipError as e:
                 raise DeleteError(e.msg) from e
             self._id_map.clear()
+            self._rows_of = None
             self._meta_sig = None
             self._meta_ids = 0
+
+    def remove(self, ids: str | Sequence[str]) -> int:
+        """Remove every row whose ``_id`` is in ``ids`` (rows inserted twice under one ``_id`` all go): the capability
+        ``delete`` (local.rs:29-32, ``unimplemented!()``) lacks.  Tombstones: ids stay stable and ``vectors.meta.json``
+        is unchanged; the removals are saved beside the store (``vectors.mxdead``) before this returns.  An unknown
+        ``_id`` removes nothing (OpenSearch's delete of a missing document).  -> rows newly removed."""
+        wanted = [ids] if isinstance(ids, str) else [str(i) for i in ids]
+        with self._lock:
+            if self._index is None or not self._id_map:
+                return 0
+            if self._rows_of is None:  # once per store: every later call looks its _ids up
+                rows_of: Dict[str, List[int]] = {}
+                for i, d_id in self._id_map.items():
+                    rows_of.setdefault(d_id, []).append(i)
+                self._rows_of = rows_of
+            rows = [i for w in dict.fromkeys(wanted) for i in self._rows_of.get(w, ())]
+            if not rows:
+                return 0
+            try:
+                n = self._index.remove(rows)
+            except _lib.MemexHipError as e:
+                raise DeleteError(e.msg) from e
+            try:
+                self.save()
+            except VectorStoreError as e:
+                raise DeleteError(str(e)) from e
+            return n
 
     def bulk_insert(self, data: Sequence[VectorData]) -> None:
         """local.rs:55-69 semantics (ids in order, store persisted before returning), one device
@@ -336,6 +366,8 @@ class HipFlatStore(VectorStore):
             assert first == next_id, (first, next_id)
             for i, d in enumerate(data):
                 self._id_map[next_id + i] = str(d._id)
+                if self._rows_of is not None:
+                    self._rows_of.setdefault(str(d._id), []).append(next_id + i)
             try:
                 self.save()  # local.rs:67 `let _ = self.save(..)`: errors are ignored there too
             except VectorStoreError:
