@@ -138,7 +138,7 @@ int mx_index_clear(mx_index *idx);
 /*
  * Remove single rows (HnswStore::delete, storage/local.rs:29-32, which the reference leaves unimplemented).
  * Tombstones: a removed row keeps its storage and its id and never appears in a search result again; ids
- * are never reused or renumbered, so mx_index_size still counts every row ever added and
+ * are never reused or renumbered until mx_index_compact, so mx_index_size still counts every row ever added and
  * mx_index_get_rows still returns a removed row's stored values.  `ids` are the ids search returns
  * (id_offset applied).  Every id is checked first: one outside [id_offset + 1, id_offset + size] gives
  * MX_EINVAL and nothing is removed.  An id already removed, or named twice, is not an error;
@@ -148,6 +148,17 @@ int mx_index_clear(mx_index *idx);
  */
 int mx_index_remove(mx_index *idx, const uint64_t *ids, uint64_t n, uint64_t *n_removed);
 int mx_index_removed(mx_index *idx, uint64_t *n_removed); /* rows removed so far */
+
+/* Drop removed rows for good.  Live rows keep their order and get dense ids again:
+ * the i-th live row (0-based) gets id id_offset + i + 1.  kept_ids (may be NULL) receives, for
+ * each new id in order, the id the row had before (it must hold size - removed entries, checked
+ * with kept_cap BEFORE anything changes: MX_EINVAL).  Afterwards size == live rows, removed == 0.
+ * Nothing removed: a no-op that returns the identity, with the index and its disk state untouched.
+ * Holds the index like a search does: a search sees either the old rows and ids or the new ones.
+ * Ids a caller holds from before the call no longer name the same rows.  The move is in place: a device
+ * error after the first row moved marks the index failed (every later call: MX_EDEVICE) until
+ * mx_index_clear or mx_index_load.  The next mx_index_save rewrites the store whole. */
+int mx_index_compact(mx_index *idx, uint64_t *kept_ids, uint64_t kept_cap, uint64_t *n_live);
 
 /*
  * Top-k cosine search.  Replaces HnswStore::search (storage/local.rs:71-91) + hnsw_rs DistCosine:
@@ -216,7 +227,10 @@ int mx_index_get_rows(mx_index *idx, uint64_t first_row, uint64_t n, float *out)
  * `dir`: `vectors.mxflat` (header + raw f32 rows) and, once rows have been removed, `vectors.mxdead`
  * (magic "MXDEAD01" | u64 count | count x u64 removed rows, 0-based without id offset; entries are
  * appended and the count patched last; no file = nothing removed; a damaged one fails the load with
- * MX_EIO and leaves the index as it was).  The string-id map `vectors.meta.json`
+ * MX_EIO and leaves the index as it was).  A compacted index (mx_index_compact) writes "MXFLAT02" and
+ * "MXDEAD02", whose headers carry its compaction generation (u64, after the row count); a removal file
+ * whose generation is not the vector file's is stale: ignored on load, replaced on the next save.
+ * The string-id map `vectors.meta.json`
  * (local.rs:19,156-163) stays on the Rust side unchanged.
  */
 int mx_index_save(mx_index *idx, const char *dir);

@@ -270,6 +270,38 @@ class HipFlatStore : public VectorStore {
     }
     size_t remove(const std::string &id) { return remove(std::vector<std::string>{id}); }
 
+    // Drop the rows remove() took out for good (mx_index_compact): the live rows get dense ids again and _id_map is renumbered
+    // to match.  Saved before this returns: vectors.mxflat is rewritten whole, then vectors.meta.json through a temporary file; a
+    // crash between the two leaves more ids than vectors, which load() rejects (FileIOError), never a wrong id -> _id mapping.
+    // Nothing removed: a no-op.  -> rows kept.
+    size_t compact() {
+        uint64_t n_live = 0;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || _id_map.empty()) return 0;
+            uint64_t size = 0, removed = 0;
+            if (mx_index_size(idx_, &size) != MX_OK || mx_index_removed(idx_, &removed) != MX_OK)
+                throw VectorStoreError(VectorStoreError::DeleteError, mx_last_error());
+            if (removed == 0) return (size_t)size;
+            std::vector<uint64_t> kept((size_t)(size - removed));
+            if (mx_index_compact(idx_, kept.data(), kept.size(), &n_live) != MX_OK)
+                throw VectorStoreError(VectorStoreError::DeleteError, mx_last_error());
+            std::map<size_t, std::string> renumbered;
+            for (size_t i = 0; i < (size_t)n_live; ++i) renumbered[i + 1] = _id_map.at((size_t)kept[i]);
+            _id_map.swap(renumbered);
+            rows_of_.clear();
+            rows_of_built_ = false;
+            meta_known_ = false;  // the id map is rewritten whole, never appended to
+            meta_ids_ = 0;
+        }
+        try {
+            save();
+        } catch (const VectorStoreError &e) {
+            throw VectorStoreError(VectorStoreError::DeleteError, e.what());
+        }
+        return (size_t)n_live;
+    }
+
     // local.rs:55-69 semantics (ids in order, store persisted before returning), one transfer and
     // one incremental save instead of a save per vector
     void bulk_insert(const std::vector<VectorData> &data) override {

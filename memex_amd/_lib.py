@@ -29,7 +29,7 @@ EXPORTS = [
     "mx_last_error", "mx_version", "mx_index_stats_size", "mx_device_count",
     "mx_index_open", "mx_index_open_sharded", "mx_index_n_shards", "mx_index_exchange", "mx_index_wait_stream", "mx_index_close", "mx_index_dim", "mx_index_size", "mx_index_reserve",
     "mx_index_set_id_offset", "mx_index_add", "mx_index_add_device", "mx_index_clear",
-    "mx_index_remove", "mx_index_removed",
+    "mx_index_remove", "mx_index_removed", "mx_index_compact",
     "mx_index_search", "mx_index_search_device", "mx_index_set_search_mode", "mx_index_set_filter_copy", "mx_index_set_corpus_mode", "mx_index_get_rows",
     "mx_index_save", "mx_index_load", "mx_index_has_store", "mx_index_store_info", "mx_index_remove_files",
     "mx_index_set_profiling", "mx_index_get_stats", "mx_index_reset_stats", "mx_topk_merge_device", "mx_topk_merge_packed_device", "mx_topk_merge_packed_async",
@@ -115,6 +115,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_index_clear": [vp],
         "mx_index_remove": [vp, vp, u64, P(u64)],
         "mx_index_removed": [vp, P(u64)],
+        "mx_index_compact": [vp, vp, u64, P(u64)],
         "mx_index_search": [vp, vp, i32, i32, vp, vp, vp, vp],
         "mx_index_search_device": [vp, vp, i32, i32, vp, vp, vp, vp],
         "mx_index_set_search_mode": [vp, i32],

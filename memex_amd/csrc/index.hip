@@ -231,6 +231,10 @@ struct mx_index {
     uint64_t n_dead = 0;            // rows removed (a composite: over its shards)
     std::vector<uint64_t> dead_log;  // the handle's removals in the order made, global rows without id offset (vectors.mxdead)
     uint64_t disk_dead = 0;          // ... how many of them vectors.mxdead in disk_dir holds
+    // compaction (mx_index_compact): how many times the rows were renumbered -- the generation the store files carry (0: never,
+    // and the 01 formats).  `failed`: a compaction met a device error after rows had moved; every call fails until clear / load
+    uint64_t gen = 0;
+    bool failed = false;
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -1490,6 +1494,19 @@ int composite_add(mx_index *idx, const float *rows, uint64_t n, uint64_t *first_
 
 const char kMagic[8] = {'M', 'X', 'F', 'L', 'A', 'T', '0', '1'};
 constexpr long kHeaderBytes = 24;
+// a compacted index's store (mx_index_compact): the 01 header + u64 compaction generation
+const char kMagic2[8] = {'M', 'X', 'F', 'L', 'A', 'T', '0', '2'};
+constexpr long kHeader2Bytes = 32;
+long header_bytes(uint64_t gen) { return gen ? kHeader2Bytes : kHeaderBytes; }
+
+// header of vectors.mxflat (either version) -> dim, flags word, rows, generation (0 for MXFLAT01); false: not a store header
+bool read_store_header(FILE *f, uint32_t (&hdr)[2], uint64_t *n, uint64_t *gen) {
+    char magic[8];
+    *gen = 0;
+    if (fread(magic, 1, 8, f) != 8 || fread(hdr, sizeof(hdr), 1, f) != 1 || fread(n, sizeof(*n), 1, f) != 1) return false;
+    if (memcmp(magic, kMagic, 8) == 0) return true;
+    return memcmp(magic, kMagic2, 8) == 0 && fread(gen, sizeof(*gen), 1, f) == 1 && *gen != 0;
+}
 std::string store_file(const char *dir) { return std::string(dir) + "/vectors.mxflat"; }
 
 int mkdir_p(const std::string &dir) {  // create_dir_all (local.rs:144)
@@ -1671,14 +1688,21 @@ int reset_dead(mx_index *idx) {
 
 // vectors.mxdead: magic[8] | u64 count | count x u64 removed rows (global, without id offset), in the order they were removed.
 // Entries are appended and the count is patched last (the rule of vectors.mxflat); no file = nothing removed.
+// MXDEAD02 (a compacted index) has the compaction generation behind the count: it belongs to the MXFLAT02 of that generation only.
 const char kDeadMagic[8] = {'M', 'X', 'D', 'E', 'A', 'D', '0', '1'};
 constexpr long kDeadHeaderBytes = 16;
+const char kDeadMagic2[8] = {'M', 'X', 'D', 'E', 'A', 'D', '0', '2'};
+constexpr long kDeadHeader2Bytes = 24;
+long dead_header_bytes(uint64_t gen) { return gen ? kDeadHeader2Bytes : kDeadHeaderBytes; }
+constexpr uint64_t kDeadStale = ~0ull;  // disk_dead: the removal file in disk_dir belongs to another generation (rewrite it)
 std::string dead_file(const char *dir) { return std::string(dir) + "/vectors.mxdead"; }
 
-// reads and validates vectors.mxdead of a store of n_rows rows; *present = false when there is none
-int read_dead_file(const char *dir, uint64_t n_rows, std::vector<uint64_t> *rows, bool *present) {
+// reads and validates vectors.mxdead of a store of n_rows rows and compaction generation gen; *present = false when there is
+// none, or when it is stale (*stale: it carries another generation -- a crash between the two files of a save)
+int read_dead_file(const char *dir, uint64_t n_rows, uint64_t gen, std::vector<uint64_t> *rows, bool *present, bool *stale) {
     rows->clear();
     *present = false;
+    *stale = false;
     const std::string path = dead_file(dir);
     FILE *f = fopen(path.c_str(), "rb");
     if (!f) {
@@ -1687,12 +1711,20 @@ int read_dead_file(const char *dir, uint64_t n_rows, std::vector<uint64_t> *rows
     }
     *present = true;
     char magic[8];
-    uint64_t cnt = 0;
+    uint64_t cnt = 0, fgen = 0;
     struct stat sb;
     int rc = MX_OK;
-    if (fread(magic, 1, 8, f) != 8 || memcmp(magic, kDeadMagic, 8) != 0 || fread(&cnt, sizeof(cnt), 1, f) != 1 || fstat(fileno(f), &sb) != 0)
+    const bool v1 = fread(magic, 1, 8, f) == 8 && memcmp(magic, kDeadMagic, 8) == 0;
+    const bool v2 = !v1 && memcmp(magic, kDeadMagic2, 8) == 0;
+    if ((!v1 && !v2) || fread(&cnt, sizeof(cnt), 1, f) != 1 || (v2 && (fread(&fgen, sizeof(fgen), 1, f) != 1 || fgen == 0)) ||
+        fstat(fileno(f), &sb) != 0 || (uint64_t)sb.st_size < (uint64_t)dead_header_bytes(fgen))
         rc = fail(MX_EIO, "%s: bad header", path.c_str());
-    else if (cnt > ((uint64_t)sb.st_size - kDeadHeaderBytes) / 8)
+    else if (fgen != gen) {  // another generation's removals: they name rows of another vectors.mxflat
+        fclose(f);
+        *present = false;
+        *stale = true;
+        return MX_OK;
+    } else if (cnt > ((uint64_t)sb.st_size - dead_header_bytes(fgen)) / 8)
         rc = fail(MX_EIO, "%s: truncated (%lld bytes for %llu entries)", path.c_str(), (long long)sb.st_size, (unsigned long long)cnt);
     if (rc == MX_OK) {
         rows->resize((size_t)cnt);
@@ -1719,12 +1751,13 @@ int save_dead_file(mx_index *idx, const char *dir, bool in_sync) {
         idx->disk_dead = 0;
         return MX_OK;
     }
-    if (in_sync && exists && idx->disk_dead <= total && (uint64_t)sb.st_size == (uint64_t)kDeadHeaderBytes + 8 * idx->disk_dead) {
+    const long hb = dead_header_bytes(idx->gen);
+    if (in_sync && exists && idx->disk_dead <= total && (uint64_t)sb.st_size == (uint64_t)hb + 8 * idx->disk_dead) {
         if (idx->disk_dead == total) return MX_OK;
         FILE *f = fopen(path.c_str(), "r+b");
         if (!f) return fail(MX_EIO, "cannot open %s for appending", path.c_str());
         const size_t m = (size_t)(total - idx->disk_dead);
-        int rc = fseek(f, kDeadHeaderBytes + (long)(8 * idx->disk_dead), SEEK_SET) == 0 &&
+        int rc = fseek(f, hb + (long)(8 * idx->disk_dead), SEEK_SET) == 0 &&
                          fwrite(idx->dead_log.data() + idx->disk_dead, sizeof(uint64_t), m, f) == m
                      ? MX_OK : fail(MX_EIO, "write to %s failed", path.c_str());
         // the count is patched last: a crash before this point leaves the old, consistent file
@@ -1737,7 +1770,8 @@ int save_dead_file(mx_index *idx, const char *dir, bool in_sync) {
     const std::string tmp = path + ".tmp";
     FILE *f = fopen(tmp.c_str(), "wb");
     if (!f) return fail(MX_EIO, "cannot open %s for writing", tmp.c_str());
-    int rc = fwrite(kDeadMagic, 1, 8, f) == 8 && fwrite(&total, sizeof(total), 1, f) == 1 &&
+    int rc = fwrite(idx->gen ? kDeadMagic2 : kDeadMagic, 1, 8, f) == 8 && fwrite(&total, sizeof(total), 1, f) == 1 &&
+                     (!idx->gen || fwrite(&idx->gen, sizeof(idx->gen), 1, f) == 1) &&
                      fwrite(idx->dead_log.data(), sizeof(uint64_t), (size_t)total, f) == (size_t)total
                  ? MX_OK : fail(MX_EIO, "write to %s failed", tmp.c_str());
     if (fclose(f) != 0 && rc == MX_OK) rc = fail(MX_EIO, "write to %s failed", tmp.c_str());
@@ -1779,6 +1813,7 @@ int clear_locked(mx_index *idx) {
     idx->dead_log.clear();
     idx->disk_dead = 0;
     idx->disk_dir.clear();
+    idx->failed = false;
     return MX_OK;
 }
 
@@ -1868,6 +1903,275 @@ int open_plain(const std::string &k, int dim, int device, mx_index **out) {
     }
     *out = idx.release();
     return MX_OK;
+}
+
+// ---- compaction (mx_index_compact) ----------------------------------------------------------------------
+bool row_removed(const mx_index *t, uint64_t r) {
+    return t->dead && (r >> 6) < t->dead_h.size() && ((t->dead_h[r >> 6] >> (r & 63)) & 1ull);
+}
+// global row r of a plain or composite index is removed
+bool global_removed(const mx_index *idx, uint64_t r) {
+    if (!idx->composite()) return row_removed(idx, r);
+    const uint64_t R = idx->block_rows, G = idx->shards.size(), b = r / R;
+    return row_removed(idx->shards[b % G], (b / G) * R + r % R);
+}
+
+// After a compaction: the capacity a fresh index of the same rows would have, round_up(max(n, 1024), 64), through the
+// reallocate-and-copy ensure_capacity grows with.  Old and new storage coexist for the copy; without HBM for the new one the
+// larger capacity stays (not an error).
+int release_capacity(mx_index *idx) {
+    const uint64_t want = round_up(std::max<uint64_t>(idx->n, 1024), kTile8Rows);
+    if (want >= idx->cap) return MX_OK;
+    const size_t ds = (size_t)idx->ds;
+    const size_t eb = idx->compressed ? 2 : idx->filter_i8 ? 1 : 2;  // bytes per element of the bf16 / int8 copy
+    DevBuf nx, nsc, nh, nts, nam;
+    auto get = [](DevBuf &b, size_t bytes) {
+        if (hipMalloc(&b.p, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return false;
+    };
+    bool ok = idx->compressed || (get(nx, want * ds * 4) && get(nsc, want * sizeof(float)));
+    if (ok && idx->xh) ok = get(nh, want * ds * eb);
+    if (ok && idx->tsc) ok = get(nts, (want / kTile8Rows) * kTscaleFloats * sizeof(float));
+    if (ok && idx->amean) ok = get(nam, want * sizeof(float));
+    if (!ok) return MX_OK;
+    const uint64_t used = round_up(idx->n, kTile8Rows);  // rows [n, used) were zeroed by the compaction
+    hipStream_t st = idx->stream;
+    auto move = [&](DevBuf &b, const void *old, size_t used_bytes, size_t all_bytes) -> hipError_t {
+        hipError_t e = used_bytes ? hipMemcpyAsync(b.p, old, used_bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && all_bytes > used_bytes) e = hipMemsetAsync(static_cast<char *>(b.p) + used_bytes, 0, all_bytes - used_bytes, st);
+        return e;
+    };
+    if (!idx->compressed) {
+        MX_HIP(move(nx, idx->x, used * ds * 4, want * ds * 4));
+        MX_HIP(move(nsc, idx->scale, used * sizeof(float), want * sizeof(float)));
+    }
+    if (nh.p) MX_HIP(move(nh, idx->xh, used * ds * eb, want * ds * eb));
+    if (nts.p) MX_HIP(move(nts, idx->tsc, (used / kTile8Rows) * kTscaleFloats * sizeof(float), (want / kTile8Rows) * kTscaleFloats * sizeof(float)));
+    if (nam.p) MX_HIP(move(nam, idx->amean, used * sizeof(float), want * sizeof(float)));
+    MX_HIP(hipStreamSynchronize(st));
+    auto swap = [](auto *&dst, DevBuf &b) {
+        if (!b.p) return;
+        if (dst) (void)hipFree(dst);
+        dst = static_cast<std::remove_reference_t<decltype(dst)>>(b.release());
+    };
+    swap(idx->x, nx);
+    swap(idx->scale, nsc);
+    if (nh.p) {
+        (void)hipFree(idx->xh);
+        idx->xh = nh.release();
+    }
+    swap(idx->tsc, nts);
+    swap(idx->amean, nam);
+    idx->cap = want;
+    return MX_OK;
+}
+
+// Compacts a plain index (or one shard) in place.  Everything that can fail without harm -- the plan, every allocation, the
+// device prefix checked against the host's count -- comes first; *moved turns true before the first row moves.
+int compact_plain(mx_index *idx, bool *moved) {
+    *moved = false;
+    DeviceGuard dg(idx->device);
+    hipStream_t st = idx->stream;
+    const uint64_t n = idx->n, tiles = (n + kTile8Rows - 1) / kTile8Rows, ds = (uint64_t)idx->ds;
+    if (!idx->dead || idx->dead_h.size() < tiles) return fail(MX_EDEVICE, "removal mask smaller than the index");
+    // live rows before every tile, on the host (the chunk plan) and on the device (the gather's destinations)
+    std::vector<uint64_t> hp((size_t)tiles + 1, 0);
+    uint64_t t_first = tiles;
+    for (uint64_t t = 0; t < tiles; ++t) {
+        const uint64_t r0 = t * kTile8Rows;
+        const uint64_t valid = n - r0 >= (uint64_t)kTile8Rows ? ~0ull : (1ull << (n - r0)) - 1ull;
+        const uint64_t live = ~idx->dead_h[t] & valid;
+        if (live != valid && t_first == tiles) t_first = t;
+        hp[t + 1] = hp[t] + (uint64_t)__builtin_popcountll(live);
+    }
+    const uint64_t n_live = hp[tiles];
+    if (n_live != n - idx->n_dead) return fail(MX_EDEVICE, "removal bookkeeping out of step (%llu live rows counted, %llu expected)",
+                                               (unsigned long long)n_live, (unsigned long long)(n - idx->n_dead));
+    if (idx->compressed) t_first = 0;  // the bf16 rows are re-ingested from the first: the zero-norm list is rebuilt whole
+    const uint32_t nb = compact_count_blocks(tiles);
+    DevBuf tb, bo, stage, wa, wb;
+    MX_HIP(hipMalloc(&tb.p, std::max<uint64_t>(tiles, 1) * sizeof(uint32_t)));
+    MX_HIP(hipMalloc(&bo.p, ((size_t)nb + 1) * sizeof(uint32_t)));
+    uint32_t *tile_base = static_cast<uint32_t *>(tb.p), *blk_off = static_cast<uint32_t *>(bo.p);
+    // staging of a chunk whose destination overlaps its source: 64 MiB of rows, a multiple of 64 rows
+    const uint64_t stage_tiles = std::max<uint64_t>(1, (64ull << 20) / (kTile8Rows * ds * 4));
+    constexpr uint64_t kWinTiles = 16384 / kTile8Rows;  // compressed corpus: rows widened per chunk (the append path's window holds 65536)
+    if (idx->compressed) {
+        MX_HIP(hipMalloc(&wa.p, (size_t)kWinTiles * kTile8Rows * idx->dim * sizeof(float)));
+        MX_HIP(hipMalloc(&wb.p, (size_t)kWinTiles * kTile8Rows * idx->dim * sizeof(float)));
+        if (!idx->xs) {
+            MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->xs), (size_t)(65536 + kTileRows) * idx->ds * sizeof(float)));
+            MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->ss), (size_t)(65536 + kTileRows) * sizeof(float)));
+            idx->xs_rows = 65536 + kTileRows;
+        }
+    } else {
+        MX_HIP(hipMalloc(&stage.p, (size_t)stage_tiles * kTile8Rows * (ds + 1) * sizeof(float)));
+    }
+    MX_HIP(launch_compact_prefix(st, idx->dead, n, tile_base, blk_off));
+    uint32_t dev_live = 0;
+    MX_HIP(hipMemcpyAsync(&dev_live, blk_off + nb, sizeof(dev_live), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    if (dev_live != n_live) return fail(MX_EDEVICE, "device removal mask out of step (%u live rows, %llu expected)", dev_live,
+                                        (unsigned long long)n_live);
+
+    *moved = true;  // ---- from here on rows move: an error leaves the index failed
+    if (!idx->compressed) {
+        float *sx = static_cast<float *>(stage.p), *ss = sx + stage_tiles * kTile8Rows * ds;
+        for (uint64_t t = t_first; t < tiles;) {
+            const uint64_t lag = t * kTile8Rows - hp[t];  // rows removed before tile t
+            uint64_t c;
+            if (lag >= stage_tiles * kTile8Rows) {
+                // every destination of the next lag / 64 tiles lies below their first source row: gather straight into place
+                c = std::min(tiles - t, lag / kTile8Rows);
+                MX_HIP(launch_compact_gather(st, idx->dead, n, t, c, tile_base, blk_off, idx->x + t * kTile8Rows * ds, idx->scale + t * kTile8Rows,
+                                             (int)ds, 0, idx->x, idx->scale));
+            } else {
+                c = std::min(tiles - t, stage_tiles);
+                MX_HIP(launch_compact_gather(st, idx->dead, n, t, c, tile_base, blk_off, idx->x + t * kTile8Rows * ds, idx->scale + t * kTile8Rows,
+                                             (int)ds, hp[t], sx, ss));
+                const uint64_t m = hp[t + c] - hp[t];
+                if (m) {
+                    MX_HIP(hipMemcpyAsync(idx->x + hp[t] * ds, sx, m * ds * sizeof(float), hipMemcpyDeviceToDevice, st));
+                    MX_HIP(hipMemcpyAsync(idx->scale + hp[t], ss, m * sizeof(float), hipMemcpyDeviceToDevice, st));
+                }
+            }
+            t += c;
+        }
+        // rows past the new end read as a fresh append leaves them: zeros
+        const uint64_t z1 = std::min<uint64_t>(round_up(n, kTile8Rows), idx->cap);
+        MX_HIP(hipMemsetAsync(idx->x + n_live * ds, 0, (z1 - n_live) * ds * sizeof(float), st));
+        MX_HIP(hipMemsetAsync(idx->scale + n_live, 0, (z1 - n_live) * sizeof(float), st));
+        // the side lists afresh in the new numbering: a list that had overflowed is complete again when the live rows fit
+        MX_HIP(hipMemsetAsync(idx->flags, 0, 2 * sizeof(uint32_t), st));
+        MX_HIP(hipMemsetAsync(idx->flags + 3, 0, 2 * sizeof(uint32_t), st));
+        MX_HIP(launch_relist(st, idx->x, idx->scale, n_live, idx->ds, idx->flags, idx->zero_rows, idx->wild_list));
+        idx->n = n_live;
+        idx->n_zero = 0;
+        idx->n_wild = 0;
+        uint32_t fl[5] = {0, 0, 0, 0, 0};
+        if (int rc = commit_ingest(idx, fl); rc != MX_OK) return rc;
+        // the filter copy over the compacted rows, of the kind and centring it had (a centred copy: around the live rows' mean)
+        if (idx->xh) {
+            MX_HIP(hipMemsetAsync(idx->flags + 2, 0, sizeof(uint32_t), st));
+            MX_HIP(hipMemsetAsync(idx->flags + 5, 0, sizeof(uint32_t), st));
+            const bool ctr = idx->centred && idx->amean && idx->mean && idx->msum;
+            if (ctr && n_live) MX_HIP(launch_mean_dir(st, idx->x, idx->scale, n_live, idx->ds, idx->msum, idx->mean));
+            const uint32_t t1 = (uint32_t)((n_live + kTileRows - 1) / kTileRows);
+            if (n_live) {
+                if (idx->filter_i8)
+                    MX_HIP(launch_shadow8(st, idx->x, idx->scale, idx->ds, 0, (uint32_t)round_up(t1, 2), n_live, idx->xh, idx->tsc, idx->flags + 2,
+                                          ctr ? idx->mean : nullptr, ctr ? idx->amean : nullptr, ctr ? idx->flags + 5 : nullptr));
+                else
+                    MX_HIP(launch_shadow(st, idx->x, idx->scale, idx->ds, 0, t1, idx->xh, idx->flags + 2, 0, 0, ~0ull, ctr ? idx->mean : nullptr,
+                                         ctr ? idx->amean : nullptr));
+            }
+        }
+    } else {
+        // the bf16 fragments are the only copy of the rows: per window, widen them (launch_unshadow), keep the live ones, and
+        // append those through the raw-ingest path behind the rows already moved -- how mx_index_load reproduces stored rows
+        float *wa_f = static_cast<float *>(wa.p), *wb_f = static_cast<float *>(wb.p);
+        MX_HIP(hipMemsetAsync(idx->flags + 2, 0, 3 * sizeof(uint32_t), st));
+        idx->n = 0;
+        idx->n_zero = 0;
+        idx->n_wild = 0;
+        idx->wild_rows = 0;
+        idx->raw_ingest = true;
+        int rc = MX_OK;
+        for (uint64_t t = 0; t < tiles && rc == MX_OK; t += kWinTiles) {
+            const uint64_t c = std::min(kWinTiles, tiles - t), r0 = t * kTile8Rows, rows = std::min(c * kTile8Rows, n - r0);
+            hipError_t e = launch_unshadow(st, idx->xh, idx->ds, idx->dim, r0, rows, wa_f);
+            if (e == hipSuccess) e = launch_compact_gather(st, idx->dead, n, t, c, tile_base, blk_off, wa_f, nullptr, idx->dim, hp[t], wb_f, nullptr);
+            if (e != hipSuccess) rc = fail(MX_EDEVICE, "compaction of the bf16 rows: %s", hipGetErrorString(e));
+            else rc = add_device_locked(idx, wb_f, hp[t + c] - hp[t], nullptr);
+        }
+        idx->raw_ingest = false;
+        if (rc != MX_OK) return rc;
+        // rows past the new end of its 32-row tile hold zeros, as a fresh append leaves them
+        const uint64_t z1 = round_up(n_live, kTileRows);
+        if (z1 > n_live) {
+            MX_HIP(hipMemsetAsync(idx->xs, 0, (size_t)kTileRows * ds * sizeof(float), st));
+            MX_HIP(hipMemsetAsync(idx->ss, 0, (size_t)kTileRows * sizeof(float), st));
+            const uint32_t tl = (uint32_t)(n_live / kTileRows);
+            MX_HIP(launch_shadow(st, idx->xs, idx->ss, idx->ds, tl, tl + 1, idx->xh, idx->flags + 2, tl, n_live, z1));
+        }
+    }
+    MX_HIP(hipStreamSynchronize(st));
+    // no row is removed any more: the launchers pass a null mask and run the unmasked kernels again
+    (void)hipFree(idx->dead);
+    idx->dead = nullptr;
+    idx->dead_h.clear();
+    idx->dead_h.shrink_to_fit();
+    idx->n_dead = 0;
+    // the doubling thresholds of the filter copy's promotion rules follow the rows they were set on
+    auto rescale = [&](uint64_t &v) {
+        if (v) v = std::max<uint64_t>(1, (uint64_t)((double)v * (double)n_live / (double)std::max<uint64_t>(n, 1)));
+    };
+    rescale(idx->demoted_at_rows);
+    rescale(idx->plain_bf16_rows);
+    return release_capacity(idx);
+}
+
+// Compacts a sharded handle: global row r lives on shard (r / R) % G, so compaction re-deals rows between shards.  New shards
+// (same devices and settings) take the live rows through the fetch and append paths in bounded chunks; they replace the old ones
+// only once complete, so a failure leaves the handle as it was.  Costs HBM for both sets of shards and a trip through host memory.
+int compact_composite(mx_index *idx) {
+    const uint64_t R = idx->block_rows, G = idx->shards.size(), total = idx->total;
+    std::unique_ptr<mx_index> fresh(new mx_index());  // a composite shell that composite_add fills
+    fresh->dim = idx->dim;
+    fresh->block_rows = R;
+    auto drop_fresh = [&] {
+        for (mx_index *sh : fresh->shards) free_index(sh);
+        fresh->shards.clear();
+    };
+    for (uint64_t g = 0; g < G; ++g) {
+        mx_index *old = idx->shards[g], *sh = nullptr;
+        int rc = open_plain("", idx->dim, old->device, &sh);
+        if (rc != MX_OK) {
+            drop_fresh();
+            return rc;
+        }
+        sh->idmap = old->idmap;
+        sh->mode = old->mode;
+        sh->profiling = old->profiling;
+        sh->scan8_pair = old->scan8_pair;
+        sh->want_filter = old->want_filter;
+        sh->filter_i8 = old->filter_i8;
+        sh->filter_auto = old->filter_auto;
+        sh->compressed = old->compressed;
+        sh->raw_ingest = old->compressed;  // stored values of a compressed corpus go back in unchanged
+        fresh->shards.push_back(sh);
+    }
+    const uint64_t chunk = std::max<uint64_t>(kTile8Rows, (32ull << 20) / ((uint64_t)idx->dim * 4));
+    std::vector<float> buf((size_t)std::min<uint64_t>(chunk, std::max<uint64_t>(total, 1)) * idx->dim), tmpv;
+    int rc = MX_OK;
+    for (uint64_t r0 = 0; r0 < total && rc == MX_OK; r0 += chunk) {
+        const uint64_t m = std::min(chunk, total - r0);
+        rc = fetch_rows(idx, r0, m, buf.data(), tmpv);
+        uint64_t k = 0;  // live rows of the chunk, packed to the front
+        for (uint64_t i = 0; i < m && rc == MX_OK; ++i) {
+            if (global_removed(idx, r0 + i)) continue;
+            if (k != i) memmove(buf.data() + k * idx->dim, buf.data() + i * idx->dim, (size_t)idx->dim * sizeof(float));
+            ++k;
+        }
+        if (rc == MX_OK && k) rc = composite_add(fresh.get(), buf.data(), k, nullptr, false);
+    }
+    for (mx_index *sh : fresh->shards) sh->raw_ingest = false;
+    if (rc != MX_OK) {
+        drop_fresh();
+        return rc;
+    }
+    std::swap(idx->shards, fresh->shards);
+    drop_fresh();  // (the old shards)
+    idx->total = fresh->total;
+    idx->n_dead = 0;
+    return MX_OK;
+}
+
+int usable(mx_index *idx) {
+    if (!idx->failed) return MX_OK;
+    return fail(MX_EDEVICE, "this index is unusable: a compaction failed after rows had moved (mx_index_clear or mx_index_load resets it)");
 }
 
 }  // namespace
@@ -2071,6 +2375,7 @@ int mx_index_n_shards(mx_index *idx, int *n) try {
 int mx_index_size(mx_index *idx, uint64_t *n) try {
     if (!idx || !n) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     *n = rows_of(idx);
     return MX_OK;
 } catch (...) {
@@ -2081,6 +2386,7 @@ int mx_index_remove(mx_index *idx, const uint64_t *ids, uint64_t n, uint64_t *n_
     if (n_removed) *n_removed = 0;
     if (!idx || (!ids && n)) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     const uint64_t size = rows_of(idx), off = idx->idmap.id_offset;
     std::vector<uint64_t> rows((size_t)n);
     for (uint64_t i = 0; i < n; ++i) {  // all ids are checked before anything changes
@@ -2100,7 +2406,51 @@ int mx_index_remove(mx_index *idx, const uint64_t *ids, uint64_t n, uint64_t *n_
 int mx_index_removed(mx_index *idx, uint64_t *n) try {
     if (!idx || !n) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     *n = idx->n_dead;
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_compact(mx_index *idx, uint64_t *kept_ids, uint64_t kept_cap, uint64_t *n_live) try {
+    if (n_live) *n_live = 0;
+    if (!idx) return fail(MX_EINVAL, "null index");
+    std::lock_guard<std::mutex> lk(idx->mu);  // the lock a combined search pass holds: searches see the old rows or the new ones
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    const uint64_t size = rows_of(idx), live = size - idx->n_dead, off = idx->idmap.id_offset;
+    if (kept_ids && kept_cap < live)
+        return fail(MX_EINVAL, "kept_ids holds %llu entries, %llu live rows; nothing changed", (unsigned long long)kept_cap, (unsigned long long)live);
+    if (kept_ids) {  // the id every new id had before, from the host copy of the removal masks
+        uint64_t k = 0;
+        for (uint64_t r = 0; r < size; ++r)
+            if (!idx->n_dead || !global_removed(idx, r)) kept_ids[k++] = off + r + 1;
+    }
+    if (idx->n_dead == 0) {  // nothing removed: the identity, the index and its disk state untouched
+        if (n_live) *n_live = size;
+        return MX_OK;
+    }
+    bool moved = false;
+    int rc;
+    if (idx->composite()) {
+        rc = compact_composite(idx);
+    } else {
+        rc = compact_plain(idx, &moved);
+        if (rc != MX_OK && moved) {
+            const std::string why = last_error_slot();
+            idx->failed = true;
+            return fail(MX_EDEVICE, "compaction failed after rows had moved (%s); the index is unusable until mx_index_clear or mx_index_load",
+                        why.c_str());
+        }
+    }
+    if (rc != MX_OK) return rc;
+    // the store on disk no longer matches: the next save rewrites it whole, in the next generation's formats
+    idx->gen += 1;
+    idx->n_dead = 0;
+    idx->dead_log.clear();
+    idx->disk_dead = 0;
+    idx->disk_dir.clear();
+    if (n_live) *n_live = rows_of(idx);
     return MX_OK;
 } catch (...) {
     return guard_exception();
@@ -2125,6 +2475,7 @@ static int reserve_locked(mx_index *idx, uint64_t rows) {
 int mx_index_reserve(mx_index *idx, uint64_t rows) try {
     if (!idx) return fail(MX_EINVAL, "null index");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     return reserve_locked(idx, rows);
 } catch (...) {
     return guard_exception();
@@ -2159,6 +2510,7 @@ int mx_index_wait_stream(mx_index *idx, void *stream) try {
 int mx_index_add_device(mx_index *idx, const float *d_rows, uint64_t n, uint64_t *first_id) try {
     if (!idx || (!d_rows && n)) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     if (idx->composite()) {
         {   // rows must be complete on shards[0]'s stream before other devices copy them
             DeviceGuard dg(idx->shards[0]->device);
@@ -2175,6 +2527,7 @@ int mx_index_add_device(mx_index *idx, const float *d_rows, uint64_t n, uint64_t
 int mx_index_add(mx_index *idx, const float *rows, uint64_t n, uint64_t *first_id) try {
     if (!idx || (!rows && n)) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     return add_host_locked(idx, rows, n, first_id);
 } catch (...) {
     return guard_exception();
@@ -2208,6 +2561,7 @@ int mx_index_search_device(mx_index *idx, const float *d_q, int B, int k, uint64
     if (k > 4096) return fail(MX_EUNSUPPORTED, "k = %d > 4096", k);
     std::lock_guard<std::mutex> lk(idx->mu);
     DeviceGuard g(idx->device);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
         const int nb = std::min(kMaxBatch, B - b0);
         int rc = any_batch(idx, d_q + (size_t)b0 * idx->dim, nb, k, d_ids + (size_t)b0 * k,
@@ -2225,6 +2579,7 @@ namespace {
 // pinned memory, one H2D, the search pipeline, one D2H per output array, results scattered to the callers
 int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
     DeviceGuard g(t->device);
     const int k = batch[0]->k;
@@ -2357,6 +2712,7 @@ int mx_index_set_filter_copy(mx_index *idx, int on) try {
     if (!idx) return fail(MX_EINVAL, "null index");
     if (on < 0 || on > 3) return fail(MX_EINVAL, "filter copy: 0 = none, 1 = kind chosen by the library, 2 = int8, 3 = bf16 (got %d)", on);
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     if (idx->composite()) {
         for (mx_index *sh : idx->shards) {
             int rc = mx_index_set_filter_copy(sh, on);
@@ -2430,6 +2786,7 @@ int mx_index_set_corpus_mode(mx_index *idx, int mode) try {
 int mx_index_get_rows(mx_index *idx, uint64_t first_row, uint64_t n, float *out) try {
     if (!idx || (!out && n)) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     if (first_row + n > rows_of(idx)) return fail(MX_EINVAL, "rows [%llu, %llu) outside the index", (unsigned long long)first_row,
                                                  (unsigned long long)(first_row + n));
     if (n == 0) return MX_OK;
@@ -2452,6 +2809,7 @@ int mx_index_set_profiling(mx_index *idx, int on) try {
 int mx_index_get_stats(mx_index *idx, mx_index_stats *out) try {
     if (!idx || !out) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     if (idx->composite()) {
         mx_index_stats acc = idx->stats;  // searches / queries are counted on the composite
         for (mx_index *sh : idx->shards) {
@@ -2520,6 +2878,7 @@ int mx_index_reset_stats(mx_index *idx) try {
 int mx_index_save(mx_index *idx, const char *dir) try {
     if (!idx || !dir) return fail(MX_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
     if (mkdir_p(dir) != 0) return fail(MX_EIO, "cannot create directory %s", dir);
     const uint64_t n = rows_of(idx);
     const std::string path = store_file(dir);
@@ -2539,7 +2898,7 @@ int mx_index_save(mx_index *idx, const char *dir) try {
         if (idx->disk_rows == n) return save_dead_file(idx, dir, true);  // no new rows; removals made since the last save, if any
         FILE *f = fopen(path.c_str(), "r+b");
         if (!f) return fail(MX_EIO, "cannot open %s for appending", path.c_str());
-        int rc = fseek(f, kHeaderBytes + (long)(idx->disk_rows * (uint64_t)idx->dim * 4), SEEK_SET) == 0 ? MX_OK : fail(MX_EIO, "seek in %s failed", path.c_str());
+        int rc = fseek(f, header_bytes(idx->gen) + (long)(idx->disk_rows * (uint64_t)idx->dim * 4), SEEK_SET) == 0 ? MX_OK : fail(MX_EIO, "seek in %s failed", path.c_str());
         if (rc == MX_OK) rc = write_rows(f, idx->disk_rows);
         // the header is patched last: a crash before this point leaves the old, consistent store
         if (rc == MX_OK && (fflush(f) != 0 || fseek(f, 16, SEEK_SET) != 0 || fwrite(&n, sizeof(n), 1, f) != 1))
@@ -2554,7 +2913,9 @@ int mx_index_save(mx_index *idx, const char *dir) try {
     FILE *f = fopen(tmp.c_str(), "wb");
     if (!f) return fail(MX_EIO, "cannot open %s for writing", tmp.c_str());
     uint32_t hdr[2] = {(uint32_t)idx->dim, is_compressed(idx) ? 1u : 0u};  // [1] = rows are the stored values of a compressed corpus
-    int rc = (fwrite(kMagic, 1, 8, f) == 8 && fwrite(hdr, sizeof(hdr), 1, f) == 1 && fwrite(&n, sizeof(n), 1, f) == 1)
+    // a compacted index writes MXFLAT02 with its generation: removal files of other generations beside it are stale
+    int rc = (fwrite(idx->gen ? kMagic2 : kMagic, 1, 8, f) == 8 && fwrite(hdr, sizeof(hdr), 1, f) == 1 && fwrite(&n, sizeof(n), 1, f) == 1 &&
+              (!idx->gen || fwrite(&idx->gen, sizeof(idx->gen), 1, f) == 1))
                  ? MX_OK : fail(MX_EIO, "write to %s failed", tmp.c_str());
     if (rc == MX_OK) rc = write_rows(f, 0);
     if (fclose(f) != 0 && rc == MX_OK) rc = fail(MX_EIO, "write to %s failed", tmp.c_str());
@@ -2575,35 +2936,34 @@ int mx_index_load(mx_index *idx, const char *dir) try {
     const std::string path = store_file(dir);
     FILE *f = fopen(path.c_str(), "rb");
     if (!f) return fail(MX_EIO, "cannot open %s", path.c_str());
-    char magic[8];
     uint32_t hdr[2];
-    uint64_t n = 0;
+    uint64_t n = 0, gen = 0;
     struct stat sb;
-    if (fread(magic, 1, 8, f) != 8 || memcmp(magic, kMagic, 8) != 0 || fread(hdr, sizeof(hdr), 1, f) != 1 ||
-        fread(&n, sizeof(n), 1, f) != 1 || fstat(fileno(f), &sb) != 0) {
+    if (!read_store_header(f, hdr, &n, &gen) || fstat(fileno(f), &sb) != 0) {
         fclose(f);
         return fail(MX_EIO, "%s: bad header", path.c_str());
     }
+    const long hbytes = header_bytes(gen);
     if ((int)hdr[0] != idx->dim) {
         fclose(f);
         return fail(MX_EIO, "%s holds dim %u, index has dim %d", path.c_str(), hdr[0], idx->dim);
     }
     // validate BEFORE touching the live contents: a truncated file must not destroy them
-    if (n > (UINT64_MAX - (uint64_t)kHeaderBytes) / ((uint64_t)idx->dim * 4) ||  // (a damaged row count must not wrap the product)
-        (uint64_t)sb.st_size < (uint64_t)kHeaderBytes + n * (uint64_t)idx->dim * 4) {
+    if (n > (UINT64_MAX - (uint64_t)hbytes) / ((uint64_t)idx->dim * 4) ||  // (a damaged row count must not wrap the product)
+        (uint64_t)sb.st_size < (uint64_t)hbytes + n * (uint64_t)idx->dim * 4) {
         fclose(f);
         return fail(MX_EIO, "%s: truncated (%lld bytes for %llu rows)", path.c_str(), (long long)sb.st_size, (unsigned long long)n);
     }
     // the removals beside it (vectors.mxdead), validated before anything changes as well
     std::vector<uint64_t> file_dead;
-    bool dead_present = false;
-    if (int drc = read_dead_file(dir, n, &file_dead, &dead_present); drc != MX_OK) {
+    bool dead_present = false, dead_stale = false;
+    if (int drc = read_dead_file(dir, n, gen, &file_dead, &dead_present, &dead_stale); drc != MX_OK) {
         fclose(f);
         return drc;
     }
     // get_vector_storage loads the store on every request (storage/mod.rs:115-116): when the resident
     // rows are exactly what this file holds, attaching is O(1) -- the removals are taken from the file unless they are its own
-    if (disk_in_sync(idx, dir) && idx->disk_rows == n && rows_of(idx) == n) {
+    if (disk_in_sync(idx, dir) && idx->disk_rows == n && rows_of(idx) == n && idx->gen == gen && !idx->failed) {
         fclose(f);
         if (file_dead != idx->dead_log) {
             uint64_t m = 0;
@@ -2612,10 +2972,11 @@ int mx_index_load(mx_index *idx, const char *dir) try {
             if (rc != MX_OK) return rc;
             idx->dead_log = file_dead;
         }
-        idx->disk_dead = dead_present ? file_dead.size() : 0;
+        idx->disk_dead = dead_stale ? kDeadStale : dead_present ? file_dead.size() : 0;
         return MX_OK;
     }
     clear_locked(idx);
+    idx->gen = gen;
     set_raw_ingest(idx, hdr[1] == 1);  // stored values of a compressed corpus go back in unchanged
     // Cold start (a collection after a restart): the file is read in 32 MB pieces into two PINNED buffers; a piece
     // goes to the device on a copy stream while the next one is being read and the previous one is ingested
@@ -2699,7 +3060,7 @@ int mx_index_load(mx_index *idx, const char *dir) try {
         }
     }
     idx->dead_log = file_dead;  // the file's entries as they stand (the next save appends behind them)
-    idx->disk_dead = file_dead.size();
+    idx->disk_dead = dead_stale ? kDeadStale : file_dead.size();
     remember_disk(idx, dir, n);
     return MX_OK;
 } catch (...) {
@@ -2719,11 +3080,9 @@ int mx_index_store_info(const char *dir, int *dim, uint64_t *n_rows) try {
     if (!dir || !dim || !n_rows) return fail(MX_EINVAL, "null argument");
     FILE *f = fopen(store_file(dir).c_str(), "rb");
     if (!f) return fail(MX_EIO, "cannot open %s", store_file(dir).c_str());
-    char magic[8];
     uint32_t hdr[2];
-    uint64_t n = 0;
-    const bool ok = fread(magic, 1, 8, f) == 8 && memcmp(magic, kMagic, 8) == 0 && fread(hdr, sizeof(hdr), 1, f) == 1 &&
-                    fread(&n, sizeof(n), 1, f) == 1;
+    uint64_t n = 0, gen = 0;
+    const bool ok = read_store_header(f, hdr, &n, &gen);  // MXFLAT01 or MXFLAT02
     fclose(f);
     if (!ok) return fail(MX_EIO, "%s: bad header", store_file(dir).c_str());
     *dim = (int)hdr[0];

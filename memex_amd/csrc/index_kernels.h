@@ -273,6 +273,21 @@ hipError_t launch_exact_group(hipStream_t s, int k, int ds, const float *x, cons
                               const float *qpad, const double *qnorm2, const ExactGroup &grp, void *scratch, uint64_t *ids,
                               float *scores, float *dists, int32_t *n_found, const uint64_t *dead = nullptr, uint64_t n_live = ~0ull);
 
+// compaction (compact.hip, mx_index_compact).  The destination of every live row comes from a two-level scan over the 64-row
+// tiles of the dead-row mask of an index of n rows: tile_base[t] = live rows before tile t within its block of
+// kCompactTilesPerBlock tiles, blk_off[b] = live rows before block b, blk_off[compact_count_blocks(tiles)] = all live rows.
+constexpr int kCompactTilesPerBlock = 1024;
+uint32_t compact_count_blocks(uint64_t tiles);
+hipError_t launch_compact_prefix(hipStream_t s, const uint64_t *dead, uint64_t n, uint32_t *tile_base, uint32_t *blk_off);
+// live rows of tiles [tile0, tile0 + tiles) -> dst rows (destination - dst0), W floats each (bitwise); src holds row 64 tile0
+// onwards; scale (optional) moves along.  dst may be the source array itself when no destination reaches an unread source row.
+hipError_t launch_compact_gather(hipStream_t s, const uint64_t *dead, uint64_t n, uint64_t tile0, uint64_t tiles, const uint32_t *tile_base,
+                                 const uint32_t *blk_off, const float *src, const float *src_scale, int W, uint64_t dst0, float *dst,
+                                 float *dst_scale);
+// f32 corpus rows [0, n): the zero-norm list and the out-of-range-norm list afresh (flags[3] / flags[4] count, zeroed by the caller)
+hipError_t launch_relist(hipStream_t s, const float *x, const float *scale, uint64_t n, int ds, uint32_t *flags, uint32_t *zero_rows,
+                         uint32_t *wild_rows);
+
 hipError_t launch_fill_nfound(hipStream_t s, int32_t *nf, int B, int32_t v);
 hipError_t launch_merge(hipStream_t s, const void *ids, size_t ids_stride, const void *dists, size_t dists_stride,
                         int G, int B, int k, uint64_t *out_ids, float *out_dists, float *out_scores);

@@ -176,6 +176,16 @@ class FlatIndex:
         check(lib().mx_index_removed(self._h, ctypes.byref(n)))
         return int(n.value)
 
+    def compact(self) -> np.ndarray:
+        """Drop the removed rows for good: the live rows keep their order and get dense ids again (the i-th gets
+        id_offset + i + 1).  -> uint64 [len(self) afterwards]: the id each new id had before.  Ids held from before the
+        call no longer name the same rows; the next save rewrites the store.  Nothing removed: the identity, a no-op."""
+        live = len(self) - self.removed
+        kept = np.zeros(max(live, 1), dtype=np.uint64)
+        n = ctypes.c_uint64(0)
+        check(lib().mx_index_compact(self._h, _ptr(kept), kept.size, ctypes.byref(n)))
+        return kept[: int(n.value)]
+
     # -- search --------------------------------------------------------------------------
     def search(self, queries, k: int):
         """-> (ids u64 [B,k], scores f32 [B,k], dists f32 [B,k], n_found i32 [B])."""

@@ -343,6 +343,32 @@ class HipFlatStore(VectorStore):
                 raise DeleteError(str(e)) from e
             return n
 
+    def compact(self) -> np.ndarray:
+        """Drop the rows ``remove`` took out for good (``FlatIndex.compact``): the live rows get dense ids again and
+        ``_id_map`` is renumbered to match (new id -> the ``_id`` of the id it replaces).  Saved before this returns, like
+        ``remove``: the index rewrites ``vectors.mxflat`` whole, then ``vectors.meta.json`` is rewritten through a
+        temporary file.  A crash between the two leaves an id map longer than the vectors (a compaction that removed
+        anything always shortens the store), which ``load`` rejects with ``FileIOError``: never a wrong id -> ``_id``
+        mapping.  Nothing removed: a no-op.  -> uint64 array, the id every new id had before."""
+        with self._lock:
+            if self._index is None or not self._id_map:
+                return np.zeros(0, dtype=np.uint64)
+            if self._index.removed == 0:
+                return np.arange(1, len(self._id_map) + 1, dtype=np.uint64)
+            try:
+                kept = self._index.compact()
+            except _lib.MemexHipError as e:
+                raise DeleteError(e.msg) from e
+            self._id_map = {i + 1: self._id_map[int(old)] for i, old in enumerate(kept)}
+            self._rows_of = None
+            self._meta_sig = None   # the id map is rewritten whole, never appended to
+            self._meta_ids = 0
+            try:
+                self.save()
+            except VectorStoreError as e:
+                raise DeleteError(str(e)) from e
+            return kept
+
     def bulk_insert(self, data: Sequence[VectorData]) -> None:
         """local.rs:55-69 semantics (ids in order, store persisted before returning), one device
         transfer and one incremental save instead of a save per vector."""
