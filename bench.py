@@ -17,19 +17,23 @@ N > 1: STRONG scaling on the same 10M-row corpus (north_star: "on a 10M x 384-d 
     rows [r*10M/N, (r+1)*10M/N) with global ids, every rank answers the same 256 queries on its shard, ONE
     `all_gather_into_tensor` of the packed blocks and the merge kernel give every rank the global answer.
 
-Printed JSON (ONE line on stdout, rank 0, printed last): metric/value/unit per the contract + `roofline` +
-`cpu_baseline`.  EVERY roofline claim of DESIGN.md sits inside `roofline` so that the driver's record alone lets a
-reader recompute it: the headline collect-scan kernel (bytes per launch / HIP-event time of the kernel on the
-library's stream / 8 TB/s), `section_8d_kernel` (the scan over the f32 rows themselves: SURVEY 8(d)'s N*D*4 bytes
-literally), `encoder_minilm` / `encoder_bge` (BASELINE configs[4] and the configs[3] model: 512-token chunks,
-GFLOP per chunk x chunks/s / 2.5 PFLOP/s), `encoder_minilm_128tok` (all-MiniLM-L12-v2, the reference's default
-model, at its own 128-token window) and `encoder_split_modes` (MX_PREC_BF16X3 / MX_PREC_MIXED: the modes that hold
-north_star's 1e-3 on scores, with the bf16 mode's score error beside them).  `cpu_baseline` (rank 0 at N = 1 only): the C oracle's exact brute force on all host cores, the
-reference's real algorithm -- HNSW with memex's parameters, one search thread, its recall@10 -- at 100k rows and
-(time-bounded) at up to 1M rows, and the encoder's CPU proxies.  The side legs (clustered / anisotropic corpora,
-host API, concurrent callers, small batches, query latency, configs[3]'s shard, the 1/8 shards, enc_like_10M,
-cfg2, text ingest) go to a SECOND file (`--sides-out`, default gpurun_out/bench_sides.json or ./bench_sides.json)
-and to stderr; the stdout line carries a compact `sides` summary of them.
+A plain run does only what the headline figure needs: it builds the corpus, warms up, times the --steps steps, writes
+--dump-outputs if asked and prints ONE JSON line on stdout (rank 0, last): metric/value/unit per the contract and the
+headline collect-scan kernel's `roofline` (bytes per launch / HIP-event time of the kernel on the library's stream /
+8 TB/s), read from the counters of the timed steps themselves.
+
+`--full` adds everything else, after the headline and without changing it.  EVERY roofline claim of DESIGN.md then sits
+inside `roofline` so that the driver's record alone lets a reader recompute it: `section_8d_kernel` (the scan over the
+f32 rows themselves: SURVEY 8(d)'s N*D*4 bytes literally), `other_filter_copy`, `encoder_minilm` / `encoder_bge`
+(BASELINE configs[4] and the configs[3] model: 512-token chunks, GFLOP per chunk x chunks/s / 2.5 PFLOP/s),
+`encoder_minilm_128tok` (all-MiniLM-L12-v2, the reference's default model, at its own 128-token window) and
+`encoder_split_modes` (MX_PREC_BF16X3 / MX_PREC_MIXED: the modes that hold north_star's 1e-3 on scores, with the bf16
+mode's score error beside them).  `recall_at_10` compares the headline's answers with the library's EXACT path on a few
+queries (N > 1: `merged_lists_ok`).  `cpu_baseline` (rank 0 at N = 1 only): the C oracle's exact brute force on all host
+cores, the reference's real algorithm -- HNSW with memex's parameters, one search thread, its recall@10 -- at 100k rows
+and (time-bounded) at up to 1M rows, and the encoder's CPU proxies.  The side legs (clustered / anisotropic corpora,
+host API, concurrent callers, small batches, query latency, configs[3]'s shard, the 1/8 shards, enc_like_10M, cfg2,
+text ingest) go to a SECOND file (`--sides-out`) and to stderr; the stdout line carries a compact `sides` summary of them.
 """
 from __future__ import annotations
 
@@ -50,7 +54,7 @@ MFMA_PEAK_I8_TOPS = 5000.0  # dense int8 (2x the bf16 rate, same guide)
 BLOCK = 1_000_000          # the corpus is defined by GLOBAL 1M-row blocks: every N sees the same rows
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -63,40 +67,45 @@ def parse():
                     help="rows of the headline corpus: i.i.d. N(0,1) (BASELINE's synthetic corpus) or clustered")
     ap.add_argument("--scan", choices=["i8", "bf16", "f32"], default="i8",
                     help="what the scan kernel streams: the int8 filter copy, the bf16 filter copy or the f32 rows")
-    ap.add_argument("--alt-steps", type=int, default=20,
-                    help="N=1 only: extra steps on the OTHER scan kernel, reported beside the main one (0 = skip)")
-    ap.add_argument("--side-steps", type=int, default=20,
-                    help="N=1 only: steps of each side leg (clustered data, host API, 10M x 768 shard); 0 = skip them")
-    ap.add_argument("--small-steps", type=int, default=None,
-                    help="N=1 only: steps of the 1-query and 32-query legs (default: --side-steps; 0 = skip, e.g. under a "
-                         "profiler, where their much shorter launches of the same kernel would blur its average)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the brute-force baseline sample")
-    ap.add_argument("--hnsw-rows", type=int, default=100_000, help="corpus size of the HNSW CPU baseline (0 = skip)")
-    ap.add_argument("--hnsw-big-rows", type=int, default=1_000_000,
-                    help="a second, larger HNSW CPU baseline on the clustered corpus (0 = skip); its rows are cut so that the parallel "
-                         "graph build, extrapolated from the first run's, fits --hnsw-big-seconds")
-    ap.add_argument("--hnsw-big-seconds", type=float, default=100.0)
-    ap.add_argument("--short-seqs", type=int, default=131_072, help="N=1 only: 128-token sequences of the all-MiniLM-L12-v2 leg (0 = skip)")
-    ap.add_argument("--sides-out", default=None, help="file for the side legs' full reports (default: gpurun_out/bench_sides.json or ./bench_sides.json)")
-    ap.add_argument("--recall-queries", type=int, default=4, help="queries re-answered on the EXACT path")
-    ap.add_argument("--ingest-chunks", type=int, default=262_144, help="512-token chunks per GPU for the ingest leg (0 = skip)")
-    ap.add_argument("--bge-chunks", type=int, default=24_576, help="N=1 only: 512-token chunks of the bge-base-en ingest leg (0 = skip)")
-    ap.add_argument("--cfg2-segments", type=int, default=100_000, help="N=1 only: segments of the configs[1] end-to-end leg (0 = skip)")
-    ap.add_argument("--precise-chunks", type=int, default=16384, help="N=1 only: 512-token chunks of the MX_PREC_BF16X3 ingest leg (a quarter of them for bge-base; 0 = skip)")
-    ap.add_argument("--text-docs", type=int, default=200, help="N=1 only: documents of the text-ingest leg (segmenter + encoder + add; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg, check and baseline (see below); a plain run does only "
+                         "what the headline figure needs")
+    legs = ap.add_argument_group("legs of a --full run", "ignored without --full")
+    legs.add_argument("--alt-steps", type=int, default=20,
+                      help="N=1 only: extra steps on the OTHER scan kernel, reported beside the main one (0 = skip)")
+    legs.add_argument("--side-steps", type=int, default=20,
+                      help="N=1 only: steps of each side leg (clustered data, host API, 10M x 768 shard); 0 = skip them")
+    legs.add_argument("--small-steps", type=int, default=None,
+                      help="N=1 only: steps of the 1-query and 32-query legs (default: --side-steps; 0 = skip, e.g. under a "
+                           "profiler, where their much shorter launches of the same kernel would blur its average)")
+    legs.add_argument("--no-cpu-baseline", action="store_true")
+    legs.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the brute-force baseline sample")
+    legs.add_argument("--hnsw-rows", type=int, default=100_000, help="corpus size of the HNSW CPU baseline (0 = skip)")
+    legs.add_argument("--hnsw-big-rows", type=int, default=1_000_000,
+                      help="a second, larger HNSW CPU baseline on the clustered corpus (0 = skip); its rows are cut so that the parallel "
+                           "graph build, extrapolated from the first run's, fits --hnsw-big-seconds")
+    legs.add_argument("--hnsw-big-seconds", type=float, default=100.0)
+    legs.add_argument("--short-seqs", type=int, default=131_072, help="N=1 only: 128-token sequences of the all-MiniLM-L12-v2 leg (0 = skip)")
+    legs.add_argument("--sides-out", default=None, help="file for the side legs' full reports (default: bench_sides.json in the working directory, "
+                                                      "or in the tree's output folder when there is one)")
+    legs.add_argument("--recall-queries", type=int, default=4, help="queries re-answered on the EXACT path")
+    legs.add_argument("--ingest-chunks", type=int, default=262_144, help="512-token chunks per GPU for the ingest leg (0 = skip)")
+    legs.add_argument("--bge-chunks", type=int, default=24_576, help="N=1 only: 512-token chunks of the bge-base-en ingest leg (0 = skip)")
+    legs.add_argument("--cfg2-segments", type=int, default=100_000, help="N=1 only: segments of the configs[1] end-to-end leg (0 = skip)")
+    legs.add_argument("--precise-chunks", type=int, default=16384, help="N=1 only: 512-token chunks of the MX_PREC_BF16X3 ingest leg (a quarter of them for bge-base; 0 = skip)")
+    legs.add_argument("--text-docs", type=int, default=200, help="N=1 only: documents of the text-ingest leg (segmenter + encoder + add; 0 = skip)")
     ap.add_argument("--min-seconds", type=float, default=0.5,
                     help="untimed steps of the same work run in front of every timed region until this much time has passed: the "
                          "package needs ~0.7 s of continuous load to settle at its power-capped clock (profiles/r3_power_scan8.log), "
                          "and 20 steps are 26 ms.  The timed region itself stays EXACTLY --steps steps.  0 = off")
-    ap.add_argument("--shard-legs", type=int, default=1, help="N=1 only: the 1.25M-row legs (what each of 8 GPUs runs for configs[2] / [3]); 0 = skip")
-    ap.add_argument("--enc-like-rows", type=int, default=10_000_000, help="N=1 only: rows of the leg built from encoder outputs (0 = skip)")
+    legs.add_argument("--shard-legs", type=int, default=1, help="N=1 only: the 1.25M-row legs (what each of 8 GPUs runs for configs[2] / [3]); 0 = skip")
+    legs.add_argument("--enc-like-rows", type=int, default=10_000_000, help="N=1 only: rows of the leg built from encoder outputs (0 = skip)")
     ap.add_argument("--no-fallback", action="store_true", help="N>1: do not try the other multi-GPU form when this one fails")
     ap.add_argument("--per-process", action="store_true",
                     help="N>1: insist on the one-process-per-GPU form (must be started by torch.distributed.run)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the headline's last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1112,7 +1121,8 @@ def run(a):
     exchange = idx.exchange
     alt = None
     f32_leg = None
-    single = world == 1 and not in_library
+    # everything from here to the result line runs only with --full: the headline figure needs none of it
+    single = a.full and world == 1 and not in_library   # (the N = 1 legs)
     if single and a.alt_steps > 0:
         # the same job on the other scan kernels (results must be identical: same certificate, same rescoring): the bf16
         # filter copy, and the f32 rows themselves -- the kernel SURVEY 8(d)'s N*D*4 bytes per pass describe literally
@@ -1127,7 +1137,8 @@ def run(a):
         alt = next(iter(legs.values()), None)
         idx.set_filter_copy({"f32": False, "bf16": "bf16", "i8": "i8"}[a.scan])
         step()
-    lap("other_scan + f32_rows")
+    if a.full:
+        lap("other_scan + f32_rows")
     host_api = None
     if single and a.side_steps > 0:
         # the entry point the Rust shim binds: host pointers in and out (queries H2D, results D2H inside the step)
@@ -1176,7 +1187,7 @@ def run(a):
     # ---- recall@10 against the all-f64 EXACT path on a few queries (oracle-level parity at smaller
     # sizes and the oracle-based 10M check live in tests/; the EXACT path is itself oracle-checked there)
     recall = recall_exact_order = merged_ok = None
-    if rank == 0 and a.recall_queries > 0:
+    if a.full and rank == 0 and a.recall_queries > 0:
         nq = min(a.recall_queries, a.batch)
         final_ids = (m_ids if world > 1 else bufs.ids)[:nq].clone()
         if world == 1:  # (on the in-library sharded index too: the EXACT mode reaches every shard)
@@ -1257,7 +1268,7 @@ def run(a):
                 sides["text_ingest"] = {"error": repr(e)[:300]}
             lap("text_ingest (incl. its CPU baseline)")
     ingest = None
-    if a.ingest_chunks > 0:
+    if a.full and a.ingest_chunks > 0:
         ingest = ingest_leg(a.ingest_chunks, dev, world, not a.no_cpu_baseline, devices=shard_devs if in_library and not one_device else None)
     ingest_bge = ingest_short = None
     if single and a.bge_chunks > 0:
@@ -1265,7 +1276,8 @@ def run(a):
     if single and a.short_seqs > 0:
         # the reference's default model at ITS window (embedding.rs:64-73: all-MiniLM-L12-v2, max_seq_length 128)
         ingest_short = ingest_leg(a.short_seqs, dev, 1, False, model="all-MiniLM-L12-v2", seq=128)
-    lap("ingest + ingest_bge_base + 128-token leg (incl. their CPU baselines)")
+    if a.full:
+        lap("ingest + ingest_bge_base + 128-token leg (incl. their CPU baselines)")
 
     if rank == 0:
         n_gpus = world * shards
@@ -1277,6 +1289,7 @@ def run(a):
             "n_gpus": n_gpus,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,   # the legs, checks and baselines beyond the headline ran (their keys below are None / absent otherwise)
             "settle_steps": settle_steps,   # untimed steps of the same work in front of the timed region (--min-seconds)
             "ms_per_step": dt / a.steps * 1e3,
             "higher_is_better": True,
@@ -1385,14 +1398,20 @@ def run(a):
         dist.destroy_process_group()
 
 
+def _forwarded_args(a):
+    """The options of `a` as a child's command line, plus --no-fallback (the child must not switch forms again)."""
+    switches = ("no_cpu_baseline", "full")   # store_true: forwarded by name, never as --x=False
+    args = [f"--{k.replace('_', '-')}={v}" for k, v in vars(a).items()
+            if k not in ("per_process", "no_fallback", "small_steps") + switches and v is not None]
+    return args + ["--no-fallback"] + [f"--{k.replace('_', '-')}" for k in switches if getattr(a, k)]
+
+
 def _other_form(a, err: str):
     """N > 1 and this form failed: run the OTHER multi-GPU form in a child process and relay its line, so that a first
     8-GPU run yields a measurement whichever form the node supports.  Returns the child's return code."""
     import subprocess
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    args = [f"--{k.replace('_', '-')}={v}" for k, v in vars(a).items()
-            if k not in ("per_process", "no_fallback", "no_cpu_baseline", "small_steps") and v is not None]
-    args += ["--no-fallback"] + (["--no-cpu-baseline"] if a.no_cpu_baseline else [])
+    args = _forwarded_args(a)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK",
                                                             "ROLE_RANK", "ROLE_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                                                             "TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT", "TORCHELASTIC_MAX_RESTARTS")}

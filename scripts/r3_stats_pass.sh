@@ -4,7 +4,7 @@
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/stats_r3; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python $ROOT/bench.py --ingest-chunks 0 --no-cpu-baseline --steps 50 --warmup 10 --alt-steps 20 --side-steps 20 --small-steps 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python $ROOT/bench.py --full --ingest-chunks 0 --no-cpu-baseline --steps 50 --warmup 10 --alt-steps 20 --side-steps 20 --small-steps 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log"
 F=$(find "$OUT/stats" -name "*kernel_stats.csv" | head -1)
 cp "$F" "$OUT/r3_bench_kernel_stats.csv"
 grep "^{" "$OUT/bench_under_rocprof.json" | tail -1 > "$OUT/r3_bench_under_rocprof.json"
