@@ -179,6 +179,27 @@ int mx_index_search(mx_index *idx, const float *queries, int B, int k, uint64_t 
 int mx_index_search_device(mx_index *idx, const float *d_queries, int B, int k, uint64_t *d_ids,
                            float *d_scores, float *d_dists, int32_t *d_n_found);
 
+/*
+ * Filtered search: the exact top-k among the rows whose ids lie in caller-given ranges (searching within one document, one
+ * tenant, one ingest window: process_embeddings inserts a document's segments in one call, so each document is one run of ids).
+ * `ranges` holds n_ranges pairs [lo, hi) of ids as search returns them (id_offset applied), in any order, overlapping or
+ * repeated; on the _device variant it is HOST memory, like every other argument but the queries and the outputs.  Ids outside
+ * [id_offset + 1, id_offset + size] select nothing (a filter is a predicate, not an id list to check).  n_ranges = 0 is the empty
+ * set: n_found = 0 for every query ("no filter" is mx_index_search).  lo > hi in any pair, or ranges == NULL with n_ranges > 0:
+ * MX_EINVAL and nothing is searched (checked before the other arguments; then the codes of mx_index_search).
+ * The answer is bit-identical to mx_index_search on an index holding only the allowed rows that have not been removed, reported
+ * under their own ids: ordered by (dist, id), n_found[b] = min(k, allowed live rows), unused slots id 0 / score 0 / dist +inf,
+ * k <= 4096, non-finite queries rejected, B split as there.  A filter covering every id gives what mx_index_search gives.
+ * Concurrent host-pointer calls are combined like mx_index_search's, but a pass takes requests only when k and the normalised
+ * (sorted, merged) ranges are equal, and never mixes filtered with unfiltered requests.  Filtered passes do not count towards the
+ * filter copy's demotion / promotion.  Few allowed rows (at most 16384) are scored directly by a subset kernel, more by the
+ * masked scan over the span of tiles the ranges touch.
+ */
+int mx_index_search_filtered(mx_index *idx, const float *queries, int B, int k, const uint64_t *ranges, uint64_t n_ranges,
+                             uint64_t *ids, float *scores, float *dists, int32_t *n_found);
+int mx_index_search_filtered_device(mx_index *idx, const float *d_queries, int B, int k, const uint64_t *ranges, uint64_t n_ranges,
+                                    uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_n_found);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */
@@ -262,6 +283,8 @@ typedef struct mx_index_stats {
     double exchange_ms;         /* sharded index: host time from "every shard has answered" to "merged result complete" (the
                                    all-gather or peer copies' tail, merge_kernel, n_found, one synchronise): the serial tail of
                                    a step that the shards' own work does not hide                                           */
+    uint64_t filtered_queries;  /* queries served by mx_index_search_filtered[_device]                                          */
+    uint64_t subset_queries;    /* ... of them answered by the subset kernel (few allowed rows: no scan)           */
 } mx_index_stats;
 /* sizeof(mx_index_stats) of the library that is loaded: a shim compares it with its own at start-up (the struct grows
  * at the end from version to version; mx_version() names the release). */

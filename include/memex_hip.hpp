@@ -23,6 +23,7 @@
 #pragma once
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
@@ -350,6 +351,52 @@ class HipFlatStore : public VectorStore {
         for (int j = 0; j < nf; ++j) {
             auto it = _id_map.find((size_t)ids[j]);
             if (it == _id_map.end())  // local.rs:80-83 panics; we raise
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.emplace_back(it->second, scores[j]);
+        }
+        return out;
+    }
+
+    // search() restricted to the rows inserted under the given _id strings (mx_index_search_filtered): the _ids go through the map
+    // remove() builds, their ids into sorted runs (a document's segments are inserted in one call: one run per document).  An
+    // unknown _id selects nothing; nothing selected -> no results.
+    std::vector<VectorSearchResult> search_within(const std::vector<float> &vec, size_t limit, const std::vector<std::string> &ids) {
+        std::vector<VectorSearchResult> out;
+        std::vector<uint64_t> rows;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0 || _id_map.empty()) return out;
+            if (!rows_of_built_) {
+                for (auto &kv : _id_map) rows_of_[kv.second].push_back(kv.first);
+                rows_of_built_ = true;
+            }
+            std::set<std::string> seen;
+            for (auto &id : ids) {
+                if (!seen.insert(id).second) continue;
+                auto it = rows_of_.find(id);
+                if (it != rows_of_.end()) rows.insert(rows.end(), it->second.begin(), it->second.end());
+            }
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        std::sort(rows.begin(), rows.end());
+        std::vector<uint64_t> ranges;  // [lo, hi) pairs of consecutive ids
+        for (size_t i = 0; i < rows.size();) {
+            size_t j = i + 1;
+            while (j < rows.size() && rows[j] <= rows[j - 1] + 1) ++j;
+            ranges.push_back(rows[i]);
+            ranges.push_back(rows[j - 1] + 1);
+            i = j;
+        }
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        int32_t nf = 0;
+        int rc = mx_index_search_filtered(idx_, vec.data(), 1, (int)limit, ranges.empty() ? nullptr : ranges.data(), ranges.size() / 2,
+                                          found.data(), scores.data(), nullptr, &nf);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
                 throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
             out.emplace_back(it->second, scores[j]);
         }

@@ -162,6 +162,7 @@ struct SearchReq {
     uint64_t *ids;
     float *scores, *dists;
     int32_t *n_found;
+    const std::vector<std::pair<uint64_t, uint64_t>> *filt = nullptr;  // mx_index_search_filtered: the normalised id ranges
     int rc = MX_OK;
     std::string err;
     bool done = false;
@@ -235,6 +236,15 @@ struct mx_index {
     // and the 01 formats).  `failed`: a compaction met a device error after rows had moved; every call fails until clear / load
     uint64_t gen = 0;
     bool failed = false;
+    // filtered search (mx_index_search_filtered): the per-call mask -- dead words | rows outside the filter, [cap / 64]
+    // words, reallocated when the capacity grows past it and rewritten by filter_mask_kernel before every masked pass -- the
+    // device copy of the local ranges it is built from, and the row list of the subset kernel ([kSubsetCap])
+    uint64_t *filt = nullptr;
+    size_t filt_words = 0;
+    uint64_t *filt_ranges = nullptr;
+    size_t filt_ranges_cap = 0;     // pairs
+    uint32_t *subset_rows = nullptr;
+    bool last_subset = false;       // the last search_batch answered on the subset kernel
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -322,7 +332,7 @@ int free_index(mx_index *idx) {
         if (p) (void)hipFree(p);
     };
     F(idx->x); F(idx->scale); F(idx->xh); F(idx->tsc); F(idx->flags); F(idx->xs); F(idx->ss); F(idx->zero_rows); F(idx->wild_list);
-    F(idx->amean); F(idx->mean); F(idx->msum); F(idx->dead);
+    F(idx->amean); F(idx->mean); F(idx->msum); F(idx->dead); F(idx->filt); F(idx->filt_ranges); F(idx->subset_rows);
     Scratch &s = idx->s;
     F(s.qfrag); F(s.qpad); F(s.qnorm2); F(s.theta); F(s.theta_retry); F(s.todo); F(s.dev_flags); F(s.done_ctr);
     if (s.host_flags) (void)hipHostFree(s.host_flags);
@@ -780,8 +790,9 @@ uint32_t sample_stride(uint64_t full_tiles, int nwg, int k, bool filt8, int ds, 
 
 constexpr size_t kExactKeepBytes = 256ull << 20;  // EXACT-path scratch kept between batches up to this size
 
+// mask: removed rows, or the per-call mask of a filtered search (null: none); n_live: rows it leaves
 int run_exact(mx_index *idx, const std::vector<int> &qs, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
-              int32_t *d_nfound) {
+              int32_t *d_nfound, const uint64_t *mask, uint64_t n_live) {
     if (qs.empty()) return MX_OK;
     int gcap = qs.size() <= 4 ? 4 : qs.size() <= 8 ? 8 : qs.size() <= 16 ? 16 : kExactGroup;
     int rc = ensure_exact(idx, k, &gcap);
@@ -794,8 +805,7 @@ int run_exact(mx_index *idx, const std::vector<int> &qs, int k, uint64_t *d_ids,
         grp.n = (int)std::min<size_t>((size_t)gcap, qs.size() - g0);
         for (int j = 0; j < grp.n; ++j) grp.q[j] = qs[g0 + j];
         MX_HIP(launch_exact_group(idx->stream, k, idx->ds, idx->compressed ? nullptr : idx->x, idx->xh, idx->n, idx->idmap, s.qpad,
-                                  s.qnorm2, grp, s.exact_scratch, d_ids, d_scores, d_dists, d_nfound, idx->n_dead ? idx->dead : nullptr,
-                                  idx->n - idx->n_dead));
+                                  s.qnorm2, grp, s.exact_scratch, d_ids, d_scores, d_dists, d_nfound, mask, n_live));
     }
     return MX_OK;
 }
@@ -873,14 +883,130 @@ int demote_filter(mx_index *idx) {
     return rc;
 }
 
-// one batch (B <= 256) with queries and outputs on the device
+// ---- filtered search (mx_index_search_filtered) ------------------------------------------------------------------
+// half-open [lo, hi) ranges of ids or of rows
+using Ranges = std::vector<std::pair<uint64_t, uint64_t>>;
+
+// sorted by lo, overlapping and adjacent ranges merged, empty ones dropped
+void normalise_ranges(Ranges &r) {
+    std::sort(r.begin(), r.end());
+    size_t m = 0;
+    for (const auto &x : r) {
+        if (x.first >= x.second) continue;
+        if (m && x.first <= r[m - 1].second) r[m - 1].second = std::max(r[m - 1].second, x.second);
+        else r[m++] = x;
+    }
+    r.resize(m);
+}
+
+// normalised id ranges -> the rows [0, n) they select (row = id - id_offset - 1), still normalised
+Ranges rows_of_ids(const Ranges &ids, uint64_t off, uint64_t n) {
+    Ranges out;
+    for (const auto &x : ids) {
+        const uint64_t lo = x.first > off ? x.first - off - 1 : 0, hi = std::min(x.second > off ? x.second - off - 1 : 0, n);
+        if (lo < hi) out.emplace_back(lo, hi);
+    }
+    return out;
+}
+
+// Global rows of a sharded handle -> the local rows of shard g.  Rows are dealt in blocks of R (global row r: block b = r / R, on
+// shard b % G, local row (b / G) R + r % R), so the blocks of shard g inside a global range [lo, hi) -- b1, b1 + G, ..., b2 -- are
+// consecutive local blocks b1 / G .. b2 / G: one global range is at most ONE local range per shard, from the local row of its first
+// row on the shard to that of its last.  The mapping is monotone, so sorted ranges stay sorted.
+Ranges shard_ranges(const Ranges &glob, uint64_t R, uint64_t G, uint64_t g) {
+    Ranges out;
+    for (const auto &x : glob) {
+        const uint64_t b_lo = x.first / R, b_hi = (x.second - 1) / R;
+        const uint64_t b1 = b_lo + (g + G - b_lo % G) % G;  // first block of shard g at or after b_lo
+        if (b1 > b_hi) continue;
+        const uint64_t b2 = b_hi - (b_hi % G + G - g) % G;  // last one at or before b_hi
+        const uint64_t first = std::max(x.first, b1 * R), last = std::min(x.second - 1, b2 * R + R - 1);
+        out.emplace_back((b1 / G) * R + first % R, (b2 / G) * R + last % R + 1);
+    }
+    normalise_ranges(out);  // (adjacent local ranges join)
+    return out;
+}
+
+// rows of the (clipped) ranges that are not removed: a popcount over the host copy of the dead-row words
+uint64_t count_allowed(const mx_index *t, const Ranges &r) {
+    uint64_t c = 0;
+    for (const auto &x : r) {
+        c += x.second - x.first;
+        if (!t->n_dead) continue;
+        for (uint64_t w = x.first >> 6; w * 64 < x.second; ++w) {
+            uint64_t bits = t->dead_h[w];
+            const uint64_t a = std::max(x.first, w * 64) - w * 64, b = std::min(x.second, w * 64 + 64) - w * 64;
+            bits &= (b == 64 ? ~0ull : (1ull << b) - 1ull) & ~((1ull << a) - 1ull);
+            c -= (uint64_t)__builtin_popcountll(bits);
+        }
+    }
+    return c;
+}
+
+// the per-call mask of a masked pass over the ranges (clipped to the rows): every word of the capacity (the zero-query walk and
+// the EXACT path read them all), dead words included when the index has removals
+int build_filter_mask(mx_index *idx, const Ranges &r, std::vector<uint64_t> &flat) {
+    const size_t words = (size_t)(idx->cap / kTile8Rows);
+    if (idx->filt_words < words) {
+        if (idx->filt) (void)hipFree(idx->filt);  // (every batch before this one is host-synchronised)
+        idx->filt = nullptr;
+        idx->filt_words = 0;
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->filt), words * sizeof(uint64_t)));
+        idx->filt_words = words;
+    }
+    if (idx->filt_ranges_cap < std::max<size_t>(r.size(), 1)) {
+        if (idx->filt_ranges) (void)hipFree(idx->filt_ranges);
+        idx->filt_ranges = nullptr;
+        idx->filt_ranges_cap = 0;
+        const size_t want = std::max<size_t>(r.size() + r.size() / 2, 64);
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->filt_ranges), want * 2 * sizeof(uint64_t)));
+        idx->filt_ranges_cap = want;
+    }
+    flat.resize(2 * r.size());
+    for (size_t i = 0; i < r.size(); ++i) {
+        flat[2 * i] = r[i].first;
+        flat[2 * i + 1] = r[i].second;
+    }
+    if (!flat.empty())
+        MX_HIP(hipMemcpyAsync(idx->filt_ranges, flat.data(), flat.size() * sizeof(uint64_t), hipMemcpyHostToDevice, idx->stream));
+    MX_HIP(launch_filter_mask(idx->stream, idx->n_dead ? idx->dead : nullptr, idx->filt_ranges, (uint32_t)r.size(), words, idx->filt));
+    return MX_OK;
+}
+
+// Which path answers a filtered batch of B queries whose ranges leave m <= kSubsetCap rows over a span of span_rows rows
+// (MEMEX_HIP_DEBUG=filt_subset=0|1 forces one).  A cost model fitted to profiles/filtered_10Mx384.txt (int8 copy, 384 dims,
+// k = 10):
+//   subset kernel     43 us + 0.053 us per row at 384 dims, whatever B up to 256 (one workgroup per query, each a chain of
+//                     m / 1024 rows per thread: latency-bound, so B = 1 costs what B = 256 does); once more per further 256 queries
+//   masked pipeline   75 us of fixed launches + the scan of the span: 0.065 ns per int8 byte at B <= 128, 0.10 ns above
+// The kernel wins for scattered rows (the span is the collection) up to the cap, and for a contiguous run up to ~600 rows.
+bool subset_pays(const mx_index *idx, int B, uint64_t m, uint64_t span_rows, int bytes_per_elem) {
+    if (m > (uint64_t)kSubsetCap || idx->ds > kMaxKC16 * kChunkFloats) return false;
+    const int force = debug_flag("filt_subset", -1);
+    if (force == 0 || force == 1) return force == 1;
+    const double w = (double)idx->ds / 384.0;
+    const double subset_us = (double)((B + kPassBatch - 1) / kPassBatch) * (43.0 + 0.053 * w * (double)m);
+    const double masked_us = 75.0 + (double)span_rows * w * bytes_per_elem * (B <= 128 ? 0.065e-3 : 0.10e-3);
+    return subset_us <= masked_us;
+}
+
+// one batch (B <= 256) with queries and outputs on the device; filt: the local rows a filtered search allows (normalised)
 int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
-                 int32_t *d_nfound) {
+                 int32_t *d_nfound, const Ranges *filt = nullptr) {
     int rc = ensure_scratch(idx);
     if (rc != MX_OK) return rc;
     Scratch &s = idx->s;
     hipStream_t st = idx->stream;
-    const bool trivial = idx->n == 0 || k == 0;
+    // a filtered batch: its ranges clipped to the rows, and the rows they allow that are not removed
+    Ranges fr;
+    uint64_t n_allow = 0;
+    if (filt) {
+        for (const auto &x : *filt)
+            if (x.first < std::min(x.second, idx->n)) fr.emplace_back(x.first, std::min(x.second, idx->n));
+        n_allow = count_allowed(idx, fr);
+    }
+    idx->last_subset = false;
+    const bool trivial = idx->n == 0 || k == 0 || (filt && n_allow == 0);
     if (idx->compressed && idx->kc > kMaxKC16 && !trivial)
         return fail(MX_EUNSUPPORTED, "a compressed corpus supports dim <= %d", kMaxKC16 * kChunkFloats);
     // wide rows (768 < dim_pad <= 1536) have their own scan kernel over the filter copy: 128 queries per pass
@@ -899,32 +1025,66 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     const bool pair = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch / 2 && B <= kPassBatch && idx->scan8_pair;
     const int nwg = pair ? 2 * idx->nwg : idx->nwg;  // workgroups of the scan launches; finish_kernel and theta_kernel follow
     if (B > kPassBatch && !x2 && !(fast && wide)) {
-        rc = search_batch(idx, d_q, kPassBatch, k, d_ids, d_scores, d_dists, d_nfound);
+        rc = search_batch(idx, d_q, kPassBatch, k, d_ids, d_scores, d_dists, d_nfound, filt);
         if (rc != MX_OK) return rc;
         const size_t o = (size_t)kPassBatch * k;
         return search_batch(idx, d_q + (size_t)kPassBatch * idx->dim, B - kPassBatch, k, d_ids + o, d_scores + o,
-                            d_dists ? d_dists + o : nullptr, d_nfound + kPassBatch);
+                            d_dists ? d_dists + o : nullptr, d_nfound + kPassBatch, filt);
     }
     if (fast && wide && B > kWideBatch) {
-        rc = search_batch(idx, d_q, kWideBatch, k, d_ids, d_scores, d_dists, d_nfound);
+        rc = search_batch(idx, d_q, kWideBatch, k, d_ids, d_scores, d_dists, d_nfound, filt);
         if (rc != MX_OK) return rc;
         const size_t o = (size_t)kWideBatch * k;
         return search_batch(idx, d_q + (size_t)kWideBatch * idx->dim, B - kWideBatch, k, d_ids + o, d_scores + o,
-                            d_dists ? d_dists + o : nullptr, d_nfound + kWideBatch);
+                            d_dists ? d_dists + o : nullptr, d_nfound + kWideBatch, filt);
     }
     // the bf16 copy of this index is centred on its rows' mean direction (build_filter_copy): queries are split the same way
     const bool centred = centred8 || (idx->centred && idx->xh && !filt8 && !wide && !idx->compressed && idx->amean && idx->mean && idx->kc <= kMaxKC);
-    LaneLease lease;  // every return below is host-synchronised with the kernels that used the lane buffers
-    if ((rc = lease.take(idx, x2 || pair ? 2 : 1)) != MX_OK) return rc;  // pair: 2 x nwg workgroups x 512 lanes, the 512-query set
-    MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
-                               idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
-                               centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
     const uint32_t *h_ovf = s.host_flags, *h_qfl = s.host_flags + 3 * kMaxBatch;
     auto any_bad_query = [&] {
         uint32_t bad = 0;
         for (int b = 0; b < B; ++b) bad |= h_qfl[b];
         return bad != 0;
     };
+    auto fetch_flags = [&]() -> int {  // the per-query words (overflowed batches, the EXACT path and the subset kernel only)
+        MX_HIP(hipMemcpyAsync(s.host_flags, s.dev_flags, kFlagWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MX_HIP(hipStreamSynchronize(st));
+        return MX_OK;
+    };
+    if (filt && !trivial &&
+        subset_pays(idx, B, n_allow, fr.back().second - fr.front().first, filt8 ? 1 : idx->xh ? 2 : 4)) {
+        // a small filter: the allowed live rows, ascending, and one subset_topk_kernel launch; no scan, no lane buffers
+        std::vector<uint32_t> list;
+        list.reserve((size_t)n_allow);
+        for (const auto &x : fr)
+            for (uint64_t r = x.first; r < x.second; ++r)
+                if (!idx->n_dead || !((idx->dead_h[r >> 6] >> (r & 63)) & 1ull)) list.push_back((uint32_t)r);
+        if (!idx->subset_rows) MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->subset_rows), (size_t)kSubsetCap * sizeof(uint32_t)));
+        MX_HIP(hipMemcpyAsync(idx->subset_rows, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
+                                   idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
+                                   centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
+        MX_HIP(launch_subset_topk(st, B, k, idx->ds, idx->compressed ? nullptr : idx->x, idx->xh, idx->subset_rows, (uint32_t)list.size(),
+                                  idx->idmap, s.qpad, s.qnorm2, d_ids, d_scores, d_dists, d_nfound));
+        if ((rc = fetch_flags()) != MX_OK) return rc;  // (host-synchronised: also for outputs in mapped host memory)
+        if (any_bad_query()) return fail(MX_EINVAL, "a query contains non-finite values");
+        idx->last_subset = true;
+        idx->stats.searches += 1;
+        idx->stats.queries += (uint64_t)B;
+        idx->stats.filtered_queries += (uint64_t)B;
+        idx->stats.subset_queries += (uint64_t)B;
+        return MX_OK;
+    }
+    // what masks the pipeline: the per-call mask of a filtered search, the removed rows, or nothing; the rows it leaves
+    std::vector<uint64_t> flat_ranges;  // (alive until the batch is host-synchronised: the source of an async upload)
+    if (filt && !trivial && (rc = build_filter_mask(idx, fr, flat_ranges)) != MX_OK) return rc;
+    const uint64_t *mask = filt ? idx->filt : idx->n_dead ? idx->dead : nullptr;
+    const uint64_t n_live = filt ? n_allow : idx->n - idx->n_dead;
+    LaneLease lease;  // every return below is host-synchronised with the kernels that used the lane buffers
+    if ((rc = lease.take(idx, x2 || pair ? 2 : 1)) != MX_OK) return rc;  // pair: 2 x nwg workgroups x 512 lanes, the 512-query set
+    MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
+                               idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
+                               centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
     bool timed = false;
 
     FinishParams fp;
@@ -951,8 +1111,8 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     fp.n_zero = (uint32_t)std::min<uint64_t>(idx->n_zero, kZeroCap);
     fp.wild_rows = idx->wild_list;
     fp.n_wild = (uint32_t)std::min<uint64_t>(idx->n_wild, kWildCap);
-    fp.dead = idx->n_dead ? idx->dead : nullptr;
-    fp.n_live = trivial ? 0 : idx->n - idx->n_dead;
+    fp.dead = mask;
+    fp.n_live = trivial ? 0 : n_live;
     fp.overflow = s.overflow;
     fp.todo = nullptr;
     fp.theta_retry = s.theta_retry;
@@ -1019,11 +1179,6 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         if (__atomic_load_n(&s.host_sum[4], __ATOMIC_ACQUIRE) == fp.seq) return MX_OK;
         return fail(MX_EDEVICE, "finish_kernel did not signal completion");
     };
-    auto fetch_flags = [&]() -> int {  // the per-query words (overflowed batches and the EXACT path only)
-        MX_HIP(hipMemcpyAsync(s.host_flags, s.dev_flags, kFlagWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        MX_HIP(hipStreamSynchronize(st));
-        return MX_OK;
-    };
 
     std::vector<int> exact;
     if (trivial) {
@@ -1032,6 +1187,9 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     } else if (fast) {
         const uint64_t trows = filt8 ? kTile8Rows : kTileRows;  // rows per scan tile
         const uint64_t tiles = (idx->n + trows - 1) / trows, full = idx->n / trows;
+        // the tiles the scans visit: all of them, or the span of tiles a filter's ranges touch (the sample: its full tiles)
+        const uint64_t ts0 = filt ? fr.front().first / trows : 0, ts1 = filt ? (fr.back().second + trows - 1) / trows : tiles;
+        const uint64_t full1 = std::min(ts1, full);
         ScanParams p;
         p.x = idx->x;
         p.xh = idx->xh;
@@ -1052,15 +1210,15 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         p.qb = s.qb;
         p.amean = centred ? idx->amean : nullptr;
         p.qmean = s.qmean;
-        p.dead = idx->n_dead ? idx->dead : nullptr;  // the masked kernels only for an index with removed rows
+        p.dead = mask;  // the masked kernels only for an index with removed rows, or a filtered search
         auto scan = [&](bool collect) {
             if (filt8) return launch_scan8(st, idx->kc, collect, nwg, p, pair ? Scan8Geom::kPair : x2 ? Scan8Geom::k512 : Scan8Geom::k256);
             if (wide) return launch_scan16w(st, idx->kc, collect, idx->nwg, p);
             return idx->xh ? launch_scan16(st, idx->kc, collect, idx->nwg, p) : launch_scan(st, idx->kc, collect, idx->nwg, p);
         };
         auto collect = [&](bool first) -> int {
-            p.tile_begin = 0;
-            p.tile_end = (uint32_t)tiles;
+            p.tile_begin = (uint32_t)ts0;
+            p.tile_end = (uint32_t)ts1;
             p.tile_stride = 1;
             // the first collect launch of a batch is the one the roofline is quoted on
             if (first && idx->profiling) MX_HIP(hipEventRecord(idx->ev0, st));
@@ -1071,16 +1229,16 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
             }
             if (first) {
                 idx->stats.scan_launches += 1;
-                idx->stats.scan_bytes += tiles * trows * idx->ds * (filt8 ? 1ull : idx->xh ? 2ull : 4ull);
+                idx->stats.scan_bytes += (ts1 - ts0) * trows * idx->ds * (filt8 ? 1ull : idx->xh ? 2ull : 4ull);
             }
             return MX_OK;
         };
         // a lane holds 16 scores per tile of its workgroup: up to 2 tiles per workgroup everything fits
         // in the lane buffers and no threshold is needed (counted per CU: the two-workgroup form samples the same corpora)
-        if (tiles > 2ull * idx->nwg) {
-            p.tile_begin = 0;
-            p.tile_end = (uint32_t)full;
-            p.tile_stride = sample_stride(full, nwg, k, filt8, idx->ds, centred8);
+        if (ts1 - ts0 > 2ull * idx->nwg) {
+            p.tile_begin = (uint32_t)ts0;
+            p.tile_end = (uint32_t)full1;
+            p.tile_stride = sample_stride(full1 - ts0, nwg, k, filt8, idx->ds, centred8);
             MX_HIP(scan(false));
             MX_HIP(launch_theta(st, B, k, nwg, s.lane_max, s.qa, !filt8, s.theta));
         }
@@ -1101,10 +1259,11 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
                 if (h_ovf[b] == 1) ++retry;
                 else if (h_ovf[b] >= 2) exact.push_back(b);
             }
-            if (filt8) idx->i8_retry_batches += 1;
+            // (a filtered batch leaves the copy heuristics alone: a selective filter's overflows say nothing about the corpus)
+            if (filt8 && !filt) idx->i8_retry_batches += 1;
             // ... or the retry pass (a second whole scan) has become the rule: more than a quarter of the batches
             const bool habitual = filt8 && idx->i8_batches >= 8 && idx->i8_retry_batches * 4 > idx->i8_batches;
-            if (filt8 && idx->filter_auto && ((size_t)(retry + (int)exact.size()) * 16 > (size_t)std::max(B, 16) || habitual)) {
+            if (filt8 && !filt && idx->filter_auto && ((size_t)(retry + (int)exact.size()) * 16 > (size_t)std::max(B, 16) || habitual)) {
                 // More than 1/16 of the batch (and more than one query) did not fit the int8 pass: this corpus is too dense for the int8
                 // certificate (neighbourhoods narrower than ~0.05 in cosine).  Rebuild the copy as bf16 (one pass
                 // over the f32 rows) and answer the batch on it; the index stays on bf16.
@@ -1153,7 +1312,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         for (int b = 0; b < B; ++b) exact.push_back(b);
     }
     if (!exact.empty() || trivial || !fast) {
-        rc = run_exact(idx, exact, k, d_ids, d_scores, d_dists, d_nfound);
+        rc = run_exact(idx, exact, k, d_ids, d_scores, d_dists, d_nfound, mask, n_live);
         if (rc != MX_OK) return rc;
         MX_HIP(hipStreamSynchronize(st));
         if (idx->mode == MX_SEARCH_AUTO && idx->s.exact_bytes > kExactKeepBytes) {  // a large scratch does not stay behind a fallback batch
@@ -1166,7 +1325,8 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     // the batch had been fenced to device scope -- the results are in HBM, nothing else is queued)
     idx->stats.searches += 1;
     idx->stats.queries += (uint64_t)B;
-    if (filt8 && fast) idx->i8_batches += 1;
+    if (filt) idx->stats.filtered_queries += (uint64_t)B;
+    if (filt8 && fast && !filt) idx->i8_batches += 1;
     return MX_OK;
 }
 
@@ -1309,11 +1469,22 @@ bool rccl_selftest(mx_index *idx, double seconds) {
 }
 
 // one batch on a composite: d_q and the outputs live on shards[0]'s device
+// filt: the global rows a filtered search allows (normalised); every shard searches its share of them (shard_ranges)
 int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
-                    int32_t *d_nfound) {
+                    int32_t *d_nfound, const Ranges *filt = nullptr) {
     const int G = (int)idx->shards.size();
     int rc = ensure_composite_buffers(idx, std::max(k, 1));
     if (rc != MX_OK) return rc;
+    std::vector<Ranges> loc(filt ? G : 0);
+    uint64_t n_allow = 0;  // allowed rows that are not removed, over the shards
+    for (int g = 0; g < (int)loc.size(); ++g) {
+        mx_index *sh = idx->shards[g];
+        Ranges clipped;
+        for (const auto &x : shard_ranges(*filt, idx->block_rows, (uint64_t)G, (uint64_t)g))
+            if (x.first < std::min(x.second, sh->n)) clipped.emplace_back(x.first, std::min(x.second, sh->n));
+        n_allow += count_allowed(sh, clipped);
+        loc[g] = std::move(clipped);
+    }
     const size_t ids_bytes = (size_t)B * k * sizeof(uint64_t), blk = ids_bytes + (size_t)B * k * sizeof(float);
     std::vector<int> rcs(G, MX_OK);
     std::vector<std::string> errs(G);
@@ -1325,7 +1496,7 @@ int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_i
             MX_HIP(hipMemcpyAsync(idx->sh_q[g], d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
             char *blkp = static_cast<char *>(idx->sh_block[g]);
             int r = search_batch(sh, idx->sh_q[g], B, k, reinterpret_cast<uint64_t *>(blkp), idx->sh_scores[g],
-                                 reinterpret_cast<float *>(blkp + ids_bytes), idx->sh_nf[g]);
+                                 reinterpret_cast<float *>(blkp + ids_bytes), idx->sh_nf[g], filt ? &loc[g] : nullptr);
             if (r != MX_OK) return r;
             if (!idx->use_rccl && k > 0) {  // peer copy into slot g of the gather area on shards[0]'s device
                 MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
@@ -1402,18 +1573,30 @@ int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_i
                             d_scores));
     }
     // every shard found min(k, its live rows): the merged lists hold min(k, live rows of the handle) entries
-    MX_HIP(launch_fill_nfound(s0->stream, d_nfound, B, (int32_t)std::min<uint64_t>((uint64_t)k, idx->total - idx->n_dead)));
+    MX_HIP(launch_fill_nfound(s0->stream, d_nfound, B, (int32_t)std::min<uint64_t>((uint64_t)k, filt ? n_allow : idx->total - idx->n_dead)));
     MX_HIP(hipStreamSynchronize(s0->stream));
     idx->stats.exchange_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count();
     idx->stats.searches += 1;
     idx->stats.queries += (uint64_t)B;
+    if (filt) {
+        // a query of the handle counts as answered by the subset kernel when every shard that had rows to offer used it
+        bool any = false, all = true;
+        for (int g = 0; g < G; ++g) {
+            if (loc[g].empty()) continue;
+            any = any || idx->shards[g]->last_subset;
+            all = all && idx->shards[g]->last_subset;
+        }
+        idx->stats.filtered_queries += (uint64_t)B;
+        if (any && all) idx->stats.subset_queries += (uint64_t)B;
+    }
     return MX_OK;
 }
 
+// filt: the global rows a filtered search allows (normalised), or null
 int any_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
-              int32_t *d_nfound) {
-    return idx->composite() ? composite_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound)
-                            : search_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound);
+              int32_t *d_nfound, const Ranges *filt = nullptr) {
+    return idx->composite() ? composite_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, filt)
+                            : search_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, filt);
 }
 
 // what an append can change in a plain index, and how to undo it: an insert is all-or-nothing, also when it
@@ -1864,6 +2047,7 @@ int open_plain(const std::string &k, int dim, int device, mx_index **out) {
         if (g_scan_setup_err == hipSuccess) g_scan_setup_err = scan16w_setup();
         if (g_scan_setup_err == hipSuccess) g_scan_setup_err = scan8_setup();
         if (g_scan_setup_err == hipSuccess) g_scan_setup_err = finish_setup();
+        if (g_scan_setup_err == hipSuccess) g_scan_setup_err = subset_setup();
     });
     if (g_scan_setup_err != hipSuccess)
         return fail(MX_EDEVICE, "scan kernel setup failed: %s (is this a gfx950 device?)", hipGetErrorString(g_scan_setup_err));
@@ -2182,7 +2366,7 @@ int usable(mx_index *idx) {
 extern "C" {
 
 const char *mx_last_error(void) { return last_error_slot().c_str(); }
-const char *mx_version(void) { return "memex-hip 0.5.0 (gfx950)"; }
+const char *mx_version(void) { return "memex-hip 0.6.0 (gfx950)"; }
 size_t mx_index_stats_size(void) { return sizeof(mx_index_stats); }
 
 int mx_device_count(int *n) try {
@@ -2552,8 +2736,26 @@ int mx_index_set_search_mode(mx_index *idx, int mode) try {
     return guard_exception();
 }
 
-int mx_index_search_device(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores,
-                           float *d_dists, int32_t *d_nfound) try {
+namespace {
+
+// the ranges argument of the filtered entry points -> normalised id ranges; MX_EINVAL for a null array or a pair with lo > hi
+int read_id_ranges(const uint64_t *ranges, uint64_t n_ranges, Ranges *out) {
+    if (!ranges && n_ranges) return fail(MX_EINVAL, "null ranges with n_ranges = %llu", (unsigned long long)n_ranges);
+    out->clear();
+    out->reserve((size_t)n_ranges);
+    for (uint64_t i = 0; i < n_ranges; ++i) {
+        if (ranges[2 * i] > ranges[2 * i + 1])
+            return fail(MX_EINVAL, "range %llu is [%llu, %llu): lo > hi; nothing searched", (unsigned long long)i,
+                        (unsigned long long)ranges[2 * i], (unsigned long long)ranges[2 * i + 1]);
+        out->emplace_back(ranges[2 * i], ranges[2 * i + 1]);
+    }
+    normalise_ranges(*out);
+    return MX_OK;
+}
+
+// mx_index_search_device and its filtered form (id_filt: normalised id ranges, or null)
+int search_device(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_nfound,
+                  const Ranges *id_filt) {
     if (!idx) return fail(MX_ESEARCH, "null index");
     if (B < 0 || k < 0) return fail(MX_EINVAL, "negative batch or k");
     if (B == 0) return MX_OK;
@@ -2562,13 +2764,32 @@ int mx_index_search_device(mx_index *idx, const float *d_q, int B, int k, uint64
     std::lock_guard<std::mutex> lk(idx->mu);
     DeviceGuard g(idx->device);
     if (int rc = usable(idx); rc != MX_OK) return rc;
+    Ranges rows;
+    if (id_filt) rows = rows_of_ids(*id_filt, idx->idmap.id_offset, rows_of(idx));  // (under idx->mu)
     for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
         const int nb = std::min(kMaxBatch, B - b0);
         int rc = any_batch(idx, d_q + (size_t)b0 * idx->dim, nb, k, d_ids + (size_t)b0 * k,
-                           d_scores + (size_t)b0 * k, d_dists ? d_dists + (size_t)b0 * k : nullptr, d_nfound + b0);
+                           d_scores + (size_t)b0 * k, d_dists ? d_dists + (size_t)b0 * k : nullptr, d_nfound + b0,
+                           id_filt ? &rows : nullptr);
         if (rc != MX_OK) return rc;
     }
     return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_search_device(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores,
+                           float *d_dists, int32_t *d_nfound) try {
+    return search_device(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, nullptr);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_filtered_device(mx_index *idx, const float *d_q, int B, int k, const uint64_t *ranges, uint64_t n_ranges,
+                                    uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_nfound) try {
+    Ranges ids;
+    if (int rc = read_id_ranges(ranges, n_ranges, &ids); rc != MX_OK) return rc;
+    return search_device(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, &ids);
 } catch (...) {
     return guard_exception();
 }
@@ -2583,6 +2804,9 @@ int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
     DeviceGuard g(t->device);
     const int k = batch[0]->k;
+    Ranges rows;  // a filtered pass: every request of it has the same ranges
+    if (batch[0]->filt) rows = rows_of_ids(*batch[0]->filt, idx->idmap.id_offset, rows_of(idx));
+    const Ranges *filt = batch[0]->filt ? &rows : nullptr;
     int rc = ensure_scratch(t);
     if (rc != MX_OK) return rc;
     rc = ensure_out(t, k);
@@ -2602,13 +2826,13 @@ int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     // A sharded index merges on the device and copies as before.
     if (!idx->composite()) {
         s.out_on_host = true;
-        rc = any_batch(idx, s.h_q, nb, k, s.h_ids, s.h_scores, s.h_dists, s.h_nf);
+        rc = any_batch(idx, s.h_q, nb, k, s.h_ids, s.h_scores, s.h_dists, s.h_nf, filt);
         s.out_on_host = false;
         if (rc != MX_OK) return rc;
         std::atomic_thread_fence(std::memory_order_acquire);
     } else {
     MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
-    rc = any_batch(idx, s.qstage, nb, k, s.out_ids, s.out_scores, s.out_dists, s.out_nfound);
+    rc = any_batch(idx, s.qstage, nb, k, s.out_ids, s.out_scores, s.out_dists, s.out_nfound, filt);
     if (rc != MX_OK) return rc;
     if (k > 0) {
         MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
@@ -2639,8 +2863,13 @@ int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
 // leader becomes the leader and serves batches (up to 256 queries with the same k, FIFO) until its
 // own request is done, then hands over.  A lone caller runs immediately (no timer, no added
 // latency); under load the batch is whatever queued up while the previous pass was on the GPU.
-int mx_index_search(mx_index *idx, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists,
-                    int32_t *n_found) try {
+namespace {
+
+bool same_filter(const Ranges *a, const Ranges *b) { return a == b || (a && b && *a == *b); }
+
+// mx_index_search and its filtered form (filt: normalised id ranges, or null)
+int search_host(mx_index *idx, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists, int32_t *n_found,
+                const Ranges *filt) {
     if (!idx) return fail(MX_ESEARCH, "null index");
     if (B < 0 || k < 0) return fail(MX_EINVAL, "negative batch or k");
     if (B == 0) return MX_OK;
@@ -2654,27 +2883,29 @@ int mx_index_search(mx_index *idx, const float *q, int B, int k, uint64_t *ids, 
     if (B > kMaxBatch) {  // large requests are their own batches: split and recurse
         for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
             const int nb = std::min(kMaxBatch, B - b0);
-            int rc = mx_index_search(idx, q + (size_t)b0 * idx->dim, nb, k, ids ? ids + (size_t)b0 * k : nullptr,
-                                     scores ? scores + (size_t)b0 * k : nullptr,
-                                     dists ? dists + (size_t)b0 * k : nullptr, n_found + b0);
+            int rc = search_host(idx, q + (size_t)b0 * idx->dim, nb, k, ids ? ids + (size_t)b0 * k : nullptr,
+                                 scores ? scores + (size_t)b0 * k : nullptr,
+                                 dists ? dists + (size_t)b0 * k : nullptr, n_found + b0, filt);
             if (rc != MX_OK) return rc;
         }
         return MX_OK;
     }
-    SearchReq req{q, B, k, ids, scores, dists, n_found};
+    SearchReq req{q, B, k, ids, scores, dists, n_found, filt};
     std::unique_lock<std::mutex> ql(idx->cmu);
     idx->pending.push_back(&req);
     idx->ccv.wait(ql, [&] { return req.done || !idx->leader; });
     if (!req.done) {
         idx->leader = true;
         while (!req.done) {
-            // FIFO batch: the oldest request decides k; later requests with the same k join while they fit
+            // FIFO batch: the oldest request decides k and the filter; later requests with the same k and the same filter (or none
+            // like it) join while they fit
             std::vector<SearchReq *> batch;
             int total = 0;
             const int bk = idx->pending.front()->k;
+            const Ranges *bf = idx->pending.front()->filt;
             for (auto it = idx->pending.begin(); it != idx->pending.end();) {
                 SearchReq *r = *it;
-                if (r->k == bk && total + r->B <= kMaxBatch) {
+                if (r->k == bk && same_filter(r->filt, bf) && total + r->B <= kMaxBatch) {
                     batch.push_back(r);
                     total += r->B;
                     it = idx->pending.erase(it);
@@ -2704,6 +2935,22 @@ int mx_index_search(mx_index *idx, const float *q, int B, int k, uint64_t *ids, 
     ql.unlock();
     if (req.rc != MX_OK) last_error_slot() = req.err;  // the leader's message, in the caller's thread
     return req.rc;
+}
+
+}  // namespace
+
+int mx_index_search(mx_index *idx, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists,
+                    int32_t *n_found) try {
+    return search_host(idx, q, B, k, ids, scores, dists, n_found, nullptr);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_filtered(mx_index *idx, const float *q, int B, int k, const uint64_t *ranges, uint64_t n_ranges, uint64_t *ids,
+                             float *scores, float *dists, int32_t *n_found) try {
+    Ranges id_ranges;
+    if (int rc = read_id_ranges(ranges, n_ranges, &id_ranges); rc != MX_OK) return rc;
+    return search_host(idx, q, B, k, ids, scores, dists, n_found, &id_ranges);
 } catch (...) {
     return guard_exception();
 }

@@ -233,8 +233,9 @@ struct FinishParams {
     uint32_t n_zero;
     const uint32_t *wild_rows;  // [kWildCap] rows with a norm outside the f32 stages' range, ascending: stage 3 takes them all
     uint32_t n_wild;
-    const uint64_t *dead;       // removed rows (ScanParams::dead); null: none.  The side lists above hold no removed row.
-    uint64_t n_live;            // rows not removed: a query finds min(k, n_live)
+    const uint64_t *dead;       // removed rows (ScanParams::dead), or the per-call mask of a filtered search; null: none.  The
+                                // side lists above may name masked rows (a filter does not prune them): every listed row's bit is tested
+    uint64_t n_live;            // rows not masked: a query finds min(k, n_live)
     uint32_t *overflow;         // [256]
     const uint32_t *todo;       // null = every query; else only queries with todo[q] != 0
     float *theta_retry;         // [256]
@@ -287,6 +288,20 @@ hipError_t launch_compact_gather(hipStream_t s, const uint64_t *dead, uint64_t n
 // f32 corpus rows [0, n): the zero-norm list and the out-of-range-norm list afresh (flags[3] / flags[4] count, zeroed by the caller)
 hipError_t launch_relist(hipStream_t s, const float *x, const float *scale, uint64_t n, int ds, uint32_t *flags, uint32_t *zero_rows,
                          uint32_t *wild_rows);
+
+// filtered search (mx_index_search_filtered).  mask[t] = dead[t] | ~allow(t) for every 64-row word
+// t < words (dead null: no removals), allow(t) = the rows of word t inside one of the n_ranges sorted, disjoint, non-adjacent
+// local row ranges [lo, hi), passed as u64 pairs.  The result is the dead-row mask (ScanParams::dead) of the filtered search.
+hipError_t launch_filter_mask(hipStream_t s, const uint64_t *dead, const uint64_t *ranges, uint32_t n_ranges, uint64_t words,
+                              uint64_t *mask);
+// Small filters: the m <= kSubsetCap rows of an ascending list of local rows, exact DistCosine (finish_kernel's stage-3 arithmetic)
+// for B queries (qpad / qnorm2 of launch_prep_queries), the min(k, m) smallest by (dist, row) emitted like finish_kernel.  One
+// workgroup per query, the keys in LDS (128 KiB).
+constexpr int kSubsetCap = 16384;
+hipError_t subset_setup();
+hipError_t launch_subset_topk(hipStream_t s, int B, int k, int ds, const float *x, const void *xh, const uint32_t *rows, uint32_t m,
+                              const IdMap &idmap, const float *qpad, const double *qnorm2, uint64_t *ids, float *scores, float *dists,
+                              int32_t *n_found);
 
 hipError_t launch_fill_nfound(hipStream_t s, int32_t *nf, int B, int32_t v);
 hipError_t launch_merge(hipStream_t s, const void *ids, size_t ids_stride, const void *dists, size_t dists_stride,

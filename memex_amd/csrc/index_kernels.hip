@@ -478,7 +478,10 @@ __global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float 
     if ((tid & 63) == 0) s_nvalid[tid >> 6] = nv;
     __syncthreads();
     nv = s_nvalid[0] + s_nvalid[1] + s_nvalid[2] + s_nvalid[3];
-    float kth = -INFINITY;  // fewer than k lanes saw a row: no threshold
+    // fewer than k lanes saw a row: no threshold that could drop a row -- every filter score of a row lies far above -8 -- but a
+    // finite one, which the -inf of masked rows (a removal or a filter that leaves few rows in the sample) does not reach: such
+    // rows then take no record slot in the collect launch
+    float kth = -8.0f;
     if (nv >= (uint32_t)k && k > 0) kth = key_f32(block_kth_largest<PER>(key, valid, (uint32_t)k, s_hist, s_pick));
     if (tid == 0 && theta[q] != INFINITY) theta[q] = kth - (raw ? 2.0f : 1.0f) * qa[q];
 }
@@ -693,7 +696,8 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     };
     auto is_zero_row = [&](uint32_t row) { return (nz && in_list(p.zero_rows, nz, row)) || (nw && in_list(p.wild_rows, nw, row)); };
     // removed rows: the masked scans give them scores no threshold passes, but a half tile of zeros (step 0) scores them 0, and
-    // theta may be -inf; the lists above still name removed rows.  Nothing removed: p.dead is null and this is never asked.
+    // theta may be -inf.  The lists above may name masked rows: a removal prunes them, a filter does not (the per-call mask of
+    // mx_index_search_filtered), so every listed row's bit is tested.  No mask: p.dead is null and this is never asked.
     auto is_dead = [&](uint32_t row) { return p.dead && ((p.dead[row >> 6] >> (row & 63u)) & 1ull) != 0; };
     // (a) record counts of this query's 2*nwg lane buffers -> exclusive scan in LDS
     uint32_t *s_off = reinterpret_cast<uint32_t *>(qv + ds) + 32;  // [2*kMaxScanWGs + 1], behind the staged-row ids
@@ -992,14 +996,14 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
         __syncthreads();
         if (tid < (int)mt) {
             const float d = exact_dist_row(qv, stage + (size_t)tid * pitch, ds, na, nullptr);
-            keys[tid] = tid >= (int)m2 && is_dead(srow[tid]) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | srow[tid];  // a removed listed row (the candidates are live): last
+            keys[tid] = tid >= (int)m2 && is_dead(srow[tid]) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | srow[tid];  // a masked listed row (the candidates are not): last
         }
     } else {
         // (keys[] shares ent[]'s storage, 8 bytes per entry both: thread cI reads ent[cI] and writes keys[cI] itself)
         for (uint32_t cI = tid; cI < mt; cI += kFinThreads) {
             const uint32_t r = cI < m2 ? ent[cI].row : p.wild_rows[cI - m2];
             const float d = exact_dist_stored<CMP>(qv, p.x, p.xh, ds, r, na);
-            keys[cI] = cI >= m2 && is_dead(r) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | r;  // a removed listed row (the candidates are live): last
+            keys[cI] = cI >= m2 && is_dead(r) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | r;  // a masked listed row (the candidates are not): last
         }
     }
     __syncthreads();
@@ -1465,6 +1469,147 @@ hipError_t launch_merge(hipStream_t s, const void *ids, size_t ids_stride, const
     if (B <= 0 || k <= 0) return hipSuccess;
     hipLaunchKernelGGL(merge_kernel, dim3(B), dim3(256), 0, s, static_cast<const char *>(ids), ids_stride,
                        static_cast<const char *>(dists), dists_stride, G, B, k, out_ids, out_dists, out_scores);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// filtered search (mx_index_search_filtered)
+// ---------------------------------------------------------------------------------------------
+// mask[t] = dead[t] | ~allow(t) for every 64-row word t < words.  allow(t): the bits of the rows of word t that lie in one of the
+// n_ranges sorted, disjoint, non-adjacent local ranges [lo, hi) (u64 pairs); a binary search finds the first range that ends past
+// the word, and at most 32 such ranges can meet one word.  One thread per word, one vector store each.
+__global__ __launch_bounds__(256) void filter_mask_kernel(const uint64_t *__restrict__ dead, const uint64_t *__restrict__ ranges,
+                                                          uint32_t n_ranges, uint64_t words, uint64_t *__restrict__ mask) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= words) return;
+    const uint64_t r0 = t * 64, r1 = r0 + 64;
+    uint32_t lo = 0, hi = n_ranges;  // first range with end > r0
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ranges[2 * mid + 1] <= r0) lo = mid + 1;
+        else hi = mid;
+    }
+    uint64_t allow = 0;
+    for (uint32_t i = lo; i < n_ranges && ranges[2 * i] < r1; ++i) {
+        const uint64_t a = (ranges[2 * i] > r0 ? ranges[2 * i] : r0) - r0;
+        const uint64_t b = (ranges[2 * i + 1] < r1 ? ranges[2 * i + 1] : r1) - r0;  // a < b <= 64
+        const uint64_t upto = b == 64 ? ~0ull : (1ull << b) - 1ull;
+        allow |= upto & ~((1ull << a) - 1ull);
+    }
+    mask[t] = (dead ? dead[t] : 0ull) | ~allow;
+}
+
+hipError_t launch_filter_mask(hipStream_t s, const uint64_t *dead, const uint64_t *ranges, uint32_t n_ranges, uint64_t words,
+                              uint64_t *mask) {
+    if (words == 0) return hipSuccess;
+    hipLaunchKernelGGL(filter_mask_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, dead, ranges, n_ranges, words, mask);
+    return hipGetLastError();
+}
+
+// Small filters: one workgroup per query against the m listed rows (ascending local rows, m <= kSubsetCap).  Each thread takes
+// rows i = tid, tid + 1024, ...: exact DistCosine through exact_dist_stored -- the f64 chain of finish_kernel's stage 3 and of the
+// EXACT path, so zero-norm, wide-norm and compressed rows get the same bits there and here -- into the key
+// (dist_bits << 32) | i.  The list is ascending in local row and a shard's local order is its id order, so ordering keys orders by
+// (dist, id).  Up to 2048 rows every key is ranked against all of them; above, an MSB-first select over the bits a key can have
+// (dist bits, 14 position bits) finds the want-th smallest key, the want keys at or below it move to the front, and only they
+// are ranked.  Keys are unique (the position), so exactly `want` of them qualify and every output slot is written once.
+constexpr int kSubsetPer = kSubsetCap / kFinThreads;
+constexpr int kSubsetPosBits = 14;
+static_assert((1 << kSubsetPosBits) == kSubsetCap, "position bits of a subset key");
+template <bool CMP>
+__global__ __launch_bounds__(kFinThreads) void subset_topk_kernel(int k, int ds, const float *__restrict__ x, const void *__restrict__ xh,
+                                                                 const uint32_t *__restrict__ rows, uint32_t m, IdMap idmap,
+                                                                 const float *__restrict__ qpad, const double *__restrict__ qnorm2,
+                                                                 uint64_t *ids, float *scores, float *dists, int32_t *n_found) {
+    extern __shared__ __attribute__((aligned(16))) char ssm[];
+    uint64_t *keys = reinterpret_cast<uint64_t *>(ssm);                        // [kSubsetCap]
+    float *qv = reinterpret_cast<float *>(ssm + sizeof(uint64_t) * kSubsetCap);  // [ds] raw query
+    __shared__ uint32_t s_sel[2][kFinWaves];
+    __shared__ uint32_t s_cnt;
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t want = m < (uint32_t)k ? m : (uint32_t)k;
+    uint64_t *oid = ids + (size_t)q * k;
+    float *osc = scores + (size_t)q * k;
+    float *odi = dists ? dists + (size_t)q * k : nullptr;
+    if (tid == 0) n_found[q] = (int32_t)want;
+    for (int j = (int)want + tid; j < k; j += kFinThreads) {  // unused slots (the first `want` are written below)
+        oid[j] = 0;
+        osc[j] = 0.0f;
+        if (odi) odi[j] = INFINITY;
+    }
+    if (want == 0) return;
+    for (int i = tid; i < ds; i += kFinThreads) qv[i] = qpad[(size_t)q * ds + i];
+    __syncthreads();
+    const double na = qnorm2[q];
+    for (uint32_t i = tid; i < m; i += kFinThreads) {
+        const float d = exact_dist_stored<CMP>(qv, x, xh, ds, rows[i], na);
+        keys[i] = ((uint64_t)__float_as_uint(d) << 32) | i;
+    }
+    __syncthreads();
+    uint32_t mt = m;  // keys[0, mt) are ranked
+    if (m > 2048u && m > want) {
+        uint64_t prefix = 0;
+        for (int bit = 63; bit >= 0; --bit) {
+            if (bit < 32 && bit >= kSubsetPosBits) continue;  // zero in every key (and so in the want-th smallest)
+            const uint64_t trial = prefix | (1ull << bit);
+            uint32_t cc = 0;
+            for (uint32_t i = tid; i < m; i += kFinThreads) cc += keys[i] < trial ? 1u : 0u;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) cc += __shfl_xor(cc, o);
+            uint32_t *slot = s_sel[bit & 1];  // bits 32 and 13 are consecutive passes: the slots still alternate
+            if (lane == 0) slot[wave] = cc;
+            __syncthreads();
+            cc = 0;
+#pragma unroll
+            for (int w = 0; w < kFinWaves; ++w) cc += slot[w];
+            if (cc < want) prefix = trial;  // fewer than `want` keys below trial: the want-th smallest is >= trial
+        }
+        uint64_t v[kSubsetPer];
+        bool sel[kSubsetPer];
+#pragma unroll
+        for (int e = 0; e < kSubsetPer; ++e) {
+            const uint32_t i = (uint32_t)e * kFinThreads + tid;
+            sel[e] = i < m && keys[i] <= prefix;
+            v[e] = sel[e] ? keys[i] : 0ull;
+        }
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();  // every key is in registers: the front of keys[] may be overwritten
+#pragma unroll
+        for (int e = 0; e < kSubsetPer; ++e)
+            if (sel[e]) keys[atomicAdd(&s_cnt, 1u)] = v[e];
+        __syncthreads();
+        mt = want;
+    }
+    for (uint32_t c = tid; c < mt; c += kFinThreads) {
+        const uint64_t me = keys[c];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < mt; ++j) rank += keys[j] < me ? 1u : 0u;
+        if (rank < want) {
+            const float d = __uint_as_float((uint32_t)(me >> 32));
+            oid[rank] = idmap.id_of(rows[(uint32_t)me]);
+            osc[rank] = score_from_dist(d);
+            if (odi) odi[rank] = d;
+        }
+    }
+}
+
+static size_t subset_lds_bytes(int ds) { return sizeof(uint64_t) * (size_t)kSubsetCap + sizeof(float) * (size_t)ds; }
+
+hipError_t subset_setup() {
+    const int lds = (int)subset_lds_bytes(kMaxKC16 * kChunkFloats);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&subset_topk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&subset_topk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+}
+
+hipError_t launch_subset_topk(hipStream_t s, int B, int k, int ds, const float *x, const void *xh, const uint32_t *rows, uint32_t m,
+                              const IdMap &idmap, const float *qpad, const double *qnorm2, uint64_t *ids, float *scores, float *dists,
+                              int32_t *n_found) {
+    if (B <= 0) return hipSuccess;
+    if (m > (uint32_t)kSubsetCap || ds > kMaxKC16 * kChunkFloats) return hipErrorInvalidValue;
+    const size_t lds = subset_lds_bytes(ds);
+    if (x) hipLaunchKernelGGL(subset_topk_kernel<false>, dim3(B), dim3(kFinThreads), lds, s, k, ds, x, xh, rows, m, idmap, qpad, qnorm2, ids, scores, dists, n_found);
+    else hipLaunchKernelGGL(subset_topk_kernel<true>, dim3(B), dim3(kFinThreads), lds, s, k, ds, x, xh, rows, m, idmap, qpad, qnorm2, ids, scores, dists, n_found);  // compressed corpus
     return hipGetLastError();
 }
 

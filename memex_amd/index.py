@@ -214,6 +214,38 @@ class FlatIndex:
                                            ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
                                            ctypes.c_void_p(n_found.data_ptr())))
 
+    def search_filtered(self, queries, k: int, *, ranges=None, ids=None):
+        """The exact top-k among the rows whose ids are allowed -> like ``search``.  Give exactly one of ``ranges`` (an [m, 2]
+        array of half-open id ranges [lo, hi), any order, overlaps allowed) or ``ids`` (an iterable of ids, turned into sorted
+        runs).  Ids that name no row select nothing; an empty filter finds nothing."""
+        r = _filter_ranges(ranges, ids)
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        B = q.shape[0]
+        out_ids = np.zeros((B, k), dtype=np.uint64)
+        scores = np.zeros((B, k), dtype=np.float32)
+        dists = np.zeros((B, k), dtype=np.float32)
+        nf = np.zeros(B, dtype=np.int32)
+        check(lib().mx_index_search_filtered(self._h, _ptr(q), B, int(k), _ptr(r) if r.size else None, r.shape[0],
+                                             _ptr(out_ids), _ptr(scores), _ptr(dists), _ptr(nf)))
+        return out_ids, scores, dists, nf
+
+    def search_filtered_device(self, q, k: int, ids, scores, dists, n_found, *, ranges=None, allow_ids=None) -> None:
+        """``search_device`` restricted like ``search_filtered``: the queries and outputs are device tensors, the filter
+        (``ranges`` or ``allow_ids``) stays on the host."""
+        r = _filter_ranges(ranges, allow_ids)
+        B = int(q.shape[0])
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        check(lib().mx_index_search_filtered_device(self._h, ctypes.c_void_p(q.data_ptr()), B, int(k), _ptr(r) if r.size else None,
+                                                    r.shape[0], ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
+                                                    ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
+                                                    ctypes.c_void_p(n_found.data_ptr())))
+
     # -- persistence ---------------------------------------------------------------------
     def save(self, directory: str) -> None:
         check(lib().mx_index_save(self._h, str(directory).encode()))
@@ -238,6 +270,26 @@ class FlatIndex:
     @staticmethod
     def remove_files(directory: str) -> None:
         check(lib().mx_index_remove_files(str(directory).encode()))
+
+
+def ids_to_ranges(ids) -> np.ndarray:
+    """Ids (any order, repeats allowed) -> uint64 [m, 2]: the sorted, maximal runs of consecutive ids as half-open ranges."""
+    a = np.unique(np.asarray(list(ids) if not hasattr(ids, "__len__") else ids, dtype=np.uint64).reshape(-1))
+    if a.size == 0:
+        return np.zeros((0, 2), dtype=np.uint64)
+    brk = np.flatnonzero(np.diff(a) != 1) + 1           # where a run ends
+    starts = a[np.r_[0, brk]]
+    ends = a[np.r_[brk - 1, a.size - 1]] + np.uint64(1)
+    return np.ascontiguousarray(np.stack([starts, ends], axis=1), dtype=np.uint64)
+
+
+def _filter_ranges(ranges, ids) -> np.ndarray:
+    if (ranges is None) == (ids is None):
+        raise ValueError("give exactly one of ranges= and ids=")
+    if ids is not None:
+        return ids_to_ranges(ids)
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+    return r
 
 
 def merge_topk_device(device: int, ids, dists, out_ids, out_dists, out_scores) -> None:

@@ -402,6 +402,38 @@ class HipFlatStore(VectorStore):
     def insert(self, data: VectorData) -> None:
         self.bulk_insert([data])
 
+    def search_within(self, vec: Sequence[float], limit: int, ids: Sequence[str]) -> List[VectorSearchResult]:
+        """``search`` restricted to the rows inserted under the given ``_id`` strings (one document's segments, one tenant's
+        rows): the exact top-``limit`` among them (``FlatIndex.search_filtered``), as ``(_id, score)`` pairs like ``search``.
+        A document's segments are inserted in one call, so a handful of documents is a handful of id ranges.  An unknown
+        ``_id`` selects nothing."""
+        wanted = [ids] if isinstance(ids, str) else [str(i) for i in ids]
+        with self._lock:
+            idx = self._index
+            if idx is None or limit <= 0 or not self._id_map:
+                return []
+            if self._rows_of is None:  # the map remove() builds: once per store, kept on insert
+                rows_of: Dict[str, List[int]] = {}
+                for i, d_id in self._id_map.items():
+                    rows_of.setdefault(d_id, []).append(i)
+                self._rows_of = rows_of
+            allow = [i for w in dict.fromkeys(wanted) for i in self._rows_of.get(w, ())]
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        try:
+            ids_, scores, _, nf = idx.search_filtered(q, int(limit), ids=allow)  # not under the lock: combined like search
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[VectorSearchResult] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids_[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[d_id], float(scores[0, j])))
+        return out
+
     def search(self, vec: Sequence[float], limit: int) -> List[VectorSearchResult]:
         with self._lock:
             idx = self._index        # own reference: the store may be evicted / replaced while the GPU works
