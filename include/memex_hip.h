@@ -200,6 +200,27 @@ int mx_index_search_filtered(mx_index *idx, const float *queries, int B, int k, 
 int mx_index_search_filtered_device(mx_index *idx, const float *d_queries, int B, int k, const uint64_t *ranges, uint64_t n_ranges,
                                     uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_n_found);
 
+/*
+ * Range search: every row whose score reaches a per-query threshold, exactly ("which rows are at least this similar?").
+ * Row r is in range for query b iff score(q_b, r) >= min_scores[b], score being exactly the f32 value mx_index_search reports for that
+ * pair (1 - 1/(1/dist), dist the f64 DistCosine rounded to f32).  min_scores holds B floats and is HOST memory on both variants.
+ * Per query the in-range live rows are written best-first in (dist, id) order, at most cap of them; n_found[b] = min(cap, n_in_range[b])
+ * is the number written and n_in_range[b] the EXACT number of in-range live rows, which may exceed cap.  Unused slots hold id 0,
+ * score 0, dist +inf; dists may be NULL.  Removed rows are never in range; a threshold above 1 selects nothing, one <= -1 every live row;
+ * a zero-norm query has score 1 against every row (the first cap live rows by id).  The first n_found[b] entries equal, bit for bit,
+ * those of mx_index_search with k = cap.
+ * Arguments are checked first: B < 0, cap < 1, min_scores == NULL (B > 0) or a NaN threshold: MX_EINVAL; cap > 4096: MX_EUNSUPPORTED;
+ * then a null index: MX_ESEARCH.  Non-finite queries are rejected, B is split into batches of 512, id_offset applies, sharded handles
+ * sum n_in_range over their shards.  Concurrent host-pointer calls are combined like mx_index_search's, a pass taking only range
+ * requests with the same cap (thresholds may differ).  Range passes never change the filter copy and do not count towards its
+ * demotion / promotion.  The collect scan runs with the pass threshold the caller's score implies (no sample launch); a query whose
+ * candidates overflow, and everything mx_index_search answers on the EXACT path but k > 256, takes the EXACT range path.
+ */
+int mx_index_search_range(mx_index *idx, const float *queries, int B, const float *min_scores, int cap, uint64_t *ids, float *scores,
+                          float *dists, int32_t *n_found, uint64_t *n_in_range);
+int mx_index_search_range_device(mx_index *idx, const float *d_queries, int B, const float *min_scores, int cap, uint64_t *d_ids,
+                                 float *d_scores, float *d_dists, int32_t *d_n_found, uint64_t *d_n_in_range);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

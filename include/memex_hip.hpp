@@ -403,6 +403,32 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // every row whose score against vec is at least min_score, best first, at most limit (1 .. 4096) of them (mx_index_search_range):
+    // a near-duplicate check before ingest, or context chosen by relevance rather than by count
+    std::vector<VectorSearchResult> search_above(const std::vector<float> &vec, float min_score, size_t limit) {
+        std::vector<VectorSearchResult> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0) return out;
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        int32_t nf = 0;
+        uint64_t n_in_range = 0;
+        int rc = mx_index_search_range(idx_, vec.data(), 1, &min_score, (int)std::min<size_t>(limit, (size_t)INT32_MAX), found.data(),
+                                       scores.data(), nullptr, &nf, &n_in_range);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.emplace_back(it->second, scores[j]);
+        }
+        return out;
+    }
+
     uint64_t nb_point() const {  // hnsw.get_nb_point() in the reference's test (local.rs:238)
         uint64_t n = 0;
         if (idx_) mx_index_size(idx_, &n);

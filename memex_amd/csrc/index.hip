@@ -103,6 +103,10 @@ struct Scratch {
     uint64_t *h_ids = nullptr;
     float *h_scores = nullptr, *h_dists = nullptr;
     int32_t *h_nf = nullptr;
+    // range search (range_batch): per-query dist bound, device and pinned counts
+    uint32_t *rlim = nullptr;      // [kMaxBatch] dlim of the batch (launch_range_theta)
+    uint64_t *out_nrange = nullptr;  // [kMaxBatch] device n_in_range of a combined sharded pass
+    uint64_t *h_nr = nullptr;      // [kMaxBatch] pinned, mapped: n_in_range of a combined pass
     bool ready = false;
 };
 
@@ -163,6 +167,8 @@ struct SearchReq {
     float *scores, *dists;
     int32_t *n_found;
     const std::vector<std::pair<uint64_t, uint64_t>> *filt = nullptr;  // mx_index_search_filtered: the normalised id ranges
+    const uint32_t *dlim = nullptr;     // mx_index_search_range: per-query dist bounds (k is the cap); null: a top-k request
+    uint64_t *n_in_range = nullptr;
     int rc = MX_OK;
     std::string err;
     bool done = false;
@@ -337,8 +343,9 @@ int free_index(mx_index *idx) {
     F(s.qfrag); F(s.qpad); F(s.qnorm2); F(s.theta); F(s.theta_retry); F(s.todo); F(s.dev_flags); F(s.done_ctr);
     if (s.host_flags) (void)hipHostFree(s.host_flags);
     if (s.host_sum) (void)hipHostFree(s.host_sum);
-    for (void *hp : {(void *)s.h_q, (void *)s.h_ids, (void *)s.h_scores, (void *)s.h_dists, (void *)s.h_nf})
+    for (void *hp : {(void *)s.h_q, (void *)s.h_ids, (void *)s.h_scores, (void *)s.h_dists, (void *)s.h_nf, (void *)s.h_nr})
         if (hp) (void)hipHostFree(hp);
+    F(s.rlim); F(s.out_nrange);
     F(s.qstage); F(s.qscale); F(s.qa); F(s.qb); F(s.qmean); F(s.out_ids); F(s.out_scores); F(s.out_dists); F(s.out_nfound);
     F(s.exact_scratch); F(s.max_err);
     if (idx->ev0) (void)hipEventDestroy(idx->ev0);
@@ -443,6 +450,9 @@ int ensure_scratch(mx_index *idx) {
     MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_q), (size_t)kMaxBatch * idx->dim * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
     MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_nf), kMaxBatch * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
     MX_HIP(hipMalloc(&s.max_err, sizeof(float)));
+    MX_HIP(hipMalloc(&s.rlim, kMaxBatch * sizeof(uint32_t)));
+    MX_HIP(hipMalloc(&s.out_nrange, kMaxBatch * sizeof(uint64_t)));
+    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_nr), kMaxBatch * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
     MX_HIP(hipMemsetAsync(s.max_err, 0, sizeof(float), idx->stream));
     s.ready = true;
     return MX_OK;
@@ -990,6 +1000,55 @@ bool subset_pays(const mx_index *idx, int B, uint64_t m, uint64_t span_rows, int
     return subset_us <= masked_us;
 }
 
+// Wait for the completion word of a finish launch (finish_kernel, range_finish_kernel) with sequence number seq, for a batch of B
+// queries.  A kernel that never signals (fault) is caught by the synchronize after the spin budget.
+int await_finish(mx_index *idx, int B, uint32_t seq) {
+    Scratch &s = idx->s;
+    // Default: a SLEEPING wait -- a server thread must not burn a core for the ~1 ms of a batch.  The HIP runtime's
+    // own waits do not help: hipStreamSynchronize and hipEventSynchronize (also on a hipEventBlockingSync event)
+    // poll with the default scheduling policy -- 100 % of a core in all three forms (scripts/gpu_wait_modes.py) --
+    // and hipSetDeviceFlags(BlockingSync) is not this library's to set in a host process.  So: sleep for most of
+    // what the last batches took (clock_nanosleep), then poll the completion word; the estimate follows the
+    // workload (an EMA of the wait just observed).  MEMEX_HIP_SPIN=1 (bench.py sets it) polls from the start.
+    static const bool no_spin = [] {
+        const char *sp = getenv("MEMEX_HIP_SPIN");
+        return !(sp && sp[0] == '1');
+    }();
+    const auto t0 = std::chrono::steady_clock::now();
+    double &ema = idx->wait_ema_us[B <= 32 ? 0 : B <= 128 ? 1 : B <= 256 ? 2 : 3];
+    bool overslept = false;  // the batch was already complete when the nap ended: the estimate is too long
+    if (no_spin && ema > 150.0) {
+        const double nap_us = 0.8 * ema - 60.0;  // timer slack and wake-up latency stay inside the estimate
+        if (nap_us > 50.0) {
+            struct timespec ts;
+            ts.tv_sec = (time_t)(nap_us / 1e6);
+            ts.tv_nsec = (long)((nap_us - (double)ts.tv_sec * 1e6) * 1e3);
+            (void)clock_nanosleep(CLOCK_MONOTONIC, 0, &ts, nullptr);
+            overslept = __atomic_load_n(&s.host_sum[4], __ATOMIC_ACQUIRE) == seq;
+        }
+    }
+    bool done = false;
+    for (unsigned spins = 1;; ++spins) {
+        if (__atomic_load_n(&s.host_sum[4], __ATOMIC_ACQUIRE) == seq) {
+            done = true;
+            break;
+        }
+        if ((spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
+        __builtin_ia32_pause();
+    }
+    if (done) {
+        // what was observed includes the nap: when the batch had finished before the nap did (batches got faster: a
+        // cleared or smaller index, another k) only an upper bound is known, so the estimate is halved instead of
+        // creeping down 5 % per batch
+        const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        ema = overslept ? 0.5 * ema : ema > 0.0 ? 0.75 * ema + 0.25 * us : us;
+        return MX_OK;
+    }
+    MX_HIP(hipStreamSynchronize(idx->stream));  // a kernel that never signals (fault): the synchronize reports it
+    if (__atomic_load_n(&s.host_sum[4], __ATOMIC_ACQUIRE) == seq) return MX_OK;
+    return fail(MX_EDEVICE, "finish_kernel did not signal completion");
+}
+
 // one batch (B <= 256) with queries and outputs on the device; filt: the local rows a filtered search allows (normalised)
 int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
                  int32_t *d_nfound, const Ranges *filt = nullptr) {
@@ -1135,51 +1194,8 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     auto finish_and_wait = [&]() -> int {
         fp.seq = ++s.flag_seq;
         MX_HIP(launch_finish(st, B, fp));
-        // Default: a SLEEPING wait -- a server thread must not burn a core for the ~1 ms of a batch.  The HIP runtime's
-        // own waits do not help: hipStreamSynchronize and hipEventSynchronize (also on a hipEventBlockingSync event)
-        // poll with the default scheduling policy -- 100 % of a core in all three forms (scripts/gpu_wait_modes.py) --
-        // and hipSetDeviceFlags(BlockingSync) is not this library's to set in a host process.  So: sleep for most of
-        // what the last batches took (clock_nanosleep), then poll the completion word; the estimate follows the
-        // workload (an EMA of the wait just observed).  MEMEX_HIP_SPIN=1 (bench.py sets it) polls from the start.
-        static const bool no_spin = [] {
-            const char *sp = getenv("MEMEX_HIP_SPIN");
-            return !(sp && sp[0] == '1');
-        }();
-        const auto t0 = std::chrono::steady_clock::now();
-        double &ema = idx->wait_ema_us[B <= 32 ? 0 : B <= 128 ? 1 : B <= 256 ? 2 : 3];
-        bool overslept = false;  // the batch was already complete when the nap ended: the estimate is too long
-        if (no_spin && ema > 150.0) {
-            const double nap_us = 0.8 * ema - 60.0;  // timer slack and wake-up latency stay inside the estimate
-            if (nap_us > 50.0) {
-                struct timespec ts;
-                ts.tv_sec = (time_t)(nap_us / 1e6);
-                ts.tv_nsec = (long)((nap_us - (double)ts.tv_sec * 1e6) * 1e3);
-                (void)clock_nanosleep(CLOCK_MONOTONIC, 0, &ts, nullptr);
-                overslept = __atomic_load_n(&s.host_sum[4], __ATOMIC_ACQUIRE) == fp.seq;
-            }
-        }
-        bool done = false;
-        for (unsigned spins = 1;; ++spins) {
-            if (__atomic_load_n(&s.host_sum[4], __ATOMIC_ACQUIRE) == fp.seq) {
-                done = true;
-                break;
-            }
-            if ((spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-            __builtin_ia32_pause();
-        }
-        if (done) {
-            // what was observed includes the nap: when the batch had finished before the nap did (batches got faster: a
-            // cleared or smaller index, another k) only an upper bound is known, so the estimate is halved instead of
-            // creeping down 5 % per batch
-            const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-            ema = overslept ? 0.5 * ema : ema > 0.0 ? 0.75 * ema + 0.25 * us : us;
-            return MX_OK;
-        }
-        MX_HIP(hipStreamSynchronize(st));  // a kernel that never signals (fault): the synchronize reports it
-        if (__atomic_load_n(&s.host_sum[4], __ATOMIC_ACQUIRE) == fp.seq) return MX_OK;
-        return fail(MX_EDEVICE, "finish_kernel did not signal completion");
+        return await_finish(idx, B, fp.seq);
     };
-
     std::vector<int> exact;
     if (trivial) {
         fp.seq = ++s.flag_seq;
@@ -1330,6 +1346,227 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     return MX_OK;
 }
 
+// the per-query flag words of the batch, host-synchronised
+int fetch_flags_now(mx_index *idx) {
+    MX_HIP(hipMemcpyAsync(idx->s.host_flags, idx->s.dev_flags, kFlagWords * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
+    MX_HIP(hipStreamSynchronize(idx->stream));
+    return MX_OK;
+}
+
+// ---- range search (mx_index_search_range) -----------------------------------------------------------------
+// Score of a dist, exactly as the device computes it (score_from_dist) and as the reference reports it: f32 1 / (1 / d), 1 - that
+float host_score_from_dist(float d) {
+    const volatile float t = 1.0f / d;  // (volatile: each rounding to f32 happens, whatever the host compiler keeps in registers)
+    const volatile float u = 1.0f / t;
+    return 1.0f - u;
+}
+
+// The threshold t as a dist bound: score is a non-increasing function of the f32 dist (three monotone roundings), so "score >= t" is
+// "dist <= D(t)" with D(t) the largest f32 in [0, 4] whose score reaches t -- found by bisection over the bit patterns, which order the
+// non-negative floats.  Returned as bits(D) + 1 (in range <=> bits(dist) < it); 0 when t > 1 selects nothing.  t must not be NaN.
+uint32_t range_dist_limit(float t) {
+    if (!(t <= 1.0f)) return 0;                // score(0) = 1 is the largest score
+    uint32_t lo = 0, hi = 0x40800000u;         // score(bits lo) >= t holds; 4.0 is past every dist (cos >= -1 - 2^-22)
+    if (host_score_from_dist(4.0f) >= t) return hi + 1;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        float d;
+        memcpy(&d, &mid, sizeof d);
+        if (host_score_from_dist(d) >= t) lo = mid;
+        else hi = mid;
+    }
+    return lo + 1;
+}
+
+// |cos - (1 - dist)| of the reference's chain on f32 rows: f32 products (relative 2^-24 each), f64 sums (ds 2^-53), the f64 sqrt /
+// divide / subtract (a few 2^-53), then the f32 rounding of dist (at most 2^-24 below 2, 2^-23 up to 4): at most 2^-22 + 2^-23 + ...
+// for |cos| <= 1.  kRangeEps = 2^-20 leaves room for the f32 arithmetic of the bounds it is combined with.
+constexpr float kRangeEps = 9.5367431640625e-7f;
+
+// EXACT range path for the queries qs of the batch
+int run_exact_range(mx_index *idx, const std::vector<int> &qs, int cap, uint64_t *d_ids, float *d_scores, float *d_dists,
+                    int32_t *d_nfound, uint64_t *d_nrange, const uint64_t *mask, uint64_t n_live) {
+    if (qs.empty()) return MX_OK;
+    int gcap = qs.size() <= 4 ? 4 : qs.size() <= 8 ? 8 : qs.size() <= 16 ? 16 : kExactGroup;
+    int rc = ensure_exact(idx, cap, &gcap);
+    if (rc != MX_OK) return rc;
+    Scratch &s = idx->s;
+    for (size_t g0 = 0; g0 < qs.size(); g0 += (size_t)gcap) {
+        ExactGroup grp{};
+        grp.n = (int)std::min<size_t>((size_t)gcap, qs.size() - g0);
+        for (int j = 0; j < grp.n; ++j) grp.q[j] = qs[g0 + j];
+        MX_HIP(launch_exact_range_group(idx->stream, cap, idx->ds, idx->compressed ? nullptr : idx->x, idx->xh, idx->n, idx->idmap, s.qpad,
+                                        s.qnorm2, grp, s.exact_scratch, s.rlim, d_ids, d_scores, d_dists, d_nfound, d_nrange, mask, n_live));
+    }
+    return MX_OK;
+}
+
+// one range batch (B <= 512) with queries and outputs on the device; dlim: the B dist bounds (host memory).  The top-k pipeline minus
+// the sample and theta launches: theta follows from the caller's threshold (launch_range_theta), one collect launch over every tile with
+// the geometry search_batch picks for B, range_finish_kernel.  No retry pass; its overflows and everything search_batch sends to the
+// EXACT path (but k > 256) take the EXACT range path.  The filter copy's heuristics are left alone.
+int range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t *dlim, uint64_t *d_ids, float *d_scores, float *d_dists,
+                int32_t *d_nfound, uint64_t *d_nrange) {
+    int rc = ensure_scratch(idx);
+    if (rc != MX_OK) return rc;
+    Scratch &s = idx->s;
+    hipStream_t st = idx->stream;
+    const uint64_t n_live = idx->n - idx->n_dead;
+    const bool trivial = idx->n == 0 || n_live == 0;
+    if (idx->compressed && idx->kc > kMaxKC16 && !trivial)
+        return fail(MX_EUNSUPPORTED, "a compressed corpus supports dim <= %d", kMaxKC16 * kChunkFloats);
+    const bool filt8 = idx->xh != nullptr && idx->filter_i8 && !idx->compressed;
+    const bool wide = idx->kc > kMaxKC && !filt8;
+    const bool fast = !trivial && idx->mode == MX_SEARCH_AUTO && (idx->kc > kMaxKC ? idx->xh != nullptr && idx->kc <= kMaxKC16 : true) &&
+                      (!idx->compressed || idx->wild_rows == 0) && idx->n_zero <= (uint64_t)kZeroCap && idx->n_wild <= (uint64_t)kWildCap;
+    const bool centred8 = idx->centred && filt8 && idx->amean && idx->mean && idx->kc <= kMaxKC;
+    const bool x2 = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch;
+    const bool pair = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch / 2 && B <= kPassBatch && idx->scan8_pair;
+    const int nwg = pair ? 2 * idx->nwg : idx->nwg;
+    const int split = B > kPassBatch && !x2 && !(fast && wide) ? kPassBatch : fast && wide && B > kWideBatch ? kWideBatch : 0;
+    if (split) {
+        rc = range_batch(idx, d_q, split, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange);
+        if (rc != MX_OK) return rc;
+        const size_t o = (size_t)split * cap;
+        return range_batch(idx, d_q + (size_t)split * idx->dim, B - split, cap, dlim + split, d_ids + o, d_scores + o,
+                           d_dists ? d_dists + o : nullptr, d_nfound + split, d_nrange + split);
+    }
+    const bool centred = centred8 || (idx->centred && idx->xh && !filt8 && !wide && !idx->compressed && idx->amean && idx->mean && idx->kc <= kMaxKC);
+    const uint32_t *h_ovf = s.host_flags, *h_qfl = s.host_flags + 3 * kMaxBatch;
+    const uint64_t *mask = idx->n_dead ? idx->dead : nullptr;
+    LaneLease lease;
+    if (fast && (rc = lease.take(idx, x2 || pair ? 2 : 1)) != MX_OK) return rc;
+    MX_HIP(hipMemcpyAsync(s.rlim, dlim, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
+                               idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
+                               centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
+    std::vector<int> exact;
+    if (fast) {
+        MX_HIP(launch_range_theta(st, B, s.rlim, kRangeEps, s.qa, s.theta));
+        const uint64_t trows = filt8 ? kTile8Rows : kTileRows;
+        const uint64_t tiles = (idx->n + trows - 1) / trows;
+        ScanParams p;
+        p.x = idx->x;
+        p.xh = idx->xh;
+        p.scale = idx->scale;
+        p.qfrag = s.qfrag;
+        p.theta = s.theta;
+        p.n_rows = idx->n;
+        p.ds = (uint32_t)idx->ds;
+        p.wave_mask = (1u << ((B + 31) / 32)) - 1u;
+        p.lane_rec = s.lane_rec;
+        p.lane_tile = s.lane_tile;
+        p.lane_cnt = s.lane_cnt;
+        p.lane_max = s.lane_max;
+        p.overflow = s.overflow;
+        p.tscale = idx->tsc;
+        p.qscale = s.qscale;
+        p.qa = s.qa;
+        p.qb = s.qb;
+        p.amean = centred ? idx->amean : nullptr;
+        p.qmean = s.qmean;
+        p.dead = mask;
+        p.tile_begin = 0;
+        p.tile_end = (uint32_t)tiles;
+        p.tile_stride = 1;
+        if (filt8) MX_HIP(launch_scan8(st, idx->kc, true, nwg, p, pair ? Scan8Geom::kPair : x2 ? Scan8Geom::k512 : Scan8Geom::k256));
+        else if (wide) MX_HIP(launch_scan16w(st, idx->kc, true, idx->nwg, p));
+        else if (idx->xh) MX_HIP(launch_scan16(st, idx->kc, true, idx->nwg, p));
+        else MX_HIP(launch_scan(st, idx->kc, true, idx->nwg, p));
+        idx->stats.scan_launches += 1;
+        idx->stats.scan_bytes += tiles * trows * idx->ds * (filt8 ? 1ull : idx->xh ? 2ull : 4ull);
+
+        RangeParams rp;
+        FinishParams &fp = rp.f;
+        fp.k = cap;
+        fp.ds = idx->ds;
+        fp.nwg = nwg;
+        fp.x = idx->compressed ? nullptr : idx->x;
+        fp.xh = idx->xh;
+        fp.scale = idx->scale;
+        fp.n_rows = idx->n;
+        fp.idmap = idx->idmap;
+        fp.qpad = s.qpad;
+        fp.qnorm2 = s.qnorm2;
+        fp.e1 = s.e1;
+        fp.qa = s.qa;
+        fp.qb = s.qb;
+        fp.terr = filt8 ? idx->tsc : nullptr;
+        fp.e2 = (float)(idx->ds + 8) * 5.9604645e-8f + 1e-6f;  // (search_batch's)
+        fp.lane_rec = s.lane_rec;
+        fp.lane_tile = s.lane_tile;
+        fp.lane_cnt = s.lane_cnt;
+        fp.theta = s.theta;
+        fp.zero_rows = idx->zero_rows;
+        fp.n_zero = (uint32_t)std::min<uint64_t>(idx->n_zero, kZeroCap);
+        fp.wild_rows = idx->wild_list;
+        fp.n_wild = (uint32_t)std::min<uint64_t>(idx->n_wild, kWildCap);
+        fp.dead = mask;
+        fp.n_live = n_live;
+        fp.overflow = s.overflow;
+        fp.todo = nullptr;
+        fp.theta_retry = s.theta_retry;
+        fp.cand_cnt = s.cand_cnt;
+        fp.ids = d_ids;
+        fp.scores = d_scores;
+        fp.dists = d_dists;
+        fp.n_found = d_nfound;
+        fp.max_err = nullptr;
+        fp.done_ctr = s.done_ctr;
+        fp.dev_flags = s.dev_flags;
+        fp.host_flags = s.host_sum;
+        fp.n_queries = B;
+        fp.host_out = s.out_on_host ? 1 : 0;
+        fp.seq = ++s.flag_seq;
+        rp.dlim = s.rlim;
+        rp.eps = kRangeEps;
+        rp.n_in_range = d_nrange;
+        MX_HIP(launch_range_finish(st, B, rp));
+        if ((rc = await_finish(idx, B, fp.seq)) != MX_OK) return rc;
+        if (s.host_sum[2]) return fail(MX_EINVAL, "a query contains non-finite values");
+        idx->stats.candidates += s.host_sum[1];
+        if (s.host_sum[0]) {
+            if ((rc = fetch_flags_now(idx)) != MX_OK) return rc;
+            for (int b = 0; b < B; ++b)
+                if (h_ovf[b] != 0) exact.push_back(b);
+        }
+        idx->stats.fallback_queries += exact.size();
+    } else {
+        if ((rc = fetch_flags_now(idx)) != MX_OK) return rc;
+        for (int b = 0; b < B; ++b)
+            if (h_qfl[b]) return fail(MX_EINVAL, "a query contains non-finite values");
+        for (int b = 0; b < B && !trivial; ++b) exact.push_back(b);
+        if (trivial) {  // nothing in range: empty lists, zero counts
+            MX_HIP(hipMemsetAsync(s.rlim, 0, (size_t)B * sizeof(uint32_t), st));
+            RangeParams rp{};
+            rp.f.k = cap;
+            rp.f.ds = idx->ds;
+            rp.f.x = idx->x;
+            rp.f.ids = d_ids;
+            rp.f.scores = d_scores;
+            rp.f.dists = d_dists;
+            rp.f.n_found = d_nfound;
+            rp.f.cand_cnt = s.cand_cnt;
+            rp.dlim = s.rlim;
+            rp.n_in_range = d_nrange;
+            MX_HIP(launch_range_finish(st, B, rp));
+        }
+    }
+    if (!exact.empty() || trivial) {
+        rc = run_exact_range(idx, exact, cap, d_ids, d_scores, d_dists, d_nfound, d_nrange, mask, n_live);
+        if (rc != MX_OK) return rc;
+        MX_HIP(hipStreamSynchronize(st));
+        if (idx->mode == MX_SEARCH_AUTO && idx->s.exact_bytes > kExactKeepBytes) {
+            (void)hipFree(idx->s.exact_scratch);
+            idx->s.exact_scratch = nullptr;
+            idx->s.exact_bytes = 0;
+        }
+    }
+    idx->stats.searches += 1;
+    idx->stats.queries += (uint64_t)B;
+    return MX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // composite: rows dealt block-cyclically to shard indexes (one per device), local top-k per shard,
 // exchange of the packed [ids | dists] blocks (RCCL all-gather over xGMI, or peer copies), merge
@@ -1368,7 +1605,7 @@ int ensure_composite_buffers(mx_index *idx, int k) {
     free_composite_buffers(idx);
     const int kc = std::max(k, 16);
     const size_t G = idx->shards.size();
-    const size_t blk = (size_t)kMaxBatch * kc * 12;
+    const size_t blk = (size_t)kMaxBatch * kc * 12 + kMaxBatch * sizeof(uint64_t);  // [ids | dists] (+ the counts of a range pass)
     idx->sh_block.assign(G, nullptr); idx->sh_gather.assign(G, nullptr); idx->sh_q.assign(G, nullptr);
     idx->sh_scores.assign(G, nullptr); idx->sh_nf.assign(G, nullptr);
     for (size_t g = 0; g < G; ++g) {
@@ -1597,6 +1834,89 @@ int any_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, fl
               int32_t *d_nfound, const Ranges *filt = nullptr) {
     return idx->composite() ? composite_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, filt)
                             : search_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, filt);
+}
+
+// one range batch on a composite: every shard answers its rows with range_batch; the per-shard counts travel behind the packed
+// [ids | dists] block (RCCL all-gather or peer copy), are summed, and the lists merged by (dist, id) at k = cap
+int composite_range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t *dlim, uint64_t *d_ids, float *d_scores,
+                          float *d_dists, int32_t *d_nfound, uint64_t *d_nrange) {
+    const int G = (int)idx->shards.size();
+    int rc = ensure_composite_buffers(idx, cap);
+    if (rc != MX_OK) return rc;
+    const size_t ids_bytes = (size_t)B * cap * sizeof(uint64_t), lists = ids_bytes + (size_t)B * cap * sizeof(float);
+    const size_t blk = lists + (size_t)B * sizeof(uint64_t);  // ... | counts [B]
+    std::vector<int> rcs(G, MX_OK);
+    std::vector<std::string> errs(G);
+    auto local = [&](int g) {
+        mx_index *sh = idx->shards[g];
+        std::lock_guard<std::mutex> lk(sh->mu);
+        DeviceGuard dg(sh->device);
+        auto run = [&]() -> int {
+            MX_HIP(hipMemcpyAsync(idx->sh_q[g], d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
+            char *blkp = static_cast<char *>(idx->sh_block[g]);
+            int r = range_batch(sh, idx->sh_q[g], B, cap, dlim, reinterpret_cast<uint64_t *>(blkp), idx->sh_scores[g],
+                                reinterpret_cast<float *>(blkp + ids_bytes), idx->sh_nf[g], reinterpret_cast<uint64_t *>(blkp + lists));
+            if (r != MX_OK) return r;
+            if (!idx->use_rccl) {
+                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
+                MX_HIP(hipStreamSynchronize(sh->stream));
+            }
+            return MX_OK;
+        };
+        try {
+            rcs[g] = run();
+        } catch (...) {
+            rcs[g] = guard_exception();
+        }
+        if (rcs[g] != MX_OK) errs[g] = last_error_slot();
+    };
+    {
+        DeviceGuard dg(idx->shards[0]->device);
+        MX_HIP(hipStreamSynchronize(idx->shards[0]->stream));
+    }
+    if (idx->pool) idx->pool->run(local);
+    else
+        for (int g = 0; g < G; ++g) local(g);
+    for (int g = 0; g < G; ++g)
+        if (rcs[g] != MX_OK) {
+            last_error_slot() = errs[g];
+            return rcs[g];
+        }
+    mx_index *s0 = idx->shards[0];
+    DeviceGuard dg(s0->device);
+    const auto t_tail = std::chrono::steady_clock::now();
+    if (idx->use_rccl) {
+        int e = g_rccl.GroupStart();
+        for (int g = 0; g < G && e == 0; ++g)
+            e = g_rccl.AllGather(idx->sh_block[g], idx->sh_gather[g], blk, 1 /*ncclUint8*/, idx->comms[g], idx->shards[g]->stream);
+        const int e2 = g_rccl.GroupEnd();
+        if (e != 0 || e2 != 0) {  // as composite_batch: this batch and every later one exchange by copies
+            fprintf(stderr, "memex-hip: RCCL all-gather failed (%s); the sharded index continues on peer copies\n",
+                    g_rccl.GetErrorString && (e > 1 || e2) ? g_rccl.GetErrorString(e ? e : e2) : "error");
+            if (!sync_shard_streams_within(idx, 10.0))
+                return fail(MX_EDEVICE, "RCCL all-gather failed and a shard stream did not drain within 10 s");
+            idx->use_rccl = false;
+            idx->stats.exchange_fallbacks += 1;
+            enable_peer_access(idx);
+            for (int g = 0; g < G; ++g)
+                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, idx->sh_block[g], blk, hipMemcpyDefault, s0->stream));
+        }
+    }
+    const char *gat = static_cast<const char *>(idx->sh_gather[0]);
+    MX_HIP(launch_merge(s0->stream, gat, blk, gat + ids_bytes, blk, G, B, cap, d_ids,
+                        d_dists ? d_dists : reinterpret_cast<float *>(static_cast<char *>(idx->sh_block[0]) + ids_bytes), d_scores));
+    MX_HIP(launch_range_sum(s0->stream, gat + lists, blk, G, B, cap, d_nrange, d_nfound));
+    MX_HIP(hipStreamSynchronize(s0->stream));
+    idx->stats.exchange_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count();
+    idx->stats.searches += 1;
+    idx->stats.queries += (uint64_t)B;
+    return MX_OK;
+}
+
+int any_range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t *dlim, uint64_t *d_ids, float *d_scores, float *d_dists,
+                    int32_t *d_nfound, uint64_t *d_nrange) {
+    return idx->composite() ? composite_range_batch(idx, d_q, B, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange)
+                            : range_batch(idx, d_q, B, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange);
 }
 
 // what an append can change in a plain index, and how to undo it: an insert is all-or-nothing, also when it
@@ -2048,6 +2368,7 @@ int open_plain(const std::string &k, int dim, int device, mx_index **out) {
         if (g_scan_setup_err == hipSuccess) g_scan_setup_err = scan8_setup();
         if (g_scan_setup_err == hipSuccess) g_scan_setup_err = finish_setup();
         if (g_scan_setup_err == hipSuccess) g_scan_setup_err = subset_setup();
+        if (g_scan_setup_err == hipSuccess) g_scan_setup_err = range_setup();
     });
     if (g_scan_setup_err != hipSuccess)
         return fail(MX_EDEVICE, "scan kernel setup failed: %s (is this a gfx950 device?)", hipGetErrorString(g_scan_setup_err));
@@ -2796,6 +3117,53 @@ int mx_index_search_filtered_device(mx_index *idx, const float *d_q, int B, int 
 
 namespace {
 
+// run_combined for a range pass (every request of it has the same cap): the requests' dist bounds side by side, outputs as run_combined's
+// plus the pinned n_in_range staging
+int run_combined_range(mx_index *idx, const std::vector<SearchReq *> &batch) {
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    DeviceGuard g(t->device);
+    const int cap = batch[0]->k;
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, cap)) != MX_OK) return rc;
+    Scratch &s = t->s;
+    const size_t dim = (size_t)idx->dim;
+    int nb = 0;
+    std::vector<uint32_t> dl;
+    for (const SearchReq *r : batch) {
+        memcpy(s.h_q + (size_t)nb * dim, r->q, (size_t)r->B * dim * sizeof(float));
+        dl.insert(dl.end(), r->dlim, r->dlim + r->B);
+        nb += r->B;
+    }
+    if (!idx->composite()) {  // outputs straight into the mapped staging buffers (see run_combined)
+        s.out_on_host = true;
+        rc = any_range_batch(idx, s.h_q, nb, cap, dl.data(), s.h_ids, s.h_scores, s.h_dists, s.h_nf, s.h_nr);
+        s.out_on_host = false;
+        if (rc != MX_OK) return rc;
+        std::atomic_thread_fence(std::memory_order_acquire);
+    } else {
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        rc = any_range_batch(idx, s.qstage, nb, cap, dl.data(), s.out_ids, s.out_scores, s.out_dists, s.out_nfound, s.out_nrange);
+        if (rc != MX_OK) return rc;
+        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * cap * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * cap * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * cap * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_nr, s.out_nrange, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipStreamSynchronize(t->stream));
+    }
+    int b0 = 0;
+    for (SearchReq *r : batch) {
+        memcpy(r->ids, s.h_ids + (size_t)b0 * cap, (size_t)r->B * cap * sizeof(uint64_t));
+        memcpy(r->scores, s.h_scores + (size_t)b0 * cap, (size_t)r->B * cap * sizeof(float));
+        if (r->dists) memcpy(r->dists, s.h_dists + (size_t)b0 * cap, (size_t)r->B * cap * sizeof(float));
+        memcpy(r->n_found, s.h_nf + b0, (size_t)r->B * sizeof(int32_t));
+        memcpy(r->n_in_range, s.h_nr + b0, (size_t)r->B * sizeof(uint64_t));
+        b0 += r->B;
+    }
+    return MX_OK;
+}
+
 // one GPU batch (sum of B <= 256, same k) for a group of host requests: queries are packed into
 // pinned memory, one H2D, the search pipeline, one D2H per output array, results scattered to the callers
 int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
@@ -2804,6 +3172,7 @@ int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
     DeviceGuard g(t->device);
     const int k = batch[0]->k;
+    if (batch[0]->dlim) return run_combined_range(idx, batch);
     Ranges rows;  // a filtered pass: every request of it has the same ranges
     if (batch[0]->filt) rows = rows_of_ids(*batch[0]->filt, idx->idmap.id_offset, rows_of(idx));
     const Ranges *filt = batch[0]->filt ? &rows : nullptr;
@@ -2867,30 +3236,8 @@ namespace {
 
 bool same_filter(const Ranges *a, const Ranges *b) { return a == b || (a && b && *a == *b); }
 
-// mx_index_search and its filtered form (filt: normalised id ranges, or null)
-int search_host(mx_index *idx, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists, int32_t *n_found,
-                const Ranges *filt) {
-    if (!idx) return fail(MX_ESEARCH, "null index");
-    if (B < 0 || k < 0) return fail(MX_EINVAL, "negative batch or k");
-    if (B == 0) return MX_OK;
-    if (!q || !n_found || (k > 0 && (!ids || !scores))) return fail(MX_EINVAL, "null argument");
-    if (k > 4096) return fail(MX_EUNSUPPORTED, "k = %d > 4096", k);
-    {   // reject non-finite queries here, per caller: inside a combined batch they would fail everyone
-        const size_t total = (size_t)B * idx->dim;
-        for (size_t i = 0; i < total; ++i)
-            if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / idx->dim);
-    }
-    if (B > kMaxBatch) {  // large requests are their own batches: split and recurse
-        for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
-            const int nb = std::min(kMaxBatch, B - b0);
-            int rc = search_host(idx, q + (size_t)b0 * idx->dim, nb, k, ids ? ids + (size_t)b0 * k : nullptr,
-                                 scores ? scores + (size_t)b0 * k : nullptr,
-                                 dists ? dists + (size_t)b0 * k : nullptr, n_found + b0, filt);
-            if (rc != MX_OK) return rc;
-        }
-        return MX_OK;
-    }
-    SearchReq req{q, B, k, ids, scores, dists, n_found, filt};
+// queues one host request and waits for its answer; the caller that finds no leader serves batches until its own request is done
+int serve(mx_index *idx, SearchReq &req) {
     std::unique_lock<std::mutex> ql(idx->cmu);
     idx->pending.push_back(&req);
     idx->ccv.wait(ql, [&] { return req.done || !idx->leader; });
@@ -2903,9 +3250,10 @@ int search_host(mx_index *idx, const float *q, int B, int k, uint64_t *ids, floa
             int total = 0;
             const int bk = idx->pending.front()->k;
             const Ranges *bf = idx->pending.front()->filt;
+            const bool brange = idx->pending.front()->dlim != nullptr;  // range requests combine only with range requests
             for (auto it = idx->pending.begin(); it != idx->pending.end();) {
                 SearchReq *r = *it;
-                if (r->k == bk && same_filter(r->filt, bf) && total + r->B <= kMaxBatch) {
+                if (r->k == bk && same_filter(r->filt, bf) && (r->dlim != nullptr) == brange && total + r->B <= kMaxBatch) {
                     batch.push_back(r);
                     total += r->B;
                     it = idx->pending.erase(it);
@@ -2937,6 +3285,33 @@ int search_host(mx_index *idx, const float *q, int B, int k, uint64_t *ids, floa
     return req.rc;
 }
 
+// mx_index_search and its filtered form (filt: normalised id ranges, or null)
+int search_host(mx_index *idx, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists, int32_t *n_found,
+                const Ranges *filt) {
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B < 0 || k < 0) return fail(MX_EINVAL, "negative batch or k");
+    if (B == 0) return MX_OK;
+    if (!q || !n_found || (k > 0 && (!ids || !scores))) return fail(MX_EINVAL, "null argument");
+    if (k > 4096) return fail(MX_EUNSUPPORTED, "k = %d > 4096", k);
+    {   // reject non-finite queries here, per caller: inside a combined batch they would fail everyone
+        const size_t total = (size_t)B * idx->dim;
+        for (size_t i = 0; i < total; ++i)
+            if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / idx->dim);
+    }
+    if (B > kMaxBatch) {  // large requests are their own batches: split and recurse
+        for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+            const int nb = std::min(kMaxBatch, B - b0);
+            int rc = search_host(idx, q + (size_t)b0 * idx->dim, nb, k, ids ? ids + (size_t)b0 * k : nullptr,
+                                 scores ? scores + (size_t)b0 * k : nullptr,
+                                 dists ? dists + (size_t)b0 * k : nullptr, n_found + b0, filt);
+            if (rc != MX_OK) return rc;
+        }
+        return MX_OK;
+    }
+    SearchReq req{q, B, k, ids, scores, dists, n_found, filt};
+    return serve(idx, req);
+}
+
 }  // namespace
 
 int mx_index_search(mx_index *idx, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists,
@@ -2951,6 +3326,69 @@ int mx_index_search_filtered(mx_index *idx, const float *q, int B, int k, const 
     Ranges id_ranges;
     if (int rc = read_id_ranges(ranges, n_ranges, &id_ranges); rc != MX_OK) return rc;
     return search_host(idx, q, B, k, ids, scores, dists, n_found, &id_ranges);
+} catch (...) {
+    return guard_exception();
+}
+
+namespace {
+
+// arguments of the range entry points, checked before the index is looked at; dlim: the thresholds as dist bounds
+int read_range_args(int B, const float *min_scores, int cap, std::vector<uint32_t> *dlim) {
+    if (B < 0) return fail(MX_EINVAL, "negative batch");
+    if (cap < 1) return fail(MX_EINVAL, "cap = %d < 1", cap);
+    if (cap > 4096) return fail(MX_EUNSUPPORTED, "cap = %d > 4096", cap);
+    if (B > 0 && !min_scores) return fail(MX_EINVAL, "null min_scores");
+    dlim->resize((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        if (std::isnan(min_scores[b])) return fail(MX_EINVAL, "min_scores[%d] is NaN", b);
+        (*dlim)[b] = range_dist_limit(min_scores[b]);
+    }
+    return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_search_range(mx_index *idx, const float *q, int B, const float *min_scores, int cap, uint64_t *ids, float *scores, float *dists,
+                          int32_t *n_found, uint64_t *n_in_range) try {
+    std::vector<uint32_t> dlim;
+    if (int rc = read_range_args(B, min_scores, cap, &dlim); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B == 0) return MX_OK;
+    if (!q || !ids || !scores || !n_found || !n_in_range) return fail(MX_EINVAL, "null argument");
+    const size_t total = (size_t)B * idx->dim;
+    for (size_t i = 0; i < total; ++i)
+        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / idx->dim);
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {  // large requests are their own batches
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * cap;
+        SearchReq req{q + (size_t)b0 * idx->dim, nb, cap, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, nullptr};
+        req.dlim = dlim.data() + b0;
+        req.n_in_range = n_in_range + b0;
+        if (int rc = serve(idx, req); rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_range_device(mx_index *idx, const float *d_q, int B, const float *min_scores, int cap, uint64_t *d_ids,
+                                 float *d_scores, float *d_dists, int32_t *d_nfound, uint64_t *d_n_in_range) try {
+    std::vector<uint32_t> dlim;
+    if (int rc = read_range_args(B, min_scores, cap, &dlim); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B == 0) return MX_OK;
+    if (!d_q || !d_ids || !d_scores || !d_nfound || !d_n_in_range) return fail(MX_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    DeviceGuard g(idx->device);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * cap;
+        int rc = any_range_batch(idx, d_q + (size_t)b0 * idx->dim, nb, cap, dlim.data() + b0, d_ids + o, d_scores + o,
+                                 d_dists ? d_dists + o : nullptr, d_nfound + b0, d_n_in_range + b0);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
 } catch (...) {
     return guard_exception();
 }

@@ -259,6 +259,22 @@ hipError_t finish_setup();
 hipError_t launch_finish(hipStream_t s, int B, const FinishParams &p);
 hipError_t launch_retry_setup(hipStream_t s, float *theta, const float *theta_retry, uint32_t *overflow, uint32_t *todo);
 
+// range search (mx_index_search_range).  dlim[q]: row r is in range for query q iff the bits of its f32 dist
+// are < dlim[q] (0: nothing is).  theta[q] = 1 - D - eps - qa[q] for the collect launch (D: the largest dist in range), zero-norm and
+// padded queries stay at +inf.
+hipError_t launch_range_theta(hipStream_t s, int B, const uint32_t *dlim, float eps, const float *qa, float *theta);
+// finish stage of a range batch: f.k = cap; the exact count of in-range live rows per query goes to n_in_range, the best
+// min(cap, count) of them to ids / scores / dists / n_found (best first, unused slots id 0, score 0, dist +inf).  overflow[q] = 2: the
+// query needs the EXACT range path.  Completion signal as finish_kernel's.
+struct RangeParams {
+    FinishParams f;
+    const uint32_t *dlim;  // [256]
+    float eps;             // bound on |cos - (1 - dist)| of the f64 chain and the f32 rounding of dist, with slack
+    uint64_t *n_in_range;
+};
+hipError_t range_setup();
+hipError_t launch_range_finish(hipStream_t s, int B, const RangeParams &rp);
+
 // EXACT path, batched: a group of up to kExactGroup queries against every row in one pass (f32 products, sequential f64
 // sums per pair: DistCosine), then a 3-pass radix select per query with ties ordered by row.  Queries are named by
 // their slot in qpad / qnorm2 / the output arrays; scratch holds exact_group_scratch_bytes(n_rows, k).
@@ -304,6 +320,15 @@ hipError_t launch_subset_topk(hipStream_t s, int B, int k, int ds, const float *
                               int32_t *n_found);
 
 hipError_t launch_fill_nfound(hipStream_t s, int32_t *nf, int B, int32_t v);
+// EXACT range path: launch_exact_group with k = cap, the in-range count of every query of the group (dist key < dlim[q]) into
+// n_in_range[q], and each list trimmed to min(cap, count)
+hipError_t launch_exact_range_group(hipStream_t s, int cap, int ds, const float *x, const void *xh, uint64_t n_rows, const IdMap &idmap,
+                                    const float *qpad, const double *qnorm2, const ExactGroup &grp, void *scratch, const uint32_t *dlim,
+                                    uint64_t *ids, float *scores, float *dists, int32_t *n_found, uint64_t *n_in_range,
+                                    const uint64_t *dead = nullptr, uint64_t n_live = ~0ull);
+// sharded range search: n_in_range[b] = sum of the G per-shard counts (shard g's [B] u64 at counts + g * stride bytes), n_found[b] =
+// min(cap, n_in_range[b])
+hipError_t launch_range_sum(hipStream_t s, const void *counts, size_t stride, int G, int B, int cap, uint64_t *n_in_range, int32_t *n_found);
 hipError_t launch_merge(hipStream_t s, const void *ids, size_t ids_stride, const void *dists, size_t dists_stride,
                         int G, int B, int k, uint64_t *out_ids, float *out_dists, float *out_scores);
 

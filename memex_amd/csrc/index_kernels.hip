@@ -1613,4 +1613,576 @@ hipError_t launch_subset_topk(hipStream_t s, int B, int k, int ds, const float *
     return hipGetLastError();
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// range search (mx_index_search_range): every row whose score reaches the query's threshold t.  The host
+// turns t into an exclusive bound on the f32 dist's bits, dlim (in range <=> bits(dist) < dlim; 0 = nothing, t > 1), and the collect
+// launch runs with theta = 1 - D - eps - qa (range_theta_kernel): every in-range row reaches the lane records.
+// ---------------------------------------------------------------------------------------------
+__global__ void range_theta_kernel(int B, const uint32_t *__restrict__ dlim, float eps, const float *__restrict__ qa,
+                                   float *__restrict__ theta) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= B || theta[q] == INFINITY) return;  // zero-norm and padded queries stay parked
+    const uint32_t lim = dlim[q];
+    theta[q] = lim == 0 ? INFINITY : 1.0f - __uint_as_float(lim - 1u) - eps - qa[q];
+}
+
+hipError_t launch_range_theta(hipStream_t s, int B, const uint32_t *dlim, float eps, const float *qa, float *theta) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(range_theta_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, dlim, eps, qa, theta);
+    return hipGetLastError();
+}
+
+// One workgroup per query.  Gather exactly as finish_query does; then decide every candidate: by its filter bounds (certainly in /
+// certainly out / undecided), the undecided by f32 rescoring (error e2), what is still undecided -- and the listed wide-norm rows --
+// by the exact f64 DistCosine against dlim.  n_in_range = the rows decided in.  Emit: all of them when they are at most cap, else the
+// cap-th best lower bound L and the rows whose upper bound reaches L - 2 eps; exact dists for those, order by (dist, row), first
+// min(cap, n_in_range).  A lane-buffer overflow, or more candidates than the block holds, flags the query for the EXACT path (2).
+template <bool CMP>
+__device__ __forceinline__ void range_query(const RangeParams &rp) {
+    const FinishParams &p = rp.f;
+    extern __shared__ __attribute__((aligned(16))) char fsm[];
+    Cand *ent = reinterpret_cast<Cand *>(fsm);                                        // [kCandCap]
+    uint64_t *keys = reinterpret_cast<uint64_t *>(fsm);                               // same storage, at the end
+    float *qv = reinterpret_cast<float *>(fsm + sizeof(Cand) * (size_t)kCandCap);     // [ds] raw query
+    __shared__ uint32_t s_w[kFinWaves];
+    __shared__ uint32_t s_sel[2][kFinWaves];
+    __shared__ uint32_t s_hist[256];
+    __shared__ uint32_t s_pick[2];
+    __shared__ uint32_t s_cnt;
+
+    const int q = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int cap = p.k, ds = p.ds;
+    const uint32_t dlim = rp.dlim[q];
+    const float eps = rp.eps;
+    uint64_t *oid = p.ids + (size_t)q * cap;
+    float *osc = p.scores + (size_t)q * cap;
+    float *odi = p.dists ? p.dists + (size_t)q * cap : nullptr;
+    if (tid == 0) {
+        p.n_found[q] = 0;
+        rp.n_in_range[q] = 0;
+        p.cand_cnt[q] = 0;
+    }
+    for (int j = tid; j < cap; j += kFinThreads) {
+        oid[j] = 0;
+        osc[j] = 0.0f;
+        if (odi) odi[j] = INFINITY;
+    }
+    if (dlim == 0 || p.n_live == 0) return;  // threshold above 1, or no live row
+    const double na = p.qnorm2[q];
+    if (!(na > 0.0)) {
+        // zero-norm query: dist 0 (score 1) against every row, so every live row is in range; the first cap of them by id
+        const uint32_t want = (uint32_t)(p.n_live < (uint64_t)cap ? p.n_live : (uint64_t)cap);
+        if (tid == 0) {
+            p.n_found[q] = (int32_t)want;
+            rp.n_in_range[q] = p.n_live;
+        }
+        uint32_t found = 0;  // block-uniform
+        for (uint64_t w0 = 0; found < want && w0 * 64 < p.n_rows; w0 += kFinThreads) {
+            const uint64_t w = w0 + (uint64_t)tid;
+            uint64_t live = 0;
+            if (w * 64 < p.n_rows) {
+                live = p.dead ? ~p.dead[w] : ~0ull;
+                const uint64_t rem = p.n_rows - w * 64;
+                if (rem < 64) live &= (1ull << rem) - 1ull;
+            }
+            uint32_t tot;
+            uint32_t j = found + block_scan_1024((uint32_t)__popcll(live), s_w, &tot);
+            for (; live && j < want; ++j) {
+                const uint64_t row = w * 64 + (uint64_t)__builtin_ctzll(live);
+                live &= live - 1;
+                oid[j] = p.idmap.id_of((uint32_t)row);
+                osc[j] = 1.0f;
+                if (odi) odi[j] = 0.0f;
+            }
+            found += tot;
+        }
+        return;
+    }
+    const float D = __uint_as_float(dlim - 1u);
+    const float cin = 1.0f - D + eps, cout = 1.0f - D - eps;  // cosine >= cin: certainly in; < cout: certainly out
+    const uint32_t lane_ovf = p.overflow[q];
+    const float qa = p.qa[q], qb = p.qb[q];
+    auto resid = [&](uint32_t row) { return p.terr ? p.terr[kTscaleFloats * (size_t)(row >> 6) + 2 + ((row >> 5) & 1u)] : 0.0f; };
+    for (int i = tid; i < ds; i += kFinThreads) qv[i] = p.qpad[(size_t)q * ds + i];
+
+    // ---- gather (finish_query's, unchanged): candidates carry the lower bound of their cosine
+    const int nwg = p.nwg;
+    const float th = p.theta[q];
+    const uint32_t nz = p.n_zero, nw = p.n_wild;
+    auto in_list = [&](const uint32_t *list, uint32_t n, uint32_t row) {
+        uint32_t lo = 0, hi = n;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (list[mid] < row) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo < n && list[lo] == row;
+    };
+    auto is_zero_row = [&](uint32_t row) { return (nz && in_list(p.zero_rows, nz, row)) || (nw && in_list(p.wild_rows, nw, row)); };
+    auto is_dead = [&](uint32_t row) { return p.dead && ((p.dead[row >> 6] >> (row & 63u)) & 1ull) != 0; };
+    uint32_t *s_off = reinterpret_cast<uint32_t *>(qv + ds) + 32;
+    uint32_t nrec = 0;
+    if (tid < 2 * nwg) {
+        const uint32_t hh0 = (uint32_t)(tid / nwg);
+        const int w = tid - (int)hh0 * nwg;
+        nrec = p.lane_cnt[(size_t)((uint32_t)(q >> 5) * 64 + (uint32_t)(q & 31) + 32u * hh0) * nwg + w];
+        nrec = nrec > (uint32_t)kRecCap ? (uint32_t)kRecCap : nrec;
+    }
+    uint32_t R;
+    const uint32_t roff = block_scan_1024(nrec, s_w, &R);
+    if (tid < 2 * nwg) s_off[tid] = roff;
+    if (tid == 0) s_off[2 * nwg] = R;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    auto put = [&](uint32_t at, float sc, uint32_t row) {
+        if (at < (uint32_t)kCandCap) {
+            Cand cd;
+            cd.score = sc;
+            cd.row = row;
+            ent[at] = cd;
+        }
+    };
+    for (uint32_t j0 = 0; j0 < R; j0 += kFinThreads) {
+        const uint32_t j = j0 + tid;
+        uint32_t mask = 0, rowb = 0;
+        float v[16];
+        if (j < R) {
+            uint32_t lo = 0, hi = (uint32_t)(2 * nwg) - 1;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi + 1) >> 1;
+                if (s_off[mid] <= j) lo = mid;
+                else hi = mid - 1;
+            }
+            const uint32_t e = j - s_off[lo], hh = lo / (uint32_t)nwg, w = lo - hh * (uint32_t)nwg;
+            const size_t l = (size_t)((uint32_t)(q >> 5) * 64 + (uint32_t)(q & 31) + 32u * hh) * nwg + w;
+            const f32x4 *rec = reinterpret_cast<const f32x4 *>(p.lane_rec + l * (kRecCap * 16)) + e * 4;
+            const uint32_t t32 = p.lane_tile[l * kRecCap + e];
+            rowb = t32 * kTileRows + 4u * hh;
+            const uint32_t dm = p.dead ? lane_dead16(dead_half(p.dead, t32), hh) : 0u;
+            const f32x4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = a[r], v[4 + r] = b[r], v[8 + r] = c[r], v[12 + r] = d[r];
+            const float er = resid(rowb);
+            const float thr = fmaf(-qb, er, th), eb = fmaf(qb, er, qa);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t row = rowb + (r & 3) + 8 * (r >> 2);
+                const bool pass = v[r] >= thr && (uint64_t)row < p.n_rows && !(v[r] == 0.0f && (nz | nw) && is_zero_row(row)) && !((dm >> r) & 1u);
+                mask |= pass ? (1u << r) : 0u;
+                v[r] -= eb;
+            }
+        }
+        const uint32_t cnt = (uint32_t)__popc(mask);
+        uint32_t inc = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        uint32_t wbase = 0;
+        if (lane == 63 && inc) wbase = atomicAdd(&s_cnt, inc);
+        wbase = __shfl(wbase, 63);
+        uint32_t at = wbase + inc - cnt;
+        if (mask) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (mask & (1u << r)) put(at++, v[r], rowb + (r & 3) + 8 * (r >> 2));
+        }
+    }
+    for (uint32_t z = tid; z < nz; z += kFinThreads)
+        if ((uint64_t)p.zero_rows[z] < p.n_rows && !is_dead(p.zero_rows[z])) put(atomicAdd(&s_cnt, 1u), 1.0f, p.zero_rows[z]);
+    __syncthreads();
+    const uint32_t M = s_cnt;
+    uint32_t nwv = 0;  // listed wide-norm rows below n_rows (ascending: a prefix)
+    for (uint32_t i = 0; i < nw; ++i) nwv += (uint64_t)p.wild_rows[i] < p.n_rows ? 1u : 0u;
+    if (lane_ovf || M + nwv > (uint32_t)kCandCap) {  // an incomplete or too large candidate set: the EXACT range path
+        if (tid == 0) p.overflow[q] = 2;
+        return;
+    }
+
+    // ---- stage A: filter bounds.  ent becomes [in (nA) | undecided (nU)]
+    uint32_t row[kFinPer];
+    float lb[kFinPer];
+    uint32_t st[kFinPer];  // 0 out, 1 in, 2 undecided
+    uint32_t mi = 0, mu = 0;
+#pragma unroll
+    for (int e = 0; e < kFinPer; ++e) {
+        const uint32_t i = (uint32_t)e * kFinThreads + tid;
+        st[e] = 0;
+        row[e] = 0;
+        lb[e] = 0.0f;
+        if (i < M) {
+            const Cand cd = ent[i];
+            row[e] = cd.row;
+            lb[e] = cd.score;
+            st[e] = lb[e] >= cin ? 1u : lb[e] + 2.0f * fmaf(qb, resid(cd.row), qa) < cout ? 0u : 2u;
+            mi += st[e] == 1u ? 1u : 0u;
+            mu += st[e] == 2u ? 1u : 0u;
+        }
+    }
+    uint32_t nA, nU;
+    {
+        uint32_t pi = block_scan_1024(mi, s_w, &nA);
+        uint32_t pu = block_scan_1024(mu, s_w, &nU);  // (every entry is in registers: both scans synchronise the block)
+        pu += nA;
+#pragma unroll
+        for (int e = 0; e < kFinPer; ++e) {
+            if (st[e] == 0u) continue;
+            Cand cd;
+            cd.score = lb[e];
+            cd.row = row[e];
+            ent[st[e] == 1u ? pi++ : pu++] = cd;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) p.cand_cnt[q] = nU;
+
+    // ---- stage B: f32 rescoring of the undecided (finish_query's stage 2): s2, |s2 - cos| <= e2
+    const float invq = (float)(1.0 / sqrt(na));
+    const int nc4 = ds >> 2;
+    for (uint32_t base = (uint32_t)wave * 4; base < nU; base += kFinWaves * 4) {
+        float dot[4];
+        float sc[4];
+        uint32_t rr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t i = base + j < nU ? base + j : base;
+            rr[j] = ent[nA + i].row;
+            sc[j] = CMP ? 0.0f : p.scale[rr[j]];
+            dot[j] = 0.0f;
+        }
+        for (int tb = 0; tb * 64 < nc4; tb += kMaxKC / 2) {
+            float4 x[4][kMaxKC / 2];
+#pragma unroll
+            for (int t = 0; t < kMaxKC / 2; ++t) {
+                const int c4 = lane + 64 * (tb + t);
+                if (c4 < nc4) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) x[j][t] = row_load4<CMP>(p.x, p.xh, ds, rr[j], c4);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < kMaxKC / 2; ++t) {
+                const int c4 = lane + 64 * (tb + t);
+                if (c4 < nc4) {
+                    const float4 a = *reinterpret_cast<const float4 *>(qv + 4 * c4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float m = CMP ? 1.0f : sc[j];
+                        dot[j] = fmaf(a.x * invq, x[j][t].x * m, dot[j]);
+                        dot[j] = fmaf(a.y * invq, x[j][t].y * m, dot[j]);
+                        dot[j] = fmaf(a.z * invq, x[j][t].z * m, dot[j]);
+                        dot[j] = fmaf(a.w * invq, x[j][t].w * m, dot[j]);
+                        if (CMP) sc[j] = fmaf(x[j][t].x, x[j][t].x, fmaf(x[j][t].y, x[j][t].y, fmaf(x[j][t].z, x[j][t].z, fmaf(x[j][t].w, x[j][t].w, sc[j]))));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                dot[j] += __shfl_xor(dot[j], o);
+                if (CMP) sc[j] += __shfl_xor(sc[j], o);
+            }
+        }
+        if (lane < 4 && base + lane < nU) {
+            const float d0 = lane == 0 ? dot[0] : lane == 1 ? dot[1] : lane == 2 ? dot[2] : dot[3];
+            const float s0 = lane == 0 ? sc[0] : lane == 1 ? sc[1] : lane == 2 ? sc[2] : sc[3];
+            const bool zero_row = !(s0 > 0.0f);
+            ent[nA + base + lane].score = zero_row ? 1.0f : (CMP ? d0 * __frsqrt_rn(s0) : d0);
+        }
+    }
+    __syncthreads();
+    // ... the undecided region becomes [in (nB) | undecided (n2)]
+    uint32_t nB, n2;
+    {
+        mi = mu = 0;
+#pragma unroll
+        for (int e = 0; e < kFinPer; ++e) {
+            const uint32_t i = (uint32_t)e * kFinThreads + tid;
+            st[e] = 0;
+            if (i < nU) {
+                const Cand cd = ent[nA + i];
+                row[e] = cd.row;
+                lb[e] = cd.score;
+                st[e] = cd.score - p.e2 >= cin ? 1u : cd.score + p.e2 < cout ? 0u : 2u;
+                mi += st[e] == 1u ? 1u : 0u;
+                mu += st[e] == 2u ? 1u : 0u;
+            }
+        }
+        uint32_t pi = block_scan_1024(mi, s_w, &nB);
+        uint32_t pu = block_scan_1024(mu, s_w, &n2);
+        pi += nA;
+        pu += nA + nB;
+#pragma unroll
+        for (int e = 0; e < kFinPer; ++e) {
+            if (st[e] == 0u) continue;
+            Cand cd;
+            cd.score = lb[e];
+            cd.row = row[e];
+            ent[st[e] == 1u ? pi++ : pu++] = cd;
+        }
+        __syncthreads();
+    }
+
+    // ---- stage C: exact DistCosine of the still undecided and of the listed wide-norm rows; the entry keeps its row and gets the
+    // exact dist as its score when the row is in range, -1 when it is not (or is masked)
+    const uint32_t c0 = nA + nB, nC = n2 + nwv;  // c0 + nC <= M + nwv <= kCandCap
+    for (uint32_t i = tid; i < nC; i += kFinThreads) {
+        const uint32_t r = i < n2 ? ent[c0 + i].row : p.wild_rows[i - n2];
+        const float d = exact_dist_stored<CMP>(qv, p.x, p.xh, ds, r, na);
+        Cand cd;
+        cd.score = (i >= n2 && is_dead(r)) || __float_as_uint(d) >= dlim ? -1.0f : d;
+        cd.row = r;
+        ent[c0 + i] = cd;
+    }
+    __syncthreads();
+
+    // ---- count, and the rows to order: [0, nA) filter-certified (lower bound), [nA, c0) f32-certified (s2), [c0, T) exact.
+    // stm: two bits per entry (0 not in range, 1 in range by bounds, 3 in range with its exact dist in ent[].score)
+    const uint32_t T = c0 + nC;
+    uint32_t stm = 0, mine = 0;
+#pragma unroll
+    for (int e = 0; e < kFinPer; ++e) {
+        const uint32_t i = (uint32_t)e * kFinThreads + tid;
+        lb[e] = 0.0f;
+        row[e] = 0;
+        if (i < T) {
+            const Cand cd = ent[i];
+            row[e] = cd.row;
+            uint32_t s = 0;
+            if (i < nA) lb[e] = cd.score, s = 1;
+            else if (i < c0) lb[e] = cd.score - p.e2, s = 1;
+            else if (cd.score >= 0.0f) lb[e] = 1.0f - cd.score - eps, s = 3;
+            stm |= s << (2 * e);
+            mine += s ? 1u : 0u;
+        }
+    }
+    uint32_t C;
+    (void)block_scan_1024(mine, s_w, &C);
+    const uint32_t want = C < (uint32_t)cap ? C : (uint32_t)cap;
+    if (tid == 0) {
+        p.n_found[q] = (int32_t)want;
+        rp.n_in_range[q] = C;
+    }
+    if (C == 0) return;
+    if (C > (uint32_t)cap) {
+        // more than cap: L = the cap-th best lower bound; a row whose upper bound stays below L - 2 eps has cap rows strictly ahead
+        // of it
+        uint32_t key[kFinPer];
+        bool valid[kFinPer];
+#pragma unroll
+        for (int e = 0; e < kFinPer; ++e) {
+            valid[e] = ((stm >> (2 * e)) & 3u) != 0u;
+            key[e] = valid[e] ? f32_key(lb[e]) : 0u;
+        }
+        const float L = key_f32(block_kth_largest<kFinPer>(key, valid, (uint32_t)cap, s_hist, s_pick)) - 2.0f * eps;
+#pragma unroll
+        for (int e = 0; e < kFinPer; ++e) {
+            const uint32_t s = (stm >> (2 * e)) & 3u;
+            if (!s) continue;
+            const uint32_t i = (uint32_t)e * kFinThreads + tid;
+            const float v = ent[i].score;  // (ent[] is intact until the keys are written)
+            const float ubv = i < nA ? v + 2.0f * fmaf(qb, resid(row[e]), qa) : i < c0 ? v + p.e2 : 1.0f - v + eps;
+            if (!(ubv >= L)) stm &= ~(3u << (2 * e));
+        }
+    }
+    uint32_t K;
+    {
+        mine = 0;
+#pragma unroll
+        for (int e = 0; e < kFinPer; ++e) {
+            const uint32_t s = (stm >> (2 * e)) & 3u;
+            mine += s ? 1u : 0u;
+            if (s == 3u) lb[e] = ent[(uint32_t)e * kFinThreads + tid].score;  // the exact dist
+        }
+        uint32_t at = block_scan_1024(mine, s_w, &K);
+        __syncthreads();  // every entry is in registers: ent[]'s storage becomes the keys
+#pragma unroll
+        for (int e = 0; e < kFinPer; ++e) {
+            const uint32_t s = (stm >> (2 * e)) & 3u;
+            if (!s) continue;
+            const uint64_t hi = s == 3u ? (uint64_t)__float_as_uint(lb[e]) : 0xffffffffull;  // all ones: dist still to compute
+            keys[at++] = (hi << 32) | row[e];
+        }
+        __syncthreads();
+    }
+    // exact dists of the rows certified by bounds
+    for (uint32_t cI = tid; cI < K; cI += kFinThreads) {
+        const uint64_t me = keys[cI];
+        if ((me >> 32) != 0xffffffffull) continue;
+        const uint32_t r = (uint32_t)me;
+        const float d = exact_dist_stored<CMP>(qv, p.x, p.xh, ds, r, na);
+        keys[cI] = ((uint64_t)__float_as_uint(d) << 32) | r;
+    }
+    __syncthreads();
+
+    // ---- order by (dist, row) and emit the first `want` (finish_query's ranking)
+    uint64_t lim = ~0ull;
+    if (K > 2048u) {
+        uint64_t prefix = 0;
+        for (int bit = 63; bit >= 0; --bit) {
+            const uint64_t trial = prefix | (1ull << bit);
+            uint32_t cc = 0;
+            for (uint32_t cI = tid; cI < K; cI += kFinThreads) cc += keys[cI] < trial ? 1u : 0u;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) cc += __shfl_xor(cc, o);
+            uint32_t *slot = s_sel[bit & 1];
+            if (lane == 0) slot[wave] = cc;
+            __syncthreads();
+            cc = 0;
+#pragma unroll
+            for (int w = 0; w < kFinWaves; ++w) cc += slot[w];
+            if (cc < want) prefix = trial;
+        }
+        lim = prefix;
+    }
+    for (uint32_t cI = tid; cI < K; cI += kFinThreads) {
+        const uint64_t me = keys[cI];
+        if (me > lim) continue;
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < K; ++j) rank += keys[j] < me ? 1u : 0u;
+        if (rank < want) {
+            const float d = __uint_as_float((uint32_t)(me >> 32));
+            oid[rank] = p.idmap.id_of((uint32_t)me);
+            osc[rank] = score_from_dist(d);
+            if (odi) odi[rank] = d;
+        }
+    }
+}
+
+// One workgroup per query (range_query above), then finish_kernel's completion signal: the summary words of the batch's flag block
+// into host-mapped memory, the sequence number behind them
+template <bool CMP>
+__global__ __launch_bounds__(kFinThreads) void range_finish_kernel(const RangeParams rp) {
+    range_query<CMP>(rp);  // every exit of it is workgroup-uniform
+    const FinishParams &p = rp.f;
+    if (!p.host_flags) return;
+    __shared__ uint32_t s_last;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (p.host_out) __threadfence_system();
+        else __threadfence();
+        s_last = atomicAdd(p.done_ctr, 1u) == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __shared__ uint32_t s_sum[4];
+    if (threadIdx.x < 4) s_sum[threadIdx.x] = 0;
+    __threadfence();
+    __syncthreads();
+    if ((int)threadIdx.x < p.n_queries) {
+        const uint32_t ovf = __hip_atomic_load(&p.dev_flags[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t cnt = __hip_atomic_load(&p.dev_flags[kMaxBatch + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t bad = __hip_atomic_load(&p.dev_flags[3 * kMaxBatch + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ovf) atomicMax(&s_sum[0], ovf);
+        atomicAdd(&s_sum[1], cnt);
+        if (bad) atomicOr(&s_sum[2], 1u);
+        atomicMax(&s_sum[3], __hip_atomic_load(&p.dev_flags[2 * kMaxBatch + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p.host_flags[0] = s_sum[0];
+        p.host_flags[1] = s_sum[1];
+        p.host_flags[2] = s_sum[2];
+        p.host_flags[3] = s_sum[3];
+        *p.done_ctr = 0;
+        __hip_atomic_store(&p.host_flags[4], p.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+hipError_t range_setup() {
+    const int lds = (int)(sizeof(Cand) * (size_t)kCandCap + sizeof(float) * (size_t)kMaxKC16 * kChunkFloats + kFinishTailBytes);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&range_finish_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&range_finish_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+}
+
+hipError_t launch_range_finish(hipStream_t s, int B, const RangeParams &rp) {
+    if (B <= 0) return hipSuccess;
+    const FinishParams &p = rp.f;
+    if (p.nwg > kMaxScanWGs || 2 * p.nwg > kFinThreads || p.ds > kMaxKC16 * kChunkFloats) return hipErrorInvalidValue;
+    const size_t lds = sizeof(Cand) * (size_t)kCandCap + sizeof(float) * (size_t)p.ds + kFinishTailBytes;
+    if (p.x) hipLaunchKernelGGL(range_finish_kernel<false>, dim3(B), dim3(kFinThreads), lds, s, rp);
+    else hipLaunchKernelGGL(range_finish_kernel<true>, dim3(B), dim3(kFinThreads), lds, s, rp);
+    return hipGetLastError();
+}
+
+// EXACT range path: in-range rows of each query of the group per row slice (dist key < dlim; masked rows carry the all-ones key)
+__global__ __launch_bounds__(256) void xrange_count_kernel(const uint32_t *__restrict__ dist, uint64_t n_rows, ExactGroup grp,
+                                                           const uint32_t *__restrict__ dlim, uint32_t *__restrict__ cnt) {
+    __shared__ uint32_t s4[4];
+    const int g = blockIdx.y;
+    const uint32_t lim = dlim[grp.q[g]];
+    const uint64_t per = (n_rows + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * per, hi = lo + per < n_rows ? lo + per : n_rows;
+    const uint32_t *d = dist + (size_t)g * n_rows;
+    uint32_t c = 0;
+    for (uint64_t r = lo + threadIdx.x; r < hi; r += 256) c += d[r] < lim ? 1u : 0u;
+    c = block_sum_256(c, s4);
+    if (threadIdx.x == 0) cnt[(size_t)g * gridDim.x + blockIdx.x] = c;
+}
+// the count over the slices; the emitted list (the kk best rows, best first) trimmed to min(cap, count)
+__global__ __launch_bounds__(256) void xrange_trim_kernel(int cap, uint32_t kk, unsigned slices, ExactGroup grp,
+                                                          const uint32_t *__restrict__ cnt, uint64_t *ids_all, float *scores_all,
+                                                          float *dists_all, int32_t *n_found, uint64_t *n_in_range) {
+    __shared__ uint32_t s4[4];
+    const int g = blockIdx.x, q = grp.q[g];
+    uint32_t c = 0;
+    if (cnt)
+        for (unsigned i = threadIdx.x; i < slices; i += 256) c += cnt[(size_t)g * slices + i];
+    c = block_sum_256(c, s4);
+    const uint32_t nf = c < (uint32_t)cap ? c : (uint32_t)cap;
+    if (threadIdx.x == 0) {
+        n_found[q] = (int32_t)nf;
+        n_in_range[q] = c;
+    }
+    for (uint32_t j = nf + threadIdx.x; j < kk; j += 256) {
+        ids_all[(size_t)q * cap + j] = 0;
+        scores_all[(size_t)q * cap + j] = 0.0f;
+        if (dists_all) dists_all[(size_t)q * cap + j] = INFINITY;
+    }
+}
+
+hipError_t launch_exact_range_group(hipStream_t s, int cap, int ds, const float *x, const void *xh, uint64_t n_rows, const IdMap &idmap,
+                                    const float *qpad, const double *qnorm2, const ExactGroup &grp, void *scratch, const uint32_t *dlim,
+                                    uint64_t *ids, float *scores, float *dists, int32_t *n_found, uint64_t *n_in_range,
+                                    const uint64_t *dead, uint64_t n_live) {
+    if (grp.n <= 0) return hipSuccess;
+    hipError_t e = launch_exact_group(s, cap, ds, x, xh, n_rows, idmap, qpad, qnorm2, grp, scratch, ids, scores, dists, n_found, dead, n_live);
+    if (e != hipSuccess) return e;
+    // the layout launch_exact_group used: the histogram area is free again (xsel_pick_kernel cleared it) and holds the slice counts
+    const uint64_t live = n_live < n_rows ? n_live : n_rows;
+    const uint32_t kk = (uint32_t)(live < (uint64_t)cap ? live : (uint64_t)cap);
+    char *base = static_cast<char *>(scratch);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(base);
+    const uint32_t *dist = reinterpret_cast<const uint32_t *>(base + exact_fixed_bytes(kk));
+    const unsigned slices = (unsigned)((n_rows + 4095) / 4096 < (uint64_t)kExactSlices ? (n_rows + 4095) / 4096 : (uint64_t)kExactSlices);
+    if (kk > 0) hipLaunchKernelGGL(xrange_count_kernel, dim3(slices ? slices : 1, grp.n), dim3(256), 0, s, dist, n_rows, grp, dlim, cnt);
+    hipLaunchKernelGGL(xrange_trim_kernel, dim3(grp.n), dim3(256), 0, s, cap, kk, slices ? slices : 1u, grp, kk > 0 ? cnt : nullptr,
+                       ids, scores, dists, n_found, n_in_range);
+    return hipGetLastError();
+}
+
+// sharded handle: n_in_range[b] = sum over the G shards' counts (counts of shard g at base + g * stride bytes), n_found = min(cap, it)
+__global__ void range_sum_kernel(const char *__restrict__ base, size_t stride, int G, int B, int cap, uint64_t *n_in_range,
+                                 int32_t *n_found) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint64_t c = 0;
+    for (int g = 0; g < G; ++g) c += reinterpret_cast<const uint64_t *>(base + (size_t)g * stride)[b];
+    n_in_range[b] = c;
+    n_found[b] = (int32_t)(c < (uint64_t)cap ? c : (uint64_t)cap);
+}
+
+hipError_t launch_range_sum(hipStream_t s, const void *counts, size_t stride, int G, int B, int cap, uint64_t *n_in_range, int32_t *n_found) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(range_sum_kernel, dim3((B + 255) / 256), dim3(256), 0, s, static_cast<const char *>(counts), stride, G, B, cap,
+                       n_in_range, n_found);
+    return hipGetLastError();
+}
+
 }  // namespace mx

@@ -246,6 +246,50 @@ class FlatIndex:
                                                     ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
                                                     ctypes.c_void_p(n_found.data_ptr())))
 
+    def _min_scores(self, min_score, B: int) -> np.ndarray:
+        t = np.asarray(min_score, dtype=np.float32)
+        if t.ndim == 0:
+            t = np.full(B, t, dtype=np.float32)
+        t = np.ascontiguousarray(t.reshape(-1))
+        if t.size != B:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {B} thresholds, got {t.size}")
+        return t
+
+    def search_range(self, queries, min_score, cap: int):
+        """Every row whose score reaches ``min_score`` (a scalar, or one threshold per query), exactly.
+        -> (ids u64 [B,cap], scores f32 [B,cap], dists f32 [B,cap], n_found i32 [B], n_in_range u64 [B]): per query the in-range
+        rows best-first, at most ``cap`` (1 .. 4096) of them; ``n_found`` = min(cap, n_in_range), ``n_in_range`` the exact count."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        B = q.shape[0]
+        t = self._min_scores(min_score, B)
+        c = max(int(cap), 0)
+        ids = np.zeros((B, c), dtype=np.uint64)
+        scores = np.zeros((B, c), dtype=np.float32)
+        dists = np.zeros((B, c), dtype=np.float32)
+        nf = np.zeros(B, dtype=np.int32)
+        nr = np.zeros(B, dtype=np.uint64)
+        check(lib().mx_index_search_range(self._h, _ptr(q), B, _ptr(t) if t.size else None, int(cap), _ptr(ids) if ids.size else None,
+                                          _ptr(scores) if scores.size else None, _ptr(dists) if dists.size else None, _ptr(nf),
+                                          _ptr(nr)))
+        return ids, scores, dists, nf, nr
+
+    def search_range_device(self, q, min_score, cap: int, ids, scores, dists, n_found, n_in_range) -> None:
+        """``search_range`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,cap]; scores, dists f32 [B,cap] (dists may be
+        None); n_found i32 [B]; n_in_range i64/u64 [B].  The thresholds stay on the host.  Blocks until the results are in HBM."""
+        B = int(q.shape[0])
+        t = self._min_scores(min_score, B)
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        check(lib().mx_index_search_range_device(self._h, ctypes.c_void_p(q.data_ptr()), B, _ptr(t) if t.size else None, int(cap),
+                                                 ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
+                                                 ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
+                                                 ctypes.c_void_p(n_found.data_ptr()), ctypes.c_void_p(n_in_range.data_ptr())))
+
     # -- persistence ---------------------------------------------------------------------
     def save(self, directory: str) -> None:
         check(lib().mx_index_save(self._h, str(directory).encode()))

@@ -434,6 +434,30 @@ class HipFlatStore(VectorStore):
                 out.append((self._id_map[d_id], float(scores[0, j])))
         return out
 
+    def search_above(self, vec: Sequence[float], min_score: float, limit: int) -> List[VectorSearchResult]:
+        """Every row whose score against ``vec`` is at least ``min_score``, best first, at most ``limit`` (1 .. 4096) of them
+        (``FlatIndex.search_range``), as ``(_id, score)`` pairs like ``search``: a near-duplicate check before ingest, or context
+        chosen by relevance rather than by count.  Removed rows never appear."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0:
+            return []
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        try:
+            ids, scores, _, nf, _ = idx.search_range(q, float(min_score), int(limit))  # not under the lock: combined like search
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[VectorSearchResult] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[d_id], float(scores[0, j])))
+        return out
+
     def search(self, vec: Sequence[float], limit: int) -> List[VectorSearchResult]:
         with self._lock:
             idx = self._index        # own reference: the store may be evicted / replaced while the GPU works
