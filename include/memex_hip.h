@@ -221,6 +221,37 @@ int mx_index_search_range(mx_index *idx, const float *queries, int B, const floa
 int mx_index_search_range_device(mx_index *idx, const float *d_queries, int B, const float *min_scores, int cap, uint64_t *d_ids,
                                  float *d_scores, float *d_dists, int32_t *d_n_found, uint64_t *d_n_in_range);
 
+/*
+ * Diversified search: the k most relevant rows that do not repeat each other -- exact maximal-marginal-relevance (MMR) re-ranking of the
+ * top-`fetch` rows.  Overlapping windows of one document are near-copies of each other; a plain top-k returns them side by side.
+ * Per query:
+ *   candidates  the exact top-fetch live rows in (dist, id) order: what mx_index_search gives with k = fetch, bit for bit (removed rows,
+ *               id_offset, the AUTO path up to fetch = 256 and the EXACT path above, B split into batches of 512); m = min(fetch, live rows).
+ *               The candidate stage IS a plain search pass: it counts as one in mx_index_stats and in the filter copy's heuristics.
+ *   selection   greedy, n_found = min(k, m) picks.  The first pick is candidate 0; every later pick maximises, over the candidates not
+ *               picked yet,   v_i = (double)lambda * (double)rel_i - (1.0 - (double)lambda) * (double)pen_i   (plain IEEE f64 operations,
+ *               not contracted), rel_i the f32 score the search reports for candidate i, pen_i the largest sim(i, j) over the rows j
+ *               picked so far (f32), sim(i, j) = score(DistCosine(row_j, row_i)) on the rows AS STORED (a bf16 corpus: its values widened,
+ *               what mx_index_get_rows returns) with the arithmetic of mx_index_search: f32 products summed sequentially in f64 in element
+ *               order.  A sim that is NaN (two rows whose element products overflow f32) counts as 1, a v that is NaN as -inf.  Ties in v go
+ *               to the earlier candidate, i.e. the smaller (dist, id).
+ *   output      ids / scores / dists [B, k] in SELECTION order, each entry with the id, score (= rel) and dist of its candidate, unchanged;
+ *               unused slots id 0 / score 0 / dist +inf; dists may be NULL.
+ * lambda = 1 returns the first k entries of mx_index_search; fetch = k a permutation of the plain top-k that starts with its first entry.
+ * Arguments are checked first: B < 0, k < 1, fetch < k, lambda NaN or outside [0, 1]: MX_EINVAL; fetch > 1024: MX_EUNSUPPORTED (the
+ * selection costs O(k * fetch * dim) per query: k - 1 rounds of one f64 chain of dim terms per remaining candidate); then a null index:
+ * MX_ESEARCH.  Non-finite queries are rejected; dim <= 8192.  Thread-safe beside every other call.  Concurrent callers are NOT combined
+ * into shared passes: each call holds the index across its candidate stage and its selection (both see one snapshot of the rows; no
+ * append, removal or compaction slips between them) and never rides in a plain, filtered or range pass.  A sharded handle merges the
+ * candidates on devices[0] as a search does; then every shard copies the stored rows of the candidates it owns, widened to f32, to
+ * devices[0] (peer copies), where one kernel selects -- the answer equals the plain index's bit for bit.  Extra HBM, allocated at the
+ * first call: the candidate lists and at most 64 MiB of gathered rows per device (a batch is processed in chunks of queries that fit).
+ */
+int mx_index_search_mmr(mx_index *idx, const float *queries, int B, int k, int fetch, float lambda, uint64_t *ids, float *scores,
+                        float *dists, int32_t *n_found);
+int mx_index_search_mmr_device(mx_index *idx, const float *d_queries, int B, int k, int fetch, float lambda, uint64_t *d_ids,
+                               float *d_scores, float *d_dists, int32_t *d_n_found);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

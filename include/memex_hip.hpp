@@ -429,6 +429,33 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // the `limit` most relevant rows that do not repeat each other (mx_index_search_mmr: exact MMR re-ranking of the top-`fetch` rows),
+    // in selection order: context for a prompt without the same passage from several overlapping windows.  fetch = 0: the default
+    // min(max(4 * limit, 32), 1024); lambda = 1 is search()
+    std::vector<VectorSearchResult> search_diverse(const std::vector<float> &vec, size_t limit, size_t fetch = 0, float lambda = 0.5f) {
+        std::vector<VectorSearchResult> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0) return out;
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        if (fetch == 0) fetch = std::min<size_t>(std::max<size_t>(4 * limit, 32), 1024);
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        int32_t nf = 0;
+        int rc = mx_index_search_mmr(idx_, vec.data(), 1, (int)std::min<size_t>(limit, (size_t)INT32_MAX),
+                                     (int)std::min<size_t>(fetch, (size_t)INT32_MAX), lambda, found.data(), scores.data(), nullptr, &nf);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.emplace_back(it->second, scores[j]);
+        }
+        return out;
+    }
+
     uint64_t nb_point() const {  // hnsw.get_nb_point() in the reference's test (local.rs:238)
         uint64_t n = 0;
         if (idx_) mx_index_size(idx_, &n);

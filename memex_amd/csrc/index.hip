@@ -251,6 +251,18 @@ struct mx_index {
     size_t filt_ranges_cap = 0;     // pairs
     uint32_t *subset_rows = nullptr;
     bool last_subset = false;       // the last search_batch answered on the subset kernel
+    // diversified search (mx_index_search_mmr), allocated at the first such call.  Every plain index or shard: the
+    // row list of a gather launch and -- the handle's own index, or a shard on another device than shards[0] -- the block the
+    // gathered rows go to (at most kMmrStageBytes).  The index that owns the stream (shards[0] of a composite) also holds the
+    // candidate stage's lists [kMaxBatch, mmr_fcap], their pinned mirrors and the candidates' positions in the block.
+    uint32_t *mmr_rows = nullptr;
+    float *mmr_stage = nullptr;
+    size_t mmr_stage_bytes = 0;
+    uint64_t *mmr_ids = nullptr, *mmr_h_ids = nullptr;
+    float *mmr_scores = nullptr, *mmr_dists = nullptr;
+    int32_t *mmr_nf = nullptr, *mmr_h_nf = nullptr;
+    uint32_t *mmr_pos = nullptr;
+    int mmr_fcap = 0;
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -339,6 +351,9 @@ int free_index(mx_index *idx) {
     };
     F(idx->x); F(idx->scale); F(idx->xh); F(idx->tsc); F(idx->flags); F(idx->xs); F(idx->ss); F(idx->zero_rows); F(idx->wild_list);
     F(idx->amean); F(idx->mean); F(idx->msum); F(idx->dead); F(idx->filt); F(idx->filt_ranges); F(idx->subset_rows);
+    F(idx->mmr_rows); F(idx->mmr_stage); F(idx->mmr_ids); F(idx->mmr_scores); F(idx->mmr_dists); F(idx->mmr_nf); F(idx->mmr_pos);
+    if (idx->mmr_h_ids) (void)hipHostFree(idx->mmr_h_ids);
+    if (idx->mmr_h_nf) (void)hipHostFree(idx->mmr_h_nf);
     Scratch &s = idx->s;
     F(s.qfrag); F(s.qpad); F(s.qnorm2); F(s.theta); F(s.theta_retry); F(s.todo); F(s.dev_flags); F(s.done_ctr);
     if (s.host_flags) (void)hipHostFree(s.host_flags);
@@ -1919,6 +1934,126 @@ int any_range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint3
                             : range_batch(idx, d_q, B, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange);
 }
 
+// ---- diversified search (mx_index_search_mmr) ------------------------------------------------------
+// the candidate stage's lists on the index that owns the stream (the current device is its device)
+int ensure_mmr_lists(mx_index *t, int fetch) {
+    if (fetch <= t->mmr_fcap) return MX_OK;
+    MX_HIP(hipStreamSynchronize(t->stream));
+    auto F = [](void *p) {
+        if (p) (void)hipFree(p);
+    };
+    F(t->mmr_ids); F(t->mmr_scores); F(t->mmr_dists); F(t->mmr_nf); F(t->mmr_pos);
+    if (t->mmr_h_ids) (void)hipHostFree(t->mmr_h_ids);
+    if (t->mmr_h_nf) (void)hipHostFree(t->mmr_h_nf);
+    t->mmr_ids = nullptr; t->mmr_scores = nullptr; t->mmr_dists = nullptr; t->mmr_nf = nullptr; t->mmr_pos = nullptr;
+    t->mmr_h_ids = nullptr; t->mmr_h_nf = nullptr;
+    t->mmr_fcap = 0;
+    const size_t fc = (size_t)std::max(fetch, 64);
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_ids), (size_t)kMaxBatch * fc * sizeof(uint64_t)));
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_scores), (size_t)kMaxBatch * fc * sizeof(float)));
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_dists), (size_t)kMaxBatch * fc * sizeof(float)));
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_nf), kMaxBatch * sizeof(int32_t)));
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_pos), (size_t)kMaxBatch * fc * sizeof(uint32_t)));
+    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->mmr_h_ids), (size_t)kMaxBatch * fc * sizeof(uint64_t), hipHostMallocDefault));
+    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->mmr_h_nf), kMaxBatch * sizeof(int32_t), hipHostMallocDefault));
+    t->mmr_fcap = (int)fc;
+    return MX_OK;
+}
+
+// the row list of a gather launch on sh, and a block of `bytes` for the gathered rows (0: sh gathers into another index's block); the
+// current device is sh's
+int ensure_mmr_stage(mx_index *sh, size_t bytes) {
+    if (!sh->mmr_rows)
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->mmr_rows), kMmrStageBytes / (kChunkFloats * sizeof(float)) * sizeof(uint32_t)));
+    if (bytes <= sh->mmr_stage_bytes) return MX_OK;
+    MX_HIP(hipStreamSynchronize(sh->stream));
+    if (sh->mmr_stage) (void)hipFree(sh->mmr_stage);
+    sh->mmr_stage = nullptr;
+    sh->mmr_stage_bytes = 0;
+    const size_t want = std::min(kMmrStageBytes, (bytes + ((size_t)1 << 20) - 1) >> 20 << 20);
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->mmr_stage), want));
+    sh->mmr_stage_bytes = want;
+    return MX_OK;
+}
+
+// One batch (B <= kMaxBatch) of a diversified search, queries and outputs on the device of the index that owns the stream, the caller
+// holding idx->mu across both stages: a plain search pass at k = fetch into that index's lists, then per chunk of queries (gathered rows
+// <= kMmrStageBytes) every shard copies the stored rows of the candidates it owns into the block and mmr_select_kernel picks.
+int mmr_batch(mx_index *idx, const float *d_q, int B, int k, int fetch, float lambda, uint64_t *d_ids, float *d_scores, float *d_dists,
+              int32_t *d_nfound) {
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    const int ds = t->ds;
+    if (ds > kMmrMaxDs) return fail(MX_EUNSUPPORTED, "diversified search supports dim <= %d", kMmrMaxDs);
+    int rc = ensure_mmr_lists(t, fetch);
+    if (rc != MX_OK) return rc;
+    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf)) != MX_OK) return rc;
+    hipStream_t st = t->stream;
+    MX_HIP(hipMemcpyAsync(t->mmr_h_ids, t->mmr_ids, (size_t)B * fetch * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipMemcpyAsync(t->mmr_h_nf, t->mmr_nf, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    const size_t G = idx->composite() ? idx->shards.size() : 1;
+    const uint64_t R = idx->composite() ? idx->block_rows : 0, off = idx->idmap.id_offset, total_rows = idx->composite() ? idx->total : idx->n;
+    const size_t row_bytes = (size_t)ds * sizeof(float);
+    const int qc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, kMmrStageBytes / ((size_t)fetch * row_bytes)));
+    std::vector<std::vector<uint32_t>> rows(G);  // (alive until the chunk is host-synchronised: sources of async uploads)
+    std::vector<uint32_t> pos, owner;
+    std::vector<size_t> first(G + 1);
+    for (int q0 = 0; q0 < B; q0 += qc) {
+        const int nq = std::min(qc, B - q0);
+        for (auto &r : rows) r.clear();
+        pos.assign((size_t)nq * fetch, 0u);
+        owner.assign((size_t)nq * fetch, 0u);
+        for (int q = 0; q < nq; ++q) {
+            const int m = std::min(std::max(t->mmr_h_nf[q0 + q], 0), fetch);
+            for (int i = 0; i < m; ++i) {
+                const uint64_t id = t->mmr_h_ids[(size_t)(q0 + q) * fetch + i];
+                if (id <= off || id - off - 1 >= total_rows) return fail(MX_ESEARCH, "candidate id %llu names no row", (unsigned long long)id);
+                const uint64_t r = id - off - 1;
+                const uint64_t g = R ? (r / R) % G : 0, local = R ? (r / R / G) * R + r % R : r;
+                const mx_index *sh = idx->composite() ? idx->shards[g] : idx;
+                if (local >= sh->n) return fail(MX_ESEARCH, "candidate id %llu names no row of its shard", (unsigned long long)id);
+                const size_t s = (size_t)q * fetch + i;
+                owner[s] = (uint32_t)g;
+                pos[s] = (uint32_t)rows[g].size();
+                rows[g].push_back((uint32_t)local);
+            }
+        }
+        first[0] = 0;
+        for (size_t g = 0; g < G; ++g) first[g + 1] = first[g] + rows[g].size();
+        for (int q = 0; q < nq; ++q) {
+            const int m = std::min(std::max(t->mmr_h_nf[q0 + q], 0), fetch);
+            for (int i = 0; i < m; ++i) pos[(size_t)q * fetch + i] += (uint32_t)first[owner[(size_t)q * fetch + i]];
+        }
+        {
+            DeviceGuard dg(t->device);
+            if ((rc = ensure_mmr_stage(t, first[G] * row_bytes)) != MX_OK) return rc;
+        }
+        for (size_t g = 0; g < G; ++g) {
+            if (rows[g].empty()) continue;
+            mx_index *sh = idx->composite() ? idx->shards[g] : idx;
+            std::unique_lock<std::mutex> lk(sh->mu, std::defer_lock);
+            if (idx->composite()) lk.lock();  // (a plain index: the caller holds it)
+            DeviceGuard dg(sh->device);
+            const bool same = sh->device == t->device;
+            const size_t bytes = rows[g].size() * row_bytes;
+            if (sh != t && (rc = ensure_mmr_stage(sh, same ? 0 : bytes)) != MX_OK) return rc;
+            MX_HIP(hipMemcpyAsync(sh->mmr_rows, rows[g].data(), rows[g].size() * sizeof(uint32_t), hipMemcpyHostToDevice, sh->stream));
+            float *slot = t->mmr_stage + first[g] * (size_t)ds;
+            MX_HIP(launch_mmr_gather(sh->stream, ds, sh->compressed ? nullptr : sh->x, sh->xh, sh->mmr_rows, (uint32_t)rows[g].size(),
+                                     same ? slot : sh->mmr_stage));
+            if (!same) MX_HIP(hipMemcpyAsync(slot, sh->mmr_stage, bytes, hipMemcpyDefault, sh->stream));  // peer copy to shards[0]'s device
+            if (sh != t) MX_HIP(hipStreamSynchronize(sh->stream));
+        }
+        DeviceGuard dg(t->device);
+        MX_HIP(hipMemcpyAsync(t->mmr_pos, pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        const size_t c0 = (size_t)q0 * fetch, o0 = (size_t)q0 * k;
+        MX_HIP(launch_mmr_select(st, nq, k, fetch, ds, lambda, t->mmr_stage, t->mmr_pos, t->mmr_ids + c0, t->mmr_scores + c0, t->mmr_dists + c0,
+                                 t->mmr_nf + q0, d_ids + o0, d_scores + o0, d_dists ? d_dists + o0 : nullptr, d_nfound + q0));
+        MX_HIP(hipStreamSynchronize(st));
+    }
+    return MX_OK;
+}
+
 // what an append can change in a plain index, and how to undo it: an insert is all-or-nothing, also when it
 // spans several shards or several staging chunks and a later part fails (non-finite device rows, HBM)
 struct RowMark {
@@ -3386,6 +3521,81 @@ int mx_index_search_range_device(mx_index *idx, const float *d_q, int B, const f
         const size_t o = (size_t)b0 * cap;
         int rc = any_range_batch(idx, d_q + (size_t)b0 * idx->dim, nb, cap, dlim.data() + b0, d_ids + o, d_scores + o,
                                  d_dists ? d_dists + o : nullptr, d_nfound + b0, d_n_in_range + b0);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+namespace {
+
+// arguments of the diversified-search entry points, checked before the index is looked at
+int read_mmr_args(int B, int k, int fetch, float lambda) {
+    if (B < 0) return fail(MX_EINVAL, "negative batch");
+    if (k < 1) return fail(MX_EINVAL, "k = %d < 1", k);
+    if (fetch < k) return fail(MX_EINVAL, "fetch = %d < k = %d", fetch, k);
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(MX_EINVAL, "lambda = %g is not in [0, 1]", (double)lambda);
+    if (fetch > kMmrMaxFetch) return fail(MX_EUNSUPPORTED, "fetch = %d > %d", fetch, kMmrMaxFetch);
+    return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_search_mmr(mx_index *idx, const float *q, int B, int k, int fetch, float lambda, uint64_t *ids, float *scores, float *dists,
+                        int32_t *n_found) try {
+    if (int rc = read_mmr_args(B, k, fetch, lambda); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B == 0) return MX_OK;
+    if (!q || !ids || !scores || !n_found) return fail(MX_EINVAL, "null argument");
+    const size_t dim = (size_t)idx->dim;
+    for (size_t i = 0; i < (size_t)B * dim; ++i)
+        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    // not combined with other callers: the call holds the index across the candidate stage and the selection, like a device-pointer call
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
+    DeviceGuard g(t->device);
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, k)) != MX_OK) return rc;
+    Scratch &s = t->s;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        if ((rc = mmr_batch(idx, s.qstage, nb, k, fetch, lambda, s.out_ids, s.out_scores, s.out_dists, s.out_nfound)) != MX_OK) return rc;
+        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipStreamSynchronize(t->stream));
+        memcpy(ids + o, s.h_ids, (size_t)nb * k * sizeof(uint64_t));
+        memcpy(scores + o, s.h_scores, (size_t)nb * k * sizeof(float));
+        if (dists) memcpy(dists + o, s.h_dists, (size_t)nb * k * sizeof(float));
+        memcpy(n_found + b0, s.h_nf, (size_t)nb * sizeof(int32_t));
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_mmr_device(mx_index *idx, const float *d_q, int B, int k, int fetch, float lambda, uint64_t *d_ids, float *d_scores,
+                               float *d_dists, int32_t *d_nfound) try {
+    if (int rc = read_mmr_args(B, k, fetch, lambda); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B == 0) return MX_OK;
+    if (!d_q || !d_ids || !d_scores || !d_nfound) return fail(MX_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    DeviceGuard g(t->device);
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        int rc = mmr_batch(idx, d_q + (size_t)b0 * idx->dim, nb, k, fetch, lambda, d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr,
+                           d_nfound + b0);
         if (rc != MX_OK) return rc;
     }
     return MX_OK;

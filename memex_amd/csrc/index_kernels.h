@@ -332,4 +332,17 @@ hipError_t launch_range_sum(hipStream_t s, const void *counts, size_t stride, in
 hipError_t launch_merge(hipStream_t s, const void *ids, size_t ids_stride, const void *dists, size_t dists_stride,
                         int G, int B, int k, uint64_t *out_ids, float *out_dists, float *out_scores);
 
+// diversified search (mx_index_search_mmr)
+constexpr int kMmrMaxFetch = 1024;               // candidates per query: one thread each in mmr_select_kernel
+constexpr int kMmrMaxDs = 8192;                  // padded row width the selection stages in LDS (32 KiB)
+constexpr size_t kMmrStageBytes = 64u << 20;     // gathered rows per chunk of queries
+// stage[i, ds] = stored row rows[i] of the index (x: f32 rows, or null: the compressed corpus xh), widened to f32, i < n
+hipError_t launch_mmr_gather(hipStream_t s, int ds, const float *x, const void *xh, const uint32_t *rows, uint32_t n, float *stage);
+// greedy MMR selection of min(k, cand_nf[q]) of query q's candidates (lists [B, fetch] in (dist, id) order; the stored row of candidate i
+// of query q is row pos[q * fetch + i] of stage) into ids / scores / dists [B, k] in selection order and n_found [B]; unused slots id 0,
+// score 0, dist +inf; dists may be null.  1 <= k <= fetch <= kMmrMaxFetch, ds <= kMmrMaxDs.
+hipError_t launch_mmr_select(hipStream_t s, int B, int k, int fetch, int ds, float lambda, const float *stage, const uint32_t *pos,
+                             const uint64_t *cand_ids, const float *cand_scores, const float *cand_dists, const int32_t *cand_nf,
+                             uint64_t *ids, float *scores, float *dists, int32_t *n_found);
+
 }  // namespace mx

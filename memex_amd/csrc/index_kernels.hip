@@ -2188,4 +2188,152 @@ hipError_t launch_range_sum(hipStream_t s, const void *counts, size_t stride, in
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// diversified search (mx_index_search_mmr): the stored rows of the candidates, widened to f32, and the
+// greedy MMR selection over them
+// ---------------------------------------------------------------------------------------------
+// stage[i, ds] = the stored row rows[i] (zero padding included), one workgroup per row
+template <bool CMP>
+__global__ __launch_bounds__(256) void mmr_gather_kernel(const float *__restrict__ x, const void *__restrict__ xh, int ds,
+                                                         const uint32_t *__restrict__ rows, float *__restrict__ stage) {
+    const uint32_t row = rows[blockIdx.x];
+    float4 *dst = reinterpret_cast<float4 *>(stage + (size_t)blockIdx.x * ds);
+    for (int c4 = threadIdx.x; c4 < ds / 4; c4 += 256) dst[c4] = row_load4<CMP>(x, xh, ds, row, c4);
+}
+
+hipError_t launch_mmr_gather(hipStream_t s, int ds, const float *x, const void *xh, const uint32_t *rows, uint32_t n, float *stage) {
+    if (n == 0) return hipSuccess;
+    if (x) hipLaunchKernelGGL(mmr_gather_kernel<false>, dim3(n), dim3(256), 0, s, x, xh, ds, rows, stage);
+    else hipLaunchKernelGGL(mmr_gather_kernel<true>, dim3(n), dim3(256), 0, s, x, xh, ds, rows, stage);
+    return hipGetLastError();
+}
+
+// order-preserving map f64 -> u64 (a NaN ranks with -inf); every key is > 0
+__device__ __forceinline__ uint64_t mmr_key(double v) {
+    if (!(v == v)) v = -INFINITY;
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+// (key descending, position ascending)
+__device__ __forceinline__ void mmr_better(uint64_t &key, uint32_t &pos, uint64_t k2, uint32_t p2) {
+    if (k2 > key || (k2 == key && p2 < pos)) {
+        key = k2;
+        pos = p2;
+    }
+}
+
+// One workgroup per query, one candidate per thread (blockDim >= fetch).  Candidate i of query q is the i-th entry of the
+// candidate stage's lists (ids / rel / dists at q * fetch + i, m = cand_nf[q] of them) and its stored row is row
+// pos[q * fetch + i] of stage.  Every thread keeps its candidate's norm sum, its penalty and its state in registers; per
+// pick the row picked last is staged in LDS and every unselected candidate runs ONE sequential f64 chain against it (the
+// summation order is the contract: a chain is never split across lanes), then the block takes the arg-max of the MMR value.
+__global__ __launch_bounds__(1024) void mmr_select_kernel(int k, int fetch, int ds, float lambda, const float *__restrict__ stage,
+                                                          const uint32_t *__restrict__ pos, const uint64_t *__restrict__ cand_ids,
+                                                          const float *__restrict__ cand_rel, const float *__restrict__ cand_dists,
+                                                          const int32_t *__restrict__ cand_nf, uint64_t *__restrict__ ids,
+                                                          float *__restrict__ scores, float *__restrict__ dists,
+                                                          int32_t *__restrict__ n_found) {
+    extern __shared__ __attribute__((aligned(16))) char mmr_lds[];
+    float *sel_row = reinterpret_cast<float *>(mmr_lds);                               // [ds]
+    uint64_t *wkey = reinterpret_cast<uint64_t *>(mmr_lds + (size_t)ds * sizeof(float));  // [16] per-wave winners
+    uint32_t *wpos = reinterpret_cast<uint32_t *>(wkey + 16);                          // [16]
+    double *sel_nb = reinterpret_cast<double *>(wpos + 16);                            // [1] norm sum of the staged row
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = (blockDim.x + 63) >> 6;
+    const size_t c0 = (size_t)q * fetch, o0 = (size_t)q * k;
+    int m = cand_nf[q];
+    m = m < 0 ? 0 : m > fetch ? fetch : m;
+    const int found = k < m ? k : m;
+    // unused output slots, and the count
+    for (int t = found + tid; t < k; t += blockDim.x) {
+        ids[o0 + t] = 0;
+        scores[o0 + t] = 0.0f;
+        if (dists) dists[o0 + t] = INFINITY;
+    }
+    if (tid == 0) n_found[q] = found;
+    if (found == 0) return;  // (block-uniform)
+
+    const bool mine = tid < m;
+    const float4 *my4 = reinterpret_cast<const float4 *>(stage + (size_t)(mine ? pos[c0 + tid] : 0u) * ds);
+    const double lam = (double)lambda, one_minus = __dsub_rn(1.0, lam);
+    const float rel = mine ? cand_rel[c0 + tid] : 0.0f;
+    const double lam_rel = __dmul_rn(lam, (double)rel);
+    double nb = 0.0;  // the candidate's own norm sum: DistCosine's third chain, independent of the dot chain
+    if (mine && found > 1) {
+#pragma unroll 8
+        for (int i = 0; i < ds / 4; ++i) {
+            const float4 c = my4[i];
+            nb += (double)__fmul_rn(c.x, c.x);
+            nb += (double)__fmul_rn(c.y, c.y);
+            nb += (double)__fmul_rn(c.z, c.z);
+            nb += (double)__fmul_rn(c.w, c.w);
+        }
+    }
+    float pen = -INFINITY;
+    bool open = mine;  // not selected yet
+    uint32_t sel = 0;  // the first pick is candidate 0
+    for (int t = 0;; ++t) {
+        if (tid == (int)sel) {
+            open = false;
+            ids[o0 + t] = cand_ids[c0 + sel];
+            scores[o0 + t] = rel;
+            if (dists) dists[o0 + t] = cand_dists[c0 + sel];
+            *sel_nb = nb;
+        }
+        if (t + 1 == found) break;
+        // stage the row just picked
+        const float4 *s4 = reinterpret_cast<const float4 *>(stage + (size_t)pos[c0 + sel] * ds);
+        for (int c4 = tid; c4 < ds / 4; c4 += blockDim.x) reinterpret_cast<float4 *>(sel_row)[c4] = s4[c4];
+        __syncthreads();
+        uint64_t key = 0;
+        uint32_t at = 0xffffffffu;
+        if (open) {
+            double dot = 0.0;
+#pragma unroll 8
+            for (int i = 0; i < ds / 4; ++i) {
+                const float4 c = my4[i];
+                const float4 a = *reinterpret_cast<const float4 *>(sel_row + 4 * i);
+                dot += (double)__fmul_rn(a.x, c.x);
+                dot += (double)__fmul_rn(a.y, c.y);
+                dot += (double)__fmul_rn(a.z, c.z);
+                dot += (double)__fmul_rn(a.w, c.w);
+            }
+            float sim = score_from_dist(dist_from_sums(dot, *sel_nb, nb));
+            if (!(sim == sim)) sim = 1.0f;
+            pen = sim > pen ? sim : pen;
+            key = mmr_key(__dsub_rn(lam_rel, __dmul_rn(one_minus, (double)pen)));
+            at = (uint32_t)tid;
+        }
+        // block arg-max: within the wave by shuffles, across the waves through LDS
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(key >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)key, o);
+            const uint32_t p2 = (uint32_t)__shfl_xor((int)at, o);
+            mmr_better(key, at, ((uint64_t)hi << 32) | lo, p2);
+        }
+        if (lane == 0) {
+            wkey[wave] = key;
+            wpos[wave] = at;
+        }
+        __syncthreads();
+        key = wkey[0];
+        at = wpos[0];
+        for (int w = 1; w < nwaves; ++w) mmr_better(key, at, wkey[w], wpos[w]);
+        sel = at;
+        __syncthreads();  // wkey / wpos / sel_row / sel_nb are rewritten in the next round
+    }
+}
+
+size_t mmr_select_lds_bytes(int ds) { return (size_t)ds * sizeof(float) + 16 * sizeof(uint64_t) + 16 * sizeof(uint32_t) + 16; }
+
+hipError_t launch_mmr_select(hipStream_t s, int B, int k, int fetch, int ds, float lambda, const float *stage, const uint32_t *pos,
+                             const uint64_t *cand_ids, const float *cand_scores, const float *cand_dists, const int32_t *cand_nf,
+                             uint64_t *ids, float *scores, float *dists, int32_t *n_found) {
+    if (B <= 0) return hipSuccess;
+    if (fetch < 1 || fetch > kMmrMaxFetch || k < 1 || k > fetch || ds < 4 || ds > kMmrMaxDs || ds % 4) return hipErrorInvalidValue;
+    const int threads = (fetch + 63) / 64 * 64;
+    hipLaunchKernelGGL(mmr_select_kernel, dim3(B), dim3(threads), mmr_select_lds_bytes(ds), s, k, fetch, ds, lambda, stage, pos, cand_ids,
+                       cand_scores, cand_dists, cand_nf, ids, scores, dists, n_found);
+    return hipGetLastError();
+}
+
 }  // namespace mx

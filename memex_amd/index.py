@@ -290,6 +290,43 @@ class FlatIndex:
                                                  ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
                                                  ctypes.c_void_p(n_found.data_ptr()), ctypes.c_void_p(n_in_range.data_ptr())))
 
+    @staticmethod
+    def _mmr_fetch(k: int, fetch) -> int:
+        return min(max(4 * int(k), 32), 1024) if fetch is None else int(fetch)
+
+    def search_mmr(self, queries, k: int, fetch=None, lam: float = 0.5):
+        """Diversified search: exact maximal-marginal-relevance re-ranking of the top-``fetch`` rows (``mx_index_search_mmr``).
+        -> (ids u64 [B,k], scores f32 [B,k], dists f32 [B,k], n_found i32 [B]) in SELECTION order: the best row first, then the
+        rows that maximise ``lam * score - (1 - lam) * (largest similarity to a row already picked)``.  ``fetch=None``:
+        ``min(max(4 * k, 32), 1024)`` candidates; ``lam = 1`` is the plain top-k, ``lam = 0`` cares for diversity only."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        B = q.shape[0]
+        kk = max(int(k), 0)
+        ids = np.zeros((B, kk), dtype=np.uint64)
+        scores = np.zeros((B, kk), dtype=np.float32)
+        dists = np.zeros((B, kk), dtype=np.float32)
+        nf = np.zeros(B, dtype=np.int32)
+        check(lib().mx_index_search_mmr(self._h, _ptr(q), B, int(k), self._mmr_fetch(k, fetch), float(lam),
+                                        _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None,
+                                        _ptr(dists) if dists.size else None, _ptr(nf)))
+        return ids, scores, dists, nf
+
+    def search_mmr_device(self, q, k: int, ids, scores, dists, n_found, fetch=None, lam: float = 0.5) -> None:
+        """``search_mmr`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,k]; scores, dists f32 [B,k] (dists may be None);
+        n_found i32 [B].  Blocks until the results are in HBM."""
+        B = int(q.shape[0])
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        check(lib().mx_index_search_mmr_device(self._h, ctypes.c_void_p(q.data_ptr()), B, int(k), self._mmr_fetch(k, fetch), float(lam),
+                                               ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
+                                               ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
+                                               ctypes.c_void_p(n_found.data_ptr())))
+
     # -- persistence ---------------------------------------------------------------------
     def save(self, directory: str) -> None:
         check(lib().mx_index_save(self._h, str(directory).encode()))

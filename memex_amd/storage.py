@@ -458,6 +458,30 @@ class HipFlatStore(VectorStore):
                 out.append((self._id_map[d_id], float(scores[0, j])))
         return out
 
+    def search_diverse(self, vec: Sequence[float], limit: int, fetch: int | None = None, lam: float = 0.5) -> List[VectorSearchResult]:
+        """The ``limit`` most relevant rows that do not repeat each other (``FlatIndex.search_mmr``: exact MMR re-ranking of the
+        top-``fetch`` rows), as ``(_id, score)`` pairs in selection order: context for a prompt without the same passage from
+        several overlapping windows.  ``lam = 1`` is ``search``.  Removed rows never appear."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0:
+            return []
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        try:
+            ids, scores, _, nf = idx.search_mmr(q, int(limit), fetch, float(lam))  # not under the lock, like search
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[VectorSearchResult] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[d_id], float(scores[0, j])))
+        return out
+
     def search(self, vec: Sequence[float], limit: int) -> List[VectorSearchResult]:
         with self._lock:
             idx = self._index        # own reference: the store may be evicted / replaced while the GPU works
