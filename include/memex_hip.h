@@ -252,6 +252,39 @@ int mx_index_search_mmr(mx_index *idx, const float *queries, int B, int k, int f
 int mx_index_search_mmr_device(mx_index *idx, const float *d_queries, int B, int k, int fetch, float lambda, uint64_t *d_ids,
                                float *d_scores, float *d_dists, int32_t *d_n_found);
 
+/*
+ * Search by stored row: the queries are rows of the index, named by the ids search returns ("more like this segment", "which rows
+ * repeat this one").  The rows never leave HBM: every shard gathers the rows it owns into one query block on devices[0], one plain pass
+ * runs over it, and a last kernel takes the own row out of each list.  query_ids holds B ids and is HOST memory on both variants.
+ * Let v_b be what mx_index_get_rows returns for the row query_ids[b] names (a bf16 corpus: its values widened) and e = exclude_self.
+ *   mx_index_search_by_id        per query: the entries of mx_index_search(v_b, k + e) in their (dist, id) order, the entry whose id is
+ *                                query_ids[b] dropped if it is among them, cut to k; n_found follows.  With e = 1 that is the EXACT
+ *                                top-k of the live rows other than the own row -- also when k + 1 or more exact copies with smaller ids
+ *                                come before it: then the own row is not among the k + 1 listed, nothing is dropped, and the first k
+ *                                are the answer (stripping "the first entry" of a k + 1 search by hand is wrong exactly there).
+ *   mx_index_search_range_by_id  per query: the same procedure on mx_index_search_range(v_b, min_scores[b], cap + e).  n_in_range is the
+ *                                plain call's count, minus one (e = 1) if the own row is itself in range by the plain call's own
+ *                                membership test -- usually dist 0, but a row whose norm leaves [1e-15, 1e15] is judged by the dist
+ *                                the plain path computes for it; n_found = min(cap, n_in_range).
+ * Unused slots hold id 0, score 0, dist +inf; dists may be NULL.  An id that names no row, or a removed row, finds nothing: n_found 0,
+ * n_in_range 0, blank slots, and the call still returns MX_OK (a batch over "all ids" does not fail on a tombstone).  id_offset applies
+ * to query ids exactly as to result ids.
+ * Arguments are checked first: B < 0, k < 1 / cap < 1, exclude_self not 0 or 1, min_scores == NULL (B > 0) or a NaN threshold:
+ * MX_EINVAL; k + e > 4096 / cap + e > 4096: MX_EUNSUPPORTED; then a null index: MX_ESEARCH.  Everything else is the plain pass's:
+ * removed rows, the AUTO and EXACT paths, B split into batches of 512, statistics; a range pass never changes the filter copy.
+ * Thread-safe beside every other call.  Concurrent callers are NOT combined into shared passes: each call holds the index from the
+ * translation of its ids to the end of its last kernel, so no append, removal or compaction slips between the stages.  Extra HBM,
+ * allocated at the first call: a query block of 512 rows and lists of 512 x max(k + e, 64) entries on devices[0].
+ */
+int mx_index_search_by_id(mx_index *idx, const uint64_t *query_ids, int B, int k, int exclude_self, uint64_t *ids, float *scores,
+                          float *dists, int32_t *n_found);
+int mx_index_search_by_id_device(mx_index *idx, const uint64_t *query_ids, int B, int k, int exclude_self, uint64_t *d_ids,
+                                 float *d_scores, float *d_dists, int32_t *d_n_found);
+int mx_index_search_range_by_id(mx_index *idx, const uint64_t *query_ids, int B, const float *min_scores, int cap, int exclude_self,
+                                uint64_t *ids, float *scores, float *dists, int32_t *n_found, uint64_t *n_in_range);
+int mx_index_search_range_by_id_device(mx_index *idx, const uint64_t *query_ids, int B, const float *min_scores, int cap, int exclude_self,
+                                       uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_n_found, uint64_t *d_n_in_range);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

@@ -456,6 +456,97 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // more like this: the `limit` entries closest to what is stored under _id, the asked _id itself left out.  Every row stored under
+    // _id is a query (mx_index_search_by_id: the rows never leave the device, the own row is taken out exactly); the union of their
+    // answers is ranked by best score, each row once.  An unknown _id returns nothing
+    std::vector<VectorSearchResult> more_like(const std::string &_id, size_t limit) {
+        std::vector<VectorSearchResult> out;
+        std::vector<uint64_t> mine;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0 || _id_map.empty()) return out;
+            build_rows_of();
+            auto it = rows_of_.find(_id);
+            if (it != rows_of_.end()) mine.assign(it->second.begin(), it->second.end());
+        }
+        if (mine.empty()) return out;
+        const size_t k = std::min<size_t>(limit + mine.size(), 4095);  // the rows under _id are the only entries dropped below
+        std::vector<uint64_t> found(mine.size() * k);
+        std::vector<float> scores(found.size()), dists(found.size());
+        std::vector<int32_t> nf(mine.size());
+        int rc = mx_index_search_by_id(idx_, mine.data(), (int)mine.size(), (int)k, 1, found.data(), scores.data(), dists.data(), nf.data());
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::map<uint64_t, std::pair<float, float>> best;  // id -> (dist, score) of its best appearance
+        for (size_t b = 0; b < mine.size(); ++b)
+            for (int j = 0; j < nf[b]; ++j) {
+                const uint64_t r = found[b * k + j];
+                if (std::find(mine.begin(), mine.end(), r) != mine.end()) continue;
+                auto it = best.find(r);
+                if (it == best.end() || dists[b * k + j] < it->second.first) best[r] = {dists[b * k + j], scores[b * k + j]};
+            }
+        std::vector<std::pair<std::pair<float, uint64_t>, float>> ranked;  // ((dist, id), score): the order search reports
+        for (auto &kv : best) ranked.push_back({{kv.second.first, kv.first}, kv.second.second});
+        std::sort(ranked.begin(), ranked.end());
+        if (ranked.size() > limit) ranked.resize(limit);
+        std::lock_guard<std::mutex> lk(mu_);
+        for (auto &r : ranked) {
+            auto it = _id_map.find((size_t)r.first.second);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.emplace_back(it->second, r.second);
+        }
+        return out;
+    }
+
+    struct DuplicatePair {
+        std::string a, b;  // the _ids of the two rows, the one with the smaller row id first
+        float score;
+    };
+    // The rows of the collection that repeat each other: every pair of live rows whose score reaches min_score, in row-id order -- an
+    // exact self-join on the device (mx_index_search_range_by_id over ids 1 .. n in blocks of 512, cap = per_row, the own row
+    // excluded).  truncated (optional): the _id of every row with more than per_row rows in range, whose list was cut.  The score is
+    // symmetric bit for bit, so a pair is missing only if BOTH of its rows are in truncated; raise per_row (at most 4095) for those
+    std::vector<DuplicatePair> find_duplicates(float min_score, size_t per_row = 64, std::vector<std::string> *truncated = nullptr) {
+        std::vector<DuplicatePair> out;
+        if (truncated) truncated->clear();
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || _id_map.empty()) return out;
+        }
+        const uint64_t n = nb_point();
+        const int cap = (int)std::min<size_t>(std::max<size_t>(per_row, 1), 4095);
+        const size_t block = 512;
+        std::map<std::pair<uint64_t, uint64_t>, float> pairs;  // (smaller id, larger id) -> score, each pair once
+        std::vector<uint64_t> cut, q(block), found(block * cap), nr(block);
+        std::vector<float> scores(block * cap), thr(block, min_score);
+        std::vector<int32_t> nf(block);
+        for (uint64_t lo = 0; lo < n; lo += block) {
+            const int nb = (int)std::min<uint64_t>(block, n - lo);
+            for (int b = 0; b < nb; ++b) q[b] = lo + b + 1;
+            int rc = mx_index_search_range_by_id(idx_, q.data(), nb, thr.data(), cap, 1, found.data(), scores.data(), nullptr, nf.data(),
+                                                 nr.data());
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            for (int b = 0; b < nb; ++b) {
+                if (nr[b] > (uint64_t)cap) cut.push_back(q[b]);
+                for (int j = 0; j < nf[b]; ++j) {
+                    const uint64_t o = found[(size_t)b * cap + j];
+                    pairs[{std::min(q[b], o), std::max(q[b], o)}] = scores[(size_t)b * cap + j];
+                }
+            }
+        }
+        std::lock_guard<std::mutex> lk(mu_);
+        auto name = [&](uint64_t r) -> const std::string & {
+            auto it = _id_map.find((size_t)r);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            return it->second;
+        };
+        for (auto &kv : pairs) out.push_back({name(kv.first.first), name(kv.first.second), kv.second});
+        if (truncated)
+            for (uint64_t r : cut) truncated->push_back(name(r));
+        return out;
+    }
+
     uint64_t nb_point() const {  // hnsw.get_nb_point() in the reference's test (local.rs:238)
         uint64_t n = 0;
         if (idx_) mx_index_size(idx_, &n);
@@ -473,6 +564,12 @@ class HipFlatStore : public VectorStore {
     bool meta_known_ = false;
     std::map<std::string, std::vector<size_t>> rows_of_;  // _id -> ids (remove): built by the first remove, kept on insert
     bool rows_of_built_ = false;
+
+    void build_rows_of() {  // (under mu_)
+        if (rows_of_built_) return;
+        for (auto &kv : _id_map) rows_of_[kv.second].push_back(kv.first);
+        rows_of_built_ = true;
+    }
 
     static std::pair<long long, long long> file_sig(const std::string &p) {
         struct stat sb;

@@ -30,7 +30,9 @@ EXPORTS = [
     "mx_index_open", "mx_index_open_sharded", "mx_index_n_shards", "mx_index_exchange", "mx_index_wait_stream", "mx_index_close", "mx_index_dim", "mx_index_size", "mx_index_reserve",
     "mx_index_set_id_offset", "mx_index_add", "mx_index_add_device", "mx_index_clear",
     "mx_index_remove", "mx_index_removed", "mx_index_compact",
-    "mx_index_search", "mx_index_search_device", "mx_index_search_filtered", "mx_index_search_filtered_device", "mx_index_search_range", "mx_index_search_range_device", "mx_index_search_mmr", "mx_index_search_mmr_device", "mx_index_set_search_mode", "mx_index_set_filter_copy", "mx_index_set_corpus_mode", "mx_index_get_rows",
+    "mx_index_search", "mx_index_search_device", "mx_index_search_filtered", "mx_index_search_filtered_device", "mx_index_search_range", "mx_index_search_range_device", "mx_index_search_mmr", "mx_index_search_mmr_device",
+    "mx_index_search_by_id", "mx_index_search_by_id_device", "mx_index_search_range_by_id", "mx_index_search_range_by_id_device",
+    "mx_index_set_search_mode", "mx_index_set_filter_copy", "mx_index_set_corpus_mode", "mx_index_get_rows",
     "mx_index_save", "mx_index_load", "mx_index_has_store", "mx_index_store_info", "mx_index_remove_files",
     "mx_index_set_profiling", "mx_index_get_stats", "mx_index_reset_stats", "mx_topk_merge_device", "mx_topk_merge_packed_device", "mx_topk_merge_packed_async",
     "mx_encoder_cfg_size", "mx_encoder_weight_bytes", "mx_encoder_create", "mx_encoder_open", "mx_encoder_wait_stream", "mx_encoder_destroy", "mx_encoder_encode",
@@ -125,6 +127,10 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_mmr": [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp],
         "mx_index_search_mmr_device": [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp],
+        "mx_index_search_by_id": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
+        "mx_index_search_by_id_device": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
+        "mx_index_search_range_by_id": [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp],
+        "mx_index_search_range_by_id_device": [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp],
         "mx_index_set_search_mode": [vp, i32],
         "mx_index_set_filter_copy": [vp, i32],
         "mx_index_set_corpus_mode": [vp, i32],

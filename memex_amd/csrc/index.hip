@@ -263,6 +263,18 @@ struct mx_index {
     int32_t *mmr_nf = nullptr, *mmr_h_nf = nullptr;
     uint32_t *mmr_pos = nullptr;
     int mmr_fcap = 0;
+    // search by stored row (mx_index_search_by_id), allocated at the first such call.  Every plain index or shard: the
+    // row list of a gather launch [kMaxBatch] and -- a shard on another device than shards[0] -- the block its rows go to before the
+    // peer copy [kMaxBatch, dim].  The index that owns the stream also holds the query block [kMaxBatch, dim], the pass's own lists
+    // [kMaxBatch, byid_cap] with their counts, and per query its place in them, its id and its dist bound.
+    uint32_t *byid_rows = nullptr;
+    float *byid_stage = nullptr;
+    float *byid_q = nullptr;
+    uint64_t *byid_ids = nullptr, *byid_nr = nullptr, *byid_own = nullptr;
+    float *byid_scores = nullptr, *byid_dists = nullptr;
+    int32_t *byid_nf = nullptr;
+    uint32_t *byid_src = nullptr, *byid_dlim = nullptr;
+    int byid_cap = 0;
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -354,6 +366,8 @@ int free_index(mx_index *idx) {
     F(idx->mmr_rows); F(idx->mmr_stage); F(idx->mmr_ids); F(idx->mmr_scores); F(idx->mmr_dists); F(idx->mmr_nf); F(idx->mmr_pos);
     if (idx->mmr_h_ids) (void)hipHostFree(idx->mmr_h_ids);
     if (idx->mmr_h_nf) (void)hipHostFree(idx->mmr_h_nf);
+    F(idx->byid_rows); F(idx->byid_stage); F(idx->byid_q); F(idx->byid_ids); F(idx->byid_nr); F(idx->byid_own); F(idx->byid_scores);
+    F(idx->byid_dists); F(idx->byid_nf); F(idx->byid_src); F(idx->byid_dlim);
     Scratch &s = idx->s;
     F(s.qfrag); F(s.qpad); F(s.qnorm2); F(s.theta); F(s.theta_retry); F(s.todo); F(s.dev_flags); F(s.done_ctr);
     if (s.host_flags) (void)hipHostFree(s.host_flags);
@@ -2054,6 +2068,122 @@ int mmr_batch(mx_index *idx, const float *d_q, int B, int k, int fetch, float la
     return MX_OK;
 }
 
+// ---- search by stored row (mx_index_search_by_id / mx_index_search_range_by_id) ----------------------------
+bool row_removed(const mx_index *t, uint64_t r);
+
+// the pass's own lists, kk wide, and the per-query words on the index that owns the stream (the current device is its device)
+int ensure_byid_lists(mx_index *t, int kk) {
+    if (!t->byid_q) {
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_q), (size_t)kMaxBatch * t->dim * sizeof(float)));
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_nf), kMaxBatch * sizeof(int32_t)));
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_nr), kMaxBatch * sizeof(uint64_t)));
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_own), kMaxBatch * sizeof(uint64_t)));
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_src), kMaxBatch * sizeof(uint32_t)));
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_dlim), kMaxBatch * sizeof(uint32_t)));
+    }
+    if (kk <= t->byid_cap) return MX_OK;
+    MX_HIP(hipStreamSynchronize(t->stream));
+    auto F = [](void *p) {
+        if (p) (void)hipFree(p);
+    };
+    F(t->byid_ids); F(t->byid_scores); F(t->byid_dists);
+    t->byid_ids = nullptr; t->byid_scores = nullptr; t->byid_dists = nullptr;
+    t->byid_cap = 0;
+    const size_t c = (size_t)std::max(kk, 64);
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_ids), (size_t)kMaxBatch * c * sizeof(uint64_t)));
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_scores), (size_t)kMaxBatch * c * sizeof(float)));
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_dists), (size_t)kMaxBatch * c * sizeof(float)));
+    t->byid_cap = (int)c;
+    return MX_OK;
+}
+
+// One batch (B <= kMaxBatch) of a search whose queries are the stored rows qids names (host memory), outputs [B, k] on the device of
+// the index that owns the stream, the caller holding idx->mu from here to the end: ids -> (shard, local row) while nothing can move
+// them, every shard gathers its rows into its slice of one query block (queries that name no live row are left out of the pass), one
+// plain pass at k + exclude -- any_batch, or any_range_batch when dlim (the B dist bounds, host memory) is given, k being the cap --
+// into this index's own lists, and byid_drop_self_kernel writes the caller's.
+int byid_batch(mx_index *idx, const uint64_t *qids, int B, int k, int exclude, const uint32_t *dlim, uint64_t *d_ids, float *d_scores,
+               float *d_dists, int32_t *d_nfound, uint64_t *d_nrange) {
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    const int kk = k + exclude, dim = idx->dim;
+    int rc = ensure_byid_lists(t, kk);
+    if (rc != MX_OK) return rc;
+    hipStream_t st = t->stream;
+    const size_t G = idx->composite() ? idx->shards.size() : 1;
+    const uint64_t R = idx->composite() ? idx->block_rows : 0, off = idx->idmap.id_offset, total_rows = idx->composite() ? idx->total : idx->n;
+    std::vector<std::vector<uint32_t>> rows(G);  // (alive until the batch is host-synchronised: sources of async uploads)
+    std::vector<uint32_t> src((size_t)B, kByIdNone), owner((size_t)B, 0u), pd((size_t)B, 0u);
+    for (int b = 0; b < B; ++b) {
+        const uint64_t id = qids[b];
+        if (id <= off || id - off - 1 >= total_rows) continue;  // names no row
+        const uint64_t r = id - off - 1;
+        const uint64_t g = R ? (r / R) % G : 0, local = R ? (r / R / G) * R + r % R : r;
+        const mx_index *sh = idx->composite() ? idx->shards[g] : idx;
+        if (local >= sh->n) return fail(MX_ESEARCH, "id %llu names no row of its shard", (unsigned long long)id);
+        if (row_removed(sh, local)) continue;
+        owner[b] = (uint32_t)g;
+        src[b] = (uint32_t)rows[g].size();
+        rows[g].push_back((uint32_t)local);
+    }
+    std::vector<size_t> first(G + 1, 0);
+    for (size_t g = 0; g < G; ++g) first[g + 1] = first[g] + rows[g].size();
+    const int live = (int)first[G];
+    for (int b = 0; b < B; ++b)
+        if (src[b] != kByIdNone) {
+            src[b] += (uint32_t)first[owner[b]];
+            if (dlim) pd[src[b]] = dlim[b];
+        }
+    for (size_t g = 0; g < G; ++g) {
+        if (rows[g].empty()) continue;
+        mx_index *sh = idx->composite() ? idx->shards[g] : idx;
+        std::unique_lock<std::mutex> lk(sh->mu, std::defer_lock);
+        if (idx->composite()) lk.lock();  // (a plain index: the caller holds it)
+        DeviceGuard dg(sh->device);
+        const bool same = sh->device == t->device;
+        if (!sh->byid_rows) MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->byid_rows), kMaxBatch * sizeof(uint32_t)));
+        if (!same && !sh->byid_stage) MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->byid_stage), (size_t)kMaxBatch * dim * sizeof(float)));
+        MX_HIP(hipMemcpyAsync(sh->byid_rows, rows[g].data(), rows[g].size() * sizeof(uint32_t), hipMemcpyHostToDevice, sh->stream));
+        float *slot = t->byid_q + first[g] * (size_t)dim;
+        MX_HIP(launch_byid_gather(sh->stream, dim, sh->ds, sh->compressed ? nullptr : sh->x, sh->xh, sh->byid_rows, (uint32_t)rows[g].size(),
+                                  same ? slot : sh->byid_stage));
+        if (!same)  // peer copy to shards[0]'s device
+            MX_HIP(hipMemcpyAsync(slot, sh->byid_stage, rows[g].size() * (size_t)dim * sizeof(float), hipMemcpyDefault, sh->stream));
+        if (sh != t) MX_HIP(hipStreamSynchronize(sh->stream));
+    }
+    DeviceGuard dg(t->device);
+    if (live > 0) {
+        rc = dlim ? any_range_batch(idx, t->byid_q, live, kk, pd.data(), t->byid_ids, t->byid_scores, t->byid_dists, t->byid_nf, t->byid_nr)
+                  : any_batch(idx, t->byid_q, live, kk, t->byid_ids, t->byid_scores, t->byid_dists, t->byid_nf);
+        if (rc != MX_OK) return rc;
+    }
+    MX_HIP(hipMemcpyAsync(t->byid_src, src.data(), (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    MX_HIP(hipMemcpyAsync(t->byid_own, qids, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (dlim) MX_HIP(hipMemcpyAsync(t->byid_dlim, pd.data(), (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ByIdDrop p{};
+    p.B = B;
+    p.k = k;
+    p.kk = kk;
+    p.exclude = exclude;
+    p.dim = dim;
+    p.src = t->byid_src;
+    p.own = t->byid_own;
+    p.in_ids = t->byid_ids;
+    p.in_scores = t->byid_scores;
+    p.in_dists = t->byid_dists;
+    p.in_nfound = t->byid_nf;
+    p.in_nrange = dlim ? t->byid_nr : nullptr;
+    p.dlim = t->byid_dlim;
+    p.q = t->byid_q;
+    p.ids = d_ids;
+    p.scores = d_scores;
+    p.dists = d_dists;
+    p.n_found = d_nfound;
+    p.n_in_range = dlim ? d_nrange : nullptr;
+    MX_HIP(launch_byid_drop_self(st, p));
+    MX_HIP(hipStreamSynchronize(st));
+    return MX_OK;
+}
+
 // what an append can change in a plain index, and how to undo it: an insert is all-or-nothing, also when it
 // spans several shards or several staging chunks and a later part fails (non-finite device rows, HBM)
 struct RowMark {
@@ -3599,6 +3729,108 @@ int mx_index_search_mmr_device(mx_index *idx, const float *d_q, int B, int k, in
         if (rc != MX_OK) return rc;
     }
     return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+namespace {
+
+// arguments of the by-id entry points, checked before the index is looked at; k is the cap of a range call, whose thresholds become
+// dist bounds in dlim
+int read_by_id_args(int B, int k, int exclude_self, bool range, const float *min_scores, std::vector<uint32_t> *dlim) {
+    const char *what = range ? "cap" : "k";
+    if (B < 0) return fail(MX_EINVAL, "negative batch");
+    if (k < 1) return fail(MX_EINVAL, "%s = %d < 1", what, k);
+    if (exclude_self != 0 && exclude_self != 1) return fail(MX_EINVAL, "exclude_self = %d is neither 0 nor 1", exclude_self);
+    if (range) {
+        if (B > 0 && !min_scores) return fail(MX_EINVAL, "null min_scores");
+        dlim->resize((size_t)B);
+        for (int b = 0; b < B; ++b) {
+            if (std::isnan(min_scores[b])) return fail(MX_EINVAL, "min_scores[%d] is NaN", b);
+            (*dlim)[b] = range_dist_limit(min_scores[b]);
+        }
+    }
+    if (k > 4096 - exclude_self)
+        return fail(MX_EUNSUPPORTED, "%s = %d%s > 4096", what, k, exclude_self ? " + 1 (the own row)" : "");
+    return MX_OK;
+}
+
+// the four by-id entry points: dlim null = top-k; on_host: outputs are host memory and pass through the staging buffers
+int search_by_id(mx_index *idx, const uint64_t *qids, int B, int k, int exclude_self, const std::vector<uint32_t> *dlim, bool on_host,
+                 uint64_t *ids, float *scores, float *dists, int32_t *n_found, uint64_t *n_in_range) {
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B == 0) return MX_OK;
+    if (!qids || !ids || !scores || !n_found || (dlim && !n_in_range)) return fail(MX_EINVAL, "null argument");
+    // not combined with other callers: the call holds the index from the id translation to the end of the drop kernel
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
+    DeviceGuard g(t->device);
+    int rc;
+    if (on_host) {
+        if ((rc = ensure_scratch(t)) != MX_OK) return rc;
+        if ((rc = ensure_out(t, k)) != MX_OK) return rc;
+    }
+    Scratch &s = t->s;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        const uint32_t *dl = dlim ? dlim->data() + b0 : nullptr;
+        if (!on_host) {
+            rc = byid_batch(idx, qids + b0, nb, k, exclude_self, dl, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0,
+                            dlim ? n_in_range + b0 : nullptr);
+            if (rc != MX_OK) return rc;
+            continue;
+        }
+        if ((rc = byid_batch(idx, qids + b0, nb, k, exclude_self, dl, s.out_ids, s.out_scores, s.out_dists, s.out_nfound, s.out_nrange)) != MX_OK)
+            return rc;
+        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        if (dlim) MX_HIP(hipMemcpyAsync(s.h_nr, s.out_nrange, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipStreamSynchronize(t->stream));
+        memcpy(ids + o, s.h_ids, (size_t)nb * k * sizeof(uint64_t));
+        memcpy(scores + o, s.h_scores, (size_t)nb * k * sizeof(float));
+        if (dists) memcpy(dists + o, s.h_dists, (size_t)nb * k * sizeof(float));
+        memcpy(n_found + b0, s.h_nf, (size_t)nb * sizeof(int32_t));
+        if (dlim) memcpy(n_in_range + b0, s.h_nr, (size_t)nb * sizeof(uint64_t));
+    }
+    return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_search_by_id(mx_index *idx, const uint64_t *query_ids, int B, int k, int exclude_self, uint64_t *ids, float *scores,
+                          float *dists, int32_t *n_found) try {
+    if (int rc = read_by_id_args(B, k, exclude_self, false, nullptr, nullptr); rc != MX_OK) return rc;
+    return search_by_id(idx, query_ids, B, k, exclude_self, nullptr, true, ids, scores, dists, n_found, nullptr);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_by_id_device(mx_index *idx, const uint64_t *query_ids, int B, int k, int exclude_self, uint64_t *d_ids, float *d_scores,
+                                 float *d_dists, int32_t *d_nfound) try {
+    if (int rc = read_by_id_args(B, k, exclude_self, false, nullptr, nullptr); rc != MX_OK) return rc;
+    return search_by_id(idx, query_ids, B, k, exclude_self, nullptr, false, d_ids, d_scores, d_dists, d_nfound, nullptr);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_range_by_id(mx_index *idx, const uint64_t *query_ids, int B, const float *min_scores, int cap, int exclude_self,
+                                uint64_t *ids, float *scores, float *dists, int32_t *n_found, uint64_t *n_in_range) try {
+    std::vector<uint32_t> dlim;
+    if (int rc = read_by_id_args(B, cap, exclude_self, true, min_scores, &dlim); rc != MX_OK) return rc;
+    return search_by_id(idx, query_ids, B, cap, exclude_self, &dlim, true, ids, scores, dists, n_found, n_in_range);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_range_by_id_device(mx_index *idx, const uint64_t *query_ids, int B, const float *min_scores, int cap, int exclude_self,
+                                       uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_nfound, uint64_t *d_n_in_range) try {
+    std::vector<uint32_t> dlim;
+    if (int rc = read_by_id_args(B, cap, exclude_self, true, min_scores, &dlim); rc != MX_OK) return rc;
+    return search_by_id(idx, query_ids, B, cap, exclude_self, &dlim, false, d_ids, d_scores, d_dists, d_nfound, d_n_in_range);
 } catch (...) {
     return guard_exception();
 }

@@ -345,4 +345,32 @@ hipError_t launch_mmr_select(hipStream_t s, int B, int k, int fetch, int ds, flo
                              const uint64_t *cand_ids, const float *cand_scores, const float *cand_dists, const int32_t *cand_nf,
                              uint64_t *ids, float *scores, float *dists, int32_t *n_found);
 
+// search by stored row (mx_index_search_by_id / mx_index_search_range_by_id)
+constexpr uint32_t kByIdNone = 0xffffffffu;      // ByIdDrop::src of a query whose id names no live row
+// q[i, dim] = the first dim values of stored row rows[i] of the index (x: f32 rows, or null: the compressed corpus xh), widened to
+// f32, i < n: a query block as the search entry points take it (rows dim apart, no padding)
+hipError_t launch_byid_gather(hipStream_t s, int dim, int ds, const float *x, const void *xh, const uint32_t *rows, uint32_t n, float *q);
+// The internal lists [*, kk] (kk = k + exclude) of a pass whose queries are stored rows -> the caller's outputs [B, k].  Query b's lists
+// are row src[b] of the internal ones (the pass orders its queries by shard and leaves out ids that name no live row: src = kByIdNone,
+// blank outputs); own[b] is the id it was asked under.  With exclude, the entry whose id is own[b] is dropped if it is listed and the
+// later ones move up; either way the list is cut to k.  A range pass (in_nrange != null) also corrects the count: minus one when the own
+// row is listed, or when the list was cut short of the count and the own row is in range by the plain path's own test, bits(dist) <
+// dlim[src] with dist = DistCosine(row, row) on the gathered row q[src].  Unused slots id 0 / score 0 / dist +inf; dists may be null.
+struct ByIdDrop {
+    int B, k, kk, exclude, dim;
+    const uint32_t *src;
+    const uint64_t *own;
+    const uint64_t *in_ids;
+    const float *in_scores, *in_dists;
+    const int32_t *in_nfound;
+    const uint64_t *in_nrange;
+    const uint32_t *dlim;
+    const float *q;
+    uint64_t *ids;
+    float *scores, *dists;
+    int32_t *n_found;
+    uint64_t *n_in_range;
+};
+hipError_t launch_byid_drop_self(hipStream_t s, const ByIdDrop &p);
+
 }  // namespace mx

@@ -2336,4 +2336,98 @@ hipError_t launch_mmr_select(hipStream_t s, int B, int k, int fetch, int ds, flo
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// search by stored row (mx_index_search_by_id / mx_index_search_range_by_id): the stored rows as a query
+// block, and the own row taken out of the lists the pass returns
+// ---------------------------------------------------------------------------------------------
+// One wave per row, four rows per workgroup: lane l copies the 16 bytes l, l + 64, ... of the row, so a wave reads and writes 1 KiB of
+// consecutive addresses per trip (an f32 corpus; the compressed corpus reads the 8-byte halves of its fragments).  Rows of the block
+// are dim floats apart: 16-byte stores when that keeps them aligned, element stores otherwise.
+template <bool CMP>
+__global__ __launch_bounds__(256) void byid_gather_kernel(int dim, int ds, const float *__restrict__ x, const void *__restrict__ xh,
+                                                          const uint32_t *__restrict__ rows, uint32_t n, float *__restrict__ q) {
+    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (i >= n) return;  // (wave-uniform)
+    const int lane = threadIdx.x & 63;
+    const uint32_t row = rows[i];
+    float *dst = q + (size_t)i * dim;
+    if ((dim & 3) == 0) {
+        for (int c4 = lane; c4 < dim / 4; c4 += 64) reinterpret_cast<float4 *>(dst)[c4] = row_load4<CMP>(x, xh, ds, row, c4);
+    } else {
+        for (int c4 = lane; c4 < (dim + 3) / 4; c4 += 64) {  // (ds >= dim rounded up to a multiple of 4: the load stays inside the row)
+            const float4 v = row_load4<CMP>(x, xh, ds, row, c4);
+            const int c = 4 * c4;
+            dst[c] = v.x;
+            if (c + 1 < dim) dst[c + 1] = v.y;
+            if (c + 2 < dim) dst[c + 2] = v.z;
+            if (c + 3 < dim) dst[c + 3] = v.w;
+        }
+    }
+}
+
+hipError_t launch_byid_gather(hipStream_t s, int dim, int ds, const float *x, const void *xh, const uint32_t *rows, uint32_t n, float *q) {
+    if (n == 0) return hipSuccess;
+    if (dim < 1 || ds < dim || ds % 4) return hipErrorInvalidValue;
+    if (x) hipLaunchKernelGGL(byid_gather_kernel<false>, dim3((n + 3) / 4), dim3(256), 0, s, dim, ds, x, xh, rows, n, q);
+    else hipLaunchKernelGGL(byid_gather_kernel<true>, dim3((n + 3) / 4), dim3(256), 0, s, dim, ds, x, xh, rows, n, q);
+    return hipGetLastError();
+}
+
+// One wave per query, four queries per workgroup.  Reads the internal lists, writes the caller's: never in place.
+__global__ __launch_bounds__(256) void byid_drop_self_kernel(ByIdDrop p) {
+    const int b = (int)(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    if (b >= p.B) return;  // (wave-uniform, like everything below but the lane's own slots)
+    const int k = p.k, kk = p.kk;
+    const uint32_t src = p.src[b];
+    const bool live = src != kByIdNone;
+    const uint64_t *iid = p.in_ids + (size_t)(live ? src : 0u) * kk;
+    const float *isc = p.in_scores + (size_t)(live ? src : 0u) * kk;
+    const float *idi = p.in_dists + (size_t)(live ? src : 0u) * kk;
+    int m = live ? p.in_nfound[src] : 0;
+    m = m < 0 ? 0 : m > kk ? kk : m;
+    int at = m;  // where the own row is listed; m: nowhere
+    if (live && p.exclude) {
+        const uint64_t own = p.own[b];
+        for (int i0 = 0; i0 < m && at == m; i0 += 64) {
+            const int i = i0 + lane;
+            const unsigned long long hit = __ballot(i < m && iid[i] == own);
+            if (hit) at = i0 + __builtin_ctzll(hit);
+        }
+    }
+    const int left = m - (at < m ? 1 : 0), found = left < k ? left : k;
+    uint64_t *oid = p.ids + (size_t)b * k;
+    float *osc = p.scores + (size_t)b * k;
+    float *odi = p.dists ? p.dists + (size_t)b * k : nullptr;
+    for (int j = lane; j < k; j += 64) {
+        const int i = j < at ? j : j + 1;  // (j < found: i < m)
+        oid[j] = j < found ? iid[i] : 0;
+        osc[j] = j < found ? isc[i] : 0.0f;
+        if (odi) odi[j] = j < found ? idi[i] : INFINITY;
+    }
+    if (lane != 0) return;
+    p.n_found[b] = found;
+    if (!p.n_in_range) return;
+    uint64_t nr = live ? p.in_nrange[src] : 0;
+    if (live && p.exclude) {
+        if (at < m) {
+            nr -= 1;
+        } else if (nr > (uint64_t)m) {
+            // the list was cut before the own row, if it is in range at all: the plain path's membership test for it.  Query and row
+            // are the same values, so DistCosine's three chains are one: 0 unless na * na leaves the f64 range (a wide-norm row)
+            const float *v = p.q + (size_t)src * p.dim;
+            double na = 0.0;
+            for (int i = 0; i < p.dim; ++i) na += (double)__fmul_rn(v[i], v[i]);
+            if (__float_as_uint(dist_from_sums(na, na, na)) < p.dlim[src]) nr -= 1;
+        }
+    }
+    p.n_in_range[b] = nr;
+}
+
+hipError_t launch_byid_drop_self(hipStream_t s, const ByIdDrop &p) {
+    if (p.B <= 0) return hipSuccess;
+    if (p.k < 1 || p.kk < p.k || p.kk > p.k + 1 || (p.in_nrange && !p.n_in_range)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(byid_drop_self_kernel, dim3((p.B + 3) / 4), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 }  // namespace mx

@@ -50,6 +50,7 @@ class FlatIndex:
         self.dim = int(dim)
         self.device = int(device)
         self.key = key
+        self._id_offset = 0
 
     @property
     def n_shards(self) -> int:
@@ -99,6 +100,7 @@ class FlatIndex:
 
     def set_id_offset(self, off: int) -> None:
         check(lib().mx_index_set_id_offset(self._h, int(off)))
+        self._id_offset = int(off)
 
     def set_search_mode(self, mode: int) -> None:
         check(lib().mx_index_set_search_mode(self._h, int(mode)))
@@ -326,6 +328,106 @@ class FlatIndex:
                                                ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
                                                ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
                                                ctypes.c_void_p(n_found.data_ptr())))
+
+    # -- search by stored row --------------------------------------------------------------
+    @staticmethod
+    def _query_ids(ids) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+
+    def search_by_id(self, ids, k: int, exclude_self: bool = True):
+        """More like these rows: ``search`` with the stored rows named by ``ids`` as queries (``mx_index_search_by_id``); the rows
+        never leave HBM.  -> (ids u64 [B,k], scores f32 [B,k], dists f32 [B,k], n_found i32 [B]).  ``exclude_self``: the exact
+        top-k of the live rows OTHER than the own row (exact copies of it stay).  An id that names no row, or a removed one,
+        finds nothing."""
+        a = self._query_ids(ids)
+        B, kk = a.size, max(int(k), 0)
+        out = np.zeros((B, kk), dtype=np.uint64)
+        scores = np.zeros((B, kk), dtype=np.float32)
+        dists = np.zeros((B, kk), dtype=np.float32)
+        nf = np.zeros(B, dtype=np.int32)
+        check(lib().mx_index_search_by_id(self._h, _ptr(a) if B else None, B, int(k), int(exclude_self), _ptr(out) if out.size else None,
+                                          _ptr(scores) if scores.size else None, _ptr(dists) if dists.size else None, _ptr(nf)))
+        return out, scores, dists, nf
+
+    def search_by_id_device(self, ids, k: int, out_ids, scores, dists, n_found, exclude_self: bool = True) -> None:
+        """``search_by_id`` with device tensors for the outputs: out_ids i64/u64 [B,k]; scores, dists f32 [B,k] (dists may be
+        None); n_found i32 [B].  The query ids stay on the host.  Blocks until the results are in HBM."""
+        a = self._query_ids(ids)
+        st = _caller_stream(out_ids)
+        if st is not None:
+            self.wait_stream(st)
+        check(lib().mx_index_search_by_id_device(self._h, _ptr(a) if a.size else None, a.size, int(k), int(exclude_self),
+                                                 ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
+                                                 ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
+                                                 ctypes.c_void_p(n_found.data_ptr())))
+
+    def search_range_by_id(self, ids, min_score, cap: int, exclude_self: bool = True):
+        """``search_range`` with the stored rows named by ``ids`` as queries (``mx_index_search_range_by_id``) -> (ids u64 [B,cap],
+        scores f32 [B,cap], dists f32 [B,cap], n_found i32 [B], n_in_range u64 [B]).  ``exclude_self``: the own row is neither
+        listed nor counted."""
+        a = self._query_ids(ids)
+        B = a.size
+        t = self._min_scores(min_score, B)
+        c = max(int(cap), 0)
+        out = np.zeros((B, c), dtype=np.uint64)
+        scores = np.zeros((B, c), dtype=np.float32)
+        dists = np.zeros((B, c), dtype=np.float32)
+        nf = np.zeros(B, dtype=np.int32)
+        nr = np.zeros(B, dtype=np.uint64)
+        check(lib().mx_index_search_range_by_id(self._h, _ptr(a) if B else None, B, _ptr(t) if t.size else None, int(cap), int(exclude_self),
+                                                _ptr(out) if out.size else None, _ptr(scores) if scores.size else None,
+                                                _ptr(dists) if dists.size else None, _ptr(nf), _ptr(nr)))
+        return out, scores, dists, nf, nr
+
+    def search_range_by_id_device(self, ids, min_score, cap: int, out_ids, scores, dists, n_found, n_in_range,
+                                  exclude_self: bool = True) -> None:
+        """``search_range_by_id`` with device tensors for the outputs (as ``search_range_device``'s); the query ids and the
+        thresholds stay on the host."""
+        a = self._query_ids(ids)
+        t = self._min_scores(min_score, a.size)
+        st = _caller_stream(out_ids)
+        if st is not None:
+            self.wait_stream(st)
+        check(lib().mx_index_search_range_by_id_device(self._h, _ptr(a) if a.size else None, a.size, _ptr(t) if t.size else None, int(cap),
+                                                       int(exclude_self), ctypes.c_void_p(out_ids.data_ptr()),
+                                                       ctypes.c_void_p(scores.data_ptr()),
+                                                       ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
+                                                       ctypes.c_void_p(n_found.data_ptr()), ctypes.c_void_p(n_in_range.data_ptr())))
+
+    def near_duplicates(self, min_score: float, per_row: int = 64, block: int = 512):
+        """The exact self-join: every pair of live rows whose score reaches ``min_score``.
+        -> (pairs u64 [P, 2] with pairs[:, 0] < pairs[:, 1], sorted by (first id, second id), each pair once; scores f32 [P];
+        truncated u64 [T]: the ids with more than ``per_row`` rows in range, whose lists were cut).
+        Walks the ids id_offset + 1 .. id_offset + len in blocks of ``block`` through ``search_range_by_id(exclude_self=True,
+        cap=per_row)``, id_offset being what ``set_id_offset`` was last given on this object.
+        Guarantee: the score is symmetric bit for bit -- f32 products commute, the three f64 chains run in element order whichever
+        row is the query, and na * nb commutes -- so row j is in row i's range exactly when i is in j's, with the same score.  A
+        pair is therefore lost only when BOTH of its rows are listed in ``truncated``; raise ``per_row`` (at most 4095) to get
+        those."""
+        n = len(self)
+        empty = (np.zeros((0, 2), dtype=np.uint64), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.uint64))
+        if n == 0:
+            return empty
+        first = self._id_offset + 1
+        a_parts, b_parts, s_parts, trunc = [], [], [], []
+        for lo in range(0, n, max(int(block), 1)):
+            q = np.arange(first + lo, first + min(lo + max(int(block), 1), n), dtype=np.uint64)
+            ids, scores, _, nf, nr = self.search_range_by_id(q, float(min_score), int(per_row), exclude_self=True)
+            listed = np.arange(ids.shape[1])[None, :] < nf[:, None]
+            own = np.broadcast_to(q[:, None], ids.shape)[listed]
+            other = ids[listed]
+            a_parts.append(np.minimum(own, other))
+            b_parts.append(np.maximum(own, other))
+            s_parts.append(scores[listed])
+            trunc.append(q[nr > np.uint64(per_row)])
+        a, b, s = np.concatenate(a_parts), np.concatenate(b_parts), np.concatenate(s_parts)
+        truncated = np.concatenate(trunc)
+        if a.size == 0:
+            return empty[0], empty[1], truncated
+        order = np.lexsort((b, a))
+        a, b, s = a[order], b[order], s[order]
+        keep = np.r_[True, (a[1:] != a[:-1]) | (b[1:] != b[:-1])]      # a pair seen from both ends: the same score, kept once
+        return np.ascontiguousarray(np.stack([a[keep], b[keep]], axis=1)), s[keep], truncated
 
     # -- persistence ---------------------------------------------------------------------
     def save(self, directory: str) -> None:

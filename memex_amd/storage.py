@@ -482,6 +482,71 @@ class HipFlatStore(VectorStore):
                 out.append((self._id_map[d_id], float(scores[0, j])))
         return out
 
+    def _rows_by_name(self) -> Dict[str, List[int]]:
+        """(under the lock) ``_id`` -> the ids stored under it: built once per store, kept on insert."""
+        if self._rows_of is None:
+            rows_of: Dict[str, List[int]] = {}
+            for i, d_id in self._id_map.items():
+                rows_of.setdefault(d_id, []).append(i)
+            self._rows_of = rows_of
+        return self._rows_of
+
+    def more_like(self, _id: str, limit: int) -> List[VectorSearchResult]:
+        """More like this: the ``limit`` entries closest to what is stored under ``_id``, as ``(_id, score)`` pairs like ``search``,
+        the asked ``_id`` itself left out.  Every row stored under ``_id`` is a query (``FlatIndex.search_by_id``: the rows never
+        leave the device); the union of their answers is ranked by best score, each row once.  An unknown ``_id``, or one whose
+        rows were all removed, returns ``[]``."""
+        with self._lock:
+            idx = self._index
+            if idx is None or limit <= 0 or not self._id_map:
+                return []
+            mine = list(self._rows_by_name().get(str(_id), ()))
+        if not mine:
+            return []
+        try:
+            # limit + the rows under _id: they are the only entries dropped below, so `limit` others are among them
+            ids, scores, dists, nf = idx.search_by_id(mine, int(limit) + len(mine), exclude_self=True)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        own = set(mine)
+        best: Dict[int, Tuple[float, float]] = {}
+        for b in range(len(mine)):
+            for j in range(int(nf[b])):
+                r = int(ids[b, j])
+                if r in own:
+                    continue
+                key = (float(dists[b, j]), float(scores[b, j]))
+                if r not in best or key < best[r]:
+                    best[r] = key
+        ranked = sorted(best.items(), key=lambda kv: (kv[1][0], kv[0]))[: int(limit)]     # (dist, id): the order search reports
+        out: List[VectorSearchResult] = []
+        with self._lock:
+            for r, (_, score) in ranked:
+                if r not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[r], score))
+        return out
+
+    def find_duplicates(self, min_score: float, per_row: int = 64) -> Tuple[List[Tuple[str, str, float]], List[str]]:
+        """The rows of the collection that repeat each other: every pair of live rows whose score reaches ``min_score``
+        (``FlatIndex.near_duplicates``, an exact self-join on the device) -> (``(_id_a, _id_b, score)`` per pair, in id order;
+        the ``_id`` of every row with more than ``per_row`` rows in range).  A pair is missing only if both of its rows are
+        in the second list; raise ``per_row`` (at most 4095) for those.  Hand one end of each pair to ``remove``."""
+        with self._lock:
+            idx = self._index
+            if idx is None or not self._id_map:
+                return [], []
+        try:
+            pairs, scores, truncated = idx.near_duplicates(float(min_score), int(per_row))
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        with self._lock:
+            for r in list(pairs.reshape(-1)) + list(truncated):
+                if int(r) not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+            return ([(self._id_map[int(a)], self._id_map[int(b)], float(s)) for (a, b), s in zip(pairs, scores)],
+                    [self._id_map[int(r)] for r in truncated])
+
     def search(self, vec: Sequence[float], limit: int) -> List[VectorSearchResult]:
         with self._lock:
             idx = self._index        # own reference: the store may be evicted / replaced while the GPU works
