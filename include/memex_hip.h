@@ -201,6 +201,50 @@ int mx_index_search_filtered_device(mx_index *idx, const float *d_queries, int B
                                     uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_n_found);
 
 /*
+ * Resident filters: an allow-set that is an object (one tenant's, one ACL group's, one tag's documents).  It is built once from id
+ * ranges or a plain id list, kept as one bit per row next to the rows on every shard, edited when the tenant gains or loses a
+ * document, and named by handle in a search; a search with it uploads nothing and does no host work that grows with the ranges or
+ * ids it was built from.
+ *   mx_filter_create       the empty set of rows of `idx`.  The filter holds a reference on the index: mx_index_close by the owner
+ *                          does not pull the rows from under it; mx_filter_destroy drops the reference.
+ *   mx_filter_set_ranges   allow = 1 adds the ids of the ranges to the set, allow = 0 takes them away (any other value: MX_EINVAL).
+ *                          Ranges as in mx_index_search_filtered: pairs [lo, hi), any order, overlapping, repeated; lo > hi in any
+ *                          pair, or ranges == NULL with n_ranges > 0: MX_EINVAL.
+ *   mx_filter_set_ids      the same for a plain list of ids; they may repeat and come in any order.
+ * Ids are the ids search returns, id_offset applied at the time of the call; an id outside [id_offset + 1, id_offset + size] at
+ * that time is ignored (a filter is a predicate, not an id list to check), so rows appended later are not in the set until a later
+ * call names them.  The stored bits are per row: a later mx_index_set_id_offset moves the ids the filter stands for with the rows.
+ * A failing call changes nothing.
+ *   mx_filter_count        n_allowed: rows in the set; n_live: those of them that are not removed (either may be NULL).  Removed
+ *                          rows stay in the set and are never returned.
+ *   mx_filter_get_ranges   the set as normalised id ranges (sorted, merged, current id_offset).  *n_ranges is always the number
+ *                          of pairs needed; nothing is written when cap_pairs is smaller (MX_OK all the same: ask again).
+ *   mx_index_search_with_filter[_device]
+ *                          bit-identical to mx_index_search_filtered[_device] called at the same moment with what
+ *                          mx_filter_get_ranges returns: ids, scores, dists, n_found, empty slots, k <= 4096, the codes, the split
+ *                          of B, both search modes, every filter copy and corpus mode, the same counters.  The empty filter finds
+ *                          nothing (n_found = 0, MX_OK).  Concurrent host-pointer calls that name the same filter and the same k
+ *                          share passes; they never share one with plain, per-call-filtered or range requests.
+ * mx_index_clear, mx_index_load and an mx_index_compact that dropped at least one row renumber or replace the rows: every filter
+ * of the index is STALE afterwards, and every call with it except mx_filter_destroy returns MX_EINVAL with a message that says so.
+ * A filter named together with an index it was not made for: MX_EINVAL.  A null filter, or a null pointer where a result is
+ * required, is MX_EINVAL before anything else; a null index on the search calls is then MX_ESEARCH.  Filter calls are thread-safe
+ * beside every other call on the index, and a search sees a filter before or after a whole set_* call, never half of one; a
+ * filter must not be destroyed while a call that names it is running.
+ */
+typedef struct mx_filter mx_filter;
+int mx_filter_create(mx_index *idx, mx_filter **out);
+void mx_filter_destroy(mx_filter *f);
+int mx_filter_set_ranges(mx_filter *f, const uint64_t *ranges, uint64_t n_ranges, int allow);
+int mx_filter_set_ids(mx_filter *f, const uint64_t *ids, uint64_t n_ids, int allow);
+int mx_filter_count(mx_filter *f, uint64_t *n_allowed, uint64_t *n_live);
+int mx_filter_get_ranges(mx_filter *f, uint64_t *ranges, uint64_t cap_pairs, uint64_t *n_ranges);
+int mx_index_search_with_filter(mx_index *idx, mx_filter *f, const float *queries, int B, int k, uint64_t *ids, float *scores,
+                                float *dists, int32_t *n_found);
+int mx_index_search_with_filter_device(mx_index *idx, mx_filter *f, const float *d_queries, int B, int k, uint64_t *d_ids,
+                                       float *d_scores, float *d_dists, int32_t *d_n_found);
+
+/*
  * Range search: every row whose score reaches a per-query threshold, exactly ("which rows are at least this similar?").
  * Row r is in range for query b iff score(q_b, r) >= min_scores[b], score being exactly the f32 value mx_index_search reports for that
  * pair (1 - 1/(1/dist), dist the f64 DistCosine rounded to f32).  min_scores holds B floats and is HOST memory on both variants.

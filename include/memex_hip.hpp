@@ -403,6 +403,84 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // A resident filter (mx_filter): the rows inserted under some _id strings -- one tenant's, one ACL group's, one tag's documents --
+    // kept as a bitmap next to the rows and named in search_in().  bulk_insert of a document, then allow({its _ids}), is the
+    // tenant-ingest flow.  After compact(), delete_all() or a reload every call but the destructor throws: make a new one.
+    class Filter {
+      public:
+        Filter(const Filter &) = delete;
+        Filter &operator=(const Filter &) = delete;
+        Filter(Filter &&o) noexcept : store_(o.store_), f_(o.f_) { o.f_ = nullptr; }
+        ~Filter() {
+            if (f_) mx_filter_destroy(f_);
+        }
+        void allow(const std::vector<std::string> &ids) { edit(ids, 1); }
+        void deny(const std::vector<std::string> &ids) { edit(ids, 0); }
+        // rows in the set, and those of them that are not removed
+        std::pair<uint64_t, uint64_t> count() const {
+            uint64_t a = 0, l = 0;
+            int rc = mx_filter_count(f_, &a, &l);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            return {a, l};
+        }
+
+      private:
+        friend class HipFlatStore;
+        Filter(HipFlatStore *store, mx_filter *f) : store_(store), f_(f) {}
+        void edit(const std::vector<std::string> &ids, int allow) {
+            std::lock_guard<std::mutex> lk(store_->mu_);
+            if (!store_->rows_of_built_) {
+                for (auto &kv : store_->_id_map) store_->rows_of_[kv.second].push_back(kv.first);
+                store_->rows_of_built_ = true;
+            }
+            std::vector<uint64_t> rows;
+            for (auto &id : ids) {
+                auto it = store_->rows_of_.find(id);
+                if (it != store_->rows_of_.end()) rows.insert(rows.end(), it->second.begin(), it->second.end());
+            }
+            int rc = mx_filter_set_ids(f_, rows.empty() ? nullptr : rows.data(), rows.size(), allow);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        }
+        HipFlatStore *store_;
+        mx_filter *f_;
+    };
+
+    Filter make_filter(const std::vector<std::string> &ids) {
+        mx_filter *f = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_) throw VectorStoreError(VectorStoreError::SearchError, "a filter needs a store with rows: insert first");
+            int rc = mx_filter_create(idx_, &f);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        }
+        Filter out(this, f);
+        out.allow(ids);
+        return out;
+    }
+
+    // search() restricted to the rows of a resident filter (mx_index_search_with_filter)
+    std::vector<VectorSearchResult> search_in(const std::vector<float> &vec, size_t limit, const Filter &flt) {
+        std::vector<VectorSearchResult> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0) return out;
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        int32_t nf = 0;
+        int rc = mx_index_search_with_filter(idx_, flt.f_, vec.data(), 1, (int)limit, found.data(), scores.data(), nullptr, &nf);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.emplace_back(it->second, scores[j]);
+        }
+        return out;
+    }
+
     // every row whose score against vec is at least min_score, best first, at most limit (1 .. 4096) of them (mx_index_search_range):
     // a near-duplicate check before ingest, or context chosen by relevance rather than by count
     std::vector<VectorSearchResult> search_above(const std::vector<float> &vec, float min_score, size_t limit) {

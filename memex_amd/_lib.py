@@ -31,6 +31,8 @@ EXPORTS = [
     "mx_index_set_id_offset", "mx_index_add", "mx_index_add_device", "mx_index_clear",
     "mx_index_remove", "mx_index_removed", "mx_index_compact",
     "mx_index_search", "mx_index_search_device", "mx_index_search_filtered", "mx_index_search_filtered_device", "mx_index_search_range", "mx_index_search_range_device", "mx_index_search_mmr", "mx_index_search_mmr_device",
+    "mx_filter_create", "mx_filter_destroy", "mx_filter_set_ranges", "mx_filter_set_ids", "mx_filter_count", "mx_filter_get_ranges",
+    "mx_index_search_with_filter", "mx_index_search_with_filter_device",
     "mx_index_search_by_id", "mx_index_search_by_id_device", "mx_index_search_range_by_id", "mx_index_search_range_by_id_device",
     "mx_index_set_search_mode", "mx_index_set_filter_copy", "mx_index_set_corpus_mode", "mx_index_get_rows",
     "mx_index_save", "mx_index_load", "mx_index_has_store", "mx_index_store_info", "mx_index_remove_files",
@@ -123,6 +125,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_index_search_device": [vp, vp, i32, i32, vp, vp, vp, vp],
         "mx_index_search_filtered": [vp, vp, i32, i32, vp, u64, vp, vp, vp, vp],
         "mx_index_search_filtered_device": [vp, vp, i32, i32, vp, u64, vp, vp, vp, vp],
+        "mx_filter_create": [vp, P(vp)],
+        "mx_filter_set_ranges": [vp, vp, u64, i32],
+        "mx_filter_set_ids": [vp, vp, u64, i32],
+        "mx_filter_count": [vp, P(u64), P(u64)],
+        "mx_filter_get_ranges": [vp, vp, u64, P(u64)],
+        "mx_index_search_with_filter": [vp, vp, vp, i32, i32, vp, vp, vp, vp],
+        "mx_index_search_with_filter_device": [vp, vp, vp, i32, i32, vp, vp, vp, vp],
         "mx_index_search_range": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_mmr": [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp],
@@ -174,6 +183,8 @@ def _declare(L: ctypes.CDLL) -> None:
         fn.argtypes = argtypes
     L.mx_index_close.restype = None
     L.mx_index_close.argtypes = [vp]
+    L.mx_filter_destroy.restype = None
+    L.mx_filter_destroy.argtypes = [vp]
     L.mx_encoder_destroy.restype = None
     L.mx_encoder_destroy.argtypes = [vp]
     L.mx_tokenizer_destroy.restype = None

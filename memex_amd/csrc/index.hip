@@ -44,6 +44,7 @@
 #include "index_kernels.h"
 #include "mx_common.h"
 #include "mx_debug.h"
+#include "mx_filter_bits.h"
 #include "shard_pool.h"
 
 namespace mx {
@@ -159,6 +160,8 @@ struct Rccl {
 
 using namespace mx;
 
+struct mx_filter;
+
 // one host-API search call waiting to be served (see mx_index_search)
 struct SearchReq {
     const float *q;
@@ -167,6 +170,7 @@ struct SearchReq {
     float *scores, *dists;
     int32_t *n_found;
     const std::vector<std::pair<uint64_t, uint64_t>> *filt = nullptr;  // mx_index_search_filtered: the normalised id ranges
+    mx_filter *res = nullptr;           // mx_index_search_with_filter: the resident filter (never together with filt)
     const uint32_t *dlim = nullptr;     // mx_index_search_range: per-query dist bounds (k is the cap); null: a top-k request
     uint64_t *n_in_range = nullptr;
     int rc = MX_OK;
@@ -251,6 +255,11 @@ struct mx_index {
     size_t filt_ranges_cap = 0;     // pairs
     uint32_t *subset_rows = nullptr;
     bool last_subset = false;       // the last search_batch answered on the subset kernel
+    // resident filters (mx_filter).  row_epoch (the handle's): how many times the rows were renumbered or replaced
+    // (clear, load, a compaction that dropped rows) -- a filter made before the last one is stale.  dead_ver (every plain index or
+    // shard): moves whenever its removal mask changes, so a filter knows when its cached live count and row list are out of date.
+    uint64_t row_epoch = 0;
+    uint64_t dead_ver = 0;
     // diversified search (mx_index_search_mmr), allocated at the first such call.  Every plain index or shard: the
     // row list of a gather launch and -- the handle's own index, or a shard on another device than shards[0] -- the block the
     // gathered rows go to (at most kMmrStageBytes).  The index that owns the stream (shards[0] of a composite) also holds the
@@ -293,6 +302,29 @@ struct mx_index {
     int sh_kcap = 0;
     std::unique_ptr<ShardPool> pool;  // helper threads for shards 1 .. G-1 (shards on distinct devices only)
     bool composite() const { return !shards.empty(); }
+};
+
+// A resident filter: one allow bit per row, kept on every plain index or shard of the handle it was made for,
+// with a host mirror of the bits (kept the way dead_h is: counts, spans and the export come from it).  Every call that reads or
+// edits a filter holds the handle's mutex.
+struct FilterShard {
+    int device = 0;                  // where the shard's rows live
+    uint64_t *bits = nullptr;        // device: [words], bit r & 63 of word r >> 6 = local row r is in the set
+    size_t words = 0;                // grows to the index's capacity words at the next edit; rows past it are not in the set
+    std::vector<uint64_t> bits_h;    // host mirror [words]
+    uint64_t *stage = nullptr;       // device: the ranges or ids of the edit in progress
+    size_t stage_words = 0;
+    uint32_t *list = nullptr;        // device: [kSubsetCap] the live allowed rows, ascending (launch_filter_list), while list_ok
+    // what a search needs, valid while `cached` and cached_dead == the index's dead_ver
+    bool cached = false, list_ok = false;
+    uint64_t cached_dead = 0;
+    uint64_t n_allowed = 0, n_live = 0;  // rows in the set; those of them not removed
+    uint64_t row_lo = 0, row_hi = 0;     // first row of the set, one past its last
+};
+struct mx_filter {
+    mx_index *idx = nullptr;
+    uint64_t epoch = 0;              // idx->row_epoch when the filter was made
+    std::vector<FilterShard> sh;     // one per shard; a plain index: one
 };
 
 namespace {
@@ -923,8 +955,7 @@ int demote_filter(mx_index *idx) {
 }
 
 // ---- filtered search (mx_index_search_filtered) ------------------------------------------------------------------
-// half-open [lo, hi) ranges of ids or of rows
-using Ranges = std::vector<std::pair<uint64_t, uint64_t>>;
+// half-open [lo, hi) ranges of ids or of rows: Ranges (mx_filter_bits.h)
 
 // sorted by lo, overlapping and adjacent ranges merged, empty ones dropped
 void normalise_ranges(Ranges &r) {
@@ -982,17 +1013,13 @@ uint64_t count_allowed(const mx_index *t, const Ranges &r) {
     return c;
 }
 
+int ensure_mask_words(mx_index *idx, size_t words);
+
 // the per-call mask of a masked pass over the ranges (clipped to the rows): every word of the capacity (the zero-query walk and
 // the EXACT path read them all), dead words included when the index has removals
 int build_filter_mask(mx_index *idx, const Ranges &r, std::vector<uint64_t> &flat) {
     const size_t words = (size_t)(idx->cap / kTile8Rows);
-    if (idx->filt_words < words) {
-        if (idx->filt) (void)hipFree(idx->filt);  // (every batch before this one is host-synchronised)
-        idx->filt = nullptr;
-        idx->filt_words = 0;
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->filt), words * sizeof(uint64_t)));
-        idx->filt_words = words;
-    }
+    if (int rc = ensure_mask_words(idx, words); rc != MX_OK) return rc;
     if (idx->filt_ranges_cap < std::max<size_t>(r.size(), 1)) {
         if (idx->filt_ranges) (void)hipFree(idx->filt_ranges);
         idx->filt_ranges = nullptr;
@@ -1027,6 +1054,53 @@ bool subset_pays(const mx_index *idx, int B, uint64_t m, uint64_t span_rows, int
     const double subset_us = (double)((B + kPassBatch - 1) / kPassBatch) * (43.0 + 0.053 * w * (double)m);
     const double masked_us = 75.0 + (double)span_rows * w * bytes_per_elem * (B <= 128 ? 0.065e-3 : 0.10e-3);
     return subset_us <= masked_us;
+}
+
+// What restricts a filtered batch: the ranges of a per-call filter (search_batch: local rows; composite_batch: global rows), or a
+// resident filter and the shard of it this index holds.
+struct FilterArg {
+    const Ranges *ranges = nullptr;
+    mx_filter *res = nullptr;
+    int shard = 0;
+};
+
+// the cached counts and span of one shard of a resident filter, recomputed from the host mirrors when the filter or the shard's
+// removals have changed since they were taken (t: the plain index or shard that holds the rows)
+void refresh_filter_shard(const mx_index *t, FilterShard &fs) {
+    if (fs.cached && fs.cached_dead == t->dead_ver) return;
+    fs.n_allowed = fs.n_live = 0;
+    fs.row_lo = fs.row_hi = 0;
+    const bool dead = t->n_dead != 0;
+    for (size_t w = 0; w < fs.bits_h.size(); ++w) {
+        const uint64_t b = fs.bits_h[w];
+        if (!b) continue;
+        if (!fs.n_allowed) fs.row_lo = (uint64_t)w * 64 + (uint64_t)__builtin_ctzll(b);
+        fs.row_hi = (uint64_t)w * 64 + 64 - (uint64_t)__builtin_clzll(b);
+        fs.n_allowed += (uint64_t)__builtin_popcountll(b);
+        fs.n_live += (uint64_t)__builtin_popcountll(dead && w < t->dead_h.size() ? b & ~t->dead_h[w] : b);
+    }
+    fs.cached = true;
+    fs.cached_dead = t->dead_ver;
+    fs.list_ok = false;
+}
+
+// the index-owned mask buffer of a masked pass covers the capacity
+int ensure_mask_words(mx_index *idx, size_t words) {
+    if (idx->filt_words >= words) return MX_OK;
+    if (idx->filt) (void)hipFree(idx->filt);  // (every batch before this one is host-synchronised)
+    idx->filt = nullptr;
+    idx->filt_words = 0;
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->filt), words * sizeof(uint64_t)));
+    idx->filt_words = words;
+    return MX_OK;
+}
+
+// the per-call mask of a masked pass with a resident filter: one launch over the capacity's words, no upload
+int apply_filter_mask(mx_index *idx, const FilterShard &fs) {
+    const size_t words = (size_t)(idx->cap / kTile8Rows);
+    if (int rc = ensure_mask_words(idx, words); rc != MX_OK) return rc;
+    MX_HIP(launch_filter_apply(idx->stream, idx->n_dead ? idx->dead : nullptr, fs.bits, std::min(fs.words, words), words, idx->filt));
+    return MX_OK;
 }
 
 // Wait for the completion word of a finish launch (finish_kernel, range_finish_kernel) with sequence number seq, for a batch of B
@@ -1078,20 +1152,31 @@ int await_finish(mx_index *idx, int B, uint32_t seq) {
     return fail(MX_EDEVICE, "finish_kernel did not signal completion");
 }
 
-// one batch (B <= 256) with queries and outputs on the device; filt: the local rows a filtered search allows (normalised)
+// one batch (B <= 256) with queries and outputs on the device; filt: what a filtered search allows -- local rows (normalised
+// ranges), or this index's shard of a resident filter
 int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
-                 int32_t *d_nfound, const Ranges *filt = nullptr) {
+                 int32_t *d_nfound, const FilterArg *filt = nullptr) {
     int rc = ensure_scratch(idx);
     if (rc != MX_OK) return rc;
     Scratch &s = idx->s;
     hipStream_t st = idx->stream;
     // a filtered batch: its ranges clipped to the rows, and the rows they allow that are not removed
     Ranges fr;
-    uint64_t n_allow = 0;
-    if (filt) {
-        for (const auto &x : *filt)
+    uint64_t n_allow = 0, span_lo = 0, span_hi = 0;  // [span_lo, span_hi): from the first allowed row to the last
+    FilterShard *res = filt && filt->res ? &filt->res->sh[(size_t)filt->shard] : nullptr;
+    if (res) {  // a resident filter: nothing here grows with the rows or the ranges while the cached figures hold
+        refresh_filter_shard(idx, *res);
+        n_allow = res->n_live;
+        span_lo = res->row_lo;
+        span_hi = res->row_hi;
+    } else if (filt) {
+        for (const auto &x : *filt->ranges)
             if (x.first < std::min(x.second, idx->n)) fr.emplace_back(x.first, std::min(x.second, idx->n));
         n_allow = count_allowed(idx, fr);
+        if (!fr.empty()) {
+            span_lo = fr.front().first;
+            span_hi = fr.back().second;
+        }
     }
     idx->last_subset = false;
     const bool trivial = idx->n == 0 || k == 0 || (filt && n_allow == 0);
@@ -1140,19 +1225,32 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         return MX_OK;
     };
     if (filt && !trivial &&
-        subset_pays(idx, B, n_allow, fr.back().second - fr.front().first, filt8 ? 1 : idx->xh ? 2 : 4)) {
+        subset_pays(idx, B, n_allow, span_hi - span_lo, filt8 ? 1 : idx->xh ? 2 : 4)) {
         // a small filter: the allowed live rows, ascending, and one subset_topk_kernel launch; no scan, no lane buffers
         std::vector<uint32_t> list;
-        list.reserve((size_t)n_allow);
-        for (const auto &x : fr)
-            for (uint64_t r = x.first; r < x.second; ++r)
-                if (!idx->n_dead || !((idx->dead_h[r >> 6] >> (r & 63)) & 1ull)) list.push_back((uint32_t)r);
-        if (!idx->subset_rows) MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->subset_rows), (size_t)kSubsetCap * sizeof(uint32_t)));
-        MX_HIP(hipMemcpyAsync(idx->subset_rows, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        const uint32_t *rows_list = nullptr;
+        if (res) {  // the filter's own list, compacted on the device and kept until the filter or the removals change
+            if (!res->list) MX_HIP(hipMalloc(reinterpret_cast<void **>(&res->list), (size_t)kSubsetCap * sizeof(uint32_t)));
+            if (!res->list_ok) {
+                MX_HIP(hipMemsetAsync(res->list, 0, (size_t)kSubsetCap * sizeof(uint32_t), st));  // (no entry is ever an arbitrary row)
+                MX_HIP(launch_filter_list(st, idx->n_dead ? idx->dead : nullptr, res->bits, span_lo >> 6, (span_hi + 63) >> 6, res->list,
+                                          (uint32_t)kSubsetCap));
+                res->list_ok = true;
+            }
+            rows_list = res->list;
+        } else {
+            list.reserve((size_t)n_allow);
+            for (const auto &x : fr)
+                for (uint64_t r = x.first; r < x.second; ++r)
+                    if (!idx->n_dead || !((idx->dead_h[r >> 6] >> (r & 63)) & 1ull)) list.push_back((uint32_t)r);
+            if (!idx->subset_rows) MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->subset_rows), (size_t)kSubsetCap * sizeof(uint32_t)));
+            MX_HIP(hipMemcpyAsync(idx->subset_rows, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            rows_list = idx->subset_rows;
+        }
         MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
                                    idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
                                    centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
-        MX_HIP(launch_subset_topk(st, B, k, idx->ds, idx->compressed ? nullptr : idx->x, idx->xh, idx->subset_rows, (uint32_t)list.size(),
+        MX_HIP(launch_subset_topk(st, B, k, idx->ds, idx->compressed ? nullptr : idx->x, idx->xh, rows_list, (uint32_t)n_allow,
                                   idx->idmap, s.qpad, s.qnorm2, d_ids, d_scores, d_dists, d_nfound));
         if ((rc = fetch_flags()) != MX_OK) return rc;  // (host-synchronised: also for outputs in mapped host memory)
         if (any_bad_query()) return fail(MX_EINVAL, "a query contains non-finite values");
@@ -1165,7 +1263,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     }
     // what masks the pipeline: the per-call mask of a filtered search, the removed rows, or nothing; the rows it leaves
     std::vector<uint64_t> flat_ranges;  // (alive until the batch is host-synchronised: the source of an async upload)
-    if (filt && !trivial && (rc = build_filter_mask(idx, fr, flat_ranges)) != MX_OK) return rc;
+    if (filt && !trivial && (rc = res ? apply_filter_mask(idx, *res) : build_filter_mask(idx, fr, flat_ranges)) != MX_OK) return rc;
     const uint64_t *mask = filt ? idx->filt : idx->n_dead ? idx->dead : nullptr;
     const uint64_t n_live = filt ? n_allow : idx->n - idx->n_dead;
     LaneLease lease;  // every return below is host-synchronised with the kernels that used the lane buffers
@@ -1233,7 +1331,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         const uint64_t trows = filt8 ? kTile8Rows : kTileRows;  // rows per scan tile
         const uint64_t tiles = (idx->n + trows - 1) / trows, full = idx->n / trows;
         // the tiles the scans visit: all of them, or the span of tiles a filter's ranges touch (the sample: its full tiles)
-        const uint64_t ts0 = filt ? fr.front().first / trows : 0, ts1 = filt ? (fr.back().second + trows - 1) / trows : tiles;
+        const uint64_t ts0 = filt ? span_lo / trows : 0, ts1 = filt ? (span_hi + trows - 1) / trows : tiles;
         const uint64_t full1 = std::min(ts1, full);
         ScanParams p;
         p.x = idx->x;
@@ -1735,21 +1833,34 @@ bool rccl_selftest(mx_index *idx, double seconds) {
 }
 
 // one batch on a composite: d_q and the outputs live on shards[0]'s device
-// filt: the global rows a filtered search allows (normalised); every shard searches its share of them (shard_ranges)
+// filt: the global rows a filtered search allows (normalised): every shard searches its share of them (shard_ranges); or a
+// resident filter: every shard searches with its own bitmap
 int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
-                    int32_t *d_nfound, const Ranges *filt = nullptr) {
+                    int32_t *d_nfound, const FilterArg *filt = nullptr) {
     const int G = (int)idx->shards.size();
     int rc = ensure_composite_buffers(idx, std::max(k, 1));
     if (rc != MX_OK) return rc;
-    std::vector<Ranges> loc(filt ? G : 0);
+    std::vector<Ranges> loc(filt && !filt->res ? G : 0);
+    std::vector<FilterArg> fa(filt ? G : 0);  // what shard g searches with
+    std::vector<char> offers(filt ? G : 0, 0);  // shard g has allowed rows
     uint64_t n_allow = 0;  // allowed rows that are not removed, over the shards
     for (int g = 0; g < (int)loc.size(); ++g) {
         mx_index *sh = idx->shards[g];
         Ranges clipped;
-        for (const auto &x : shard_ranges(*filt, idx->block_rows, (uint64_t)G, (uint64_t)g))
+        for (const auto &x : shard_ranges(*filt->ranges, idx->block_rows, (uint64_t)G, (uint64_t)g))
             if (x.first < std::min(x.second, sh->n)) clipped.emplace_back(x.first, std::min(x.second, sh->n));
         n_allow += count_allowed(sh, clipped);
         loc[g] = std::move(clipped);
+        fa[g].ranges = &loc[g];
+        offers[g] = !loc[g].empty();
+    }
+    for (int g = 0; filt && filt->res && g < G; ++g) {
+        FilterShard &fs = filt->res->sh[(size_t)g];
+        refresh_filter_shard(idx->shards[g], fs);
+        n_allow += fs.n_live;
+        fa[g].res = filt->res;
+        fa[g].shard = g;
+        offers[g] = fs.n_allowed != 0;
     }
     const size_t ids_bytes = (size_t)B * k * sizeof(uint64_t), blk = ids_bytes + (size_t)B * k * sizeof(float);
     std::vector<int> rcs(G, MX_OK);
@@ -1762,7 +1873,7 @@ int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_i
             MX_HIP(hipMemcpyAsync(idx->sh_q[g], d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
             char *blkp = static_cast<char *>(idx->sh_block[g]);
             int r = search_batch(sh, idx->sh_q[g], B, k, reinterpret_cast<uint64_t *>(blkp), idx->sh_scores[g],
-                                 reinterpret_cast<float *>(blkp + ids_bytes), idx->sh_nf[g], filt ? &loc[g] : nullptr);
+                                 reinterpret_cast<float *>(blkp + ids_bytes), idx->sh_nf[g], filt ? &fa[g] : nullptr);
             if (r != MX_OK) return r;
             if (!idx->use_rccl && k > 0) {  // peer copy into slot g of the gather area on shards[0]'s device
                 MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
@@ -1848,7 +1959,7 @@ int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_i
         // a query of the handle counts as answered by the subset kernel when every shard that had rows to offer used it
         bool any = false, all = true;
         for (int g = 0; g < G; ++g) {
-            if (loc[g].empty()) continue;
+            if (!offers[g]) continue;
             any = any || idx->shards[g]->last_subset;
             all = all && idx->shards[g]->last_subset;
         }
@@ -1858,9 +1969,9 @@ int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_i
     return MX_OK;
 }
 
-// filt: the global rows a filtered search allows (normalised), or null
+// filt: the global rows a filtered search allows (normalised) or a resident filter, or null
 int any_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
-              int32_t *d_nfound, const Ranges *filt = nullptr) {
+              int32_t *d_nfound, const FilterArg *filt = nullptr) {
     return idx->composite() ? composite_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, filt)
                             : search_batch(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, filt);
 }
@@ -2377,6 +2488,7 @@ int mark_dead_local(mx_index *idx, const std::vector<uint64_t> &rows, std::vecto
     if (*newly) {
         MX_HIP(hipMemcpyAsync(idx->dead + w0, idx->dead_h.data() + w0, (w1 - w0 + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, idx->stream));
         idx->n_dead += *newly;
+        idx->dead_ver += 1;
         // The side lists (zero-norm rows, rows with an out-of-range norm) keep live rows only, so that the kZeroCap / kWildCap
         // decisions and later appends count live rows.  A list that overflowed its cap is incomplete (rows past the cap were never
         // listed) and stays as it is: such an index answers on the EXACT path either way.
@@ -2448,6 +2560,7 @@ int reset_dead(mx_index *idx) {
             MX_HIP(hipStreamSynchronize(t->stream));
         }
         t->n_dead = 0;
+        t->dead_ver += 1;
     }
     idx->n_dead = 0;
     idx->dead_log.clear();
@@ -2578,6 +2691,8 @@ int clear_locked(mx_index *idx) {
         }
     }
     idx->n_dead = 0;
+    idx->dead_ver += 1;
+    idx->row_epoch += 1;  // (every resident filter of the handle is stale: the rows it named are gone)
     idx->dead_log.clear();
     idx->disk_dead = 0;
     idx->disk_dir.clear();
@@ -3209,6 +3324,7 @@ int mx_index_compact(mx_index *idx, uint64_t *kept_ids, uint64_t kept_cap, uint6
         if (rc != MX_OK && moved) {
             const std::string why = last_error_slot();
             idx->failed = true;
+            idx->row_epoch += 1;
             return fail(MX_EDEVICE, "compaction failed after rows had moved (%s); the index is unusable until mx_index_clear or mx_index_load",
                         why.c_str());
         }
@@ -3216,6 +3332,7 @@ int mx_index_compact(mx_index *idx, uint64_t *kept_ids, uint64_t kept_cap, uint6
     if (rc != MX_OK) return rc;
     // the store on disk no longer matches: the next save rewrites it whole, in the next generation's formats
     idx->gen += 1;
+    idx->row_epoch += 1;  // the rows were renumbered: resident filters of the old numbering are stale
     idx->n_dead = 0;
     idx->dead_log.clear();
     idx->disk_dead = 0;
@@ -3339,9 +3456,17 @@ int read_id_ranges(const uint64_t *ranges, uint64_t n_ranges, Ranges *out) {
     return MX_OK;
 }
 
-// mx_index_search_device and its filtered form (id_filt: normalised id ranges, or null)
+// a resident filter named in a call on idx (under idx->mu): made for this handle, and not older than its rows
+int check_filter(const mx_index *idx, const mx_filter *f) {
+    if (f->idx != idx) return fail(MX_EINVAL, "the filter was made for another index");
+    if (f->epoch != idx->row_epoch)
+        return fail(MX_EINVAL, "the filter is stale: the index was cleared, loaded or compacted after it was made (destroy it and make a new one)");
+    return MX_OK;
+}
+
+// mx_index_search_device and its filtered forms (id_filt: normalised id ranges, res: a resident filter; at most one of them)
 int search_device(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_nfound,
-                  const Ranges *id_filt) {
+                  const Ranges *id_filt, mx_filter *res = nullptr) {
     if (!idx) return fail(MX_ESEARCH, "null index");
     if (B < 0 || k < 0) return fail(MX_EINVAL, "negative batch or k");
     if (B == 0) return MX_OK;
@@ -3350,13 +3475,16 @@ int search_device(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids
     std::lock_guard<std::mutex> lk(idx->mu);
     DeviceGuard g(idx->device);
     if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (res)
+        if (int rc = check_filter(idx, res); rc != MX_OK) return rc;
     Ranges rows;
     if (id_filt) rows = rows_of_ids(*id_filt, idx->idmap.id_offset, rows_of(idx));  // (under idx->mu)
+    const FilterArg fa{id_filt ? &rows : nullptr, res, 0};
     for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
         const int nb = std::min(kMaxBatch, B - b0);
         int rc = any_batch(idx, d_q + (size_t)b0 * idx->dim, nb, k, d_ids + (size_t)b0 * k,
                            d_scores + (size_t)b0 * k, d_dists ? d_dists + (size_t)b0 * k : nullptr, d_nfound + b0,
-                           id_filt ? &rows : nullptr);
+                           id_filt || res ? &fa : nullptr);
         if (rc != MX_OK) return rc;
     }
     return MX_OK;
@@ -3438,9 +3566,12 @@ int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     DeviceGuard g(t->device);
     const int k = batch[0]->k;
     if (batch[0]->dlim) return run_combined_range(idx, batch);
-    Ranges rows;  // a filtered pass: every request of it has the same ranges
+    Ranges rows;  // a filtered pass: every request of it has the same ranges, or names the same resident filter
     if (batch[0]->filt) rows = rows_of_ids(*batch[0]->filt, idx->idmap.id_offset, rows_of(idx));
-    const Ranges *filt = batch[0]->filt ? &rows : nullptr;
+    if (batch[0]->res)
+        if (int rc = check_filter(idx, batch[0]->res); rc != MX_OK) return rc;
+    const FilterArg fa{batch[0]->filt ? &rows : nullptr, batch[0]->res, 0};
+    const FilterArg *filt = batch[0]->filt || batch[0]->res ? &fa : nullptr;
     int rc = ensure_scratch(t);
     if (rc != MX_OK) return rc;
     rc = ensure_out(t, k);
@@ -3515,10 +3646,11 @@ int serve(mx_index *idx, SearchReq &req) {
             int total = 0;
             const int bk = idx->pending.front()->k;
             const Ranges *bf = idx->pending.front()->filt;
+            const mx_filter *br = idx->pending.front()->res;  // a resident filter: by handle
             const bool brange = idx->pending.front()->dlim != nullptr;  // range requests combine only with range requests
             for (auto it = idx->pending.begin(); it != idx->pending.end();) {
                 SearchReq *r = *it;
-                if (r->k == bk && same_filter(r->filt, bf) && (r->dlim != nullptr) == brange && total + r->B <= kMaxBatch) {
+                if (r->k == bk && same_filter(r->filt, bf) && r->res == br && (r->dlim != nullptr) == brange && total + r->B <= kMaxBatch) {
                     batch.push_back(r);
                     total += r->B;
                     it = idx->pending.erase(it);
@@ -3550,9 +3682,9 @@ int serve(mx_index *idx, SearchReq &req) {
     return req.rc;
 }
 
-// mx_index_search and its filtered form (filt: normalised id ranges, or null)
+// mx_index_search and its filtered forms (filt: normalised id ranges, res: a resident filter; at most one of them)
 int search_host(mx_index *idx, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists, int32_t *n_found,
-                const Ranges *filt) {
+                const Ranges *filt, mx_filter *res = nullptr) {
     if (!idx) return fail(MX_ESEARCH, "null index");
     if (B < 0 || k < 0) return fail(MX_EINVAL, "negative batch or k");
     if (B == 0) return MX_OK;
@@ -3568,12 +3700,12 @@ int search_host(mx_index *idx, const float *q, int B, int k, uint64_t *ids, floa
             const int nb = std::min(kMaxBatch, B - b0);
             int rc = search_host(idx, q + (size_t)b0 * idx->dim, nb, k, ids ? ids + (size_t)b0 * k : nullptr,
                                  scores ? scores + (size_t)b0 * k : nullptr,
-                                 dists ? dists + (size_t)b0 * k : nullptr, n_found + b0, filt);
+                                 dists ? dists + (size_t)b0 * k : nullptr, n_found + b0, filt, res);
             if (rc != MX_OK) return rc;
         }
         return MX_OK;
     }
-    SearchReq req{q, B, k, ids, scores, dists, n_found, filt};
+    SearchReq req{q, B, k, ids, scores, dists, n_found, filt, res};
     return serve(idx, req);
 }
 
@@ -3591,6 +3723,290 @@ int mx_index_search_filtered(mx_index *idx, const float *q, int B, int k, const 
     Ranges id_ranges;
     if (int rc = read_id_ranges(ranges, n_ranges, &id_ranges); rc != MX_OK) return rc;
     return search_host(idx, q, B, k, ids, scores, dists, n_found, &id_ranges);
+} catch (...) {
+    return guard_exception();
+}
+
+// ---- resident filters (mx_filter) ---------------------------------------------------------------------------------
+namespace {
+
+// the plain index or shard that holds shard g of a filter's rows
+mx_index *filter_target(mx_index *idx, size_t g) { return idx->composite() ? idx->shards[g] : idx; }
+
+// the bitmap of one shard covers the shard's capacity: new words hold no row of the set (t's device is current)
+int ensure_filter_bits(mx_index *t, FilterShard &fs) {
+    const size_t words = (size_t)(t->cap / kTile8Rows);
+    if (fs.words >= words) return MX_OK;
+    DevBuf nb;
+    MX_HIP(hipMalloc(&nb.p, words * sizeof(uint64_t)));
+    MX_HIP(hipMemsetAsync(nb.p, 0, words * sizeof(uint64_t), t->stream));
+    if (fs.words) MX_HIP(hipMemcpyAsync(nb.p, fs.bits, fs.words * sizeof(uint64_t), hipMemcpyDeviceToDevice, t->stream));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    if (fs.bits) (void)hipFree(fs.bits);
+    fs.bits = static_cast<uint64_t *>(nb.release());
+    fs.words = words;
+    fs.bits_h.resize(words, 0);
+    return MX_OK;
+}
+
+int ensure_filter_stage(FilterShard &fs, size_t words) {
+    if (fs.stage_words >= words) return MX_OK;
+    if (fs.stage) (void)hipFree(fs.stage);  // (every edit is host-synchronised before it returns)
+    fs.stage = nullptr;
+    fs.stage_words = 0;
+    const size_t want = std::max<size_t>(words + words / 2, 128);
+    MX_HIP(hipMalloc(reinterpret_cast<void **>(&fs.stage), want * sizeof(uint64_t)));
+    fs.stage_words = want;
+    return MX_OK;
+}
+
+void free_filter_buffers(mx_filter *f) {
+    for (FilterShard &fs : f->sh) {
+        DeviceGuard dg(fs.device);
+        if (fs.bits) (void)hipFree(fs.bits);
+        if (fs.stage) (void)hipFree(fs.stage);
+        if (fs.list) (void)hipFree(fs.list);
+        fs.bits = fs.stage = nullptr;
+        fs.list = nullptr;
+    }
+}
+
+// set_ranges on the handle's global rows (normalised, clipped to the rows); under idx->mu
+int filter_edit_ranges(mx_filter *f, const Ranges &rows, bool allow) {
+    mx_index *idx = f->idx;
+    const size_t G = f->sh.size();
+    std::vector<Ranges> loc(G);
+    // every allocation first: a call that fails leaves the set as it was
+    for (size_t g = 0; g < G; ++g) {
+        mx_index *t = filter_target(idx, g);
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        DeviceGuard dg(t->device);
+        if (idx->composite()) {
+            for (const auto &x : shard_ranges(rows, idx->block_rows, (uint64_t)G, (uint64_t)g))
+                if (x.first < std::min(x.second, t->n)) loc[g].emplace_back(x.first, std::min(x.second, t->n));
+        } else {
+            loc[g] = rows;
+        }
+        if (loc[g].size() > 0x7fffffffull) return fail(MX_EINVAL, "too many ranges");
+        if (int rc = ensure_filter_bits(t, f->sh[g]); rc != MX_OK) return rc;
+        if (int rc = ensure_filter_stage(f->sh[g], 2 * loc[g].size()); rc != MX_OK) return rc;
+        if (!loc[g].empty() && ((loc[g].back().second + 63) >> 6) > f->sh[g].words)
+            return fail(MX_EDEVICE, "filter bitmap shorter than the rows");
+    }
+    std::vector<uint64_t> flat;
+    for (size_t g = 0; g < G; ++g) {
+        if (loc[g].empty()) continue;
+        mx_index *t = filter_target(idx, g);
+        FilterShard &fs = f->sh[g];
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        DeviceGuard dg(t->device);
+        flat.clear();
+        for (const auto &x : loc[g]) {
+            flat.push_back(x.first);
+            flat.push_back(x.second);
+        }
+        fs.cached = false;
+        MX_HIP(hipMemcpyAsync(fs.stage, flat.data(), flat.size() * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+        MX_HIP(launch_filter_range_edit(t->stream, fs.stage, (uint32_t)loc[g].size(), loc[g].front().first >> 6,
+                                        (loc[g].back().second + 63) >> 6, allow, fs.bits));
+        for (const auto &x : loc[g]) edit_mirror(fs.bits_h, x.first, x.second, allow);
+        MX_HIP(hipStreamSynchronize(t->stream));
+    }
+    return MX_OK;
+}
+
+// set_ids; under idx->mu.  Every shard gets the caller's ids as they are: the kernel maps them to its own rows.
+int filter_edit_ids(mx_filter *f, const uint64_t *ids, uint64_t n_ids, bool allow) {
+    mx_index *idx = f->idx;
+    const size_t G = f->sh.size();
+    const uint64_t total = rows_of(idx), off = idx->idmap.id_offset, R = idx->block_rows;
+    for (size_t g = 0; g < G; ++g) {
+        mx_index *t = filter_target(idx, g);
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        DeviceGuard dg(t->device);
+        if (int rc = ensure_filter_bits(t, f->sh[g]); rc != MX_OK) return rc;
+        if (int rc = ensure_filter_stage(f->sh[g], (size_t)n_ids); rc != MX_OK) return rc;
+    }
+    if (n_ids == 0 || total == 0) return MX_OK;
+    for (size_t g = 0; g < G; ++g) {
+        mx_index *t = filter_target(idx, g);
+        FilterShard &fs = f->sh[g];
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        DeviceGuard dg(t->device);
+        fs.cached = false;
+        MX_HIP(hipMemcpyAsync(fs.stage, ids, (size_t)n_ids * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+        MX_HIP(launch_filter_id_edit(t->stream, fs.stage, n_ids, total, t->idmap, allow, fs.bits, fs.words));
+        MX_HIP(hipStreamSynchronize(t->stream));
+    }
+    for (uint64_t i = 0; i < n_ids; ++i) {  // the mirrors, by the kernel's mapping
+        if (ids[i] <= off || ids[i] - off > total) continue;
+        uint64_t r = ids[i] - off - 1;
+        size_t g = 0;
+        if (idx->composite()) {
+            const uint64_t b = r / R;
+            g = (size_t)(b % G);
+            r = (b / G) * R + r % R;
+        }
+        std::vector<uint64_t> &bits = f->sh[g].bits_h;
+        if ((r >> 6) >= bits.size()) continue;
+        if (allow) bits[r >> 6] |= 1ull << (r & 63);
+        else bits[r >> 6] &= ~(1ull << (r & 63));
+    }
+    return MX_OK;
+}
+
+// the set as normalised global row ranges, from the mirrors; under idx->mu
+void filter_rows(mx_filter *f, Ranges &out) {
+    mx_index *idx = f->idx;
+    out.clear();
+    if (!idx->composite()) {
+        append_runs(f->sh[0].bits_h, 0, idx->n, 0, out);
+        return;
+    }
+    const uint64_t R = idx->block_rows, G = f->sh.size();
+    for (uint64_t b = 0; b * R < idx->total; ++b) {  // global block b: local block b / G of shard b % G
+        const mx_index *t = idx->shards[(size_t)(b % G)];
+        const uint64_t lo = (b / G) * R;
+        append_runs(f->sh[(size_t)(b % G)].bits_h, lo, std::min<uint64_t>(lo + R, t->n), b * R, out);
+    }
+}
+
+}  // namespace
+
+int mx_filter_create(mx_index *idx, mx_filter **out) try {
+    if (!out) return fail(MX_EINVAL, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(MX_EINVAL, "null index");
+    {   // the filter's own reference: the rows stay while it lives, whoever closes the index
+        std::lock_guard<std::mutex> lk(g_reg_mu);
+        idx->refs += 1;
+    }
+    std::unique_ptr<mx_filter> f(new mx_filter());
+    int rc = MX_OK;
+    {
+        std::lock_guard<std::mutex> lk(idx->mu);
+        rc = usable(idx);
+        f->idx = idx;
+        f->epoch = idx->row_epoch;
+        f->sh.resize(idx->composite() ? idx->shards.size() : 1);
+        for (size_t g = 0; g < f->sh.size() && rc == MX_OK; ++g) {
+            mx_index *t = filter_target(idx, g);
+            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+            if (t != idx) l2.lock();
+            DeviceGuard dg(t->device);
+            f->sh[g].device = t->device;
+            rc = ensure_filter_bits(t, f->sh[g]);
+        }
+        if (rc != MX_OK) free_filter_buffers(f.get());
+    }
+    if (rc != MX_OK) {
+        const std::string keep = last_error_slot();
+        mx_index_close(idx);
+        last_error_slot() = keep;
+        return rc;
+    }
+    *out = f.release();
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+void mx_filter_destroy(mx_filter *f) {
+    if (!f) return;
+    mx_index *idx = f->idx;
+    try {
+        std::lock_guard<std::mutex> lk(idx->mu);  // (no search that names the filter is inside the library)
+        free_filter_buffers(f);
+    } catch (...) {
+    }
+    delete f;
+    mx_index_close(idx);
+}
+
+int mx_filter_set_ranges(mx_filter *f, const uint64_t *ranges, uint64_t n_ranges, int allow) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    if (allow != 0 && allow != 1) return fail(MX_EINVAL, "allow = %d: 1 adds the ids to the set, 0 takes them away", allow);
+    Ranges ids;
+    if (int rc = read_id_ranges(ranges, n_ranges, &ids); rc != MX_OK) return rc;
+    mx_index *idx = f->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (int rc = check_filter(idx, f); rc != MX_OK) return rc;
+    return filter_edit_ranges(f, rows_of_ids(ids, idx->idmap.id_offset, rows_of(idx)), allow == 1);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_filter_set_ids(mx_filter *f, const uint64_t *ids, uint64_t n_ids, int allow) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    if (allow != 0 && allow != 1) return fail(MX_EINVAL, "allow = %d: 1 adds the ids to the set, 0 takes them away", allow);
+    if (!ids && n_ids) return fail(MX_EINVAL, "null ids with n_ids = %llu", (unsigned long long)n_ids);
+    mx_index *idx = f->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (int rc = check_filter(idx, f); rc != MX_OK) return rc;
+    return filter_edit_ids(f, ids, n_ids, allow == 1);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_filter_count(mx_filter *f, uint64_t *n_allowed, uint64_t *n_live) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    mx_index *idx = f->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (int rc = check_filter(idx, f); rc != MX_OK) return rc;
+    uint64_t a = 0, l = 0;
+    for (size_t g = 0; g < f->sh.size(); ++g) {
+        refresh_filter_shard(filter_target(idx, g), f->sh[g]);
+        a += f->sh[g].n_allowed;
+        l += f->sh[g].n_live;
+    }
+    if (n_allowed) *n_allowed = a;
+    if (n_live) *n_live = l;
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_filter_get_ranges(mx_filter *f, uint64_t *ranges, uint64_t cap_pairs, uint64_t *n_ranges) try {
+    if (!f || !n_ranges) return fail(MX_EINVAL, "null argument");
+    *n_ranges = 0;
+    if (!ranges && cap_pairs) return fail(MX_EINVAL, "null ranges with cap_pairs = %llu", (unsigned long long)cap_pairs);
+    mx_index *idx = f->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (int rc = check_filter(idx, f); rc != MX_OK) return rc;
+    Ranges rows;
+    filter_rows(f, rows);
+    *n_ranges = rows.size();
+    if (rows.size() > cap_pairs) return MX_OK;  // the caller asks again with room for *n_ranges pairs
+    const uint64_t off = idx->idmap.id_offset;
+    for (size_t i = 0; i < rows.size(); ++i) {
+        ranges[2 * i] = off + rows[i].first + 1;
+        ranges[2 * i + 1] = off + rows[i].second + 1;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_with_filter(mx_index *idx, mx_filter *f, const float *q, int B, int k, uint64_t *ids, float *scores, float *dists,
+                                int32_t *n_found) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    return search_host(idx, q, B, k, ids, scores, dists, n_found, nullptr, f);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_with_filter_device(mx_index *idx, mx_filter *f, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores,
+                                       float *d_dists, int32_t *d_nfound) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    return search_device(idx, d_q, B, k, d_ids, d_scores, d_dists, d_nfound, nullptr, f);
 } catch (...) {
     return guard_exception();
 }
@@ -4092,6 +4508,7 @@ int mx_index_load(mx_index *idx, const char *dir) try {
     // rows are exactly what this file holds, attaching is O(1) -- the removals are taken from the file unless they are its own
     if (disk_in_sync(idx, dir) && idx->disk_rows == n && rows_of(idx) == n && idx->gen == gen && !idx->failed) {
         fclose(f);
+        idx->row_epoch += 1;  // (a load stands for new rows whether or not they had to be read: resident filters are stale either way)
         if (file_dead != idx->dead_log) {
             uint64_t m = 0;
             int rc = reset_dead(idx);

@@ -319,6 +319,24 @@ hipError_t launch_subset_topk(hipStream_t s, int B, int k, int ds, const float *
                               const IdMap &idmap, const float *qpad, const double *qnorm2, uint64_t *ids, float *scores, float *dists,
                               int32_t *n_found);
 
+// resident filters (mx_filter): `bits` holds one allow bit per local row, [bit_words] 64-row words.
+// Range edit: the rows of the n_ranges sorted, disjoint local ranges (u64 pairs) are ORed into (allow) or ANDed out of the words
+// [w0, w1) of bits (w1 <= bit_words), one thread per word and no atomics.
+hipError_t launch_filter_range_edit(hipStream_t s, const uint64_t *ranges, uint32_t n_ranges, uint64_t w0, uint64_t w1, bool allow,
+                                    uint64_t *bits);
+// Id edit: one thread per id.  Global row = id - id_offset - 1 (ids outside [id_offset + 1, id_offset + total] are skipped); a
+// shard (idmap.block_rows != 0) keeps the rows of its own blocks only, as local rows.  atomicOr / atomicAnd on the 64-bit word.
+hipError_t launch_filter_id_edit(hipStream_t s, const uint64_t *ids, uint64_t n_ids, uint64_t total, const IdMap &idmap, bool allow,
+                                 uint64_t *bits, uint64_t bit_words);
+// Apply: mask[t] = dead[t] | ~bits[t] for t < bit_words and all ones for bit_words <= t < words (dead null: no removals): the
+// per-call mask of a masked pass, every word of the capacity.
+hipError_t launch_filter_apply(hipStream_t s, const uint64_t *dead, const uint64_t *bits, uint64_t bit_words, uint64_t words,
+                               uint64_t *mask);
+// List: the rows of bits & ~dead in the words [w0, w1), ascending, into rows[0, cap) (the caller knows the count and that it fits);
+// one workgroup, a block-wide prefix sum over per-thread popcounts.
+hipError_t launch_filter_list(hipStream_t s, const uint64_t *dead, const uint64_t *bits, uint64_t w0, uint64_t w1, uint32_t *rows,
+                              uint32_t cap);
+
 hipError_t launch_fill_nfound(hipStream_t s, int32_t *nf, int B, int32_t v);
 // EXACT range path: launch_exact_group with k = cap, the in-range count of every query of the group (dist key < dlim[q]) into
 // n_in_range[q], and each list trimmed to min(cap, count)

@@ -1509,6 +1509,127 @@ hipError_t launch_filter_mask(hipStream_t s, const uint64_t *dead, const uint64_
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// resident filters (mx_filter): one allow bit per local row, kept in HBM next to the rows
+// ---------------------------------------------------------------------------------------------
+// The rows of word t inside one of the sorted, disjoint ranges, found as filter_mask_kernel finds them.
+__device__ __forceinline__ uint64_t word_selection(const uint64_t *__restrict__ ranges, uint32_t n_ranges, uint64_t t) {
+    const uint64_t r0 = t * 64, r1 = r0 + 64;
+    uint32_t lo = 0, hi = n_ranges;  // first range with end > r0
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ranges[2 * mid + 1] <= r0) lo = mid + 1;
+        else hi = mid;
+    }
+    uint64_t sel = 0;
+    for (uint32_t i = lo; i < n_ranges && ranges[2 * i] < r1; ++i) {
+        const uint64_t a = (ranges[2 * i] > r0 ? ranges[2 * i] : r0) - r0;
+        const uint64_t b = (ranges[2 * i + 1] < r1 ? ranges[2 * i + 1] : r1) - r0;  // a < b <= 64
+        const uint64_t upto = b == 64 ? ~0ull : (1ull << b) - 1ull;
+        sel |= upto & ~((1ull << a) - 1ull);
+    }
+    return sel;
+}
+
+// One thread per word of [w0, w1): a word belongs to one thread, so the read-modify-write needs no atomic.
+__global__ __launch_bounds__(256) void filter_range_edit_kernel(const uint64_t *__restrict__ ranges, uint32_t n_ranges, uint64_t w0,
+                                                                uint64_t w1, int allow, uint64_t *__restrict__ bits) {
+    const uint64_t t = w0 + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= w1) return;
+    const uint64_t sel = word_selection(ranges, n_ranges, t);
+    if (sel == 0) return;
+    bits[t] = allow ? bits[t] | sel : bits[t] & ~sel;
+}
+
+hipError_t launch_filter_range_edit(hipStream_t s, const uint64_t *ranges, uint32_t n_ranges, uint64_t w0, uint64_t w1, bool allow,
+                                    uint64_t *bits) {
+    if (w1 <= w0 || n_ranges == 0) return hipSuccess;
+    hipLaunchKernelGGL(filter_range_edit_kernel, dim3((unsigned)((w1 - w0 + 255) / 256)), dim3(256), 0, s, ranges, n_ranges, w0, w1,
+                       allow ? 1 : 0, bits);
+    return hipGetLastError();
+}
+
+// One thread per id; ids repeat and several ids share a word, hence the atomics.
+__global__ __launch_bounds__(256) void filter_id_edit_kernel(const uint64_t *__restrict__ ids, uint64_t n_ids, uint64_t total, IdMap idmap,
+                                                             int allow, unsigned long long *bits, uint64_t bit_words) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_ids) return;
+    const uint64_t id = ids[i];
+    if (id <= idmap.id_offset) return;
+    uint64_t r = id - idmap.id_offset - 1;
+    if (r >= total) return;
+    if (idmap.block_rows) {  // a shard: rows of its own blocks only, global block b -> local block b / G
+        const uint64_t b = r / idmap.block_rows;
+        if (b % idmap.n_shards != idmap.shard) return;
+        r = (b / idmap.n_shards) * idmap.block_rows + r % idmap.block_rows;
+    }
+    if ((r >> 6) >= bit_words) return;
+    const unsigned long long bit = 1ull << (r & 63);
+    if (allow) atomicOr(bits + (r >> 6), bit);
+    else atomicAnd(bits + (r >> 6), ~bit);
+}
+
+hipError_t launch_filter_id_edit(hipStream_t s, const uint64_t *ids, uint64_t n_ids, uint64_t total, const IdMap &idmap, bool allow,
+                                 uint64_t *bits, uint64_t bit_words) {
+    if (n_ids == 0 || bit_words == 0) return hipSuccess;
+    hipLaunchKernelGGL(filter_id_edit_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, s, ids, n_ids, total, idmap,
+                       allow ? 1 : 0, reinterpret_cast<unsigned long long *>(bits), bit_words);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void filter_apply_kernel(const uint64_t *__restrict__ dead, const uint64_t *__restrict__ bits,
+                                                           uint64_t bit_words, uint64_t words, uint64_t *__restrict__ mask) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= words) return;
+    mask[t] = t < bit_words ? (dead ? dead[t] : 0ull) | ~bits[t] : ~0ull;
+}
+
+hipError_t launch_filter_apply(hipStream_t s, const uint64_t *dead, const uint64_t *bits, uint64_t bit_words, uint64_t words,
+                               uint64_t *mask) {
+    if (words == 0) return hipSuccess;
+    hipLaunchKernelGGL(filter_apply_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, dead, bits, bit_words, words, mask);
+    return hipGetLastError();
+}
+
+// One workgroup.  Thread i owns the consecutive words [w0 + i * per, w0 + (i + 1) * per): it counts their live allowed rows, an
+// inclusive scan over the 1024 counts gives it the position of its first row, and it writes its rows in ascending order.
+constexpr int kListThreads = 1024;
+__global__ __launch_bounds__(kListThreads) void filter_list_kernel(const uint64_t *__restrict__ dead, const uint64_t *__restrict__ bits,
+                                                                   uint64_t w0, uint64_t w1, uint32_t *__restrict__ rows, uint32_t cap) {
+    __shared__ uint32_t s_scan[kListThreads];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (w1 - w0 + kListThreads - 1) / kListThreads;
+    const uint64_t a = w0 + (uint64_t)tid * per < w1 ? w0 + (uint64_t)tid * per : w1;
+    const uint64_t b = a + per < w1 ? a + per : w1;
+    uint32_t cnt = 0;
+    for (uint64_t t = a; t < b; ++t) cnt += (uint32_t)__popcll(bits[t] & ~(dead ? dead[t] : 0ull));
+    s_scan[tid] = cnt;
+    __syncthreads();
+    for (uint32_t o = 1; o < (uint32_t)kListThreads; o <<= 1) {
+        const uint32_t v = tid >= o ? s_scan[tid - o] : 0u;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    uint32_t pos = s_scan[tid] - cnt;
+    for (uint64_t t = a; t < b; ++t) {
+        uint64_t live = bits[t] & ~(dead ? dead[t] : 0ull);
+        while (live) {
+            const uint32_t bit = (uint32_t)__ffsll((unsigned long long)live) - 1u;
+            live &= live - 1;
+            if (pos < cap) rows[pos] = (uint32_t)(t * 64 + bit);
+            ++pos;
+        }
+    }
+}
+
+hipError_t launch_filter_list(hipStream_t s, const uint64_t *dead, const uint64_t *bits, uint64_t w0, uint64_t w1, uint32_t *rows,
+                              uint32_t cap) {
+    if (w1 <= w0) return hipSuccess;
+    hipLaunchKernelGGL(filter_list_kernel, dim3(1), dim3(kListThreads), 0, s, dead, bits, w0, w1, rows, cap);
+    return hipGetLastError();
+}
+
 // Small filters: one workgroup per query against the m listed rows (ascending local rows, m <= kSubsetCap).  Each thread takes
 // rows i = tid, tid + 1024, ...: exact DistCosine through exact_dist_stored -- the f64 chain of finish_kernel's stage 3 and of the
 // EXACT path, so zero-norm, wide-norm and compressed rows get the same bits there and here -- into the key

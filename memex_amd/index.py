@@ -248,6 +248,46 @@ class FlatIndex:
                                                     ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
                                                     ctypes.c_void_p(n_found.data_ptr())))
 
+    def make_filter(self, ranges=None, ids=None) -> "IndexFilter":
+        """A resident filter (``mx_filter``): an allow-set of this index's rows kept in HBM and named in ``search_with``.
+        It starts empty, or with ``ranges`` and / or ``ids`` allowed (as ``IndexFilter.allow`` takes them)."""
+        f = IndexFilter(self)
+        try:
+            if ranges is not None or ids is not None:
+                f.allow(ranges=ranges, ids=ids)
+        except Exception:
+            f.close()
+            raise
+        return f
+
+    def search_with(self, flt: "IndexFilter", queries, k: int):
+        """``search`` restricted to the rows of a resident filter: what ``search_filtered(queries, k, ranges=flt.ranges())``
+        returns, bit for bit, without the per-call set-up."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        B = q.shape[0]
+        out_ids = np.zeros((B, k), dtype=np.uint64)
+        scores = np.zeros((B, k), dtype=np.float32)
+        dists = np.zeros((B, k), dtype=np.float32)
+        nf = np.zeros(B, dtype=np.int32)
+        check(lib().mx_index_search_with_filter(self._h, flt._h, _ptr(q), B, int(k), _ptr(out_ids), _ptr(scores), _ptr(dists),
+                                                _ptr(nf)))
+        return out_ids, scores, dists, nf
+
+    def search_with_device(self, flt: "IndexFilter", q, k: int, ids, scores, dists, n_found) -> None:
+        """``search_device`` restricted to the rows of a resident filter."""
+        B = int(q.shape[0])
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        check(lib().mx_index_search_with_filter_device(self._h, flt._h, ctypes.c_void_p(q.data_ptr()), B, int(k),
+                                                       ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
+                                                       ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
+                                                       ctypes.c_void_p(n_found.data_ptr())))
+
     def _min_scores(self, min_score, B: int) -> np.ndarray:
         t = np.asarray(min_score, dtype=np.float32)
         if t.ndim == 0:
@@ -464,6 +504,69 @@ def ids_to_ranges(ids) -> np.ndarray:
     starts = a[np.r_[0, brk]]
     ends = a[np.r_[brk - 1, a.size - 1]] + np.uint64(1)
     return np.ascontiguousarray(np.stack([starts, ends], axis=1), dtype=np.uint64)
+
+
+class IndexFilter:
+    """A set of rows of one ``FlatIndex``, resident on the device(s) of the index (``mx_filter``).  It holds a
+    reference on the index.  After the index's ``clear``, ``load`` or a ``compact`` that dropped rows every method but ``close``
+    raises: make a new filter."""
+
+    def __init__(self, index: FlatIndex):
+        h = ctypes.c_void_p()
+        check(lib().mx_filter_create(index._h, ctypes.byref(h)))
+        self._h = h
+
+    def _edit(self, ranges, ids, allow: int) -> None:
+        if ranges is None and ids is None:
+            raise ValueError("give ranges and / or ids")
+        if ranges is not None:
+            r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+            check(lib().mx_filter_set_ranges(self._h, _ptr(r) if r.size else None, r.shape[0], allow))
+        if ids is not None:
+            a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
+            a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+            check(lib().mx_filter_set_ids(self._h, _ptr(a) if a.size else None, a.size, allow))
+
+    def allow(self, ranges=None, ids=None) -> None:
+        """Add ids to the set: ``ranges`` ([m, 2] half-open id ranges, any order, overlaps allowed) and / or ``ids`` (any order,
+        repeats allowed).  Ids that name no row at this moment are ignored."""
+        self._edit(ranges, ids, 1)
+
+    def deny(self, ranges=None, ids=None) -> None:
+        """Take ids away from the set."""
+        self._edit(ranges, ids, 0)
+
+    def count(self):
+        """-> (rows in the set, those of them that are not removed)."""
+        a, l = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().mx_filter_count(self._h, ctypes.byref(a), ctypes.byref(l)))
+        return int(a.value), int(l.value)
+
+    def ranges(self) -> np.ndarray:
+        """The set as normalised id ranges -> uint64 [m, 2], sorted and merged, under the index's current id offset."""
+        n = ctypes.c_uint64(0)
+        check(lib().mx_filter_get_ranges(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros((int(n.value), 2), dtype=np.uint64)
+        if out.size:
+            check(lib().mx_filter_get_ranges(self._h, _ptr(out), out.shape[0], ctypes.byref(n)))
+        return out[: int(n.value)]
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().mx_filter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def _filter_ranges(ranges, ids) -> np.ndarray:

@@ -155,6 +155,46 @@ def evict_resident(storage_path: str | None = None) -> None:
                 st._index = None
 
 
+class StoreFilter:
+    """A resident filter of a ``HipFlatStore``, edited by ``_id`` string (``HipFlatStore.make_filter``)."""
+
+    def __init__(self, store: "HipFlatStore", flt):
+        self._store = store
+        self._flt = flt
+
+    def _edit(self, ids, allow: bool) -> None:
+        with self._store._lock:
+            rows = np.asarray(self._store._ids_named(ids), dtype=np.uint64)
+            try:
+                (self._flt.allow if allow else self._flt.deny)(ids=rows)
+            except _lib.MemexHipError as e:
+                _raise_from(e, SearchError)
+
+    def allow(self, ids) -> None:
+        """Add every row inserted under the given ``_id`` strings; unknown ones add nothing."""
+        self._edit(ids, True)
+
+    def deny(self, ids) -> None:
+        """Take every row inserted under the given ``_id`` strings out of the set."""
+        self._edit(ids, False)
+
+    def count(self):
+        """-> (rows in the set, those of them that are not removed)."""
+        try:
+            return self._flt.count()
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+
+    def close(self) -> None:
+        self._flt.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 @dataclass
 class HipFlatStore(VectorStore):
     """Drop-in for ``HnswStore``: same id map, same score formula, exact search on the GPU."""
@@ -423,6 +463,49 @@ class HipFlatStore(VectorStore):
             raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
         try:
             ids_, scores, _, nf = idx.search_filtered(q, int(limit), ids=allow)  # not under the lock: combined like search
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[VectorSearchResult] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids_[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[d_id], float(scores[0, j])))
+        return out
+
+    def _ids_named(self, ids) -> List[int]:
+        """The index ids inserted under the given ``_id`` strings (under the lock)."""
+        wanted = [ids] if isinstance(ids, str) else [str(i) for i in ids]
+        rows_of = self._rows_by_name()
+        return [i for w in dict.fromkeys(wanted) for i in rows_of.get(w, ())]
+
+    def make_filter(self, ids: Sequence[str] = ()) -> "StoreFilter":
+        """A resident filter over the rows inserted under the given ``_id`` strings (``FlatIndex.make_filter``): one tenant's,
+        one ACL group's or one tag's documents, registered once and named in every ``search_in``.  Bulk-inserting a document
+        and then ``flt.allow([its _ids])`` is the tenant-ingest flow; ``flt.deny`` takes documents out.  After ``compact()``,
+        ``delete_all()`` or a reload the filter raises: make a new one.  The store must hold at least one row."""
+        with self._lock:
+            if self._index is None:
+                raise SearchError("a filter needs a store with rows: insert first")
+            try:
+                flt = StoreFilter(self, self._index.make_filter())
+                flt.allow(ids)
+            except _lib.MemexHipError as e:
+                _raise_from(e, SearchError)
+        return flt
+
+    def search_in(self, vec: Sequence[float], limit: int, flt: "StoreFilter") -> List[VectorSearchResult]:
+        """``search`` restricted to the rows of a resident filter (``FlatIndex.search_with``), as ``(_id, score)`` pairs."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0:
+            return []
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        try:
+            ids_, scores, _, nf = idx.search_with(flt._flt, q, int(limit))  # not under the lock: combined like search
         except _lib.MemexHipError as e:
             _raise_from(e, SearchError)
         out: List[VectorSearchResult] = []
