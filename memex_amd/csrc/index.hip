@@ -1152,6 +1152,149 @@ int await_finish(mx_index *idx, int B, uint32_t seq) {
     return fail(MX_EDEVICE, "finish_kernel did not signal completion");
 }
 
+// ---- what search_batch and range_batch share: the geometry of a batch and the parameter blocks of its launches ------------------
+// The geometry of one batch of B queries: which scan serves it, with how many workgroups and lane-buffer sets, and where it has to be
+// split.  It follows from the index state, B and the kind of search alone; `trivial` (nothing can be found) is the caller's own rule.
+enum class BatchKind { kTopK, kRange };
+struct BatchPlan {
+    bool filt8;     // 8-bit copy: 256 queries per pass at every width
+    bool wide;      // wide rows (768 < dim_pad <= 1536) have their own scan kernel over the bf16 copy: 128 queries per pass
+    bool fast;      // the scan pipeline answers the batch; otherwise the EXACT path does
+    bool centred8;  // a centred int8 copy: passes of 256 (the two-group variant has no register left for the per-row epilogue)
+    bool centred;   // the copy is centred on its rows' mean direction (build_filter_copy): queries are split the same way
+    bool x2;        // more than 256 queries as ONE pass of the int8 scan with two query groups per wave (up to 512 dims)
+    bool pair;      // 129-256 queries on a plain int8 copy up to 512 dims: two 4-wave workgroups per CU with two query groups per wave
+                    // (DESIGN.md section 3.2e).  Smaller batches stay on the 8-wave form, whose idle waves skip their MFMAs.
+    int nwg;        // workgroups of the scan launches; finish_kernel and theta_kernel follow
+    int lanes;      // lane-buffer sets per workgroup (LaneLease::take): 2 for x2 and for pair (2 x nwg workgroups x 512 lanes)
+    Scan8Geom geom;
+    int split;      // 0: one pass serves the batch; else the batch is answered as [0, split) and the rest (kPassBatch or kWideBatch)
+    uint64_t trows;      // rows per scan tile
+    int bytes_per_elem;  // of what the scan streams
+};
+
+BatchPlan plan_batch(const mx_index *idx, int B, int k_or_cap, BatchKind kind, bool trivial) {
+    BatchPlan pl;
+    pl.filt8 = idx->xh != nullptr && idx->filter_i8 && !idx->compressed;
+    pl.wide = idx->kc > kMaxKC && !pl.filt8;
+    // (a range search has no k > 256 rule: its lists are cut from what the pass collects, whatever the cap)
+    pl.fast = !trivial && idx->mode == MX_SEARCH_AUTO && (idx->kc > kMaxKC ? idx->xh != nullptr && idx->kc <= kMaxKC16 : true) &&
+              (!idx->compressed || idx->wild_rows == 0) && (kind == BatchKind::kRange || k_or_cap <= 256) &&
+              idx->n_zero <= (uint64_t)kZeroCap && idx->n_wild <= (uint64_t)kWildCap;
+    pl.centred8 = idx->centred && pl.filt8 && idx->amean && idx->mean && idx->kc <= kMaxKC;
+    const bool two_groups = pl.fast && pl.filt8 && !pl.centred8 && idx->kc <= kMaxKC8x2;
+    pl.x2 = two_groups && B > kPassBatch;
+    pl.pair = two_groups && B > kPassBatch / 2 && B <= kPassBatch && idx->scan8_pair;
+    pl.centred = pl.centred8 || (idx->centred && idx->xh && !pl.filt8 && !pl.wide && !idx->compressed && idx->amean && idx->mean && idx->kc <= kMaxKC);
+    pl.nwg = pl.pair ? 2 * idx->nwg : idx->nwg;
+    pl.lanes = pl.x2 || pl.pair ? 2 : 1;
+    pl.geom = pl.pair ? Scan8Geom::kPair : pl.x2 ? Scan8Geom::k512 : Scan8Geom::k256;
+    pl.split = B > kPassBatch && !pl.x2 && !(pl.fast && pl.wide) ? kPassBatch : pl.fast && pl.wide && B > kWideBatch ? kWideBatch : 0;
+    pl.trows = pl.filt8 ? kTile8Rows : kTileRows;
+    pl.bytes_per_elem = pl.filt8 ? 1 : idx->xh ? 2 : 4;
+    return pl;
+}
+
+int prep_queries(mx_index *idx, const BatchPlan &pl, const float *d_q, int B) {
+    Scratch &s = idx->s;
+    MX_HIP(launch_prep_queries(idx->stream, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
+                               idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, pl.filt8, s.qscale,
+                               pl.centred ? idx->mean : nullptr, s.qmean, pl.centred8 ? idx->flags + 5 : nullptr));
+    return MX_OK;
+}
+
+// everything of a scan launch but its tiles (tile_begin / tile_end / tile_stride: the caller's, per launch); mask: ScanParams::dead
+void fill_scan_params(ScanParams &p, const mx_index *idx, const BatchPlan &pl, int B, const uint64_t *mask) {
+    const Scratch &s = idx->s;
+    p.x = idx->x;
+    p.xh = idx->xh;
+    p.scale = idx->scale;
+    p.qfrag = s.qfrag;
+    p.theta = s.theta;
+    p.n_rows = idx->n;
+    p.ds = (uint32_t)idx->ds;
+    p.wave_mask = (1u << ((B + 31) / 32)) - 1u;  // waves whose 32 columns are all padding skip their MFMAs
+    p.lane_rec = s.lane_rec;
+    p.lane_tile = s.lane_tile;
+    p.lane_cnt = s.lane_cnt;
+    p.lane_max = s.lane_max;
+    p.overflow = s.overflow;
+    p.tscale = idx->tsc;
+    p.qscale = s.qscale;
+    p.qa = s.qa;
+    p.qb = s.qb;
+    p.amean = pl.centred ? idx->amean : nullptr;
+    p.qmean = s.qmean;
+    p.dead = mask;  // the masked kernels only for an index with removed rows, or a filtered search
+}
+
+hipError_t launch_scan_for(const mx_index *idx, const BatchPlan &pl, bool collect, const ScanParams &p) {
+    if (pl.filt8) return launch_scan8(idx->stream, idx->kc, collect, pl.nwg, p, pl.geom);
+    if (pl.wide) return launch_scan16w(idx->stream, idx->kc, collect, pl.nwg, p);
+    return idx->xh ? launch_scan16(idx->stream, idx->kc, collect, pl.nwg, p) : launch_scan(idx->stream, idx->kc, collect, pl.nwg, p);
+}
+
+// The finish launch of a batch over all rows: k (or the cap), the mask and what it leaves, and the outputs are the caller's; so is
+// what it sets afterwards (the retry pass's todo, max_err when profiling, no rows for a batch that can find nothing) and seq.
+void fill_finish_params(FinishParams &fp, const mx_index *idx, const BatchPlan &pl, int B, int k, const uint64_t *mask, uint64_t n_live,
+                        uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_nfound) {
+    const Scratch &s = idx->s;
+    fp.k = k;
+    fp.ds = idx->ds;
+    fp.nwg = pl.nwg;
+    fp.x = idx->compressed ? nullptr : idx->x;
+    fp.xh = idx->xh;
+    fp.scale = idx->scale;
+    fp.n_rows = idx->n;
+    fp.idmap = idx->idmap;
+    fp.qpad = s.qpad;
+    fp.qnorm2 = s.qnorm2;
+    fp.e1 = s.e1;
+    fp.qa = s.qa;
+    fp.qb = s.qb;
+    fp.terr = pl.filt8 ? idx->tsc : nullptr;
+    fp.e2 = (float)(idx->ds + 8) * 5.9604645e-8f + 1e-6f;  // f32 fma dot of <= ds terms of unit vectors, any order
+    fp.lane_rec = s.lane_rec;
+    fp.lane_tile = s.lane_tile;
+    fp.lane_cnt = s.lane_cnt;
+    fp.theta = s.theta;
+    fp.zero_rows = idx->zero_rows;
+    fp.n_zero = (uint32_t)std::min<uint64_t>(idx->n_zero, kZeroCap);
+    fp.wild_rows = idx->wild_list;
+    fp.n_wild = (uint32_t)std::min<uint64_t>(idx->n_wild, kWildCap);
+    fp.dead = mask;
+    fp.n_live = n_live;
+    fp.overflow = s.overflow;
+    fp.todo = nullptr;
+    fp.theta_retry = s.theta_retry;
+    fp.cand_cnt = s.cand_cnt;
+    fp.ids = d_ids;
+    fp.scores = d_scores;
+    fp.dists = d_dists;
+    fp.n_found = d_nfound;
+    fp.max_err = nullptr;
+    fp.done_ctr = s.done_ctr;
+    fp.dev_flags = s.dev_flags;
+    fp.host_flags = s.host_sum;
+    fp.n_queries = B;
+    fp.host_out = s.out_on_host ? 1 : 0;
+}
+
+// the per-query flag words of the batch, host-synchronised (overflowed batches, the EXACT path and the subset kernel only)
+int fetch_flags(mx_index *idx) {
+    MX_HIP(hipMemcpyAsync(idx->s.host_flags, idx->s.dev_flags, kFlagWords * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
+    MX_HIP(hipStreamSynchronize(idx->stream));
+    return MX_OK;
+}
+
+// a large exact scratch does not stay behind a fallback batch (the stream is idle)
+void drop_large_exact_scratch(mx_index *idx) {
+    if (idx->mode != MX_SEARCH_AUTO || idx->s.exact_bytes <= kExactKeepBytes) return;
+    (void)hipFree(idx->s.exact_scratch);
+    idx->s.exact_scratch = nullptr;
+    idx->s.exact_bytes = 0;
+}
+
 // one batch (B <= 256) with queries and outputs on the device; filt: what a filtered search allows -- local rows (normalised
 // ranges), or this index's shard of a resident filter
 int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids, float *d_scores, float *d_dists,
@@ -1182,50 +1325,21 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     const bool trivial = idx->n == 0 || k == 0 || (filt && n_allow == 0);
     if (idx->compressed && idx->kc > kMaxKC16 && !trivial)
         return fail(MX_EUNSUPPORTED, "a compressed corpus supports dim <= %d", kMaxKC16 * kChunkFloats);
-    // wide rows (768 < dim_pad <= 1536) have their own scan kernel over the filter copy: 128 queries per pass
-    const bool filt8 = idx->xh != nullptr && idx->filter_i8 && !idx->compressed;  // 8-bit copy: 256 queries per pass at every width
-    const bool wide = idx->kc > kMaxKC && !filt8;
-    const bool fast = !trivial && idx->mode == MX_SEARCH_AUTO && (idx->kc > kMaxKC ? idx->xh != nullptr && idx->kc <= kMaxKC16 : true) &&
-                      (!idx->compressed || idx->wild_rows == 0) && k <= 256 && idx->n_zero <= (uint64_t)kZeroCap &&
-                      idx->n_wild <= (uint64_t)kWildCap;
-    // a batch of more than 256 queries is one pass of the int8 scan with two query groups per wave (up to 512 dims),
-    // otherwise two passes
-    // (a centred int8 copy runs passes of 256: the two-group variant has no register left for the per-row epilogue)
-    const bool centred8 = idx->centred && filt8 && idx->amean && idx->mean && idx->kc <= kMaxKC;
-    const bool x2 = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch;
-    // 129-256 queries on a plain int8 copy up to 512 dims: two 4-wave workgroups per CU with two query groups per wave
-    // (DESIGN.md section 3.2e).  Smaller batches stay on the 8-wave form, whose idle waves skip their MFMAs.
-    const bool pair = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch / 2 && B <= kPassBatch && idx->scan8_pair;
-    const int nwg = pair ? 2 * idx->nwg : idx->nwg;  // workgroups of the scan launches; finish_kernel and theta_kernel follow
-    if (B > kPassBatch && !x2 && !(fast && wide)) {
-        rc = search_batch(idx, d_q, kPassBatch, k, d_ids, d_scores, d_dists, d_nfound, filt);
+    const BatchPlan pl = plan_batch(idx, B, k, BatchKind::kTopK, trivial);
+    if (pl.split) {
+        rc = search_batch(idx, d_q, pl.split, k, d_ids, d_scores, d_dists, d_nfound, filt);
         if (rc != MX_OK) return rc;
-        const size_t o = (size_t)kPassBatch * k;
-        return search_batch(idx, d_q + (size_t)kPassBatch * idx->dim, B - kPassBatch, k, d_ids + o, d_scores + o,
-                            d_dists ? d_dists + o : nullptr, d_nfound + kPassBatch, filt);
+        const size_t o = (size_t)pl.split * k;
+        return search_batch(idx, d_q + (size_t)pl.split * idx->dim, B - pl.split, k, d_ids + o, d_scores + o,
+                            d_dists ? d_dists + o : nullptr, d_nfound + pl.split, filt);
     }
-    if (fast && wide && B > kWideBatch) {
-        rc = search_batch(idx, d_q, kWideBatch, k, d_ids, d_scores, d_dists, d_nfound, filt);
-        if (rc != MX_OK) return rc;
-        const size_t o = (size_t)kWideBatch * k;
-        return search_batch(idx, d_q + (size_t)kWideBatch * idx->dim, B - kWideBatch, k, d_ids + o, d_scores + o,
-                            d_dists ? d_dists + o : nullptr, d_nfound + kWideBatch, filt);
-    }
-    // the bf16 copy of this index is centred on its rows' mean direction (build_filter_copy): queries are split the same way
-    const bool centred = centred8 || (idx->centred && idx->xh && !filt8 && !wide && !idx->compressed && idx->amean && idx->mean && idx->kc <= kMaxKC);
     const uint32_t *h_ovf = s.host_flags, *h_qfl = s.host_flags + 3 * kMaxBatch;
     auto any_bad_query = [&] {
         uint32_t bad = 0;
         for (int b = 0; b < B; ++b) bad |= h_qfl[b];
         return bad != 0;
     };
-    auto fetch_flags = [&]() -> int {  // the per-query words (overflowed batches, the EXACT path and the subset kernel only)
-        MX_HIP(hipMemcpyAsync(s.host_flags, s.dev_flags, kFlagWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        MX_HIP(hipStreamSynchronize(st));
-        return MX_OK;
-    };
-    if (filt && !trivial &&
-        subset_pays(idx, B, n_allow, span_hi - span_lo, filt8 ? 1 : idx->xh ? 2 : 4)) {
+    if (filt && !trivial && subset_pays(idx, B, n_allow, span_hi - span_lo, pl.bytes_per_elem)) {
         // a small filter: the allowed live rows, ascending, and one subset_topk_kernel launch; no scan, no lane buffers
         std::vector<uint32_t> list;
         const uint32_t *rows_list = nullptr;
@@ -1247,12 +1361,10 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
             MX_HIP(hipMemcpyAsync(idx->subset_rows, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             rows_list = idx->subset_rows;
         }
-        MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
-                                   idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
-                                   centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
+        if ((rc = prep_queries(idx, pl, d_q, B)) != MX_OK) return rc;
         MX_HIP(launch_subset_topk(st, B, k, idx->ds, idx->compressed ? nullptr : idx->x, idx->xh, rows_list, (uint32_t)n_allow,
                                   idx->idmap, s.qpad, s.qnorm2, d_ids, d_scores, d_dists, d_nfound));
-        if ((rc = fetch_flags()) != MX_OK) return rc;  // (host-synchronised: also for outputs in mapped host memory)
+        if ((rc = fetch_flags(idx)) != MX_OK) return rc;  // (host-synchronised: also for outputs in mapped host memory)
         if (any_bad_query()) return fail(MX_EINVAL, "a query contains non-finite values");
         idx->last_subset = true;
         idx->stats.searches += 1;
@@ -1267,52 +1379,14 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     const uint64_t *mask = filt ? idx->filt : idx->n_dead ? idx->dead : nullptr;
     const uint64_t n_live = filt ? n_allow : idx->n - idx->n_dead;
     LaneLease lease;  // every return below is host-synchronised with the kernels that used the lane buffers
-    if ((rc = lease.take(idx, x2 || pair ? 2 : 1)) != MX_OK) return rc;  // pair: 2 x nwg workgroups x 512 lanes, the 512-query set
-    MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
-                               idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
-                               centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
+    if ((rc = lease.take(idx, pl.lanes)) != MX_OK) return rc;
+    if ((rc = prep_queries(idx, pl, d_q, B)) != MX_OK) return rc;
     bool timed = false;
 
     FinishParams fp;
-    fp.k = k;
-    fp.ds = idx->ds;
-    fp.nwg = nwg;
-    fp.x = idx->compressed ? nullptr : idx->x;
-    fp.xh = idx->xh;
-    fp.scale = idx->scale;
-    fp.n_rows = trivial ? 0 : idx->n;
-    fp.idmap = idx->idmap;
-    fp.qpad = s.qpad;
-    fp.qnorm2 = s.qnorm2;
-    fp.e1 = s.e1;
-    fp.qa = s.qa;
-    fp.qb = s.qb;
-    fp.terr = filt8 ? idx->tsc : nullptr;
-    fp.e2 = (float)(idx->ds + 8) * 5.9604645e-8f + 1e-6f;  // f32 fma dot of <= ds terms of unit vectors, any order
-    fp.lane_rec = s.lane_rec;
-    fp.lane_tile = s.lane_tile;
-    fp.lane_cnt = s.lane_cnt;
-    fp.theta = s.theta;
-    fp.zero_rows = idx->zero_rows;
-    fp.n_zero = (uint32_t)std::min<uint64_t>(idx->n_zero, kZeroCap);
-    fp.wild_rows = idx->wild_list;
-    fp.n_wild = (uint32_t)std::min<uint64_t>(idx->n_wild, kWildCap);
-    fp.dead = mask;
-    fp.n_live = trivial ? 0 : n_live;
-    fp.overflow = s.overflow;
-    fp.todo = nullptr;
-    fp.theta_retry = s.theta_retry;
-    fp.cand_cnt = s.cand_cnt;
-    fp.ids = d_ids;
-    fp.scores = d_scores;
-    fp.dists = d_dists;
-    fp.n_found = d_nfound;
+    fill_finish_params(fp, idx, pl, B, k, mask, n_live, d_ids, d_scores, d_dists, d_nfound);
+    if (trivial) fp.n_rows = fp.n_live = 0;
     fp.max_err = idx->profiling ? s.max_err : nullptr;
-    fp.done_ctr = s.done_ctr;
-    fp.dev_flags = s.dev_flags;
-    fp.host_flags = s.host_sum;
-    fp.n_queries = B;
-    fp.host_out = s.out_on_host ? 1 : 0;
     // finish + completion: the kernel's last workgroup writes the batch summary into pinned host memory and
     // stores the launch's sequence number behind it; the host spins on that word (no D2H copy command and no
     // memset between batches: the host gap between two batches drops from 45 to 22 us, the kernel grows by
@@ -1327,52 +1401,27 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     if (trivial) {
         fp.seq = ++s.flag_seq;
         MX_HIP(launch_finish(st, B, fp));  // n_found = 0, empty slots
-    } else if (fast) {
-        const uint64_t trows = filt8 ? kTile8Rows : kTileRows;  // rows per scan tile
-        const uint64_t tiles = (idx->n + trows - 1) / trows, full = idx->n / trows;
+    } else if (pl.fast) {
+        const uint64_t tiles = (idx->n + pl.trows - 1) / pl.trows, full = idx->n / pl.trows;
         // the tiles the scans visit: all of them, or the span of tiles a filter's ranges touch (the sample: its full tiles)
-        const uint64_t ts0 = filt ? span_lo / trows : 0, ts1 = filt ? (span_hi + trows - 1) / trows : tiles;
+        const uint64_t ts0 = filt ? span_lo / pl.trows : 0, ts1 = filt ? (span_hi + pl.trows - 1) / pl.trows : tiles;
         const uint64_t full1 = std::min(ts1, full);
         ScanParams p;
-        p.x = idx->x;
-        p.xh = idx->xh;
-        p.scale = idx->scale;
-        p.qfrag = s.qfrag;
-        p.theta = s.theta;
-        p.n_rows = idx->n;
-        p.ds = (uint32_t)idx->ds;
-        p.wave_mask = (1u << ((B + 31) / 32)) - 1u;  // waves whose 32 columns are all padding skip their MFMAs
-        p.lane_rec = s.lane_rec;
-        p.lane_tile = s.lane_tile;
-        p.lane_cnt = s.lane_cnt;
-        p.lane_max = s.lane_max;
-        p.overflow = s.overflow;
-        p.tscale = idx->tsc;
-        p.qscale = s.qscale;
-        p.qa = s.qa;
-        p.qb = s.qb;
-        p.amean = centred ? idx->amean : nullptr;
-        p.qmean = s.qmean;
-        p.dead = mask;  // the masked kernels only for an index with removed rows, or a filtered search
-        auto scan = [&](bool collect) {
-            if (filt8) return launch_scan8(st, idx->kc, collect, nwg, p, pair ? Scan8Geom::kPair : x2 ? Scan8Geom::k512 : Scan8Geom::k256);
-            if (wide) return launch_scan16w(st, idx->kc, collect, idx->nwg, p);
-            return idx->xh ? launch_scan16(st, idx->kc, collect, idx->nwg, p) : launch_scan(st, idx->kc, collect, idx->nwg, p);
-        };
+        fill_scan_params(p, idx, pl, B, mask);
         auto collect = [&](bool first) -> int {
             p.tile_begin = (uint32_t)ts0;
             p.tile_end = (uint32_t)ts1;
             p.tile_stride = 1;
             // the first collect launch of a batch is the one the roofline is quoted on
             if (first && idx->profiling) MX_HIP(hipEventRecord(idx->ev0, st));
-            MX_HIP(scan(true));
+            MX_HIP(launch_scan_for(idx, pl, true, p));
             if (first && idx->profiling) {
                 MX_HIP(hipEventRecord(idx->ev1, st));
                 timed = true;
             }
             if (first) {
                 idx->stats.scan_launches += 1;
-                idx->stats.scan_bytes += (ts1 - ts0) * trows * idx->ds * (filt8 ? 1ull : idx->xh ? 2ull : 4ull);
+                idx->stats.scan_bytes += (ts1 - ts0) * pl.trows * idx->ds * (uint64_t)pl.bytes_per_elem;
             }
             return MX_OK;
         };
@@ -1381,9 +1430,9 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         if (ts1 - ts0 > 2ull * idx->nwg) {
             p.tile_begin = (uint32_t)ts0;
             p.tile_end = (uint32_t)full1;
-            p.tile_stride = sample_stride(full1 - ts0, nwg, k, filt8, idx->ds, centred8);
-            MX_HIP(scan(false));
-            MX_HIP(launch_theta(st, B, k, nwg, s.lane_max, s.qa, !filt8, s.theta));
+            p.tile_stride = sample_stride(full1 - ts0, pl.nwg, k, pl.filt8, idx->ds, pl.centred8);
+            MX_HIP(launch_scan_for(idx, pl, false, p));
+            MX_HIP(launch_theta(st, B, k, pl.nwg, s.lane_max, s.qa, !pl.filt8, s.theta));
         }
         if ((rc = collect(true)) != MX_OK) return rc;
         if ((rc = finish_and_wait()) != MX_OK) return rc;
@@ -1396,17 +1445,17 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         if (s.host_sum[2]) return fail(MX_EINVAL, "a query contains non-finite values");
         idx->stats.candidates += s.host_sum[1];
         if (s.host_sum[0]) {
-            if ((rc = fetch_flags()) != MX_OK) return rc;
+            if ((rc = fetch_flags(idx)) != MX_OK) return rc;
             int retry = 0;
             for (int b = 0; b < B; ++b) {
                 if (h_ovf[b] == 1) ++retry;
                 else if (h_ovf[b] >= 2) exact.push_back(b);
             }
             // (a filtered batch leaves the copy heuristics alone: a selective filter's overflows say nothing about the corpus)
-            if (filt8 && !filt) idx->i8_retry_batches += 1;
+            if (pl.filt8 && !filt) idx->i8_retry_batches += 1;
             // ... or the retry pass (a second whole scan) has become the rule: more than a quarter of the batches
-            const bool habitual = filt8 && idx->i8_batches >= 8 && idx->i8_retry_batches * 4 > idx->i8_batches;
-            if (filt8 && !filt && idx->filter_auto && ((size_t)(retry + (int)exact.size()) * 16 > (size_t)std::max(B, 16) || habitual)) {
+            const bool habitual = pl.filt8 && idx->i8_batches >= 8 && idx->i8_retry_batches * 4 > idx->i8_batches;
+            if (pl.filt8 && !filt && idx->filter_auto && ((size_t)(retry + (int)exact.size()) * 16 > (size_t)std::max(B, 16) || habitual)) {
                 // More than 1/16 of the batch (and more than one query) did not fit the int8 pass: this corpus is too dense for the int8
                 // certificate (neighbourhoods narrower than ~0.05 in cosine).  Rebuild the copy as bf16 (one pass
                 // over the f32 rows) and answer the batch on it; the index stays on bf16.
@@ -1442,7 +1491,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
                 if ((rc = finish_and_wait()) != MX_OK) return rc;
                 exact.clear();
                 if (s.host_sum[0]) {
-                    if ((rc = fetch_flags()) != MX_OK) return rc;
+                    if ((rc = fetch_flags(idx)) != MX_OK) return rc;
                     for (int b = 0; b < B; ++b)
                         if (h_ovf[b] != 0) exact.push_back(b);
                 }
@@ -1450,33 +1499,22 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         }
         idx->stats.fallback_queries += exact.size();
     } else {
-        if ((rc = fetch_flags()) != MX_OK) return rc;
+        if ((rc = fetch_flags(idx)) != MX_OK) return rc;
         if (any_bad_query()) return fail(MX_EINVAL, "a query contains non-finite values");
         for (int b = 0; b < B; ++b) exact.push_back(b);
     }
-    if (!exact.empty() || trivial || !fast) {
+    if (!exact.empty() || trivial || !pl.fast) {
         rc = run_exact(idx, exact, k, d_ids, d_scores, d_dists, d_nfound, mask, n_live);
         if (rc != MX_OK) return rc;
         MX_HIP(hipStreamSynchronize(st));
-        if (idx->mode == MX_SEARCH_AUTO && idx->s.exact_bytes > kExactKeepBytes) {  // a large scratch does not stay behind a fallback batch
-            (void)hipFree(idx->s.exact_scratch);
-            idx->s.exact_scratch = nullptr;
-            idx->s.exact_bytes = 0;
-        }
+        drop_large_exact_scratch(idx);
     }
     // (fast path with nothing left to do: finish_kernel's completion word was stored after every result of
     // the batch had been fenced to device scope -- the results are in HBM, nothing else is queued)
     idx->stats.searches += 1;
     idx->stats.queries += (uint64_t)B;
     if (filt) idx->stats.filtered_queries += (uint64_t)B;
-    if (filt8 && fast && !filt) idx->i8_batches += 1;
-    return MX_OK;
-}
-
-// the per-query flag words of the batch, host-synchronised
-int fetch_flags_now(mx_index *idx) {
-    MX_HIP(hipMemcpyAsync(idx->s.host_flags, idx->s.dev_flags, kFlagWords * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
-    MX_HIP(hipStreamSynchronize(idx->stream));
+    if (pl.filt8 && pl.fast && !filt) idx->i8_batches += 1;
     return MX_OK;
 }
 
@@ -1530,8 +1568,8 @@ int run_exact_range(mx_index *idx, const std::vector<int> &qs, int cap, uint64_t
 
 // one range batch (B <= 512) with queries and outputs on the device; dlim: the B dist bounds (host memory).  The top-k pipeline minus
 // the sample and theta launches: theta follows from the caller's threshold (launch_range_theta), one collect launch over every tile with
-// the geometry search_batch picks for B, range_finish_kernel.  No retry pass; its overflows and everything search_batch sends to the
-// EXACT path (but k > 256) take the EXACT range path.  The filter copy's heuristics are left alone.
+// the geometry of the shared plan (plan_batch: what search_batch runs for B), range_finish_kernel.  No retry pass; its overflows and
+// everything search_batch sends to the EXACT path (but k > 256) take the EXACT range path.  The filter copy's heuristics are left alone.
 int range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t *dlim, uint64_t *d_ids, float *d_scores, float *d_dists,
                 int32_t *d_nfound, uint64_t *d_nrange) {
     int rc = ensure_scratch(idx);
@@ -1542,108 +1580,36 @@ int range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t 
     const bool trivial = idx->n == 0 || n_live == 0;
     if (idx->compressed && idx->kc > kMaxKC16 && !trivial)
         return fail(MX_EUNSUPPORTED, "a compressed corpus supports dim <= %d", kMaxKC16 * kChunkFloats);
-    const bool filt8 = idx->xh != nullptr && idx->filter_i8 && !idx->compressed;
-    const bool wide = idx->kc > kMaxKC && !filt8;
-    const bool fast = !trivial && idx->mode == MX_SEARCH_AUTO && (idx->kc > kMaxKC ? idx->xh != nullptr && idx->kc <= kMaxKC16 : true) &&
-                      (!idx->compressed || idx->wild_rows == 0) && idx->n_zero <= (uint64_t)kZeroCap && idx->n_wild <= (uint64_t)kWildCap;
-    const bool centred8 = idx->centred && filt8 && idx->amean && idx->mean && idx->kc <= kMaxKC;
-    const bool x2 = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch;
-    const bool pair = fast && filt8 && !centred8 && idx->kc <= kMaxKC8x2 && B > kPassBatch / 2 && B <= kPassBatch && idx->scan8_pair;
-    const int nwg = pair ? 2 * idx->nwg : idx->nwg;
-    const int split = B > kPassBatch && !x2 && !(fast && wide) ? kPassBatch : fast && wide && B > kWideBatch ? kWideBatch : 0;
-    if (split) {
-        rc = range_batch(idx, d_q, split, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange);
+    const BatchPlan pl = plan_batch(idx, B, cap, BatchKind::kRange, trivial);
+    if (pl.split) {
+        rc = range_batch(idx, d_q, pl.split, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange);
         if (rc != MX_OK) return rc;
-        const size_t o = (size_t)split * cap;
-        return range_batch(idx, d_q + (size_t)split * idx->dim, B - split, cap, dlim + split, d_ids + o, d_scores + o,
-                           d_dists ? d_dists + o : nullptr, d_nfound + split, d_nrange + split);
+        const size_t o = (size_t)pl.split * cap;
+        return range_batch(idx, d_q + (size_t)pl.split * idx->dim, B - pl.split, cap, dlim + pl.split, d_ids + o, d_scores + o,
+                           d_dists ? d_dists + o : nullptr, d_nfound + pl.split, d_nrange + pl.split);
     }
-    const bool centred = centred8 || (idx->centred && idx->xh && !filt8 && !wide && !idx->compressed && idx->amean && idx->mean && idx->kc <= kMaxKC);
     const uint32_t *h_ovf = s.host_flags, *h_qfl = s.host_flags + 3 * kMaxBatch;
     const uint64_t *mask = idx->n_dead ? idx->dead : nullptr;
     LaneLease lease;
-    if (fast && (rc = lease.take(idx, x2 || pair ? 2 : 1)) != MX_OK) return rc;
+    if (pl.fast && (rc = lease.take(idx, pl.lanes)) != MX_OK) return rc;
     MX_HIP(hipMemcpyAsync(s.rlim, dlim, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    MX_HIP(launch_prep_queries(st, d_q, B, idx->dim, idx->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1,
-                               idx->xh ? idx->flags + 2 : nullptr, s.overflow, s.qflags, s.qa, s.qb, filt8, s.qscale,
-                               centred ? idx->mean : nullptr, s.qmean, centred8 ? idx->flags + 5 : nullptr));
+    if ((rc = prep_queries(idx, pl, d_q, B)) != MX_OK) return rc;
     std::vector<int> exact;
-    if (fast) {
+    if (pl.fast) {
         MX_HIP(launch_range_theta(st, B, s.rlim, kRangeEps, s.qa, s.theta));
-        const uint64_t trows = filt8 ? kTile8Rows : kTileRows;
-        const uint64_t tiles = (idx->n + trows - 1) / trows;
+        const uint64_t tiles = (idx->n + pl.trows - 1) / pl.trows;
         ScanParams p;
-        p.x = idx->x;
-        p.xh = idx->xh;
-        p.scale = idx->scale;
-        p.qfrag = s.qfrag;
-        p.theta = s.theta;
-        p.n_rows = idx->n;
-        p.ds = (uint32_t)idx->ds;
-        p.wave_mask = (1u << ((B + 31) / 32)) - 1u;
-        p.lane_rec = s.lane_rec;
-        p.lane_tile = s.lane_tile;
-        p.lane_cnt = s.lane_cnt;
-        p.lane_max = s.lane_max;
-        p.overflow = s.overflow;
-        p.tscale = idx->tsc;
-        p.qscale = s.qscale;
-        p.qa = s.qa;
-        p.qb = s.qb;
-        p.amean = centred ? idx->amean : nullptr;
-        p.qmean = s.qmean;
-        p.dead = mask;
+        fill_scan_params(p, idx, pl, B, mask);
         p.tile_begin = 0;
         p.tile_end = (uint32_t)tiles;
         p.tile_stride = 1;
-        if (filt8) MX_HIP(launch_scan8(st, idx->kc, true, nwg, p, pair ? Scan8Geom::kPair : x2 ? Scan8Geom::k512 : Scan8Geom::k256));
-        else if (wide) MX_HIP(launch_scan16w(st, idx->kc, true, idx->nwg, p));
-        else if (idx->xh) MX_HIP(launch_scan16(st, idx->kc, true, idx->nwg, p));
-        else MX_HIP(launch_scan(st, idx->kc, true, idx->nwg, p));
+        MX_HIP(launch_scan_for(idx, pl, true, p));
         idx->stats.scan_launches += 1;
-        idx->stats.scan_bytes += tiles * trows * idx->ds * (filt8 ? 1ull : idx->xh ? 2ull : 4ull);
+        idx->stats.scan_bytes += tiles * pl.trows * idx->ds * (uint64_t)pl.bytes_per_elem;
 
         RangeParams rp;
         FinishParams &fp = rp.f;
-        fp.k = cap;
-        fp.ds = idx->ds;
-        fp.nwg = nwg;
-        fp.x = idx->compressed ? nullptr : idx->x;
-        fp.xh = idx->xh;
-        fp.scale = idx->scale;
-        fp.n_rows = idx->n;
-        fp.idmap = idx->idmap;
-        fp.qpad = s.qpad;
-        fp.qnorm2 = s.qnorm2;
-        fp.e1 = s.e1;
-        fp.qa = s.qa;
-        fp.qb = s.qb;
-        fp.terr = filt8 ? idx->tsc : nullptr;
-        fp.e2 = (float)(idx->ds + 8) * 5.9604645e-8f + 1e-6f;  // (search_batch's)
-        fp.lane_rec = s.lane_rec;
-        fp.lane_tile = s.lane_tile;
-        fp.lane_cnt = s.lane_cnt;
-        fp.theta = s.theta;
-        fp.zero_rows = idx->zero_rows;
-        fp.n_zero = (uint32_t)std::min<uint64_t>(idx->n_zero, kZeroCap);
-        fp.wild_rows = idx->wild_list;
-        fp.n_wild = (uint32_t)std::min<uint64_t>(idx->n_wild, kWildCap);
-        fp.dead = mask;
-        fp.n_live = n_live;
-        fp.overflow = s.overflow;
-        fp.todo = nullptr;
-        fp.theta_retry = s.theta_retry;
-        fp.cand_cnt = s.cand_cnt;
-        fp.ids = d_ids;
-        fp.scores = d_scores;
-        fp.dists = d_dists;
-        fp.n_found = d_nfound;
-        fp.max_err = nullptr;
-        fp.done_ctr = s.done_ctr;
-        fp.dev_flags = s.dev_flags;
-        fp.host_flags = s.host_sum;
-        fp.n_queries = B;
-        fp.host_out = s.out_on_host ? 1 : 0;
+        fill_finish_params(fp, idx, pl, B, cap, mask, n_live, d_ids, d_scores, d_dists, d_nfound);
         fp.seq = ++s.flag_seq;
         rp.dlim = s.rlim;
         rp.eps = kRangeEps;
@@ -1653,13 +1619,13 @@ int range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t 
         if (s.host_sum[2]) return fail(MX_EINVAL, "a query contains non-finite values");
         idx->stats.candidates += s.host_sum[1];
         if (s.host_sum[0]) {
-            if ((rc = fetch_flags_now(idx)) != MX_OK) return rc;
+            if ((rc = fetch_flags(idx)) != MX_OK) return rc;
             for (int b = 0; b < B; ++b)
                 if (h_ovf[b] != 0) exact.push_back(b);
         }
         idx->stats.fallback_queries += exact.size();
     } else {
-        if ((rc = fetch_flags_now(idx)) != MX_OK) return rc;
+        if ((rc = fetch_flags(idx)) != MX_OK) return rc;
         for (int b = 0; b < B; ++b)
             if (h_qfl[b]) return fail(MX_EINVAL, "a query contains non-finite values");
         for (int b = 0; b < B && !trivial; ++b) exact.push_back(b);
@@ -1683,11 +1649,7 @@ int range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t 
         rc = run_exact_range(idx, exact, cap, d_ids, d_scores, d_dists, d_nfound, d_nrange, mask, n_live);
         if (rc != MX_OK) return rc;
         MX_HIP(hipStreamSynchronize(st));
-        if (idx->mode == MX_SEARCH_AUTO && idx->s.exact_bytes > kExactKeepBytes) {
-            (void)hipFree(idx->s.exact_scratch);
-            idx->s.exact_scratch = nullptr;
-            idx->s.exact_bytes = 0;
-        }
+        drop_large_exact_scratch(idx);
     }
     idx->stats.searches += 1;
     idx->stats.queries += (uint64_t)B;
@@ -1832,6 +1794,113 @@ bool rccl_selftest(mx_index *idx, double seconds) {
     return ok;
 }
 
+#ifdef MEMEX_TESTING
+// libmemex_hip_testing.so only: the first all-gather of the process reports an error (one flag for every kind of search: not a static
+// of the template below, which would have one per instantiation)
+bool inject_all_gather_failure() {
+    static std::atomic<bool> injected{false};
+    return !injected.exchange(true);
+}
+#endif
+
+// The part of a batch on a composite that does not depend on the kind of search.  Every shard takes the queries (d_q, on shards[0]'s
+// device) and answers into its packed block -- local(g, shard, its queries, its block): ids [B, k] | dists [B, k] | whatever the caller
+// keeps behind the lists, blk bytes in all -- the blocks meet in the gather area on shards[0]'s device (ONE RCCL all-gather over xGMI,
+// or peer copies) and the lists are merged by (dist, id) into the caller's outputs; tail(stream) queues what the caller adds behind the
+// merge.  Returns host-synchronised.  exchange = false: the blocks are empty, the shards run and nothing travels.
+template <class Local, class Tail>
+int exchange_and_merge(mx_index *idx, const float *d_q, int B, int k, size_t blk, bool exchange, uint64_t *d_ids, float *d_scores,
+                       float *d_dists, Local &&local, Tail &&tail) {
+    const int G = (int)idx->shards.size();
+    const size_t ids_bytes = (size_t)B * k * sizeof(uint64_t);
+    std::vector<int> rcs(G, MX_OK);
+    std::vector<std::string> errs(G);
+    auto shard = [&](int g) {
+        mx_index *sh = idx->shards[g];
+        std::lock_guard<std::mutex> lk(sh->mu);
+        DeviceGuard dg(sh->device);
+        auto run = [&]() -> int {
+            MX_HIP(hipMemcpyAsync(idx->sh_q[g], d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
+            char *blkp = static_cast<char *>(idx->sh_block[g]);
+            int r = local(g, sh, idx->sh_q[g], blkp);
+            if (r != MX_OK) return r;
+            if (!idx->use_rccl && exchange) {  // peer copy into slot g of the gather area on shards[0]'s device
+                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
+                MX_HIP(hipStreamSynchronize(sh->stream));
+            }
+            return MX_OK;
+        };
+        try {  // (a helper thread of the pool: an exception must not leave it)
+            rcs[g] = run();
+        } catch (...) {
+            rcs[g] = guard_exception();
+        }
+        if (rcs[g] != MX_OK) errs[g] = last_error_slot();
+    };
+    // the query batch must be complete on shards[0]'s stream before other devices read it
+    {
+        DeviceGuard dg(idx->shards[0]->device);
+        MX_HIP(hipStreamSynchronize(idx->shards[0]->stream));
+    }
+    if (idx->pool) {  // one persistent helper thread per shard >= 1 (shard_pool.h); shard 0 on this thread
+        idx->pool->run(shard);
+    } else {          // logical shards on one device: their streams would only take turns on the GPU anyway
+        for (int g = 0; g < G; ++g) shard(g);
+    }
+    for (int g = 0; g < G; ++g)
+        if (rcs[g] != MX_OK) {
+            last_error_slot() = errs[g];
+            return rcs[g];
+        }
+    mx_index *s0 = idx->shards[0];
+    DeviceGuard dg(s0->device);
+    const auto t_tail = std::chrono::steady_clock::now();  // every shard has answered: what follows is the step's serial tail
+    if (exchange) {
+        if (idx->use_rccl) {
+            // ONE all-gather of blk bytes per shard over xGMI; every device receives all blocks, device 0 merges
+            int e = 0, e2 = 0;
+#ifdef MEMEX_TESTING
+            if (inject_all_gather_failure()) {
+                e = 1;
+            } else
+#endif
+            {
+                e = g_rccl.GroupStart();
+                for (int g = 0; g < G && e == 0; ++g)
+                    e = g_rccl.AllGather(idx->sh_block[g], idx->sh_gather[g], blk, 1 /*ncclUint8*/, idx->comms[g], idx->shards[g]->stream);
+                e2 = g_rccl.GroupEnd();
+            }
+            if (e != 0 || e2 != 0) {
+                // The collective could not be queued: this batch and every later one exchange by copies into the slots
+                // of the gather area on shards[0]'s device (what an index without RCCL does from the start).  Every shard
+                // is host-synchronised at this point (its batch returned), so the blocks are complete.
+                fprintf(stderr, "memex-hip: RCCL all-gather failed (%s); the sharded index continues on peer copies\n",
+                        g_rccl.GetErrorString && (e > 1 || e2) ? g_rccl.GetErrorString(e ? e : e2) : "error");
+                // (part of the group may have been queued on some shard streams before the failure: wait with a deadline, and
+                // give the batch up rather than hang the caller if a stream never drains)
+                if (!sync_shard_streams_within(idx, 10.0))
+                    return fail(MX_EDEVICE, "RCCL all-gather failed and a shard stream did not drain within 10 s");
+                idx->use_rccl = false;
+                idx->stats.exchange_fallbacks += 1;
+                enable_peer_access(idx);
+                for (int g = 0; g < G; ++g)  // (the shards left their blocks in place for the all-gather)
+                    MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, idx->sh_block[g], blk, hipMemcpyDefault, s0->stream));
+            }
+            // no host wait on shards >= 1: their part of the collective is ordered on their own streams (the
+            // next batch's kernels queue behind it), and the merge below follows shard 0's part in stream order
+        }
+        const char *gat = static_cast<const char *>(idx->sh_gather[0]);
+        MX_HIP(launch_merge(s0->stream, gat, blk, gat + ids_bytes, blk, G, B, k, d_ids,
+                            d_dists ? d_dists : reinterpret_cast<float *>(static_cast<char *>(idx->sh_block[0]) + ids_bytes), d_scores));
+    }
+    MX_HIP(tail(s0->stream));
+    MX_HIP(hipStreamSynchronize(s0->stream));
+    idx->stats.exchange_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count();
+    idx->stats.searches += 1;
+    idx->stats.queries += (uint64_t)B;
+    return MX_OK;
+}
+
 // one batch on a composite: d_q and the outputs live on shards[0]'s device
 // filt: the global rows a filtered search allows (normalised): every shard searches its share of them (shard_ranges); or a
 // resident filter: every shard searches with its own bitmap
@@ -1863,98 +1932,16 @@ int composite_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_i
         offers[g] = fs.n_allowed != 0;
     }
     const size_t ids_bytes = (size_t)B * k * sizeof(uint64_t), blk = ids_bytes + (size_t)B * k * sizeof(float);
-    std::vector<int> rcs(G, MX_OK);
-    std::vector<std::string> errs(G);
-    auto local = [&](int g) {
-        mx_index *sh = idx->shards[g];
-        std::lock_guard<std::mutex> lk(sh->mu);
-        DeviceGuard dg(sh->device);
-        auto run = [&]() -> int {
-            MX_HIP(hipMemcpyAsync(idx->sh_q[g], d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
-            char *blkp = static_cast<char *>(idx->sh_block[g]);
-            int r = search_batch(sh, idx->sh_q[g], B, k, reinterpret_cast<uint64_t *>(blkp), idx->sh_scores[g],
-                                 reinterpret_cast<float *>(blkp + ids_bytes), idx->sh_nf[g], filt ? &fa[g] : nullptr);
-            if (r != MX_OK) return r;
-            if (!idx->use_rccl && k > 0) {  // peer copy into slot g of the gather area on shards[0]'s device
-                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
-                MX_HIP(hipStreamSynchronize(sh->stream));
-            }
-            return MX_OK;
-        };
-        try {  // (a helper thread of the pool: an exception must not leave it)
-            rcs[g] = run();
-        } catch (...) {
-            rcs[g] = guard_exception();
-        }
-        if (rcs[g] != MX_OK) errs[g] = last_error_slot();
+    auto local = [&](int g, mx_index *sh, const float *q, char *blkp) {
+        return search_batch(sh, q, B, k, reinterpret_cast<uint64_t *>(blkp), idx->sh_scores[g], reinterpret_cast<float *>(blkp + ids_bytes),
+                            idx->sh_nf[g], filt ? &fa[g] : nullptr);
     };
-    // the query batch must be complete on shards[0]'s stream before other devices read it
-    {
-        DeviceGuard dg(idx->shards[0]->device);
-        MX_HIP(hipStreamSynchronize(idx->shards[0]->stream));
-    }
-    if (idx->pool) {  // one persistent helper thread per shard >= 1 (shard_pool.h); shard 0 on this thread
-        idx->pool->run(local);
-    } else {          // logical shards on one device: their streams would only take turns on the GPU anyway
-        for (int g = 0; g < G; ++g) local(g);
-    }
-    for (int g = 0; g < G; ++g)
-        if (rcs[g] != MX_OK) {
-            last_error_slot() = errs[g];
-            return rcs[g];
-        }
-    mx_index *s0 = idx->shards[0];
-    DeviceGuard dg(s0->device);
-    const auto t_tail = std::chrono::steady_clock::now();  // every shard has answered: what follows is the step's serial tail
-    const bool copies_pending = idx->use_rccl;  // the shards left their blocks in place for the all-gather
-    if (k > 0) {
-        if (idx->use_rccl) {
-            // ONE all-gather of B*k*12 bytes per shard over xGMI; every device receives all
-            // blocks, device 0 merges
-            int e = 0, e2 = 0;
-#ifdef MEMEX_TESTING  // libmemex_hip_testing.so only: the first all-gather of the process reports an error
-            static std::atomic<bool> injected{false};
-            if (!injected.exchange(true)) {
-                e = 1;
-            } else
-#endif
-            {
-                e = g_rccl.GroupStart();
-                for (int g = 0; g < G && e == 0; ++g)
-                    e = g_rccl.AllGather(idx->sh_block[g], idx->sh_gather[g], blk, 1 /*ncclUint8*/, idx->comms[g], idx->shards[g]->stream);
-                e2 = g_rccl.GroupEnd();
-            }
-            if (e != 0 || e2 != 0) {
-                // The collective could not be queued: this batch and every later one exchange by copies into the slots
-                // of the gather area on shards[0]'s device (what an index without RCCL does from the start).  Every shard
-                // is host-synchronised at this point (search_batch returned), so the blocks are complete.
-                fprintf(stderr, "memex-hip: RCCL all-gather failed (%s); the sharded index continues on peer copies\n",
-                        g_rccl.GetErrorString && (e > 1 || e2) ? g_rccl.GetErrorString(e ? e : e2) : "error");
-                // (part of the group may have been queued on some shard streams before the failure: wait with a deadline, and
-                // give the batch up rather than hang the caller if a stream never drains)
-                if (!sync_shard_streams_within(idx, 10.0))
-                    return fail(MX_EDEVICE, "RCCL all-gather failed and a shard stream did not drain within 10 s");
-                idx->use_rccl = false;
-                idx->stats.exchange_fallbacks += 1;
-                enable_peer_access(idx);
-            }
-            // no host wait on shards >= 1: their part of the collective is ordered on their own streams (the
-            // next batch's kernels queue behind it), and the merge below follows shard 0's part in stream order
-        }
-        if (!idx->use_rccl && copies_pending) {  // (only right after a fallback: the shards did not copy their blocks themselves)
-            for (int g = 0; g < G; ++g)
-                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, idx->sh_block[g], blk, hipMemcpyDefault, s0->stream));
-        }
-        MX_HIP(launch_merge(s0->stream, idx->sh_gather[0], blk, static_cast<const char *>(idx->sh_gather[0]) + ids_bytes, blk, G, B,
-                            k, d_ids, d_dists ? d_dists : reinterpret_cast<float *>(static_cast<char *>(idx->sh_block[0]) + ids_bytes),
-                            d_scores));
-    }
     // every shard found min(k, its live rows): the merged lists hold min(k, live rows of the handle) entries
-    MX_HIP(launch_fill_nfound(s0->stream, d_nfound, B, (int32_t)std::min<uint64_t>((uint64_t)k, filt ? n_allow : idx->total - idx->n_dead)));
-    MX_HIP(hipStreamSynchronize(s0->stream));
-    idx->stats.exchange_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count();
-    idx->stats.searches += 1;
-    idx->stats.queries += (uint64_t)B;
+    auto tail = [&](hipStream_t st) {
+        return launch_fill_nfound(st, d_nfound, B, (int32_t)std::min<uint64_t>((uint64_t)k, filt ? n_allow : idx->total - idx->n_dead));
+    };
+    // (k = 0: the blocks are empty, nothing is exchanged or merged)
+    if ((rc = exchange_and_merge(idx, d_q, B, k, blk, k > 0, d_ids, d_scores, d_dists, local, tail)) != MX_OK) return rc;
     if (filt) {
         // a query of the handle counts as answered by the subset kernel when every shard that had rows to offer used it
         bool any = false, all = true;
@@ -1985,78 +1972,31 @@ int composite_range_batch(mx_index *idx, const float *d_q, int B, int cap, const
     if (rc != MX_OK) return rc;
     const size_t ids_bytes = (size_t)B * cap * sizeof(uint64_t), lists = ids_bytes + (size_t)B * cap * sizeof(float);
     const size_t blk = lists + (size_t)B * sizeof(uint64_t);  // ... | counts [B]
-    std::vector<int> rcs(G, MX_OK);
-    std::vector<std::string> errs(G);
-    auto local = [&](int g) {
-        mx_index *sh = idx->shards[g];
-        std::lock_guard<std::mutex> lk(sh->mu);
-        DeviceGuard dg(sh->device);
-        auto run = [&]() -> int {
-            MX_HIP(hipMemcpyAsync(idx->sh_q[g], d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
-            char *blkp = static_cast<char *>(idx->sh_block[g]);
-            int r = range_batch(sh, idx->sh_q[g], B, cap, dlim, reinterpret_cast<uint64_t *>(blkp), idx->sh_scores[g],
-                                reinterpret_cast<float *>(blkp + ids_bytes), idx->sh_nf[g], reinterpret_cast<uint64_t *>(blkp + lists));
-            if (r != MX_OK) return r;
-            if (!idx->use_rccl) {
-                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
-                MX_HIP(hipStreamSynchronize(sh->stream));
-            }
-            return MX_OK;
-        };
-        try {
-            rcs[g] = run();
-        } catch (...) {
-            rcs[g] = guard_exception();
-        }
-        if (rcs[g] != MX_OK) errs[g] = last_error_slot();
+    auto local = [&](int g, mx_index *sh, const float *q, char *blkp) {
+        return range_batch(sh, q, B, cap, dlim, reinterpret_cast<uint64_t *>(blkp), idx->sh_scores[g], reinterpret_cast<float *>(blkp + ids_bytes),
+                           idx->sh_nf[g], reinterpret_cast<uint64_t *>(blkp + lists));
     };
-    {
-        DeviceGuard dg(idx->shards[0]->device);
-        MX_HIP(hipStreamSynchronize(idx->shards[0]->stream));
-    }
-    if (idx->pool) idx->pool->run(local);
-    else
-        for (int g = 0; g < G; ++g) local(g);
-    for (int g = 0; g < G; ++g)
-        if (rcs[g] != MX_OK) {
-            last_error_slot() = errs[g];
-            return rcs[g];
-        }
-    mx_index *s0 = idx->shards[0];
-    DeviceGuard dg(s0->device);
-    const auto t_tail = std::chrono::steady_clock::now();
-    if (idx->use_rccl) {
-        int e = g_rccl.GroupStart();
-        for (int g = 0; g < G && e == 0; ++g)
-            e = g_rccl.AllGather(idx->sh_block[g], idx->sh_gather[g], blk, 1 /*ncclUint8*/, idx->comms[g], idx->shards[g]->stream);
-        const int e2 = g_rccl.GroupEnd();
-        if (e != 0 || e2 != 0) {  // as composite_batch: this batch and every later one exchange by copies
-            fprintf(stderr, "memex-hip: RCCL all-gather failed (%s); the sharded index continues on peer copies\n",
-                    g_rccl.GetErrorString && (e > 1 || e2) ? g_rccl.GetErrorString(e ? e : e2) : "error");
-            if (!sync_shard_streams_within(idx, 10.0))
-                return fail(MX_EDEVICE, "RCCL all-gather failed and a shard stream did not drain within 10 s");
-            idx->use_rccl = false;
-            idx->stats.exchange_fallbacks += 1;
-            enable_peer_access(idx);
-            for (int g = 0; g < G; ++g)
-                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, idx->sh_block[g], blk, hipMemcpyDefault, s0->stream));
-        }
-    }
-    const char *gat = static_cast<const char *>(idx->sh_gather[0]);
-    MX_HIP(launch_merge(s0->stream, gat, blk, gat + ids_bytes, blk, G, B, cap, d_ids,
-                        d_dists ? d_dists : reinterpret_cast<float *>(static_cast<char *>(idx->sh_block[0]) + ids_bytes), d_scores));
-    MX_HIP(launch_range_sum(s0->stream, gat + lists, blk, G, B, cap, d_nrange, d_nfound));
-    MX_HIP(hipStreamSynchronize(s0->stream));
-    idx->stats.exchange_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count();
-    idx->stats.searches += 1;
-    idx->stats.queries += (uint64_t)B;
-    return MX_OK;
+    auto tail = [&](hipStream_t st) {
+        return launch_range_sum(st, static_cast<const char *>(idx->sh_gather[0]) + lists, blk, G, B, cap, d_nrange, d_nfound);
+    };
+    return exchange_and_merge(idx, d_q, B, cap, blk, true, d_ids, d_scores, d_dists, local, tail);
 }
 
 int any_range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t *dlim, uint64_t *d_ids, float *d_scores, float *d_dists,
                     int32_t *d_nfound, uint64_t *d_nrange) {
     return idx->composite() ? composite_range_batch(idx, d_q, B, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange)
                             : range_batch(idx, d_q, B, cap, dlim, d_ids, d_scores, d_dists, d_nfound, d_nrange);
+}
+
+// The row an id names, as (shard, row of that shard): global row r = id - id_offset - 1 lies in block r / R, which was dealt to shard
+// block % G (composite_add); a plain index is its own shard 0.  false: the id names no row of the handle.
+bool locate_row(const mx_index *idx, uint64_t id, size_t *shard, uint64_t *local) {
+    const uint64_t off = idx->idmap.id_offset, total_rows = idx->composite() ? idx->total : idx->n;
+    if (id <= off || id - off - 1 >= total_rows) return false;
+    const uint64_t r = id - off - 1, R = idx->composite() ? idx->block_rows : 0, G = idx->shards.size();
+    *shard = R ? (size_t)((r / R) % G) : 0;
+    *local = R ? (r / R / G) * R + r % R : r;
+    return true;
 }
 
 // ---- diversified search (mx_index_search_mmr) ------------------------------------------------------
@@ -2117,7 +2057,6 @@ int mmr_batch(mx_index *idx, const float *d_q, int B, int k, int fetch, float la
     MX_HIP(hipMemcpyAsync(t->mmr_h_nf, t->mmr_nf, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     MX_HIP(hipStreamSynchronize(st));
     const size_t G = idx->composite() ? idx->shards.size() : 1;
-    const uint64_t R = idx->composite() ? idx->block_rows : 0, off = idx->idmap.id_offset, total_rows = idx->composite() ? idx->total : idx->n;
     const size_t row_bytes = (size_t)ds * sizeof(float);
     const int qc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, kMmrStageBytes / ((size_t)fetch * row_bytes)));
     std::vector<std::vector<uint32_t>> rows(G);  // (alive until the chunk is host-synchronised: sources of async uploads)
@@ -2132,9 +2071,9 @@ int mmr_batch(mx_index *idx, const float *d_q, int B, int k, int fetch, float la
             const int m = std::min(std::max(t->mmr_h_nf[q0 + q], 0), fetch);
             for (int i = 0; i < m; ++i) {
                 const uint64_t id = t->mmr_h_ids[(size_t)(q0 + q) * fetch + i];
-                if (id <= off || id - off - 1 >= total_rows) return fail(MX_ESEARCH, "candidate id %llu names no row", (unsigned long long)id);
-                const uint64_t r = id - off - 1;
-                const uint64_t g = R ? (r / R) % G : 0, local = R ? (r / R / G) * R + r % R : r;
+                size_t g;
+                uint64_t local;
+                if (!locate_row(idx, id, &g, &local)) return fail(MX_ESEARCH, "candidate id %llu names no row", (unsigned long long)id);
                 const mx_index *sh = idx->composite() ? idx->shards[g] : idx;
                 if (local >= sh->n) return fail(MX_ESEARCH, "candidate id %llu names no row of its shard", (unsigned long long)id);
                 const size_t s = (size_t)q * fetch + i;
@@ -2221,14 +2160,13 @@ int byid_batch(mx_index *idx, const uint64_t *qids, int B, int k, int exclude, c
     if (rc != MX_OK) return rc;
     hipStream_t st = t->stream;
     const size_t G = idx->composite() ? idx->shards.size() : 1;
-    const uint64_t R = idx->composite() ? idx->block_rows : 0, off = idx->idmap.id_offset, total_rows = idx->composite() ? idx->total : idx->n;
     std::vector<std::vector<uint32_t>> rows(G);  // (alive until the batch is host-synchronised: sources of async uploads)
     std::vector<uint32_t> src((size_t)B, kByIdNone), owner((size_t)B, 0u), pd((size_t)B, 0u);
     for (int b = 0; b < B; ++b) {
         const uint64_t id = qids[b];
-        if (id <= off || id - off - 1 >= total_rows) continue;  // names no row
-        const uint64_t r = id - off - 1;
-        const uint64_t g = R ? (r / R) % G : 0, local = R ? (r / R / G) * R + r % R : r;
+        size_t g;
+        uint64_t local;
+        if (!locate_row(idx, id, &g, &local)) continue;  // names no row
         const mx_index *sh = idx->composite() ? idx->shards[g] : idx;
         if (local >= sh->n) return fail(MX_ESEARCH, "id %llu names no row of its shard", (unsigned long long)id);
         if (row_removed(sh, local)) continue;
@@ -3510,62 +3448,44 @@ int mx_index_search_filtered_device(mx_index *idx, const float *d_q, int B, int 
 
 namespace {
 
-// run_combined for a range pass (every request of it has the same cap): the requests' dist bounds side by side, outputs as run_combined's
-// plus the pinned n_in_range staging
-int run_combined_range(mx_index *idx, const std::vector<SearchReq *> &batch) {
-    mx_index *t = idx->composite() ? idx->shards[0] : idx;
-    DeviceGuard g(t->device);
-    const int cap = batch[0]->k;
-    int rc = ensure_scratch(t);
-    if (rc != MX_OK) return rc;
-    if ((rc = ensure_out(t, cap)) != MX_OK) return rc;
+// the results of a batch of nb queries, `width` wide, from the index's device outputs into its pinned staging buffers: one D2H per
+// output array, host-synchronised (width = 0, a top-k search at k = 0: the counts alone).  static, like scatter_to_caller: a function
+// of an unnamed namespace inside extern "C" is exported under its plain name
+static int copy_out_to_host(mx_index *t, int nb, int width, bool want_nrange) {
     Scratch &s = t->s;
-    const size_t dim = (size_t)idx->dim;
-    int nb = 0;
-    std::vector<uint32_t> dl;
-    for (const SearchReq *r : batch) {
-        memcpy(s.h_q + (size_t)nb * dim, r->q, (size_t)r->B * dim * sizeof(float));
-        dl.insert(dl.end(), r->dlim, r->dlim + r->B);
-        nb += r->B;
+    if (width > 0) {
+        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * width * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * width * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * width * sizeof(float), hipMemcpyDeviceToHost, t->stream));
     }
-    if (!idx->composite()) {  // outputs straight into the mapped staging buffers (see run_combined)
-        s.out_on_host = true;
-        rc = any_range_batch(idx, s.h_q, nb, cap, dl.data(), s.h_ids, s.h_scores, s.h_dists, s.h_nf, s.h_nr);
-        s.out_on_host = false;
-        if (rc != MX_OK) return rc;
-        std::atomic_thread_fence(std::memory_order_acquire);
-    } else {
-        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
-        rc = any_range_batch(idx, s.qstage, nb, cap, dl.data(), s.out_ids, s.out_scores, s.out_dists, s.out_nfound, s.out_nrange);
-        if (rc != MX_OK) return rc;
-        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * cap * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * cap * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * cap * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_nr, s.out_nrange, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipStreamSynchronize(t->stream));
-    }
-    int b0 = 0;
-    for (SearchReq *r : batch) {
-        memcpy(r->ids, s.h_ids + (size_t)b0 * cap, (size_t)r->B * cap * sizeof(uint64_t));
-        memcpy(r->scores, s.h_scores + (size_t)b0 * cap, (size_t)r->B * cap * sizeof(float));
-        if (r->dists) memcpy(r->dists, s.h_dists + (size_t)b0 * cap, (size_t)r->B * cap * sizeof(float));
-        memcpy(r->n_found, s.h_nf + b0, (size_t)r->B * sizeof(int32_t));
-        memcpy(r->n_in_range, s.h_nr + b0, (size_t)r->B * sizeof(uint64_t));
-        b0 += r->B;
-    }
+    MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+    if (want_nrange) MX_HIP(hipMemcpyAsync(s.h_nr, s.out_nrange, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+    MX_HIP(hipStreamSynchronize(t->stream));
     return MX_OK;
 }
 
+// queries [b0, b0 + n) of the staged results to a caller's arrays (dists, n_in_range: null = not wanted)
+static void scatter_to_caller(const Scratch &s, int b0, int n, int width, uint64_t *ids, float *scores, float *dists, int32_t *n_found,
+                              uint64_t *n_in_range) {
+    if (width > 0) {
+        memcpy(ids, s.h_ids + (size_t)b0 * width, (size_t)n * width * sizeof(uint64_t));
+        memcpy(scores, s.h_scores + (size_t)b0 * width, (size_t)n * width * sizeof(float));
+        if (dists) memcpy(dists, s.h_dists + (size_t)b0 * width, (size_t)n * width * sizeof(float));
+    }
+    memcpy(n_found, s.h_nf + b0, (size_t)n * sizeof(int32_t));
+    if (n_in_range) memcpy(n_in_range, s.h_nr + b0, (size_t)n * sizeof(uint64_t));
+}
+
 // one GPU batch (sum of B <= 256, same k) for a group of host requests: queries are packed into
-// pinned memory, one H2D, the search pipeline, one D2H per output array, results scattered to the callers
+// pinned memory, one H2D, the search pipeline, one D2H per output array, results scattered to the callers.
+// A range pass (every request of it has the same cap, k): the requests' dist bounds side by side, and the n_in_range staging
 int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     std::lock_guard<std::mutex> lk(idx->mu);
     if (int rc = usable(idx); rc != MX_OK) return rc;
     mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
     DeviceGuard g(t->device);
     const int k = batch[0]->k;
-    if (batch[0]->dlim) return run_combined_range(idx, batch);
+    const bool range = batch[0]->dlim != nullptr;
     Ranges rows;  // a filtered pass: every request of it has the same ranges, or names the same resident filter
     if (batch[0]->filt) rows = rows_of_ids(*batch[0]->filt, idx->idmap.id_offset, rows_of(idx));
     if (batch[0]->res)
@@ -3579,8 +3499,10 @@ int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     Scratch &s = t->s;
     const size_t dim = (size_t)idx->dim;
     int nb = 0;
+    std::vector<uint32_t> dl;
     for (const SearchReq *r : batch) {
         memcpy(s.h_q + (size_t)nb * dim, r->q, (size_t)r->B * dim * sizeof(float));
+        if (range) dl.insert(dl.end(), r->dlim, r->dlim + r->B);
         nb += r->B;
     }
     // A plain index reads the queries from, and writes the answers into, the pinned staging buffers themselves (they are mapped
@@ -3591,30 +3513,21 @@ int run_combined(mx_index *idx, const std::vector<SearchReq *> &batch) {
     // A sharded index merges on the device and copies as before.
     if (!idx->composite()) {
         s.out_on_host = true;
-        rc = any_batch(idx, s.h_q, nb, k, s.h_ids, s.h_scores, s.h_dists, s.h_nf, filt);
+        rc = range ? any_range_batch(idx, s.h_q, nb, k, dl.data(), s.h_ids, s.h_scores, s.h_dists, s.h_nf, s.h_nr)
+                   : any_batch(idx, s.h_q, nb, k, s.h_ids, s.h_scores, s.h_dists, s.h_nf, filt);
         s.out_on_host = false;
         if (rc != MX_OK) return rc;
         std::atomic_thread_fence(std::memory_order_acquire);
     } else {
-    MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
-    rc = any_batch(idx, s.qstage, nb, k, s.out_ids, s.out_scores, s.out_dists, s.out_nfound, filt);
-    if (rc != MX_OK) return rc;
-    if (k > 0) {
-        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-    }
-    MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-    MX_HIP(hipStreamSynchronize(t->stream));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        rc = range ? any_range_batch(idx, s.qstage, nb, k, dl.data(), s.out_ids, s.out_scores, s.out_dists, s.out_nfound, s.out_nrange)
+                   : any_batch(idx, s.qstage, nb, k, s.out_ids, s.out_scores, s.out_dists, s.out_nfound, filt);
+        if (rc != MX_OK) return rc;
+        if ((rc = copy_out_to_host(t, nb, k, range)) != MX_OK) return rc;
     }
     int b0 = 0;
     for (SearchReq *r : batch) {
-        if (k > 0) {
-            memcpy(r->ids, s.h_ids + (size_t)b0 * k, (size_t)r->B * k * sizeof(uint64_t));
-            memcpy(r->scores, s.h_scores + (size_t)b0 * k, (size_t)r->B * k * sizeof(float));
-            if (r->dists) memcpy(r->dists, s.h_dists + (size_t)b0 * k, (size_t)r->B * k * sizeof(float));
-        }
-        memcpy(r->n_found, s.h_nf + b0, (size_t)r->B * sizeof(int32_t));
+        scatter_to_caller(s, b0, r->B, k, r->ids, r->scores, r->dists, r->n_found, range ? r->n_in_range : nullptr);
         b0 += r->B;
     }
     return MX_OK;
@@ -4112,15 +4025,8 @@ int mx_index_search_mmr(mx_index *idx, const float *q, int B, int k, int fetch, 
         memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
         MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
         if ((rc = mmr_batch(idx, s.qstage, nb, k, fetch, lambda, s.out_ids, s.out_scores, s.out_dists, s.out_nfound)) != MX_OK) return rc;
-        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipStreamSynchronize(t->stream));
-        memcpy(ids + o, s.h_ids, (size_t)nb * k * sizeof(uint64_t));
-        memcpy(scores + o, s.h_scores, (size_t)nb * k * sizeof(float));
-        if (dists) memcpy(dists + o, s.h_dists, (size_t)nb * k * sizeof(float));
-        memcpy(n_found + b0, s.h_nf, (size_t)nb * sizeof(int32_t));
+        if ((rc = copy_out_to_host(t, nb, k, false)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nb, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, nullptr);
     }
     return MX_OK;
 } catch (...) {
@@ -4200,17 +4106,8 @@ int search_by_id(mx_index *idx, const uint64_t *qids, int B, int k, int exclude_
         }
         if ((rc = byid_batch(idx, qids + b0, nb, k, exclude_self, dl, s.out_ids, s.out_scores, s.out_dists, s.out_nfound, s.out_nrange)) != MX_OK)
             return rc;
-        MX_HIP(hipMemcpyAsync(s.h_ids, s.out_ids, (size_t)nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_scores, s.out_scores, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_dists, s.out_dists, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipMemcpyAsync(s.h_nf, s.out_nfound, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        if (dlim) MX_HIP(hipMemcpyAsync(s.h_nr, s.out_nrange, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
-        MX_HIP(hipStreamSynchronize(t->stream));
-        memcpy(ids + o, s.h_ids, (size_t)nb * k * sizeof(uint64_t));
-        memcpy(scores + o, s.h_scores, (size_t)nb * k * sizeof(float));
-        if (dists) memcpy(dists + o, s.h_dists, (size_t)nb * k * sizeof(float));
-        memcpy(n_found + b0, s.h_nf, (size_t)nb * sizeof(int32_t));
-        if (dlim) memcpy(n_in_range + b0, s.h_nr, (size_t)nb * sizeof(uint64_t));
+        if ((rc = copy_out_to_host(t, nb, k, dlim != nullptr)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nb, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, dlim ? n_in_range + b0 : nullptr);
     }
     return MX_OK;
 }

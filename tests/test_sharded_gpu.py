@@ -130,6 +130,64 @@ print("FALLBACK_OK")
     assert "continues on peer copies" in r.stderr
 
 
+def test_rccl_failure_at_range_search_time_falls_back_to_copies(oracle, lib_built, tmp_path):
+    """The same injected failure when the first search of the process is a range search: the exchange is one function for both
+    kinds of search, so the range batch finishes on peer copies with the oracle's answer, the fallback is counted once, and a
+    top-k search that follows is correct and leaves the count at 1.  The child process searches; this process compares."""
+    import subprocess
+    import sys
+    from test_range_gpu import oracle_dists, range_oracle, same
+    from oracle.search_oracle import score_from_dist
+    rng = np.random.default_rng(8)
+    X = rng.standard_normal((20000, 384), dtype=np.float32)
+    Q = rng.standard_normal((9, 384), dtype=np.float32)
+    Q[::2] = X[rng.integers(0, len(X), 5)] + Q[::2] * 0.05
+    D = oracle_dists(oracle, X, Q)
+    cap = 50
+    S = np.sort(score_from_dist(D), axis=1)[:, ::-1]
+    t = S[np.arange(9), [3, 10, 20, 30, 49, 50, 80, 5, 0]].astype(np.float32)   # counts below, at and above the cap
+    t[7] = np.nextafter(t[7], np.float32(2.0))
+    np.savez(tmp_path / "in.npz", X=X, Q=Q, t=t)
+    code = r'''
+import os, sys, numpy as np
+sys.path.insert(0, os.getcwd())
+from memex_amd import _lib
+_lib.use_testing_library()
+from memex_amd.index import FlatIndex
+a = np.load(sys.argv[1])
+out = {}
+with FlatIndex(384, devices=[0]) as idx:
+    assert idx.exchange == "rccl", idx.exchange
+    idx.add(a["X"])
+    for i in range(2):
+        for j, v in enumerate(idx.search_range(a["Q"], a["t"], 50)):
+            out[f"range{i}_{j}"] = v
+        assert idx.exchange == "p2p", idx.exchange
+        assert idx.stats().exchange_fallbacks == 1
+    for j, v in enumerate(idx.search(a["Q"], 10)):
+        out[f"topk_{j}"] = v
+    assert idx.exchange == "p2p", idx.exchange
+    assert idx.stats().exchange_fallbacks == 1
+np.savez(sys.argv[2], **out)
+print("FALLBACK_OK")
+'''
+    env = dict(os.environ, MEMEX_HIP_EXCHANGE="rccl")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code, str(tmp_path / "in.npz"), str(tmp_path / "out.npz")], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "FALLBACK_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "continues on peer copies" in r.stderr
+    got = np.load(tmp_path / "out.npz")
+    want = range_oracle(D, np.ones(len(X), dtype=bool), t, cap)
+    for i in range(2):
+        same([got[f"range{i}_{j}"] for j in range(5)], want, f"range search {i}, after the failed all-gather")
+    oi, od, os_, onf = oracle.search(X, Q, 10)
+    np.testing.assert_array_equal(got["topk_0"], oi)
+    np.testing.assert_array_equal(bits(got["topk_2"]), bits(od))
+    np.testing.assert_array_equal(bits(got["topk_1"]), bits(os_))
+    np.testing.assert_array_equal(got["topk_3"], onf)
+
+
 def test_store_on_sharded_index(tmp_path, lib_built):
     """get_vector_storage(..., devices=[...]): the reference's store surface over the sharded index."""
     from memex_amd import storage
