@@ -1,6 +1,8 @@
 // index_kernels.h -- device-side contract of the flat cosine index (launch wrappers + shared
-// constants).  Kernels live in scan.hip (the streaming scan) and index_kernels.hip (everything
-// else); index.hip holds the host logic behind the C ABI.
+// constants).  The streaming scans live in scan.hip (f32 rows), scan16.hip / scan16w.hip (bf16 filter
+// copy, with its builder) and scan8.hip (int8 filter copy, with its builder), what they share in
+// scan_common.h; compaction in compact.hip, every other kernel in index_kernels.hip; index.hip holds
+// the host logic behind the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

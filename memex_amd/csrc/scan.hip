@@ -22,7 +22,7 @@
 // (512 MFMA cycles per SIMD per slot vs ~1250 cycles of HBM time per slot per CU: HBM-bound).
 // Approximate scores are within kApproxErr of the exact cosine; exactness of the final answer is
 // restored by index_kernels.hip (pool select + f64 rescoring).
-#include "index_kernels.h"
+#include "scan_common.h"
 
 // Ablation switch for scripts/scan_ubench.hip only (0 = production kernel):
 //   1 = DMA + waits + LDS reads of the conversion pass, 2 = + bf16 conversion and tile writes,
@@ -33,14 +33,6 @@
 
 namespace mx {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-#define MX_LDS_DMA16(rsrc, ldsptr, voff, soff, aux) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lds_void *)(ldsptr), 16, (voff), (soff), 0, (aux))
-
 constexpr int kTilePitch = kChunkFloats * 2 + 16;          // bf16 tile row pitch: 272 B (odd # of 16-B slots)
 constexpr int kTileBytes = kTileRows * kTilePitch;         // 8704 B
 constexpr uint32_t kTileOff = kNumSlots * kSlotBytes;      // two bf16 tiles after the ring
@@ -48,7 +40,6 @@ constexpr uint32_t kScaleOff = kTileOff + 2 * kTileBytes;  // per-tile 1/|c| rin
 static_assert(kScaleOff + kScaleRing * kTileRows * 4 == kScanLdsBytes, "LDS layout");
 static_assert(kPrefetch == kNumSlots && kNumSlots == 8, "waits below assume an 8-slot ring, all in flight");
 
-// DEAD: the variant that honours ScanParams::dead (launched only when the index has removed rows)
 template <int KC, int MODE, bool DEAD = false>
 __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -68,11 +59,8 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
     }
     const float theta = MODE == 1 ? p.theta[wave * 32 + m] : 0.0f;
 
-    // ---- tiles of this workgroup: tile_begin + (blockIdx + i*grid) * tile_stride
-    const uint32_t grid = gridDim.x;
-    const uint32_t t0 = p.tile_begin + blockIdx.x * p.tile_stride;
-    const uint32_t tstep = grid * p.tile_stride;
-    const uint32_t nT = (t0 < p.tile_end) ? (p.tile_end - t0 + tstep - 1) / tstep : 0;
+    const TileSpan span = tile_span(p);
+    const uint32_t t0 = span.t0, tstep = span.tstep, nT = span.nT;
     const uint32_t total = nT * KC;  // slots this workgroup consumes
     const uint32_t rowbytes = p.ds * 4;
 
@@ -131,14 +119,12 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
     // A-fragment read base: row m, bf16 [8h, 8h+8) of k-step ks at + ks*32 (immediate offsets)
     const uint32_t frag_base = kTileOff + (uint32_t)m * kTilePitch + (uint32_t)h * 16u;
 
-    // lane buffers are laid out [thread-in-workgroup][workgroup]: everything one query ever receives
-    // (2 lanes x all workgroups) is contiguous for the gather in update_kernel
     const size_t mylane = (size_t)tid * gridDim.x + blockIdx.x;
     f32x4 *myrec = reinterpret_cast<f32x4 *>(p.lane_rec + mylane * (kRecCap * 16));
     uint32_t *mytile = p.lane_tile + mylane * kRecCap;
     uint32_t cnt = 0;
     uint32_t ovf = 0;
-    float best = -INFINITY;  // MODE 0 (sample): running maximum of this lane's scores (scan16.hip)
+    float best = -INFINITY;  // MODE 0: running maximum of this lane's scores
 
     // ---- prologue: fill the ring, convert slot 0
 #pragma unroll 1
@@ -158,10 +144,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        // removed rows (DEAD): the 64-row word of this 32-row tile, one SCALAR load issued with the wait for the tile's first slot
-        // (scan8.hip: a plain load would be a vector load outside the ring's counted vmcnt waits, and the compiler's vmcnt(0)
-        // in front of its use would drain the ring once per tile)
-        uint64_t dw = 0;
+        uint64_t dw = 0;  // removed rows (DEAD): the 64-row word of this 32-row tile, a scalar load as in wait_slot_dead()
 
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc, ++j) {
@@ -237,25 +220,24 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const f32x4 sv = (r >> 2) == 0 ? s0 : (r >> 2) == 1 ? s1 : (r >> 2) == 2 ? s2 : s3;
-            v[r] = acc[r] * sv[r & 3];  // 1/|c| is 0 for a zero-norm row: score 0 (see scan16.hip)
+            v[r] = acc[r] * sv[r & 3];  // 1/|c| is 0 for a zero-norm row: score 0 (its exact dist is 0 too: the index's zero-row list)
         }
-        if constexpr (DEAD) {  // removed rows (ScanParams::dead): a score no test passes, and no lower bound for the sample
+        // From here on this kernel spells out what scan_common.h's mask_dead16 / store_record / write_lane do for the other scans:
+        // every form of those calls that was tried changed the code generated for this kernel (the others' did not move).
+        if constexpr (DEAD) {
             const uint32_t hw = (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u)));  // the tile's half of its 64-row word
             if (hw) {
                 const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
-        #pragma unroll
+#pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if ((lb >> r) & 1u) v[r] = -INFINITY;
             }
         }
-        float mx = fmaxf(fmaxf(v[0], v[1]), v[2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, v[r]), v[r + 1]);
-        mx = fmaxf(mx, v[15]);
+        const float mx = max16(v);
         if (MODE == 0) {
             best = fmaxf(best, mx);
         } else if (__builtin_amdgcn_ballot_w64(mx >= theta) != 0) {
-            if (mx >= theta) {  // one 64-byte record per passing lane and tile (scan16.hip)
+            if (mx >= theta) {  // one record per passing lane and tile
                 if (cnt < (uint32_t)kRecCap) {
                     f32x4 *dst = myrec + cnt * 4;
                     dst[0] = f32x4{v[0], v[1], v[2], v[3]};
@@ -270,58 +252,22 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
             }
         }
     }
-
     if (MODE == 0) {
         p.lane_max[(size_t)tid * gridDim.x + blockIdx.x] = best;
-        return;
+    } else {
+        p.lane_cnt[(size_t)tid * gridDim.x + blockIdx.x] = cnt;
+        if (ovf) p.overflow[wave * 32 + m] = 1;
     }
-    p.lane_cnt[(size_t)tid * gridDim.x + blockIdx.x] = cnt;
-    if (ovf) p.overflow[wave * 32 + m] = 1;
 }
 
-template <int KC, int MODE>
-static hipError_t setup_one() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_kernel<KC, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, kScanLdsBytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_kernel<KC, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kScanLdsBytes);
-}
+template <int... KC>
+static const ScanEntry kEntries[] = {ScanEntry{KC, {{scan_kernel<KC, 0, false>, scan_kernel<KC, 0, true>}, {scan_kernel<KC, 1, false>, scan_kernel<KC, 1, true>}}}...};
+static const ScanFamily kFamily(kEntries<1, 2, 3, 4, 5, 6>, kScanLdsBytes, kScanThreads);
 
-hipError_t scan_setup() {
-    hipError_t e;
-#define MX_SETUP(KC)                                         \
-    if ((e = setup_one<KC, 0>()) != hipSuccess) return e;    \
-    if ((e = setup_one<KC, 1>()) != hipSuccess) return e;
-    MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4) MX_SETUP(5) MX_SETUP(6)
-#undef MX_SETUP
-    return hipSuccess;
-}
+hipError_t scan_setup() { return scan_family_setup(kFamily); }
 
-template <int KC>
-static hipError_t launch_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
-    if (p.dead) {
-        if (collect) hipLaunchKernelGGL((scan_kernel<KC, 1, true>), dim3(nwg), dim3(kScanThreads), kScanLdsBytes, s, p);
-        else hipLaunchKernelGGL((scan_kernel<KC, 0, true>), dim3(nwg), dim3(kScanThreads), kScanLdsBytes, s, p);
-        return hipGetLastError();
-    }
-    if (collect)
-        hipLaunchKernelGGL((scan_kernel<KC, 1>), dim3(nwg), dim3(kScanThreads), kScanLdsBytes, s, p);
-    else
-        hipLaunchKernelGGL((scan_kernel<KC, 0>), dim3(nwg), dim3(kScanThreads), kScanLdsBytes, s, p);
-    return hipGetLastError();
-}
-
-// MODE 1 (collect) is the launch that covers the corpus; MODE 0 is the short sample launch.  They are
-// distinct symbols, so rocprofv3 --stats averages them separately.
 hipError_t launch_scan(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p) {
-    switch (kc) {
-        case 1: return launch_kc<1>(s, collect, nwg, p);
-        case 2: return launch_kc<2>(s, collect, nwg, p);
-        case 3: return launch_kc<3>(s, collect, nwg, p);
-        case 4: return launch_kc<4>(s, collect, nwg, p);
-        case 5: return launch_kc<5>(s, collect, nwg, p);
-        case 6: return launch_kc<6>(s, collect, nwg, p);
-        default: return hipErrorInvalidValue;
-    }
+    return scan_family_launch(kFamily, s, kc, collect, nwg, p);
 }
 
 }  // namespace mx

@@ -39,42 +39,13 @@
 // in cycles (81 % at 768-d); the DMA stream alone runs at 7.1 TB/s and the MFMA + fragment-read half alone at
 // 1.86 PFLOP/s, both at full clock and below the cap: together they need more than the cap allows, so what
 // pays is energy per launch, not cycles.
-#include <type_traits>
-
-#include "index_kernels.h"
+#include "scan_common.h"
 
 namespace mx {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-#define MX_LDS_DMA16(rsrc, ldsptr, voff, soff, aux) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lds_void *)(ldsptr), 16, (voff), (soff), 0, (aux))
-
 static_assert(kRing16 == 16, "waits below assume a 16-slot ring with 15 slots in flight");
-
-namespace {
-template <int N>
-using ic16 = std::integral_constant<int, N>;
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for16(F &&f) {
-    if constexpr (B < E) {
-        f(ic16<B>{});
-        static_for16<B + 1, E>(f);
-    }
-}
-// DMA operations a wave has issued after the one of slot j+1 when it waits for that slot: the slots lo .. hi (relative to the
-// tile start), plus the one a_c operation of every tile that starts among them (as scan8_kernel's tile scales)
-template <int KC>
-constexpr int ops_after16(int lo, int hi) {
-    int n = 0;
-    for (int i = lo; i <= hi; ++i) n += 1 + (i % KC == 0 ? 1 : 0);
-    return n;
-}
-static_assert(ops_after16<3>(2, 14) == 17 && ops_after16<6>(5, 17) == 15 && ops_after16<1>(2, 14) == 26, "");
-}  // namespace
+// a wave's DMA operations: one per slot, plus the one a_c operation of every tile (ops_after<KC, 1, 1>)
+static_assert(ops_after<3, 1, 1>(2, 14) == 17 && ops_after<6, 1, 1>(5, 17) == 15 && ops_after<1, 1, 1>(2, 14) == 26, "");
 
 // Ablation switch for scripts/scan16_ubench.hip only (0 = production kernel):
 //   1 = DMA + waits + barriers, 2 = + fragment reads (no MFMA), 4 = everything except the DMA
@@ -88,7 +59,6 @@ static_assert(ops_after16<3>(2, 14) == 17 && ops_after16<6>(5, 17) == 15 && ops_
 #define MX_SCAN16_AUX 2 /* nt */
 #endif
 
-// DEAD: the variant that honours ScanParams::dead (launched only when the index has removed rows)
 template <int KC, int MODE, bool DEAD = false>
 __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParams p) {
     // Fragment ring: the A fragment of k-step f lives in ring[f % R] and is re-read R k-steps ahead
@@ -118,12 +88,8 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
     }
     const float theta = MODE == 1 ? p.theta[wave * 32 + m] : 0.0f;
 
-    // ---- tiles of this workgroup: tile_begin + (blockIdx + i*grid) * tile_stride
-    const uint32_t grid = gridDim.x;
-    const uint32_t stride = p.tile_stride;
-    const uint32_t t0 = p.tile_begin + blockIdx.x * stride;
-    const uint32_t tstep = grid * stride;
-    const uint32_t nT = (t0 < p.tile_end) ? (p.tile_end - t0 + tstep - 1) / tstep : 0;
+    const TileSpan span = tile_span(p);
+    const uint32_t t0 = span.t0, tstep = span.tstep, nT = span.nT;
     const uint32_t tilebytes = p.ds * (kTileRows * 2);
 
     const uint32_t voff = (uint32_t)wave * 1024u + (uint32_t)lane * 16u;  // this lane's 16 B of a slot
@@ -173,8 +139,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
     for (int i = 0; i < kRing16 - 1; ++i) issue(i % KC, (uint32_t)i);
 
     bf16x8 a[R];
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after16<KC>(1, kRing16 - 2)) : "memory");  // slot 0 (and its tile's a_c) landed
-    __builtin_amdgcn_s_barrier();
+    wait_slot<ops_after<KC, 1, 1>(1, kRing16 - 2)>();  // slot 0 (and its tile's a_c) landed
 #if MX_SCAN16_ABLATE != 1
 #pragma unroll
     for (int ks = 0; ks < R; ++ks) a[ks] = *reinterpret_cast<const bf16x8 *>(smem + lane16 + ks * 1024);
@@ -191,12 +156,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
         f32x16 acc, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f, acc1[r] = 0.0f;
-        // removed rows (DEAD): the 64-row word of this 32-row tile, one SCALAR load issued with the wait for the tile's first slot
-        // (scan8.hip: a plain load would be a vector load outside the ring's counted vmcnt waits, and the compiler's vmcnt(0)
-        // in front of its use would drain the ring once per tile)
-        uint64_t dw = 0;
+        uint64_t dw = 0;  // removed rows (DEAD): the 64-row word of this 32-row tile
 
-        static_for16<0, KC>([&](auto kct) __attribute__((always_inline)) {
+        static_for<0, KC>([&](auto kct) __attribute__((always_inline)) {
             constexpr int kc = decltype(kct)::value;
             const uint32_t rp1 = (rp + 1) & (kRing16 - 1);
             const uint32_t rpi = (rp + kRing16 - 1) & (kRing16 - 1);  // ring position of slot j+15 = of slot j-1
@@ -204,15 +166,11 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
             // the 13 newer ones (and the a_c operations of the tiles that start among them) may be in flight.
             // One barrier per slot: every wave's piece of slot j+1 is in LDS, and every wave has
             // consumed (MFMA issued) its fragments of slot j-1, whose ring position is refilled below.
-            if constexpr (DEAD && kc == 0) {
-                asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt vmcnt(%2)\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)"
-                             : "=s"(dw)
-                             : "s"(p.dead + ((t0 + ti * tstep) >> 1)), "n"(ops_after16<KC>(kc + 2, kc + kRing16 - 2))
-                             : "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after16<KC>(kc + 2, kc + kRing16 - 2)) : "memory");
-                __builtin_amdgcn_s_barrier();
-            }
+            constexpr int vm = ops_after<KC, 1, 1>(kc + 2, kc + kRing16 - 2);
+            if constexpr (DEAD && kc == 0)
+                dw = wait_slot_dead<vm>(p.dead + ((t0 + ti * tstep) >> 1));
+            else
+                wait_slot<vm>();
             const uint32_t fb0 = rp * kSlot16Bytes + lane16, fb1 = rp1 * kSlot16Bytes + lane16;
             if (!live) {
                 issue((kc + kRing16 - 1) % KC, rpi);
@@ -254,7 +212,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
         // ---- tile epilogue: lane holds query (wave*32 + m), rows (r&3) + 8*(r>>2) + 4*h.
         // The copy holds c/|c|, so the accumulator already is the approximate cosine (a zero-norm row is
         // stored as zeros and scores 0: such rows reach finish_kernel through the index's zero-row list).
-        float v[16];
+        f32x16 v;
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = DUAL ? acc[r] + acc1[r] : acc[r];
         if (centred) {  // score = a_q a_c + r_q . r_c; this lane's rows: (r & 3) + 8 (r >> 2) + 4 h
@@ -267,33 +225,14 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
                 for (int e = 0; e < 4; ++e) v[4 * j + e] = __builtin_fmaf(aq, a4[e], v[4 * j + e]);
             }
         }
-        if constexpr (DEAD) {  // removed rows (ScanParams::dead): a score no test passes, and no lower bound for the sample
-            const uint32_t hw = (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u)));  // the tile's half of its 64-row word
-            if (hw) {
-                const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
-        #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if ((lb >> r) & 1u) v[r] = -INFINITY;
-            }
-        }
-        float mx = fmaxf(fmaxf(v[0], v[1]), v[2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, v[r]), v[r + 1]);
-        mx = fmaxf(mx, v[15]);
+        if constexpr (DEAD) v = mask_dead16(v, (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u))), lane, -INFINITY);  // the tile's half of its 64-row word
+        const float mx = max16(v);
         if (MODE == 0) {
-            // sample: only full tiles are sampled (index.hip), so every row is a real row
-            best = fmaxf(best, mx);
+            best = fmaxf(best, mx);  // only full tiles are sampled (index.hip), so every row is a real row
         } else if (__builtin_amdgcn_ballot_w64(mx >= theta) != 0) {
-            // a few percent of the tiles: the lanes that pass store their 16 scores as ONE record
-            // (4 x 16 bytes + the tile index); which rows pass is sorted out by finish_kernel
             if (mx >= theta) {
                 if (cnt < (uint32_t)kRecCap) {
-                    f32x4 *dst = myrec + cnt * 4;
-                    dst[0] = f32x4{v[0], v[1], v[2], v[3]};
-                    dst[1] = f32x4{v[4], v[5], v[6], v[7]};
-                    dst[2] = f32x4{v[8], v[9], v[10], v[11]};
-                    dst[3] = f32x4{v[12], v[13], v[14], v[15]};
-                    mytile[cnt] = t0 + ti * tstep;
+                    store_record(myrec, mytile, cnt, [&] { return t0 + ti * tstep; }, [&](int r) { return v[r]; });
                     ++cnt;
                 } else {
                     ovf = 1;
@@ -306,12 +245,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16_kernel(const ScanParam
 #ifdef MX_SCAN16_CLOCK
     cnt = (uint32_t)(__builtin_amdgcn_s_memtime() - clk0);
 #endif
-    if (MODE == 0) {
-        p.lane_max[(size_t)tid * gridDim.x + blockIdx.x] = best;
-    } else {
-        p.lane_cnt[(size_t)tid * gridDim.x + blockIdx.x] = cnt;
-        if (ovf) p.overflow[wave * 32 + m] = 1;
-    }
+    write_lane<MODE>(p.lane_max, p.lane_cnt, p.overflow, [&] { return (size_t)tid * gridDim.x + blockIdx.x; }, wave * 32 + m, best, cnt, ovf);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -410,47 +344,14 @@ hipError_t launch_shadow(hipStream_t s, const float *x, const float *scale, int 
     return hipGetLastError();
 }
 
-template <int KC, int MODE>
-static hipError_t setup16_one() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16_kernel<KC, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16LdsBytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16_kernel<KC, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16LdsBytes);
-}
+template <int... KC>
+static const ScanEntry kEntries[] = {ScanEntry{KC, {{scan16_kernel<KC, 0, false>, scan16_kernel<KC, 0, true>}, {scan16_kernel<KC, 1, false>, scan16_kernel<KC, 1, true>}}}...};
+static const ScanFamily kFamily(kEntries<1, 2, 3, 4, 5, 6>, kScan16LdsBytes, kScanThreads);
 
-hipError_t scan16_setup() {
-    hipError_t e;
-#define MX_SETUP(KC)                                           \
-    if ((e = setup16_one<KC, 0>()) != hipSuccess) return e;    \
-    if ((e = setup16_one<KC, 1>()) != hipSuccess) return e;
-    MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4) MX_SETUP(5) MX_SETUP(6)
-#undef MX_SETUP
-    return hipSuccess;
-}
-
-template <int KC>
-static hipError_t launch16_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
-    if (p.dead) {
-        if (collect) hipLaunchKernelGGL((scan16_kernel<KC, 1, true>), dim3(nwg), dim3(kScanThreads), kScan16LdsBytes, s, p);
-        else hipLaunchKernelGGL((scan16_kernel<KC, 0, true>), dim3(nwg), dim3(kScanThreads), kScan16LdsBytes, s, p);
-        return hipGetLastError();
-    }
-    if (collect)
-        hipLaunchKernelGGL((scan16_kernel<KC, 1>), dim3(nwg), dim3(kScanThreads), kScan16LdsBytes, s, p);
-    else
-        hipLaunchKernelGGL((scan16_kernel<KC, 0>), dim3(nwg), dim3(kScanThreads), kScan16LdsBytes, s, p);
-    return hipGetLastError();
-}
+hipError_t scan16_setup() { return scan_family_setup(kFamily); }
 
 hipError_t launch_scan16(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p) {
-    switch (kc) {
-        case 1: return launch16_kc<1>(s, collect, nwg, p);
-        case 2: return launch16_kc<2>(s, collect, nwg, p);
-        case 3: return launch16_kc<3>(s, collect, nwg, p);
-        case 4: return launch16_kc<4>(s, collect, nwg, p);
-        case 5: return launch16_kc<5>(s, collect, nwg, p);
-        case 6: return launch16_kc<6>(s, collect, nwg, p);
-        default: return hipErrorInvalidValue;
-    }
+    return scan_family_launch(kFamily, s, kc, collect, nwg, p);
 }
 
 }  // namespace mx

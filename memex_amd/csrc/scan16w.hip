@@ -20,23 +20,12 @@
 // MFMA density is half of scan16_kernel's (one of the two waves of a SIMD multiplies at any time), which
 // at 32 B/clk/CU of stream still outruns HBM: the launch is bound by the DMA stream.  256 queries are two
 // launches (index.hip splits the batch).
-#include <type_traits>
-
-#include "index_kernels.h"
+#include "scan_common.h"
 
 namespace mx {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-#define MX_LDS_DMA16(rsrc, ldsptr, voff, soff, aux) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lds_void *)(ldsptr), 16, (voff), (soff), 0, (aux))
-
 static_assert(kRing16 == 16, "waits below assume a 16-slot ring with 15 slots in flight");
 
-// DEAD: the variant that honours ScanParams::dead (launched only when the index has removed rows)
 template <int KC, int MODE, bool DEAD = false>
 __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanParams p) {
     static_assert(KC % 2 == 0 && KC >= 4, "slot parities need an even slot count per tile");
@@ -62,11 +51,8 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
     }
     const float theta = MODE == 1 ? p.theta[grp * 32 + m] : 0.0f;
 
-    const uint32_t grid = gridDim.x;
-    const uint32_t stride = p.tile_stride;
-    const uint32_t t0 = p.tile_begin + blockIdx.x * stride;
-    const uint32_t tstep = grid * stride;
-    const uint32_t nT = (t0 < p.tile_end) ? (p.tile_end - t0 + tstep - 1) / tstep : 0;
+    const TileSpan span = tile_span(p);
+    const uint32_t t0 = span.t0, tstep = span.tstep, nT = span.nT;
     const uint32_t tilebytes = p.ds * (kTileRows * 2);
 
     const uint32_t lane16 = (uint32_t)lane * 16u;
@@ -85,9 +71,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
         MX_LDS_DMA16(rsrc, dst, lane16, kci * kSlot16Bytes + wave * 1024, 2 /* nt */);  // wave's KiB of the slot: scalar offset
     };
 
-    // records go where scan16_kernel's wave `grp` would put them (only waves 0-3 write any); the addresses
-    // are rebuilt from this one word where a record is stored (a few percent of the tiles): registers are
-    // what this kernel is short of
+    // records go where scan16_kernel's wave `grp` would put them (only waves 0-3 write any)
     auto mylane = [&]() { return (uint32_t)(grp * 64 + (lane16 >> 4)) * gridDim.x + blockIdx.x; };
     uint32_t cnt = 0;  // records written; bit 31: a record did not fit
     float best = -INFINITY;
@@ -96,8 +80,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
     for (int i = 0; i < kRing16 - 1; ++i) issue(i % KC, (uint32_t)i);
 
     bf16x8 a[R];
-    asm volatile("s_waitcnt vmcnt(13)" ::: "memory");  // slots 0 and 1 landed
-    __builtin_amdgcn_s_barrier();
+    wait_slot<13>();  // slots 0 and 1 landed
     {
         const uint32_t fb = (uint32_t)par * kSlot16Bytes + lane16;
 #pragma unroll
@@ -112,24 +95,16 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
         f32x16 acc, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f, acc1[r] = 0.0f;
-        // removed rows (DEAD): the 64-row word of this 32-row tile, one SCALAR load issued with the wait for the tile's first slot
-        // (scan8.hip: a plain load would be a vector load outside the ring's counted vmcnt waits, and the compiler's vmcnt(0)
-        // in front of its use would drain the ring once per tile)
-        uint64_t dw = 0;
+        uint64_t dw = 0;  // removed rows (DEAD): the 64-row word of this 32-row tile
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             const uint32_t rp1 = (rp + 1) & (kRing16 - 1);
             const uint32_t rp2 = (rp + 2) & (kRing16 - 1);
             const uint32_t rpi = (rp + kRing16 - 1) & (kRing16 - 1);
-            if (DEAD && kc == 0) {
-                asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt vmcnt(12)\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)"
-                             : "=s"(dw)
-                             : "s"(p.dead + ((t0 + ti * tstep) >> 1))
-                             : "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
+            if (DEAD && kc == 0)
+                dw = wait_slot_dead<12>(p.dead + ((t0 + ti * tstep) >> 1));
+            else
+                wait_slot<12>();
             if ((kc & 1) == PAR) {
                 const int c = kc >> 1;  // local chunk
                 const uint32_t fb0 = rp * kSlot16Bytes + lane16, fb2 = rp2 * kSlot16Bytes + lane16;
@@ -168,30 +143,15 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[4 * i + j] += o[j];
         }
-        if constexpr (DEAD) {  // removed rows (ScanParams::dead): a score no test passes, and no lower bound for the sample
-            const uint32_t hw = (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u)));  // the tile's half of its 64-row word
-            if (hw) {
-                const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
-        #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if ((lb >> r) & 1u) acc[r] = -INFINITY;
-            }
-        }
-        float mx = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, acc[r]), acc[r + 1]);
-        mx = fmaxf(mx, acc[15]);
+        if constexpr (DEAD) acc = mask_dead16(acc, (uint32_t)(dw >> (32u * ((t0 + ti * tstep) & 1u))), lane, -INFINITY);  // the tile's half of its 64-row word
+        const float mx = max16(acc);
         if (MODE == 0) {
             best = fmaxf(best, mx);
         } else if (__builtin_amdgcn_ballot_w64(mx >= theta) != 0) {
             if (mx >= theta) {
                 if ((cnt & 0x7fffffffu) < (uint32_t)kRecCap) {
-                    f32x4 *dst = reinterpret_cast<f32x4 *>(p.lane_rec + ((size_t)mylane() * kRecCap + (cnt & 0x7fffffffu)) * 16);
-                    dst[0] = f32x4{acc[0], acc[1], acc[2], acc[3]};
-                    dst[1] = f32x4{acc[4], acc[5], acc[6], acc[7]};
-                    dst[2] = f32x4{acc[8], acc[9], acc[10], acc[11]};
-                    dst[3] = f32x4{acc[12], acc[13], acc[14], acc[15]};
-                    p.lane_tile[(size_t)mylane() * kRecCap + (cnt & 0x7fffffffu)] = t0 + ti * tstep;
+                    store_record(p.lane_rec, p.lane_tile, [&] { return (size_t)mylane() * kRecCap + (cnt & 0x7fffffffu); },
+                                 [&] { return t0 + ti * tstep; }, [&](int r) { return acc[r]; });
                     ++cnt;
                 } else {
                     cnt |= 0x80000000u;  // overflow flag
@@ -211,53 +171,18 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan16w_kernel(const ScanPara
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // dead DMA ops must not outlive the workgroup's LDS
 
     if (par) {
-        if (MODE == 0) {
-            p.lane_max[mylane()] = best;
-        } else {
-            p.lane_cnt[mylane()] = cnt & 0x7fffffffu;
-            if (cnt >> 31) p.overflow[grp * 32 + m] = 1;
-        }
+        write_lane<MODE>(p.lane_max, p.lane_cnt, p.overflow, mylane, grp * 32 + m, best, cnt & 0x7fffffffu, cnt >> 31);
     }
 }
 
-template <int KC, int MODE>
-static hipError_t setup16w_one() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16w_kernel<KC, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16WideLdsBytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan16w_kernel<KC, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kScan16WideLdsBytes);
-}
+template <int... KC>
+static const ScanEntry kEntries[] = {ScanEntry{KC, {{scan16w_kernel<KC, 0, false>, scan16w_kernel<KC, 0, true>}, {scan16w_kernel<KC, 1, false>, scan16w_kernel<KC, 1, true>}}}...};
+static const ScanFamily kFamily(kEntries<8, 10, 12>, kScan16WideLdsBytes, kScanThreads);
 
-hipError_t scan16w_setup() {
-    hipError_t e;
-#define MX_SETUP(KC)                                            \
-    if ((e = setup16w_one<KC, 0>()) != hipSuccess) return e;    \
-    if ((e = setup16w_one<KC, 1>()) != hipSuccess) return e;
-    MX_SETUP(8) MX_SETUP(10) MX_SETUP(12)
-#undef MX_SETUP
-    return hipSuccess;
-}
-
-template <int KC>
-static hipError_t launch16w_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
-    if (p.dead) {
-        if (collect) hipLaunchKernelGGL((scan16w_kernel<KC, 1, true>), dim3(nwg), dim3(kScanThreads), kScan16WideLdsBytes, s, p);
-        else hipLaunchKernelGGL((scan16w_kernel<KC, 0, true>), dim3(nwg), dim3(kScanThreads), kScan16WideLdsBytes, s, p);
-        return hipGetLastError();
-    }
-    if (collect)
-        hipLaunchKernelGGL((scan16w_kernel<KC, 1>), dim3(nwg), dim3(kScanThreads), kScan16WideLdsBytes, s, p);
-    else
-        hipLaunchKernelGGL((scan16w_kernel<KC, 0>), dim3(nwg), dim3(kScanThreads), kScan16WideLdsBytes, s, p);
-    return hipGetLastError();
-}
+hipError_t scan16w_setup() { return scan_family_setup(kFamily); }
 
 hipError_t launch_scan16w(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p) {
-    switch (kc) {
-        case 8: return launch16w_kc<8>(s, collect, nwg, p);
-        case 10: return launch16w_kc<10>(s, collect, nwg, p);
-        case 12: return launch16w_kc<12>(s, collect, nwg, p);
-        default: return hipErrorInvalidValue;
-    }
+    return scan_family_launch(kFamily, s, kc, collect, nwg, p);
 }
 
 }  // namespace mx

@@ -38,21 +38,10 @@
 // Tile epilogue, per half: integer max over the lane's 16 sums, one conversion, two multiplications (s_h, s_q),
 // one FMA (theta - qb * e_h), one compare; a passing lane stores its 16 scores as floats -- the record format of
 // scan16_kernel with the 32-row tile index 2T + u, so theta_kernel and finish_kernel do not know which scan ran.
-#include <climits>
-#include <type_traits>
-
-#include "index_kernels.h"
 #include "mx_rotate.h"
+#include "scan_common.h"
 
 namespace mx {
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(16))) int i32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-#define MX_LDS_DMA16(rsrc, ldsptr, voff, soff, aux) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lds_void *)(ldsptr), 16, (voff), (soff), 0, (aux))
 
 // Ablation switch for scripts/scan8_ubench.hip only (0 = production kernel): 1 = tile scales are constants (no LDS read),
 // 2 = every second fragment read dropped
@@ -60,33 +49,14 @@ typedef __attribute__((address_space(3))) void lds_void;
 #define MX_SCAN8_ABLATE 0
 #endif
 
-namespace {
-template <int N>
-using ic = std::integral_constant<int, N>;
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (B < E) {
-        f(ic<B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-// DMA operations a wave has issued after the last one of slot j+1 when it waits for that slot at position kc of a
-// tile: the RING - 3 slots j+2 .. j+RING-2 (13 with the 16-slot ring), DPS operations each (a wave's share of a slot's
-// eight 1-KiB pieces), plus the TOPS per-tile operations of every tile that starts among them (scales; with 8 waves also
-// a_c of the centred copy, issued with num_records = 0 for a plain one: the kernel has one wait schedule)
-template <int KC, int DPS = 1, int TOPS = 2>
-constexpr int ops_after(int lo, int hi) {  // slots lo .. hi relative to the tile start
-    int n = 0;
-    for (int i = lo; i <= hi; ++i) n += DPS + (i % KC == 0 ? TOPS : 0);
-    return n;
-}
+// ops_after<KC, DPS, TOPS>: the per-tile operations are the scales and, with 8 waves, also a_c of the centred copy, issued
+// with num_records = 0 for a plain one: the kernel has one wait schedule.
 // 384 dims (3 slots per tile): after slot j+1 come 13 slots and the per-tile operations of the tiles that start at
 // relative slots 3, 6, 9, 12 (position 0 and 2) or 3 .. 15 (position 1); before the loop, after slot 0: 14 + 2 x 4.
 static_assert(ops_after<3>(2, 14) == 21 && ops_after<3>(3, 15) == 23 && ops_after<3>(4, 16) == 21 && ops_after<3>(1, 14) == 22, "");
 static_assert(ops_after<1>(2, 14) == 39 && ops_after<12>(2, 14) == 15 && ops_after<12>(13, 25) == 15 && ops_after<6>(5, 17) == 17, "");
 // two-workgroup form (8-slot ring, 2 slot operations and 1 per-tile operation per wave): at most 5 x 3 = 15 < 64 (vmcnt)
 static_assert(ops_after<3, 2, 1>(2, 6) == 12 && ops_after<3, 2, 1>(4, 8) == 11 && ops_after<1, 2, 1>(2, 6) == 15, "");
-}  // namespace
 
 // QG = query groups (of 32) per wave: 1 = a pass of 256 queries (the kernel every batch size up to 256 runs);
 // 2 = a pass of 512 (each fragment read feeds two MFMAs; wave w holds the "virtual waves" 2w and 2w+1 of
@@ -96,7 +66,6 @@ static_assert(ops_after<3, 2, 1>(2, 6) == 12 && ops_after<3, 2, 1>(4, 8) == 11 &
 // 4 / 8: the two-workgroup form (Scan8Geom::kPair, two query groups per wave, plain copy only): a wave issues two of a
 // slot's eight 1-KiB pieces and only the scales' per-tile operation; wave w holds the virtual waves 2w and 2w+1, so the
 // lane numbering is the 512-query pass's with twice the workgroups and half the waves
-// DEAD = the variant that honours ScanParams::dead (launched only when the index has removed rows)
 template <int KC, int MODE, int QG, bool CEN, int NW = kScanWaves, int RING = kRing16, bool DEAD = false>
 __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
     static_assert(!CEN || (KC <= kMaxKC && QG == 1), "the centred form exists up to kMaxKC slots with one query group");
@@ -151,11 +120,8 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
     const float kq = CEN && sq[0] > 0.0f ? aq / sq[0] : 0.0f;  // a_q in units of the query's step
 
     // ---- 64-row tiles of this workgroup: tile_begin + (blockIdx + i*grid) * tile_stride
-    const uint32_t grid = gridDim.x;
-    const uint32_t stride = p.tile_stride;
-    const uint32_t t0 = p.tile_begin + blockIdx.x * stride;
-    const uint32_t tstep = grid * stride;
-    const uint32_t nT = (t0 < p.tile_end) ? (p.tile_end - t0 + tstep - 1) / tstep : 0;
+    const TileSpan span = tile_span(p);
+    const uint32_t t0 = span.t0, tstep = span.tstep, nT = span.nT;
     const uint32_t tilebytes = p.ds * (uint32_t)kTile8Rows;
     const uint32_t lane16 = (uint32_t)lane * 16u;
     const uint32_t lane4 = (uint32_t)lane * 4u;
@@ -216,8 +182,7 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
     for (int i = 0; i < RING - 1; ++i) issue(i % KC, (uint32_t)i);
 
     i32x4 a[R];
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC, DPS, TOPS>(1, RING - 2)) : "memory");  // slot 0 (and its tile's scales) landed
-    __builtin_amdgcn_s_barrier();
+    wait_slot<ops_after<KC, DPS, TOPS>(1, RING - 2)>();  // slot 0 (and its tile's scales) landed
 #pragma unroll
     for (int f = 0; f < R; ++f) a[f] = *reinterpret_cast<const i32x4 *>(smem + lane16 + f * 1024);
 
@@ -258,9 +223,7 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
 #pragma unroll 1
     for (uint32_t ti = 0; ti < nT; ++ti) {
         const uint32_t tile = t0 + ti * tstep;
-        // removed rows of the tile (DEAD): one SCALAR load, issued with the wait for the tile's first slot below.  (A plain load of
-        // p.dead[tile] becomes a vector load: one more operation on vmcnt that the hand-counted waits of the ring do not know about.)
-        uint64_t dw = 0;
+        uint64_t dw = 0;  // removed rows (DEAD): the word of this 64-row tile
         if constexpr (!CEN) {
 #pragma unroll
             for (int g = 0; g < QG * 2; ++g)
@@ -272,18 +235,12 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
             constexpr int kc = decltype(kct)::value;
             const uint32_t rp1 = (rp + 1) & (RING - 1);
             const uint32_t rpi = (rp + RING - 1) & (RING - 1);
-            // slot j+1 landed (the ring reads ahead into it): everything issued after it may still be in flight
-            if constexpr (DEAD && kc == 0) {
-                // the dead-row word of the tile: its latency hides under the slot wait and the barrier; lgkmcnt(0) behind them, in the same
-                // statement, so that no LDS wait the compiler counts runs while it is in flight
-                asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt vmcnt(%2)\n\ts_barrier\n\ts_waitcnt lgkmcnt(0)"
-                             : "=s"(dw)
-                             : "s"(p.dead + tile), "n"(ops_after<KC, DPS, TOPS>(kc + 2, kc + RING - 2))
-                             : "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ops_after<KC, DPS, TOPS>(kc + 2, kc + RING - 2)) : "memory");
-                __builtin_amdgcn_s_barrier();  // ... for every wave of the workgroup; slot j-1 is free for slot j+RING-1
-            }
+            // slot j+1 landed (the ring reads ahead into it): everything issued after it may still be in flight; slot j-1 is free for slot j+RING-1
+            constexpr int vm = ops_after<KC, DPS, TOPS>(kc + 2, kc + RING - 2);
+            if constexpr (DEAD && kc == 0)
+                dw = wait_slot_dead<vm>(p.dead + tile);
+            else
+                wait_slot<vm>();
             const uint32_t fb0 = rp * kSlot16Bytes + lane16, fb1 = rp1 * kSlot16Bytes + lane16;
             if (live) {
                 static_for<0, 8>([&](auto ft) __attribute__((always_inline)) {
@@ -336,19 +293,9 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
             for (int u = 0; u < 2; ++u) {
                 i32x16 &ac = acc[g * 2 + u];
                 const float sh = u ? shs[1] : shs[0], er = u ? shs[3] : shs[2];
-                if constexpr (DEAD) {  // removed rows: the smallest sum (no live row comes near it), then a score no test passes
-                    const uint32_t hw = (uint32_t)(dw >> (32 * u));
-                    if (hw) {
-                        const uint32_t lb = lane_dead16(hw, (uint32_t)lane >> 5);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            if ((lb >> r) & 1u) ac[r] = INT_MIN;
-                    }
-                }
-                int mxi = max(max(ac[0], ac[1]), ac[2]);
-#pragma unroll
-                for (int r = 3; r < 15; r += 2) mxi = max(max(mxi, ac[r]), ac[r + 1]);
-                mxi = max(mxi, ac[15]);
+                // removed rows: the smallest sum (no live row comes near it), then a score no test passes
+                if constexpr (DEAD) ac = mask_dead16(ac, (uint32_t)(dw >> (32 * u)), lane, INT_MIN);
+                const int mxi = max16(ac);
                 // score of a sum: ((float)sum * s_h) * s_q -- monotone in the sum, so the test on the maximum is the
                 // test on "any of the 16 scores" as finish_kernel will see them
                 float mx = ((float)mxi * sh) * sq[g];
@@ -359,13 +306,9 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
                 } else if (__builtin_amdgcn_ballot_w64(mx >= thr) != 0) {
                     if (mx >= thr) {
                         if ((cnt[g] & 0x7fffffffu) < (uint32_t)kRecCap) {
-                            const size_t at = (size_t)mylane(g) * kRecCap + (cnt[g] & 0x7fffffffu);
-                            f32x4 *dst = reinterpret_cast<f32x4 *>(p.lane_rec + at * 16);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i)
-                                dst[i] = f32x4{((float)ac[4 * i] * sh) * sq[g], ((float)ac[4 * i + 1] * sh) * sq[g],
-                                               ((float)ac[4 * i + 2] * sh) * sq[g], ((float)ac[4 * i + 3] * sh) * sq[g]};
-                            p.lane_tile[at] = 2 * tile + u;  // 32-row tile index, as finish_kernel counts them
+                            store_record(p.lane_rec, p.lane_tile, (size_t)mylane(g) * kRecCap + (cnt[g] & 0x7fffffffu),
+                                         [&] { return 2 * tile + u; },  // 32-row tile index, as finish_kernel counts them
+                                         [&](int r) { return ((float)ac[r] * sh) * sq[g]; });
                             ++cnt[g];
                         } else {
                             cnt[g] |= 0x80000000u;
@@ -388,12 +331,7 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
 
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
-        if (MODE == 0) {
-            p.lane_max[mylane(g)] = best[g];
-        } else {
-            p.lane_cnt[mylane(g)] = cnt[g] & 0x7fffffffu;
-            if (cnt[g] >> 31) p.overflow[(wave * QG + g) * 32 + m] = 1;
-        }
+        write_lane<MODE>(p.lane_max, p.lane_cnt, p.overflow, [&] { return mylane(g); }, (wave * QG + g) * 32 + m, best[g], cnt[g] & 0x7fffffffu, cnt[g] >> 31);
     }
 }
 
@@ -535,129 +473,35 @@ hipError_t launch_shadow8(hipStream_t s, const float *x, const float *scale, int
     return hipGetLastError();
 }
 
-template <int KC, int MODE, int QG, bool CEN = false>
-static hipError_t setup8_one() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, QG, CEN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScan8LdsBytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, QG, CEN, kScanWaves, kRing16, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kScan8LdsBytes);
-}
-template <int KC, int MODE>
-static hipError_t setup8_pair() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, 2, false, kScan8PairWaves, kScan8PairRing>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScan8PairLdsBytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<KC, MODE, 2, false, kScan8PairWaves, kScan8PairRing, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kScan8PairLdsBytes);
-}
+// The four families of scan8_kernel, in Scan8Family order; every one has its four MODE / DEAD instances per slot count.
+template <int QG, bool CEN, int NW, int RING, int... KC>
+static const ScanEntry kEntries[] = {ScanEntry{KC, {{scan8_kernel<KC, 0, QG, CEN, NW, RING, false>, scan8_kernel<KC, 0, QG, CEN, NW, RING, true>},
+                                                    {scan8_kernel<KC, 1, QG, CEN, NW, RING, false>, scan8_kernel<KC, 1, QG, CEN, NW, RING, true>}}}...};
+enum Scan8Family { kPlain, kTwoGroups, kPairForm, kCentred };
+static const ScanFamily kFamilies[] = {
+    // Scan8Geom::k256, plain copy: every width
+    {kEntries<1, false, kScanWaves, kRing16, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>, kScan8LdsBytes, kScanThreads},
+    // Scan8Geom::k512, 512 queries per pass: up to 512 dims (kMaxKC8x2)
+    {kEntries<2, false, kScanWaves, kRing16, 1, 2, 3, 4>, kScan8LdsBytes, kScanThreads},
+    // Scan8Geom::kPair, 256 queries on two 4-wave workgroups per CU: up to 512 dims (kMaxKC8x2)
+    {kEntries<2, false, kScan8PairWaves, kScan8PairRing, 1, 2, 3, 4>, kScan8PairLdsBytes, kScan8PairWaves * 64},
+    // Scan8Geom::k256, centred copy: one query group, up to kMaxKC slots (index.hip builds no other)
+    {kEntries<1, true, kScanWaves, kRing16, 1, 2, 3, 4, 5, 6>, kScan8LdsBytes, kScanThreads},
+};
+static_assert(kMaxKC8x2 == 4 && kMaxKC == 6 && kMaxKC16 == 12, "the slot counts listed above");
 
 hipError_t scan8_setup() {
-    hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(&shadow8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)shadow8_lds(kMaxKC16 * kChunkFloats))) != hipSuccess)
-        return e;
-#define MX_SETUP(KC)                                             \
-    if ((e = setup8_one<KC, 0, 1>()) != hipSuccess) return e;    \
-    if ((e = setup8_one<KC, 1, 1>()) != hipSuccess) return e;
-    MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4) MX_SETUP(5) MX_SETUP(6)
-    MX_SETUP(7) MX_SETUP(8) MX_SETUP(9) MX_SETUP(10) MX_SETUP(11) MX_SETUP(12)
-#undef MX_SETUP
-#define MX_SETUP(KC)                                             \
-    if ((e = setup8_one<KC, 0, 2>()) != hipSuccess) return e;    \
-    if ((e = setup8_one<KC, 1, 2>()) != hipSuccess) return e;
-    MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4)
-#undef MX_SETUP
-#define MX_SETUP(KC)                                             \
-    if ((e = setup8_pair<KC, 0>()) != hipSuccess) return e;      \
-    if ((e = setup8_pair<KC, 1>()) != hipSuccess) return e;
-    MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4)  // the two-workgroup form
-#undef MX_SETUP
-#define MX_SETUP(KC)                                                   \
-    if ((e = setup8_one<KC, 0, 1, true>()) != hipSuccess) return e;    \
-    if ((e = setup8_one<KC, 1, 1, true>()) != hipSuccess) return e;
-    MX_SETUP(1) MX_SETUP(2) MX_SETUP(3) MX_SETUP(4) MX_SETUP(5) MX_SETUP(6)  // the centred forms: up to kMaxKC slots
-#undef MX_SETUP
-    static_assert(kMaxKC == 6, "one centred scan8_kernel per slot count up to kMaxKC");
-    return hipSuccess;
-}
-
-template <int KC, int QG, bool CEN = false>
-static hipError_t launch8_kc(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
-    if (p.dead) {
-        if (collect) hipLaunchKernelGGL((scan8_kernel<KC, 1, QG, CEN, kScanWaves, kRing16, true>), dim3(nwg), dim3(kScanThreads), kScan8LdsBytes, s, p);
-        else hipLaunchKernelGGL((scan8_kernel<KC, 0, QG, CEN, kScanWaves, kRing16, true>), dim3(nwg), dim3(kScanThreads), kScan8LdsBytes, s, p);
-        return hipGetLastError();
-    }
-    if (collect)
-        hipLaunchKernelGGL((scan8_kernel<KC, 1, QG, CEN>), dim3(nwg), dim3(kScanThreads), kScan8LdsBytes, s, p);
-    else
-        hipLaunchKernelGGL((scan8_kernel<KC, 0, QG, CEN>), dim3(nwg), dim3(kScanThreads), kScan8LdsBytes, s, p);
-    return hipGetLastError();
-}
-
-template <int KC>
-static hipError_t launch8_pair(hipStream_t s, bool collect, int nwg, const ScanParams &p) {
-    constexpr int NW = kScan8PairWaves, RING = kScan8PairRing;
-    if (p.dead) {
-        if (collect) hipLaunchKernelGGL((scan8_kernel<KC, 1, 2, false, NW, RING, true>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
-        else hipLaunchKernelGGL((scan8_kernel<KC, 0, 2, false, NW, RING, true>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
-        return hipGetLastError();
-    }
-    if (collect)
-        hipLaunchKernelGGL((scan8_kernel<KC, 1, 2, false, NW, RING>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
-    else
-        hipLaunchKernelGGL((scan8_kernel<KC, 0, 2, false, NW, RING>), dim3(nwg), dim3(NW * 64), kScan8PairLdsBytes, s, p);
-    return hipGetLastError();
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&shadow8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)shadow8_lds(kMaxKC16 * kChunkFloats));
+    for (const ScanFamily &f : kFamilies)
+        if (e == hipSuccess) e = scan_family_setup(f);
+    return e;
 }
 
 hipError_t launch_scan8(hipStream_t s, int kc, bool collect, int nwg, const ScanParams &p, Scan8Geom geom) {
-    if (geom == Scan8Geom::kPair) {  // 256 queries, two 4-wave workgroups per CU: up to 512 dims (kMaxKC8x2), plain copy
-        if (p.amean) return hipErrorInvalidValue;
-        switch (kc) {
-            case 1: return launch8_pair<1>(s, collect, nwg, p);
-            case 2: return launch8_pair<2>(s, collect, nwg, p);
-            case 3: return launch8_pair<3>(s, collect, nwg, p);
-            case 4: return launch8_pair<4>(s, collect, nwg, p);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    if (geom == Scan8Geom::k512) {  // 512 queries per pass: up to 512 dims (kMaxKC8x2)
-        if (p.amean) return hipErrorInvalidValue;
-        switch (kc) {
-            case 1: return launch8_kc<1, 2>(s, collect, nwg, p);
-            case 2: return launch8_kc<2, 2>(s, collect, nwg, p);
-            case 3: return launch8_kc<3, 2>(s, collect, nwg, p);
-            case 4: return launch8_kc<4, 2>(s, collect, nwg, p);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    if (p.amean) {  // centred copy: one query group, up to kMaxKC slots (index.hip builds no other)
-        switch (kc) {
-            case 1: return launch8_kc<1, 1, true>(s, collect, nwg, p);
-            case 2: return launch8_kc<2, 1, true>(s, collect, nwg, p);
-            case 3: return launch8_kc<3, 1, true>(s, collect, nwg, p);
-            case 4: return launch8_kc<4, 1, true>(s, collect, nwg, p);
-            case 5: return launch8_kc<5, 1, true>(s, collect, nwg, p);
-            case 6: return launch8_kc<6, 1, true>(s, collect, nwg, p);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (kc) {
-        case 1: return launch8_kc<1, 1>(s, collect, nwg, p);
-        case 2: return launch8_kc<2, 1>(s, collect, nwg, p);
-        case 3: return launch8_kc<3, 1>(s, collect, nwg, p);
-        case 4: return launch8_kc<4, 1>(s, collect, nwg, p);
-        case 5: return launch8_kc<5, 1>(s, collect, nwg, p);
-        case 6: return launch8_kc<6, 1>(s, collect, nwg, p);
-        case 7: return launch8_kc<7, 1>(s, collect, nwg, p);
-        case 8: return launch8_kc<8, 1>(s, collect, nwg, p);
-        case 9: return launch8_kc<9, 1>(s, collect, nwg, p);
-        case 10: return launch8_kc<10, 1>(s, collect, nwg, p);
-        case 11: return launch8_kc<11, 1>(s, collect, nwg, p);
-        case 12: return launch8_kc<12, 1>(s, collect, nwg, p);
-        default: return hipErrorInvalidValue;
-    }
+    if (geom != Scan8Geom::k256 && p.amean) return hipErrorInvalidValue;  // two query groups per wave: plain copy only
+    const Scan8Family f = geom == Scan8Geom::kPair ? kPairForm : geom == Scan8Geom::k512 ? kTwoGroups : p.amean ? kCentred : kPlain;
+    return scan_family_launch(kFamilies[f], s, kc, collect, nwg, p);
 }
 
 }  // namespace mx
