@@ -28,6 +28,9 @@
  *   MEMEX_HIP_RCCL_TIMEOUT=s    deadline of ncclCommInitAll and of the communicator self-test (30)
  *   MEMEX_HIP_SHARD_THREADS=0|1 per-shard helper threads never / also for logical shards on one device
  *   MEMEX_HIP_FILTER=i8|bf16    pins the filter copy of every index opened afterwards (mx_index_set_filter_copy)
+ *   MEMEX_HIP_EXACT_THETA=0     indexes opened afterwards keep the int8 scan's collect threshold from the sample's lane maxima
+ *                               alone, without rescoring the sample's best rows, and the larger sample that goes with it (A/B
+ *                               runs; results do not depend on it)
  *   MEMEX_HIP_DEBUG=key=v,...   which of two equivalent kernel forms runs (parity tests; keys in
  *                               memex_amd/csrc/mx_debug.h).  Results do not depend on it beyond the bounds
  *                               stated there (bit-identical forms, or different f32 summation orders).

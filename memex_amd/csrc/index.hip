@@ -87,6 +87,7 @@ struct Scratch {
     uint32_t *lane_tile = nullptr;
     uint32_t *lane_cnt = nullptr;
     float *lane_max = nullptr;
+    uint32_t *lane_arg = nullptr;    // the row behind each lane maximum (sample launch of the plain int8 copy)
     float *qstage = nullptr;       // [256, dim] host->device query staging
     float *qscale = nullptr;       // [256] quantisation step of each query (8-bit filter copy)
     float *qa = nullptr, *qb = nullptr;  // [256] a row's filter-score bound is qa + qb * residual (launch_prep_queries)
@@ -122,6 +123,7 @@ struct LaneBufs {
     float *rec = nullptr;
     uint32_t *tile = nullptr, *cnt = nullptr;
     float *max = nullptr;
+    uint32_t *arg = nullptr;  // ScanParams::lane_arg, sized like max
     int nwg = 0;
     int groups = 1;  // query groups per wave the set is sized for (2: a 512-query pass, or the int8 scan's two-workgroup form:
                      // twice the workgroups with half the waves, the same 1024 lanes per CU)
@@ -139,6 +141,7 @@ void lane_free(LaneBufs &b) {
     if (b.tile) (void)hipFree(b.tile);
     if (b.cnt) (void)hipFree(b.cnt);
     if (b.max) (void)hipFree(b.max);
+    if (b.arg) (void)hipFree(b.arg);
     b = LaneBufs{};
 }
 
@@ -229,6 +232,11 @@ struct mx_index {
     bool profiling = false;
     int n_cu = 0, nwg = 0;       // nwg: workgroups of the one-per-CU scans (min(CUs, kMaxScanCUs))
     bool scan8_pair = true;      // plain int8 copy, 129-256 queries: the two-workgroup form (Scan8Geom::kPair, 2 x nwg workgroups)
+    bool exact_theta = true;     // plain int8 copy: the collect threshold also from exact scores of the sample's best rows (launch_theta's
+                                 // ThetaExact), and the smaller sample that threshold allows; MEMEX_HIP_EXACT_THETA=0: neither
+    int sample_div = 0;          // MEMEX_HIP_DEBUG=sample_div=N as it stood when the index was created (0: the built-in sample sizes)
+    uint64_t crowded_at_rows = 0;  // rows the index held when a crowded f32 stage last had its plain int8 copy rebuilt (search_batch); 0: never
+    bool print_records = false;  // MEMEX_HIP_DEBUG=records=1 (at creation): every batch prints the records of its first collect launch to stderr
     Scratch s;
     mx_index_stats stats{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wait = nullptr;
@@ -451,6 +459,7 @@ struct LaneLease {
             if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.tile), lanes * kRecCap * sizeof(uint32_t));
             if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.cnt), lanes * sizeof(uint32_t));
             if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.max), lanes * sizeof(float));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.arg), lanes * sizeof(uint32_t));
             if (e != hipSuccess) {
                 lane_free(b);
                 idx = nullptr;
@@ -462,6 +471,7 @@ struct LaneLease {
         s.lane_tile = b.tile;
         s.lane_cnt = b.cnt;
         s.lane_max = b.max;
+        s.lane_arg = b.arg;
         return MX_OK;
     }
     void drop() {  // the caller is host-synchronised with everything that used the buffers
@@ -471,6 +481,7 @@ struct LaneLease {
         s.lane_tile = nullptr;
         s.lane_cnt = nullptr;
         s.lane_max = nullptr;
+        s.lane_arg = nullptr;
         LanePool &lp = g_lanes[idx->device];
         std::lock_guard<std::mutex> lk(lp.mu);
         if (lp.open_indexes > 0) lp.idle.push_back(b);
@@ -834,10 +845,11 @@ int add_device_locked(mx_index *idx, const float *d_rows, uint64_t n, uint64_t *
     return MX_OK;
 }
 
+constexpr double kExactThetaDiv = 32.0;  // sample of the plain int8 copy up to 512 dims when theta_kernel rescores its best rows (below)
 // how many tiles the sample launch visits: enough that the k-th largest of 2*nwg lane maxima is a
 // useful threshold (expected survivors of the collect launch ~ k * N / sample, times the margin's
 // share) and small enough to stay a few percent of the pass
-uint32_t sample_stride(uint64_t full_tiles, int nwg, int k, bool filt8, int ds, bool centred8 = false) {
+uint32_t sample_stride(uint64_t full_tiles, int nwg, int k, bool filt8, int ds, bool exact_theta, int debug_div) {
     // 1/64 of the tiles for k <= 10.  Measured at 10M x 384 (B = 256): the sample launch costs 65 / 38 / 24 /
     // 17 us at 1/32, 1/64, 1/128, 1/256; a weaker threshold means more records for finish_kernel to sift
     // (62 / 63 / 72 us, and at 1/256 lanes start to overflow their 32 records), while the collect launch
@@ -849,9 +861,12 @@ uint32_t sample_stride(uint64_t full_tiles, int nwg, int k, bool filt8, int ds, 
     // (MEMEX_HIP_DEBUG=sample_div=N tries others: a tuning knob, results do not depend on it.)
     // (a centred int8 copy, whose certificate is four to five times tighter again, gains nothing from a smaller sample: 1/32 against
     // 1/16 on the enc_like leg 169.3k against 169.0k queries/s; at 1/64 lanes overflow and the copy is demoted: gpurun_out/r6m_*)
-    (void)centred8;
-    double div = !filt8 ? 64.0 : ds <= 512 ? 16.0 : ds <= 768 ? 8.0 : 4.0;
-    if (const int dv = debug_flag("sample_div", 0); dv >= 2 && dv <= 4096) div = (double)dv;
+    // The plain int8 copy with the exact threshold (launch_theta's ThetaExact: the best sampled rows rescored in f32, so the threshold no
+    // longer carries the a-priori bracket): 1/32 of the tiles up to 512 dims.  10M x 384, B = 256, k = 10, queries/s at 1/16 | 1/32 |
+    // 1/64 (and 1/16 without the exact threshold): Gaussian 244.2k | 249.6k | 245.3k (236.1k), clustered 241.1k | 248.6k | 247.6k
+    // (243.4k), anisotropic 247.9k | 248.7k | 246.2k (233.1k); no retry query in any of them (profiles/exact_theta_sample_sweep.txt).
+    double div = !filt8 ? 64.0 : ds <= 512 ? (exact_theta ? kExactThetaDiv : 16.0) : ds <= 768 ? 8.0 : 4.0;
+    if (debug_div >= 2 && debug_div <= 4096) div = (double)debug_div;  // mx_index::sample_div
     // larger k: the sample grows like k / 640 for every copy (int8 at k = 30 / 100: 1.33 / 1.56 ms per step with
     // 1/16 / 0.16 of the tiles against 1.93 / 1.77 with three and ten times the k = 10 sample)
     const double f = std::min(0.5, std::max(1.0 / div, (double)k / 640.0));
@@ -1203,6 +1218,10 @@ int prep_queries(mx_index *idx, const BatchPlan &pl, const float *d_q, int B) {
     return MX_OK;
 }
 
+// the plain int8 copy of an f32 corpus, unless switched off: the sample launch names the rows behind its lane maxima and theta_kernel
+// rescores the best of them (every geometry of scan8_kernel; the centred copy keeps the lane maxima alone)
+bool exact_theta_for(const mx_index *idx, const BatchPlan &pl) { return idx->exact_theta && pl.filt8 && !pl.centred8 && idx->x != nullptr; }
+
 // everything of a scan launch but its tiles (tile_begin / tile_end / tile_stride: the caller's, per launch); mask: ScanParams::dead
 void fill_scan_params(ScanParams &p, const mx_index *idx, const BatchPlan &pl, int B, const uint64_t *mask) {
     const Scratch &s = idx->s;
@@ -1218,6 +1237,7 @@ void fill_scan_params(ScanParams &p, const mx_index *idx, const BatchPlan &pl, i
     p.lane_tile = s.lane_tile;
     p.lane_cnt = s.lane_cnt;
     p.lane_max = s.lane_max;
+    p.lane_arg = exact_theta_for(idx, pl) ? s.lane_arg : nullptr;
     p.overflow = s.overflow;
     p.tscale = idx->tsc;
     p.qscale = s.qscale;
@@ -1382,6 +1402,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     if ((rc = lease.take(idx, pl.lanes)) != MX_OK) return rc;
     if ((rc = prep_queries(idx, pl, d_q, B)) != MX_OK) return rc;
     bool timed = false;
+    bool crowded = false;  // the plain int8 copy sent too many rows to the f32 stage (below)
 
     FinishParams fp;
     fill_finish_params(fp, idx, pl, B, k, mask, n_live, d_ids, d_scores, d_dists, d_nfound);
@@ -1430,12 +1451,21 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         if (ts1 - ts0 > 2ull * idx->nwg) {
             p.tile_begin = (uint32_t)ts0;
             p.tile_end = (uint32_t)full1;
-            p.tile_stride = sample_stride(full1 - ts0, pl.nwg, k, pl.filt8, idx->ds, pl.centred8);
+            const bool exact_theta = exact_theta_for(idx, pl);
+            p.tile_stride = sample_stride(full1 - ts0, pl.nwg, k, pl.filt8, idx->ds, exact_theta, idx->sample_div);
             MX_HIP(launch_scan_for(idx, pl, false, p));
-            MX_HIP(launch_theta(st, B, k, pl.nwg, s.lane_max, s.qa, !pl.filt8, s.theta));
+            const ThetaExact tx{s.lane_arg, idx->x, idx->scale, s.qpad, s.qnorm2, idx->n, idx->ds, fp.e2};
+            MX_HIP(launch_theta(st, B, k, pl.nwg, s.lane_max, s.qa, !pl.filt8, s.theta, exact_theta ? &tx : nullptr));
         }
         if ((rc = collect(true)) != MX_OK) return rc;
         if ((rc = finish_and_wait()) != MX_OK) return rc;
+        if (idx->print_records) {  // measurement only: what the collect launch wrote, summed over the lanes (the stats do not carry it)
+            std::vector<uint32_t> cnt((size_t)pl.nwg * kScanThreads * (pl.x2 ? 2 : 1));
+            MX_HIP(hipMemcpy(cnt.data(), s.lane_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            uint64_t rec = 0;
+            for (const uint32_t c : cnt) rec += std::min<uint32_t>(c, (uint32_t)kRecCap);
+            fprintf(stderr, "memex_hip: collect records %llu queries %d\n", (unsigned long long)rec, B);
+        }
         if (timed) {
             float ms = 0.f;
             MX_HIP(hipEventElapsedTime(&ms, idx->ev0, idx->ev1));
@@ -1444,6 +1474,13 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         }
         if (s.host_sum[2]) return fail(MX_EINVAL, "a query contains non-finite values");
         idx->stats.candidates += s.host_sum[1];
+        // The exact threshold keeps a plain int8 copy from overflowing on corpora whose certificate is nevertheless too wide: a cone
+        // with cosines spread by 0.012 used to overflow finish_kernel's candidate list and was rebuilt centred for it (below); now it
+        // fits, and 3000 rows per query reach the f32 stage where the centred copy sends 130.  So an automatic plain copy is also
+        // rebuilt centred when a batch that fitted rescored more than 64 (k + 6) rows per query in f32 (four times the headline's
+        // 250 at k = 10, twice the clustered and anisotropic corpora's 500) -- once per doubling of the index, after the batch is answered.
+        crowded = !s.host_sum[0] && !filt && idx->filter_auto && exact_theta_for(idx, pl) && !idx->centred && idx->kc <= kMaxKC &&
+                  idx->n >= 256 && idx->n >= 2 * idx->crowded_at_rows && (uint64_t)s.host_sum[1] > (uint64_t)B * 64u * (uint64_t)(k + 6);
         if (s.host_sum[0]) {
             if ((rc = fetch_flags(idx)) != MX_OK) return rc;
             int retry = 0;
@@ -1515,6 +1552,12 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     idx->stats.queries += (uint64_t)B;
     if (filt) idx->stats.filtered_queries += (uint64_t)B;
     if (pl.filt8 && pl.fast && !filt) idx->i8_batches += 1;
+    if (crowded) {  // (the batch is answered; a corpus without a cone gets its plain copy back, and no second try until it has doubled)
+        idx->crowded_at_rows = idx->n;
+        const std::string keep = last_error_slot();
+        lease.drop();
+        if (build_filter_copy(idx, true) != MX_OK) last_error_slot() = keep;
+    }
     return MX_OK;
 }
 
@@ -2711,6 +2754,12 @@ int open_plain(const std::string &k, int dim, int device, mx_index **out) {
         const char *pv = getenv("MEMEX_HIP_SCAN8_PAIR");
         idx->scan8_pair = !(pv && pv[0] == '0');
     }
+    {   // MEMEX_HIP_EXACT_THETA=0: the int8 collect threshold from the lane maxima alone, and the sample size that goes with it (A/B runs)
+        const char *pv = getenv("MEMEX_HIP_EXACT_THETA");
+        idx->exact_theta = !(pv && pv[0] == '0');
+    }
+    idx->sample_div = debug_flag("sample_div", 0);  // read here, not per batch: debug_flag costs a getenv, a mutex and a string compare
+    idx->print_records = debug_flag("records", 0) != 0;
     MX_HIP(hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking));
     MX_HIP(hipEventCreate(&idx->ev0));
     MX_HIP(hipEventCreate(&idx->ev1));
@@ -2959,6 +3008,9 @@ int compact_composite(mx_index *idx) {
         sh->mode = old->mode;
         sh->profiling = old->profiling;
         sh->scan8_pair = old->scan8_pair;
+        sh->exact_theta = old->exact_theta;
+        sh->sample_div = old->sample_div;
+        sh->print_records = old->print_records;
         sh->want_filter = old->want_filter;
         sh->filter_i8 = old->filter_i8;
         sh->filter_auto = old->filter_auto;

@@ -105,7 +105,11 @@ struct ScanParams {
     // removed rows (mx_index_remove): bit j of dead[t] = row 64t + j.  null: nothing removed, and the launchers run the kernels
     // without the mask; otherwise the masked variants score a removed row so low that it passes no test
     const uint64_t *dead = nullptr;  // [cap_rows / 64]
+    // sample launch of the plain int8 copy: the row that gave each lane its maximum, laid out like lane_max (kNoRow: the lane saw
+    // no row); theta_kernel rescores the best of them exactly.  null: not wanted
+    uint32_t *lane_arg = nullptr;    // [512][nwg]
 };
+constexpr uint32_t kNoRow = 0xffffffffu;  // ScanParams::lane_arg of a lane without a row
 
 // The 16 rows an MFMA lane holds of a 32-row half tile are (r & 3) + 8 (r >> 2) + 4h (h = lane >> 5): bit r of the result is
 // bit (r & 3) + 8 (r >> 2) + 4h of `half`, the half tile's 32 dead-row bits
@@ -208,7 +212,20 @@ hipError_t launch_prep_queries(hipStream_t s, const float *q, int B, int d, int 
 // theta[q] = (k-th largest of query q's lane maxima) - 2*e1[q]
 // raw: the lane maxima are plain scores (theta = k-th - 2 * qa); otherwise they are lower bounds of cosines already
 // (scan8_kernel: theta = k-th - qa)
-hipError_t launch_theta(hipStream_t s, int B, int k, int nwg, const float *lane_max, const float *qa, bool raw, float *theta);
+// ex (with a lane_arg; the plain int8 copy, raw = false): theta = max(that, L' - qa), L' = the k-th largest s2 - e2 over the rows behind
+// the max(32, 2k + 12) largest lane maxima, rescored in f32 like finish_kernel's stage 2.  null, or no lane_arg: the kernel above alone
+struct ThetaExact {
+    const uint32_t *lane_arg;  // [lanes] like lane_max: the row of each lane maximum (ScanParams::lane_arg), kNoRow for none
+    const float *x;            // [cap_rows, ds] f32 rows
+    const float *scale;        // [cap_rows] 1/|c| (0: a row without a norm, which is left out)
+    const float *qpad;         // [256, ds] raw queries
+    const double *qnorm2;      // [256]
+    uint64_t n_rows;
+    int ds;
+    float e2;                  // FinishParams::e2
+};
+hipError_t launch_theta(hipStream_t s, int B, int k, int nwg, const float *lane_max, const float *qa, bool raw, float *theta,
+                        const ThetaExact *ex = nullptr);
 
 // per query: gather the collect launch's lane buffers -> keep [kth approx - 2*e1, inf) -> f32
 // rescoring (error e2) -> keep [kth - 2*e2, inf) -> exact DistCosine -> order by (dist, id) -> emit.

@@ -451,19 +451,34 @@ hipError_t launch_mean_dir(hipStream_t s, const float *x, const float *scale, ui
 // k-th best cosine, a row of the top-k has score + (qa + qb * residual) >= L_k, and the scan tests
 // score >= theta - qb * residual with theta = L_k - qa.  `raw` = 1: lane maxima are plain scores, theta = a_k - 2*qa
 // (qa = e1 there).
+// Exact form (ThetaExact in index_kernels.h, the plain int8 copy: DESIGN.md section 3.1): the sample launch also left the ROW
+// behind every lane maximum (lane_arg).  The C = min(lanes, max(32, 2k + 12)) lanes with the largest maxima name C distinct stored rows; they are rescored in f32
+// against the raw query with the arithmetic and the bound e2 of finish_kernel's stage 2 (one wave per row, eight rows in flight), rows
+// without a norm and lanes without a row left out.  L' = the k-th largest s2 - e2 (-inf when fewer than k rows were rescored) is a lower
+// bound of the k-th best cosine that does not carry the scan's a-priori bracket qa + qb * residual, and so is max(L_k, L'):
+// theta = max(L_k - qa, L' - qa).  Both terms are certified thresholds, so the collect launch's records are a subset of those under
+// L_k - qa alone.
+constexpr int kThetaMaxC = 2 * 256 + 12;  // C at the largest k of the scan pipeline
+constexpr int kThetaRows = 8;             // rows a wave rescores together
+
 // PER values per thread: 2 up to 256 workgroups, 4 up to 512 (the int8 scan's two-workgroup form)
-template <int PER>
-__global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float *__restrict__ lane_max,
-                                                    const float *__restrict__ qa, int raw, float *__restrict__ theta) {
+template <int PER, bool EXACT>
+__device__ __forceinline__ void theta_query(int k, int nwg, const float *__restrict__ lane_max, const float *__restrict__ qa, int raw,
+                                            float *__restrict__ theta, const ThetaExact &x) {
     __shared__ uint32_t s_hist[256];
     __shared__ uint32_t s_pick[2];
     __shared__ uint32_t s_nvalid[4];
+    __shared__ uint32_t s_crow[EXACT ? kThetaMaxC : 1];  // rows of the C best lanes, then (as float bits) their s2 - e2
+    __shared__ uint32_t s_ckey[EXACT ? kThetaMaxC : 1];  // ... and their lane maxima (keys)
+    __shared__ uint32_t s_cn, s_kth;
+    __shared__ float s_lp;
     const int q = blockIdx.x;
     const int tid = threadIdx.x;
     const int n = 2 * nwg;  // <= 256 * PER
     const uint32_t t0 = (uint32_t)(q >> 5) * 64 + (uint32_t)(q & 31);
-    uint32_t key[PER];
+    uint32_t key[PER], arg[EXACT ? PER : 1];
     bool valid[PER];
+    if (EXACT && tid == 0) s_cn = 0, s_lp = -INFINITY;
 #pragma unroll
     for (int e = 0; e < PER; ++e) {
         const int i = e * 256 + tid;
@@ -471,6 +486,7 @@ __global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float 
         if (i < n) {
             const int hh = i / nwg, w = i - hh * nwg;
             v = lane_max[(size_t)(t0 + 32 * hh) * nwg + w];
+            if constexpr (EXACT) arg[e] = x.lane_arg[(size_t)(t0 + 32 * hh) * nwg + w];  // (fetched with the maximum: no second round trip)
         }
         valid[e] = v > -INFINITY;  // a lane that saw no row keeps -inf
         key[e] = f32_key(v);
@@ -485,13 +501,140 @@ __global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float 
     // finite one, which the -inf of masked rows (a removal or a filter that leaves few rows in the sample) does not reach: such
     // rows then take no record slot in the collect launch
     float kth = -8.0f;
-    if (nv >= (uint32_t)k && k > 0) kth = key_f32(block_kth_largest<PER>(key, valid, (uint32_t)k, s_hist, s_pick));
-    if (tid == 0 && theta[q] != INFINITY) theta[q] = kth - (raw ? 2.0f : 1.0f) * qa[q];
+    bool exact = false;  // (uniform over the workgroup)
+    uint32_t C = 0;
+    double na = 0.0;
+    if constexpr (EXACT) {
+        na = x.qnorm2[q];
+        C = (uint32_t)min(n, max(32, 2 * k + 12));
+        exact = nv >= (uint32_t)k && k > 0 && C <= (uint32_t)kThetaMaxC && theta[q] != INFINITY && na > 0.0 && na < INFINITY;
+    }
+    if (!exact && nv >= (uint32_t)k && k > 0) kth = key_f32(block_kth_largest<PER>(key, valid, (uint32_t)k, s_hist, s_pick));
+    float th = 0.0f;
+    if constexpr (EXACT) {
+        if (exact) {
+            // ---- the C lanes with the largest maxima, C >= k: ONE radix select (none when at most C lanes saw a row); the k-th largest
+            // maximum is then ranked among those C.  Ties at the C-th value beyond C are dropped: every larger value is kept, so the
+            // k-th largest of what is kept is the k-th largest of all, and any C of the lanes would do for the rows.
+            const uint32_t cut = nv > C ? block_kth_largest<PER>(key, valid, C, s_hist, s_pick) : 0u;
+#pragma unroll
+            for (int e = 0; e < PER; ++e)
+                if (valid[e] && key[e] >= cut) {
+                    const uint32_t at = atomicAdd(&s_cn, 1u);
+                    if (at < C) s_crow[at] = arg[e], s_ckey[at] = key[e];
+                }
+            __syncthreads();
+            const uint32_t nc = s_cn < C ? s_cn : C;  // >= k
+            for (uint32_t i = tid; i < nc; i += 256) {
+                const uint32_t mine = s_ckey[i];
+                uint32_t gt = 0, ge = 0;
+                for (uint32_t j = 0; j < nc; ++j) {
+                    const uint32_t o = s_ckey[j];
+                    gt += o > mine ? 1u : 0u;
+                    ge += o >= mine ? 1u : 0u;
+                }
+                if (gt < (uint32_t)k && (uint32_t)k <= ge) s_kth = mine;  // ties write the same value
+            }
+            // ---- f32 rescoring: s2 = sum fma(q_i/|q|, c_i/|c|), |s2 - cos| <= e2 (finish_kernel's stage 2)
+            const int lane = tid & 63, wave = tid >> 6;
+            const float invq = (float)(1.0 / sqrt(na));
+            const int nc4 = x.ds >> 2;
+            const float4 *qv = reinterpret_cast<const float4 *>(x.qpad + (size_t)q * x.ds);
+            for (uint32_t base = (uint32_t)wave * kThetaRows; base < nc; base += 4 * kThetaRows) {
+                float dot[kThetaRows], sc[kThetaRows];
+                const float4 *rp[kThetaRows];
+#pragma unroll
+                for (int j = 0; j < kThetaRows; ++j) {
+                    const uint32_t row = base + j < nc ? s_crow[base + j] : kNoRow;
+                    const bool ok = row != kNoRow && (uint64_t)row < x.n_rows;
+                    sc[j] = ok ? x.scale[row] : 0.0f;
+                    rp[j] = reinterpret_cast<const float4 *>(x.x + (size_t)(ok ? row : 0u) * x.ds);  // (does not wait for the norm)
+                    dot[j] = 0.0f;
+                }
+                for (int tb = 0; tb * 64 < nc4; tb += kMaxKC / 2) {
+                    float4 c[kThetaRows][kMaxKC / 2];
+#pragma unroll
+                    for (int t = 0; t < kMaxKC / 2; ++t) {
+                        const int c4 = lane + 64 * (tb + t);
+                        if (c4 < nc4) {
+#pragma unroll
+                            for (int j = 0; j < kThetaRows; ++j) c[j][t] = rp[j][c4];
+                        }
+                    }
+#pragma unroll
+                    for (int t = 0; t < kMaxKC / 2; ++t) {
+                        const int c4 = lane + 64 * (tb + t);
+                        if (c4 < nc4) {
+                            const float4 a = qv[c4];
+#pragma unroll
+                            for (int j = 0; j < kThetaRows; ++j) {
+                                dot[j] = fmaf(a.x * invq, c[j][t].x * sc[j], dot[j]);
+                                dot[j] = fmaf(a.y * invq, c[j][t].y * sc[j], dot[j]);
+                                dot[j] = fmaf(a.z * invq, c[j][t].z * sc[j], dot[j]);
+                                dot[j] = fmaf(a.w * invq, c[j][t].w * sc[j], dot[j]);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < kThetaRows; ++j) {
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) dot[j] += __shfl_xor(dot[j], o);
+                }
+                // (a wave reads and rewrites its own slots of s_crow only: no barrier, and none could stand in this wave-dependent loop)
+#pragma unroll
+                for (int j = 0; j < kThetaRows; ++j)
+                    if (lane == j && base + j < nc) {
+                        const float lb = dot[j] - x.e2;
+                        // no row, a row without a norm (1/|c| kept as 0), or a score that is no number: not counted
+                        s_crow[base + j] = __float_as_uint(sc[j] > 0.0f && sc[j] < INFINITY && lb == lb ? lb : -INFINITY);
+                    }
+            }
+            __syncthreads();
+            // ---- L' = the k-th largest lower bound (nc >= k entries, -inf for the rows left out)
+            for (uint32_t i = tid; i < nc; i += 256) {
+                const float mine = __uint_as_float(s_crow[i]);
+                uint32_t gt = 0, ge = 0;
+                for (uint32_t j = 0; j < nc; ++j) {
+                    const float o = __uint_as_float(s_crow[j]);
+                    gt += o > mine ? 1u : 0u;
+                    ge += o >= mine ? 1u : 0u;
+                }
+                if (gt < (uint32_t)k && (uint32_t)k <= ge) s_lp = mine;  // ties write the same value
+            }
+            __syncthreads();
+            kth = key_f32(s_kth);
+            th = fmaxf(kth - qa[q], s_lp - qa[q]);
+        }
+    }
+    if (!exact) th = kth - (raw ? 2.0f : 1.0f) * qa[q];
+    if (tid == 0 && theta[q] != INFINITY) theta[q] = th;
 }
 
-hipError_t launch_theta(hipStream_t s, int B, int k, int nwg, const float *lane_max, const float *qa, bool raw, float *theta) {
+template <int PER>
+__global__ __launch_bounds__(256) void theta_kernel(int k, int nwg, const float *__restrict__ lane_max,
+                                                    const float *__restrict__ qa, int raw, float *__restrict__ theta) {
+    theta_query<PER, false>(k, nwg, lane_max, qa, raw, theta, ThetaExact{});
+}
+template <int PER>
+__global__ __launch_bounds__(256) void theta_exact_kernel(int k, int nwg, const float *__restrict__ lane_max,
+                                                          const float *__restrict__ qa, float *__restrict__ theta, const ThetaExact x) {
+    theta_query<PER, true>(k, nwg, lane_max, qa, 0, theta, x);
+}
+
+hipError_t launch_theta(hipStream_t s, int B, int k, int nwg, const float *lane_max, const float *qa, bool raw, float *theta,
+                        const ThetaExact *ex) {
     if (B <= 0) return hipSuccess;
     if (nwg > kMaxScanWGs) return hipErrorInvalidValue;
+    if (ex && ex->lane_arg) {
+        if (raw || !ex->x || !ex->scale || !ex->qpad || !ex->qnorm2) return hipErrorInvalidValue;
+        const ThetaExact x = *ex;
+        if (nwg <= 256)
+            hipLaunchKernelGGL(theta_exact_kernel<2>, dim3(B), dim3(256), 0, s, k, nwg, lane_max, qa, theta, x);
+        else
+            hipLaunchKernelGGL(theta_exact_kernel<4>, dim3(B), dim3(256), 0, s, k, nwg, lane_max, qa, theta, x);
+        return hipGetLastError();
+    }
     if (nwg <= 256)
         hipLaunchKernelGGL(theta_kernel<2>, dim3(B), dim3(256), 0, s, k, nwg, lane_max, qa, raw ? 1 : 0, theta);
     else

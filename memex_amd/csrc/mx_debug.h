@@ -14,7 +14,10 @@
 //   attn_short_lds=0 [1]  attention_short_kernel fetches K / V^T per wave from global memory
 //   attn_pair=0|1    [per pass]  never / always two heads per item of the staged attention
 //   attn_safe=1      [0]  running-maximum softmax loop only
-//   sample_div=N          the search's sample pass visits 1/N of the scan tiles (a tuning knob: results do not depend on it)
+//   sample_div=N          the search's sample pass visits 1/N of the scan tiles (a tuning knob: results do not depend on it); read
+//                         when an index is created, like records: debug_flag costs a getenv, a mutex and a string compare, which
+//                         do not belong on the path of every batch
+//   records=1        [0]  every batch prints the record count of its collect launch to stderr (a measurement aid)
 //   filt_subset=0|1  [by size]  a filtered search of at most 16384 allowed rows always takes the masked scan pipeline / the
 //                         subset kernel (bit-identical answers; tests/test_filtered_gpu.py holds the two against each other)
 // Unknown keys are ignored.  Operational switches (wait mode, exchange, filter copy) are separate, documented in

@@ -102,7 +102,8 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
     // ---- register-resident query fragments (B operand): k-step ks = 32 dims, 16 int8 per lane
     i32x4 qf[QG * KC * 4];
     // MODE 1: a half tile with residual bound e passes when a score reaches theta - qb * e (theta_kernel);
-    // MODE 0: the lane keeps the best LOWER bound of a cosine, score - (qa + qb * e)
+    // MODE 0: the lane keeps the best LOWER bound of a cosine, score - (qa + qb * e) -- and, on a plain copy, the row that gave it
+    // (ScanParams::lane_arg: theta_kernel rescores the best of those rows exactly)
     float theta[QG], qa[QG], qb[QG], sq[QG];
     float aq = 0.0f;
 #pragma unroll
@@ -174,8 +175,11 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
     auto mylane = [&](int g) { return (uint32_t)((wave * QG + g) * 64 + lane) * gridDim.x + blockIdx.x; };
     uint32_t cnt[QG];  // records written; bit 31: a record did not fit
     float best[QG];
+    // sample launch of a plain copy: the row behind best[g] (ScanParams::lane_arg), which theta_kernel rescores exactly
+    constexpr bool kArg = MODE == 0 && !CEN;
+    uint32_t arg[QG];
 #pragma unroll
-    for (int g = 0; g < QG; ++g) cnt[g] = 0, best[g] = -INFINITY;
+    for (int g = 0; g < QG; ++g) cnt[g] = 0, best[g] = -INFINITY, arg[g] = kNoRow;
 
     tile_ops(0);
 #pragma unroll
@@ -302,7 +306,16 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
                 if (DEAD && mxi == INT_MIN) mx = -INFINITY;  // every row of the lane removed (also when the step is 0)
                 const float thr = fmaf(-qb[g], er, theta[g]);
                 if (MODE == 0) {
-                    best[g] = fmaxf(best[g], mx - fmaf(qb[g], er, qa[g]));  // only full tiles are sampled (index.hip): every row is a real row
+                    const float lb = mx - fmaf(qb[g], er, qa[g]);  // only full tiles are sampled (index.hip): every row is a real row
+                    if constexpr (kArg) {
+                        if (lb > best[g]) {  // (a lane of removed rows only: lb = -inf, never taken)
+                            int rr = 15;     // the first r with ac[r] == mxi
+#pragma unroll
+                            for (int r = 14; r >= 0; --r) rr = ac[r] == mxi ? r : rr;
+                            arg[g] = (uint32_t)kTile8Rows * tile + 32u * (uint32_t)u + (uint32_t)((rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5));
+                        }
+                    }
+                    best[g] = fmaxf(best[g], lb);
                 } else if (__builtin_amdgcn_ballot_w64(mx >= thr) != 0) {
                     if (mx >= thr) {
                         if ((cnt[g] & 0x7fffffffu) < (uint32_t)kRecCap) {
@@ -331,7 +344,11 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
 
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
-        write_lane<MODE>(p.lane_max, p.lane_cnt, p.overflow, [&] { return mylane(g); }, (wave * QG + g) * 32 + m, best[g], cnt[g] & 0x7fffffffu, cnt[g] >> 31);
+        if constexpr (kArg)
+            write_lane<MODE>(p.lane_max, p.lane_cnt, p.overflow, [&] { return mylane(g); }, (wave * QG + g) * 32 + m, best[g], cnt[g] & 0x7fffffffu, cnt[g] >> 31,
+                             p.lane_arg, arg[g]);
+        else
+            write_lane<MODE>(p.lane_max, p.lane_cnt, p.overflow, [&] { return mylane(g); }, (wave * QG + g) * 32 + m, best[g], cnt[g] & 0x7fffffffu, cnt[g] >> 31);
     }
 }
 

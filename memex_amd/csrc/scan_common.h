@@ -132,11 +132,14 @@ __device__ __forceinline__ void store_record(R *rec, uint32_t *tiles, A at, T ti
     else tiles[at] = tile();
 }
 
-// what a lane leaves behind at the end of the launch: entry lane() of lane_max, or of lane_cnt and (set only) its query's overflow word
+// what a lane leaves behind at the end of the launch: entry lane() of lane_max, or of lane_cnt and (set only) its query's overflow word;
+// a sample launch that tracks which row gave the maximum (scan8_kernel, plain copy) also leaves that row in lane_arg
 template <int MODE, class L>
-__device__ __forceinline__ void write_lane(float *lane_max, uint32_t *lane_cnt, uint32_t *overflow, L lane, int query, float best, uint32_t cnt, uint32_t ovf) {
+__device__ __forceinline__ void write_lane(float *lane_max, uint32_t *lane_cnt, uint32_t *overflow, L lane, int query, float best, uint32_t cnt, uint32_t ovf,
+                                           uint32_t *lane_arg = nullptr, uint32_t arg = kNoRow) {
     if (MODE == 0) {
         lane_max[lane()] = best;
+        if (lane_arg) lane_arg[lane()] = arg;
     } else {
         lane_cnt[lane()] = cnt;
         if (ovf) overflow[query] = 1;
