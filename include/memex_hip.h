@@ -332,6 +332,47 @@ int mx_index_search_range_by_id(mx_index *idx, const uint64_t *query_ids, int B,
 int mx_index_search_range_by_id_device(mx_index *idx, const uint64_t *query_ids, int B, const float *min_scores, int cap, int exclude_self,
                                        uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_n_found, uint64_t *d_n_in_range);
 
+/*
+ * Fused search: ONE ranked list from several query vectors -- the phrasings of a question, a question and a hypothetical answer, the
+ * last turns of a conversation.  queries is [R, m, dim] row-major, R requests of m sub-queries each; the outputs are [R, k].  weights
+ * is [R, m] in HOST memory on both variants (NULL: all ones); a weight of exactly 0 marks the sub-query ABSENT for that request (the
+ * padding of ragged requests): its vector is still checked and still rides in the pass, but its list is never consulted.
+ * Per request:
+ *   candidates  for every sub-query i with weight > 0, list i = what mx_index_search gives for it with k = fetch, bit for bit: (dist, id)
+ *               order, removed rows, id_offset, the AUTO and EXACT modes.  The candidate stage IS a plain search pass over the R * m
+ *               queries (split into passes of floor(512 / m) whole requests): it counts as one in mx_index_stats and in the filter
+ *               copy's heuristics.
+ *   best list   a row of the union of the consulted lists is reported ONCE, with the entry of its best sub-query: the consulted list that
+ *               holds it with the smallest (dist, sub-query index).  scores / dists are that entry's, unchanged; best_sub is that index.
+ *   MX_FUSE_MAX ("any of these phrasings") the rows ordered by (best dist ascending, id ascending), cut to k; weights matter only as
+ *               present or absent; fused = (double)score.  This is the EXACT global top-k by min_i dist_i(row) over ALL live rows, for
+ *               any fetch >= k, not only among the listed rows (DESIGN.md 3.13 has the proof: a row outside list i has fetch >= k rows
+ *               ahead of it there, each with a fused key no larger than its own).  Hence n_found = min(k, live rows) whenever a
+ *               weight is > 0, and fetch = k is enough.
+ *   MX_FUSE_RRF reciprocal-rank fusion of the top-fetch lists:  fused(row) = sum over the consulted lists i that hold the row, in
+ *               ASCENDING i, of  (double)w_i / ((double)rrf_c + (double)rank_i(row)),  rank_i the row's 1-based position in list i;
+ *               plain IEEE f64 operations, not contracted, a true division (no reciprocal approximation).  The rows are ordered by
+ *               (fused descending, id ascending) and cut to k.  Exact with respect to the top-fetch lists (a row outside every list
+ *               has no rank), the framing of mx_index_search_mmr.  n_found = min(k, size of the union).
+ * Unused slots hold id 0, score 0, dist +inf, best_sub -1, fused 0; dists, best_sub and fused may be NULL.  A request whose weights are
+ * all 0 finds nothing, and the call still returns MX_OK.
+ * Arguments are checked first: R < 0, m < 1, k < 1, fetch < k, a mode that is neither of the two, a weight that is NaN, infinite or
+ * negative, (MX_FUSE_RRF) an rrf_c that is NaN, infinite or < 0, a NULL queries / ids / scores / n_found with R > 0: MX_EINVAL;
+ * m > 16 or fetch > 256: MX_EUNSUPPORTED (one workgroup fuses one request from LDS, at most 16 x 256 = 4096 entries; fetch <= 256 keeps
+ * the candidate stage on the AUTO path); then a null index: MX_ESEARCH.  Non-finite queries are rejected as by mx_index_search.
+ * Thread-safe beside every other call.  Concurrent callers are NOT combined into shared passes: each call holds the index across its
+ * candidate stage and its fusion (both see one snapshot of the rows) and never rides in a plain, filtered or range pass.  A sharded
+ * handle merges the candidate lists on devices[0] as a search does and fuses there: no rows are gathered, and the answer equals the
+ * plain index's bit for bit.  The fusion costs O(m * fetch * log^2(m * fetch)) per request, independent of dim and of the row count.
+ * Extra HBM, allocated at the first call: the candidate lists (shared with mx_index_search_mmr) and 1.5 MiB of outputs on devices[0].
+ */
+enum { MX_FUSE_MAX = 0, MX_FUSE_RRF = 1 };
+int mx_index_search_fused(mx_index *idx, const float *queries, int R, int m, const float *weights, int mode, int k, int fetch,
+                          float rrf_c, uint64_t *ids, float *scores, float *dists, int32_t *best_sub, double *fused, int32_t *n_found);
+int mx_index_search_fused_device(mx_index *idx, const float *d_queries, int R, int m, const float *weights, int mode, int k, int fetch,
+                                 float rrf_c, uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_best_sub, double *d_fused,
+                                 int32_t *d_n_found);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

@@ -534,6 +534,42 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // one ranked list for SEVERAL query vectors -- the phrasings of a question, a question and a hypothetical answer, the last turns of a
+    // conversation (mx_index_search_fused) -- each row once, with the score of its best vector.  mode MX_FUSE_MAX: the exact top-`limit`
+    // by the best score over the vectors; MX_FUSE_RRF: reciprocal-rank fusion of their top-`fetch` lists (rrf_c = 60).  fetch = 0: the
+    // default, limit for MAX and min(max(4 * limit, 32), 256) for RRF; weights: one per vector or empty (all ones), 0 leaves a vector out
+    std::vector<VectorSearchResult> search_fused(const std::vector<std::vector<float>> &vecs, size_t limit, int mode = MX_FUSE_MAX,
+                                                 size_t fetch = 0, const std::vector<float> &weights = {}) {
+        std::vector<VectorSearchResult> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0 || vecs.empty()) return out;
+        }
+        std::vector<float> q;
+        for (const std::vector<float> &v : vecs) {
+            if (v.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+            q.insert(q.end(), v.begin(), v.end());
+        }
+        if (!weights.empty() && weights.size() != vecs.size())
+            throw VectorStoreError(VectorStoreError::SearchError, "one weight per query vector expected");
+        if (fetch == 0) fetch = mode == MX_FUSE_MAX ? limit : std::min<size_t>(std::max<size_t>(4 * limit, 32), 256);
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        int32_t nf = 0;
+        int rc = mx_index_search_fused(idx_, q.data(), 1, (int)std::min<size_t>(vecs.size(), (size_t)INT32_MAX), weights.empty() ? nullptr : weights.data(),
+                                       mode, (int)std::min<size_t>(limit, (size_t)INT32_MAX), (int)std::min<size_t>(fetch, (size_t)INT32_MAX), 60.0f,
+                                       found.data(), scores.data(), nullptr, nullptr, nullptr, &nf);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.emplace_back(it->second, scores[j]);
+        }
+        return out;
+    }
+
     // more like this: the `limit` entries closest to what is stored under _id, the asked _id itself left out.  Every row stored under
     // _id is a query (mx_index_search_by_id: the rows never leave the device, the own row is taken out exactly); the union of their
     // answers is ranked by best score, each row once.  An unknown _id returns nothing
@@ -1262,6 +1298,20 @@ inline std::vector<VectorSearchResult> search_docs(VectorStorage &client, Senten
     const std::optional<EmbeddingResult> res = embedder.encode_single(query);
     if (!res) throw std::invalid_argument("Invalid query");
     return client.search(res->vector, limit);
+}
+
+// search_docs for several texts at once (no counterpart in the reference): each is embedded with encode_single, the vectors go to
+// HipFlatStore::search_fused and ONE list comes back.  std::invalid_argument("Invalid query") if any text embeds to nothing
+inline std::vector<VectorSearchResult> search_docs_multi(HipFlatStore &store, SentenceEmbedder &embedder, const std::vector<std::string> &queries,
+                                                         size_t limit = 10, int mode = MX_FUSE_MAX) {
+    std::vector<std::vector<float>> vectors;
+    for (const std::string &query : queries) {
+        const std::optional<EmbeddingResult> res = embedder.encode_single(query);
+        if (!res) throw std::invalid_argument("Invalid query");
+        vectors.push_back(res->vector);
+    }
+    if (vectors.empty()) throw std::invalid_argument("Invalid query");
+    return store.search_fused(vectors, limit, mode);
 }
 
 }  // namespace memex

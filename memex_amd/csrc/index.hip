@@ -292,6 +292,12 @@ struct mx_index {
     int32_t *byid_nf = nullptr;
     uint32_t *byid_src = nullptr, *byid_dlim = nullptr;
     int byid_cap = 0;
+    // fused search (mx_index_search_fused), allocated at the first such call on the index that owns the stream: a
+    // chunk's weights [kMaxBatch] and, for the host-pointer variant, best_sub and fused [kMaxBatch, kFuseMaxFetch].  The candidate
+    // lists are the diversified search's (mmr_ids ...).
+    float *fuse_w = nullptr;
+    int32_t *fuse_best = nullptr;
+    double *fuse_val = nullptr;
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -408,6 +414,7 @@ int free_index(mx_index *idx) {
     if (idx->mmr_h_nf) (void)hipHostFree(idx->mmr_h_nf);
     F(idx->byid_rows); F(idx->byid_stage); F(idx->byid_q); F(idx->byid_ids); F(idx->byid_nr); F(idx->byid_own); F(idx->byid_scores);
     F(idx->byid_dists); F(idx->byid_nf); F(idx->byid_src); F(idx->byid_dlim);
+    F(idx->fuse_w); F(idx->fuse_best); F(idx->fuse_val);
     Scratch &s = idx->s;
     F(s.qfrag); F(s.qpad); F(s.qnorm2); F(s.theta); F(s.theta_retry); F(s.todo); F(s.dev_flags); F(s.done_ctr);
     if (s.host_flags) (void)hipHostFree(s.host_flags);
@@ -2158,6 +2165,30 @@ int mmr_batch(mx_index *idx, const float *d_q, int B, int k, int fetch, float la
                                  t->mmr_nf + q0, d_ids + o0, d_scores + o0, d_dists ? d_dists + o0 : nullptr, d_nfound + q0));
         MX_HIP(hipStreamSynchronize(st));
     }
+    return MX_OK;
+}
+
+// ---- fused search (mx_index_search_fused) -----------------------------------------------------------
+// One chunk of a fused search: nreq requests of m sub-queries each (nreq * m <= kMaxBatch), queries and outputs on the device of the
+// index that owns the stream, the caller holding idx->mu across both stages.  A plain search pass over the nreq * m queries at
+// k = fetch into that index's lists (the diversified search's: a sharded handle has them merged on devices[0] already, no rows are
+// gathered), the chunk's weights (host memory, [nreq, m]; null: all ones) uploaded, one fuse_kernel launch; host-synchronised.
+int fused_batch(mx_index *idx, const float *d_q, int nreq, int m, const float *weights, int mode, int k, int fetch, float rrf_c,
+                uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_best, double *d_fused, int32_t *d_nfound) {
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    int rc = ensure_mmr_lists(t, fetch);
+    if (rc != MX_OK) return rc;
+    if (!t->fuse_w) MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->fuse_w), kMaxBatch * sizeof(float)));
+    const int B = nreq * m;
+    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf)) != MX_OK) return rc;
+    hipStream_t st = t->stream;
+    std::vector<float> w(weights ? weights : nullptr, weights ? weights + B : nullptr);  // (alive until the stream is synchronised)
+    if (!weights) w.assign((size_t)B, 1.0f);
+    MX_HIP(hipMemcpyAsync(t->fuse_w, w.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
+    FuseArgs p{nreq, m, fetch, k, mode, (double)rrf_c, t->fuse_w, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf,
+               d_ids, d_scores, d_dists, d_best, d_fused, d_nfound};
+    MX_HIP(launch_fuse(st, p));
+    MX_HIP(hipStreamSynchronize(st));
     return MX_OK;
 }
 
@@ -4100,6 +4131,93 @@ int mx_index_search_mmr_device(mx_index *idx, const float *d_q, int B, int k, in
         const size_t o = (size_t)b0 * k;
         int rc = mmr_batch(idx, d_q + (size_t)b0 * idx->dim, nb, k, fetch, lambda, d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr,
                            d_nfound + b0);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+namespace {
+
+// arguments of the fused-search entry points, checked before the index is looked at (weights: host memory [R, m] or null)
+int read_fused_args(const void *q, int R, int m, const float *weights, int mode, int k, int fetch, float rrf_c, const void *ids,
+                    const void *scores, const void *n_found) {
+    if (R < 0) return fail(MX_EINVAL, "negative batch");
+    if (m < 1) return fail(MX_EINVAL, "m = %d < 1", m);
+    if (k < 1) return fail(MX_EINVAL, "k = %d < 1", k);
+    if (fetch < k) return fail(MX_EINVAL, "fetch = %d < k = %d", fetch, k);
+    if (mode != MX_FUSE_MAX && mode != MX_FUSE_RRF) return fail(MX_EINVAL, "mode = %d is neither MX_FUSE_MAX nor MX_FUSE_RRF", mode);
+    if (weights)
+        for (size_t i = 0; i < (size_t)R * (size_t)m; ++i)
+            if (!(weights[i] >= 0.0f) || std::isinf(weights[i]))
+                return fail(MX_EINVAL, "weights[%zu] = %g is not a finite value >= 0", i, (double)weights[i]);
+    if (mode == MX_FUSE_RRF && (!(rrf_c >= 0.0f) || std::isinf(rrf_c)))
+        return fail(MX_EINVAL, "rrf_c = %g is not a finite value >= 0", (double)rrf_c);
+    if (R > 0 && (!q || !ids || !scores || !n_found)) return fail(MX_EINVAL, "null argument");
+    if (m > kFuseMaxSub) return fail(MX_EUNSUPPORTED, "m = %d > %d", m, kFuseMaxSub);
+    if (fetch > kFuseMaxFetch) return fail(MX_EUNSUPPORTED, "fetch = %d > %d", fetch, kFuseMaxFetch);
+    return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_search_fused(mx_index *idx, const float *q, int R, int m, const float *weights, int mode, int k, int fetch, float rrf_c,
+                          uint64_t *ids, float *scores, float *dists, int32_t *best_sub, double *fused, int32_t *n_found) try {
+    if (int rc = read_fused_args(q, R, m, weights, mode, k, fetch, rrf_c, ids, scores, n_found); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (R == 0) return MX_OK;
+    const size_t dim = (size_t)idx->dim;
+    for (size_t i = 0; i < (size_t)R * m * dim; ++i)
+        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    // not combined with other callers: the call holds the index across the candidate stage and the fusion, like a device-pointer call
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
+    DeviceGuard g(t->device);
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, k)) != MX_OK) return rc;
+    if (best_sub && !t->fuse_best)
+        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->fuse_best), (size_t)kMaxBatch * kFuseMaxFetch * sizeof(int32_t)));
+    if (fused && !t->fuse_val) MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->fuse_val), (size_t)kMaxBatch * kFuseMaxFetch * sizeof(double)));
+    Scratch &s = t->s;
+    const int per = kMaxBatch / m;  // whole requests per pass
+    for (int r0 = 0; r0 < R; r0 += per) {
+        const int nr = std::min(per, R - r0);
+        const size_t o = (size_t)r0 * k, nq = (size_t)nr * m;
+        memcpy(s.h_q, q + (size_t)r0 * m * dim, nq * dim * sizeof(float));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, nq * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        if ((rc = fused_batch(idx, s.qstage, nr, m, weights ? weights + (size_t)r0 * m : nullptr, mode, k, fetch, rrf_c, s.out_ids, s.out_scores,
+                              s.out_dists, best_sub ? t->fuse_best : nullptr, fused ? t->fuse_val : nullptr, s.out_nfound)) != MX_OK)
+            return rc;
+        if (best_sub) MX_HIP(hipMemcpyAsync(best_sub + o, t->fuse_best, (size_t)nr * k * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        if (fused) MX_HIP(hipMemcpyAsync(fused + o, t->fuse_val, (size_t)nr * k * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+        if ((rc = copy_out_to_host(t, nr, k, false)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nr, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + r0, nullptr);
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_fused_device(mx_index *idx, const float *d_q, int R, int m, const float *weights, int mode, int k, int fetch,
+                                 float rrf_c, uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_best_sub, double *d_fused,
+                                 int32_t *d_nfound) try {
+    if (int rc = read_fused_args(d_q, R, m, weights, mode, k, fetch, rrf_c, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (R == 0) return MX_OK;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    DeviceGuard g(t->device);
+    const int per = kMaxBatch / m;
+    for (int r0 = 0; r0 < R; r0 += per) {
+        const int nr = std::min(per, R - r0);
+        const size_t o = (size_t)r0 * k;
+        int rc = fused_batch(idx, d_q + (size_t)r0 * m * idx->dim, nr, m, weights ? weights + (size_t)r0 * m : nullptr, mode, k, fetch, rrf_c,
+                             d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr, d_best_sub ? d_best_sub + o : nullptr,
+                             d_fused ? d_fused + o : nullptr, d_nfound + r0);
         if (rc != MX_OK) return rc;
     }
     return MX_OK;

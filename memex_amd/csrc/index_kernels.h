@@ -410,4 +410,29 @@ struct ByIdDrop {
 };
 hipError_t launch_byid_drop_self(hipStream_t s, const ByIdDrop &p);
 
+// fused search (mx_index_search_fused)
+constexpr int kFuseMaxSub = 16;                  // sub-queries per request
+constexpr int kFuseMaxFetch = 256;               // entries per list: kFuseMaxSub * kFuseMaxFetch = 4096 entries sorted in LDS per request
+// One ranked list [R, k] per request from the m candidate lists of its sub-queries: list i of request r is row r * m + i of cand_*
+// [R * m, fetch] ((dist, id) order, cand_nf entries) and is consulted iff weights[r * m + i] > 0.  A row of the union is reported with
+// the entry of its best list (smallest (dist, sub-query)) and that list's index; mode 0 orders by (best dist, id), mode 1 by
+// (fused descending, id) with fused = the f64 sum over the consulted lists that hold the row, in ascending i, of
+// (double)weight / (rrf_c + 1-based rank); fused of mode 0 is (double)score.  n_found = min(k, rows in the union); unused slots id 0 /
+// score 0 / dist +inf / best_sub -1 / fused 0.  dists, best_sub and fused may be null.  1 <= m <= kFuseMaxSub, 1 <= k <= fetch <=
+// kFuseMaxFetch.
+struct FuseArgs {
+    int R, m, fetch, k, mode;
+    double rrf_c;
+    const float *weights;
+    const uint64_t *cand_ids;
+    const float *cand_scores, *cand_dists;
+    const int32_t *cand_nf;
+    uint64_t *ids;
+    float *scores, *dists;
+    int32_t *best_sub;
+    double *fused;
+    int32_t *n_found;
+};
+hipError_t launch_fuse(hipStream_t s, const FuseArgs &p);
+
 }  // namespace mx

@@ -2694,4 +2694,151 @@ hipError_t launch_byid_drop_self(hipStream_t s, const ByIdDrop &p) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// fused search (mx_index_search_fused): one ranked list from the candidate lists of a request's sub-queries
+// ---------------------------------------------------------------------------------------------
+// a record is (a, b): sorted by (b >> 31, a, b), i.e. the records whose top bit of b is set (padding, dropped entries) go last
+__device__ __forceinline__ bool fuse_less(uint64_t a1, uint32_t b1, uint64_t a2, uint32_t b2) {
+    const uint32_t v1 = b1 >> 31, v2 = b2 >> 31;
+    if (v1 != v2) return v1 < v2;
+    if (a1 != a2) return a1 < a2;
+    return b1 < b2;
+}
+
+// bitonic network over the P (a power of two) records of the block, ascending; ends with a barrier
+__device__ __forceinline__ void fuse_sort(uint64_t *ka, uint32_t *kb, int P) {
+    for (int k2 = 2; k2 <= P; k2 <<= 1) {
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;  // (i < l < P)
+                const uint64_t ai = ka[i], al = ka[l];
+                const uint32_t bi = kb[i], bl = kb[l];
+                const bool up = (i & k2) == 0;
+                if (up ? fuse_less(al, bl, ai, bi) : fuse_less(ai, bi, al, bl)) {
+                    ka[i] = al; kb[i] = bl;
+                    ka[l] = ai; kb[l] = bi;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+constexpr uint32_t kFusePad = 0x80000000u;  // b of a record that is no entry
+constexpr int kFusePer = 4;                 // records per thread at the largest block: 4096 / 1024
+
+// One workgroup per request; P = the power of two >= m * fetch (at least 128), blockDim = min(P / 2, 1024).  The entries of the
+// consulted lists go to LDS as (id, sub << 8 | rank) -- 12 bytes each, 48 KiB at 4096 -- and are sorted by (id, sub): the entries of one
+// row become a run in ascending sub.  The head of each run walks it (at most m entries): the f64 sum in that order, the best (dist, sub)
+// with the dists re-read from the lists.  The heads are then sorted in the same LDS by the mode's key; the head's position in the
+// first order stands in for its id (both ascend together) and travels with the best entry's (sub, rank), from which the outputs are
+// re-read.  No atomics: every record is written by one thread between two barriers.
+__global__ __launch_bounds__(1024) void fuse_kernel(FuseArgs p, int P) {
+    extern __shared__ __attribute__((aligned(16))) char fuse_lds[];
+    uint64_t *ka = reinterpret_cast<uint64_t *>(fuse_lds);                        // [P]
+    uint32_t *kb = reinterpret_cast<uint32_t *>(fuse_lds + (size_t)P * 8);        // [P]
+    float *w = reinterpret_cast<float *>(fuse_lds + (size_t)P * 12);              // [kFuseMaxSub]
+    int *nfl = reinterpret_cast<int *>(w + kFuseMaxSub);                          // [kFuseMaxSub]
+    int *heads = nfl + kFuseMaxSub;                                               // [1]
+    const int r = blockIdx.x, tid = threadIdx.x, T = blockDim.x, m = p.m, fetch = p.fetch, k = p.k, N = m * fetch;
+    const size_t l0 = (size_t)r * m * fetch, o0 = (size_t)r * k;  // the request's lists; its outputs
+    if (tid < m) {
+        const float wi = p.weights[(size_t)r * m + tid];
+        int n = p.cand_nf[(size_t)r * m + tid];
+        n = n < 0 ? 0 : n > fetch ? fetch : n;
+        w[tid] = wi;
+        nfl[tid] = wi > 0.0f ? n : 0;  // an absent sub-query: its list is never consulted
+    }
+    if (tid == 0) *heads = 0;
+    __syncthreads();
+    for (int e = tid; e < P; e += T) {
+        bool valid = false;
+        uint32_t sub = 0, rank = 0;
+        if (e < N) {
+            sub = (uint32_t)(e / fetch);
+            rank = (uint32_t)(e % fetch);
+            valid = (int)rank < nfl[sub];
+        }
+        ka[e] = valid ? p.cand_ids[l0 + e] : 0;
+        kb[e] = valid ? (sub << 8 | rank) : kFusePad;
+    }
+    __syncthreads();
+    fuse_sort(ka, kb, P);
+
+    uint64_t hk[kFusePer];
+    uint32_t hb[kFusePer];
+#pragma unroll
+    for (int i = 0; i < kFusePer; ++i) {
+        const int e = tid + i * T;
+        hk[i] = 0;
+        hb[i] = kFusePad;
+        if (e >= P || (kb[e] >> 31)) continue;
+        const uint64_t id = ka[e];
+        if (e > 0 && ka[e - 1] == id) continue;  // (the record before a valid one is valid: they sort first)
+        double sum = 0.0;
+        float bd = 0.0f;
+        uint32_t best = 0;
+        for (int j = e; j < P && !(kb[j] >> 31) && ka[j] == id; ++j) {
+            const uint32_t b = kb[j], sub = b >> 8, rank = b & 255u;
+            if (p.mode == 1) sum = __dadd_rn(sum, __ddiv_rn((double)w[sub], __dadd_rn(p.rrf_c, (double)(rank + 1u))));
+            const float d = p.cand_dists[l0 + (size_t)sub * fetch + rank];
+            if (j == e || d < bd) {  // (ascending sub: an equal dist keeps the earlier list)
+                bd = d;
+                best = b;
+            }
+        }
+        // descending fused = ascending ~key; dists are >= +0, so their bits order them
+        hk[i] = p.mode == 1 ? ~mmr_key(sum) : (uint64_t)__float_as_uint(bd) << 32;
+        hb[i] = (uint32_t)e << 12 | best;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kFusePer; ++i) {
+        const int e = tid + i * T;
+        if (e < P) {
+            ka[e] = hk[i];
+            kb[e] = hb[i];
+        }
+    }
+    __syncthreads();
+    fuse_sort(ka, kb, P);
+    for (int e = tid; e < P; e += T)
+        if (!(kb[e] >> 31) && (e + 1 == P || (kb[e + 1] >> 31))) *heads = e + 1;  // the last head: one thread at most
+    __syncthreads();
+    const int found = *heads < k ? *heads : k;
+    for (int t = tid; t < k; t += T) {  // (k <= fetch <= P)
+        const bool have = t < found;
+        const uint32_t b = have ? kb[t] : 0u, sub = (b >> 8) & 15u;
+        const size_t src = l0 + (size_t)sub * fetch + (b & 255u);  // (entry 0 of list 0 for a blank slot: read, not used)
+        const float sc = have ? p.cand_scores[src] : 0.0f;
+        p.ids[o0 + t] = have ? p.cand_ids[src] : 0;
+        p.scores[o0 + t] = sc;
+        if (p.dists) p.dists[o0 + t] = have ? p.cand_dists[src] : INFINITY;
+        if (p.best_sub) p.best_sub[o0 + t] = have ? (int32_t)sub : -1;
+        if (p.fused) {
+            double f = 0.0;
+            if (have && p.mode == 1) {
+                const uint64_t key = ~ka[t];  // mmr_key of the sum, undone
+                f = __longlong_as_double((long long)((key >> 63) ? key ^ 0x8000000000000000ull : ~key));
+            } else if (have) {
+                f = (double)sc;
+            }
+            p.fused[o0 + t] = f;
+        }
+    }
+    if (tid == 0) p.n_found[r] = found;
+}
+
+hipError_t launch_fuse(hipStream_t s, const FuseArgs &p) {
+    if (p.R <= 0) return hipSuccess;
+    if (p.m < 1 || p.m > kFuseMaxSub || p.fetch < 1 || p.fetch > kFuseMaxFetch || p.k < 1 || p.k > p.fetch || (p.mode != 0 && p.mode != 1))
+        return hipErrorInvalidValue;
+    int P = 128;
+    while (P < p.m * p.fetch) P <<= 1;  // <= 4096 = kFusePer * 1024
+    const int threads = P / 2 < 1024 ? P / 2 : 1024;
+    const size_t lds = (size_t)P * 12 + kFuseMaxSub * (sizeof(float) + sizeof(int)) + sizeof(int);
+    hipLaunchKernelGGL(fuse_kernel, dim3(p.R), dim3(threads), lds, s, p, P);
+    return hipGetLastError();
+}
+
 }  // namespace mx

@@ -369,6 +369,70 @@ class FlatIndex:
                                                ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
                                                ctypes.c_void_p(n_found.data_ptr())))
 
+    # -- fused search ----------------------------------------------------------------------
+    _FUSE_MODES = {"max": _lib.MX_FUSE_MAX, "rrf": _lib.MX_FUSE_RRF}
+
+    @staticmethod
+    def _fused_fetch(k: int, mode: str, fetch) -> int:
+        if fetch is not None:
+            return int(fetch)
+        return int(k) if mode == "max" else min(max(4 * int(k), 32), 256)
+
+    def _fused_args(self, shape, mode, weights):
+        """-> (R, m, mode code, weights f32 [R, m] or None) for queries of ``shape`` ([R, m, dim] or [m, dim])"""
+        if mode not in self._FUSE_MODES:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"mode {mode!r} is neither 'max' nor 'rrf'")
+        shape = tuple(int(s) for s in shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3 or shape[2] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [R, m, {self.dim}] queries, got {shape}")
+        R, m = shape[0], shape[1]
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.ndim == 1 and w.size == m:
+                w = np.ascontiguousarray(np.broadcast_to(w, (R, m)))
+            if w.shape != (R, m):
+                raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [{R}, {m}] weights, got {w.shape}")
+        return R, m, self._FUSE_MODES[mode], w
+
+    def search_fused(self, queries, k: int, mode: str = "max", fetch=None, weights=None, rrf_c: float = 60.0):
+        """One ranked list per request from SEVERAL query vectors (``mx_index_search_fused``): queries [R, m, dim], or [m, dim] for
+        one request.  -> (ids u64 [R,k], scores f32 [R,k], dists f32 [R,k], n_found i32 [R], best_sub i32 [R,k], fused f64 [R,k]).
+        ``mode="max"``: the exact top-k by the best score over the sub-queries ("any of these phrasings"); ``"rrf"``: reciprocal-rank
+        fusion of the top-``fetch`` lists, ``sum w_i / (rrf_c + rank_i)``.  Each row appears once, with the score and dist of its
+        best sub-query, whose index is ``best_sub``.  ``fetch=None``: ``k`` for "max", ``min(max(4 * k, 32), 256)`` for "rrf".
+        ``weights`` [R, m] or [m]: a weight of 0 leaves that sub-query out of the request (padding of ragged requests)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        R, m, code, w = self._fused_args(q.shape, mode, weights)
+        kk = max(int(k), 0)
+        ids = np.zeros((R, kk), dtype=np.uint64)
+        scores = np.zeros((R, kk), dtype=np.float32)
+        dists = np.zeros((R, kk), dtype=np.float32)
+        best = np.zeros((R, kk), dtype=np.int32)
+        fused = np.zeros((R, kk), dtype=np.float64)
+        nf = np.zeros(R, dtype=np.int32)
+        check(lib().mx_index_search_fused(self._h, _ptr(q) if q.size else None, R, m, _ptr(w) if w is not None and w.size else None, code,
+                                          int(k), self._fused_fetch(k, mode, fetch), float(rrf_c), _ptr(ids) if ids.size else None,
+                                          _ptr(scores) if scores.size else None, _ptr(dists) if dists.size else None,
+                                          _ptr(best) if best.size else None, _ptr(fused) if fused.size else None, _ptr(nf)))
+        return ids, scores, dists, nf, best, fused
+
+    def search_fused_device(self, q, k: int, ids, scores, dists, n_found, best_sub=None, fused=None, mode: str = "max", fetch=None,
+                            weights=None, rrf_c: float = 60.0) -> None:
+        """``search_fused`` on device tensors: q f32 [R,m,dim]; ids i64/u64 [R,k]; scores, dists f32 [R,k]; best_sub i32 [R,k];
+        fused f64 [R,k] (dists, best_sub and fused may be None); n_found i32 [R].  The weights stay on the host.  Blocks until the
+        results are in HBM."""
+        R, m, code, w = self._fused_args(q.shape, mode, weights)
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().mx_index_search_fused_device(self._h, dp(q), R, m, _ptr(w) if w is not None and w.size else None, code, int(k),
+                                                 self._fused_fetch(k, mode, fetch), float(rrf_c), dp(ids), dp(scores), dp(dists),
+                                                 dp(best_sub), dp(fused), dp(n_found)))
+
     # -- search by stored row --------------------------------------------------------------
     @staticmethod
     def _query_ids(ids) -> np.ndarray:

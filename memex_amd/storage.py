@@ -565,6 +565,32 @@ class HipFlatStore(VectorStore):
                 out.append((self._id_map[d_id], float(scores[0, j])))
         return out
 
+    def search_fused(self, vecs: Sequence[Sequence[float]], limit: int, mode: str = "max", fetch: int | None = None,
+                     weights: Sequence[float] | None = None) -> List[VectorSearchResult]:
+        """One ranked list for SEVERAL query vectors -- the phrasings of a question, a question and a hypothetical answer, the last
+        turns of a conversation (``FlatIndex.search_fused``) -- as ``(_id, score)`` pairs, each row once with the score of its best
+        vector.  ``mode="max"``: the exact top-``limit`` by the best score over the vectors; ``"rrf"``: reciprocal-rank fusion of
+        their top-``fetch`` lists.  ``weights``: one per vector, 0 leaves the vector out.  Removed rows never appear."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0 or len(vecs) == 0:
+            return []
+        q = np.asarray(vecs, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self._dim:
+            raise SearchError(f"query dimension {q.shape} != [m, store dimension {self._dim}]")
+        try:
+            ids, scores, _, nf, _, _ = idx.search_fused(q, int(limit), mode, fetch, weights)  # not under the lock, like search
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[VectorSearchResult] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[d_id], float(scores[0, j])))
+        return out
+
     def _rows_by_name(self) -> Dict[str, List[int]]:
         """(under the lock) ``_id`` -> the ids stored under it: built once per store, kept on insert."""
         if self._rows_of is None:
@@ -670,6 +696,11 @@ class VectorStorage:
     def search(self, query: Sequence[float], limit: int) -> List[VectorSearchResult]:
         with self._mu:
             return self.client.search(query, limit)
+
+    def search_fused(self, queries: Sequence[Sequence[float]], limit: int, mode: str = "max", fetch: int | None = None,
+                     weights: Sequence[float] | None = None) -> List[VectorSearchResult]:
+        with self._mu:
+            return self.client.search_fused(queries, limit, mode, fetch, weights)
 
 
 def get_vector_storage(uri: str, collection: str, device: int = 0, devices: Sequence[int] | None = None) -> VectorStorage:

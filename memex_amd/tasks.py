@@ -12,6 +12,9 @@ reference                          here
 (lib/api/.../handlers.rs:55-109)   ``(segment _id, score)`` pairs (the handler then looks each _id up in SQL)
 =================================  ==========================================================================
 
+:func:`search_docs_multi` has no counterpart in the reference: several texts for one request (the phrasings of a question, a question
+and a hypothetical answer, the last turns of a conversation), one ranked list back (``search_fused``).
+
 The ids are the reference's own (RFC 4122 v5 over the same namespace), so a collection filled through this mirror lines up
 with the rows a memex worker would have written for the same task ids.
 """
@@ -52,3 +55,19 @@ def search_docs(client, embedder, query: str, limit: int = 10) -> List[Tuple[str
     if res is None:
         raise ValueError("Invalid query")
     return client.search(res.vector, limit)
+
+
+def search_docs_multi(client, embedder, queries: Sequence[str], limit: int = 10, mode: str = "max") -> List[Tuple[str, float]]:
+    """``search_docs`` for several texts at once: each is embedded with ``encode_single`` (the embedder's actor batches what is
+    queued), the vectors go to ``client.search_fused`` and ONE list of ``(segment _id, score)`` pairs comes back -- ``mode="max"``:
+    the best score over the texts, ``"rrf"``: reciprocal-rank fusion.  ``ValueError("Invalid query")`` if any text embeds to nothing
+    (or none is given)."""
+    vectors = []
+    for text in queries:
+        res = embedder.encode_single(text)
+        if res is None:
+            raise ValueError("Invalid query")
+        vectors.append(res.vector)
+    if not vectors:
+        raise ValueError("Invalid query")
+    return client.search_fused(vectors, limit, mode)
