@@ -7,7 +7,6 @@ Result of round 5 (profiles/r5_encoder_rounding_sim.txt): the f32 residual strea
 -> 1.2e-2); the weights alone in bf16 cost 6e-3; only 16 significant bits on EVERY operand (bf16 hi + lo) reach 5e-5.  That
 is what memex_amd/csrc/encoder_precise.hip (MX_PREC_BF16X3) implements.  Uses oracle/ as the checker: a test tool, not
 product code."""
-import math
 import os
 import sys
 
@@ -16,29 +15,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from memex_amd.weights import EncoderConfig, checkpoint_like_weights  # noqa: E402
 from oracle import bert_oracle  # noqa: E402
-from scipy.special import erf  # noqa: E402
-
-
-def bf(x):  # round to nearest even bf16, returned as f32
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    u = x.view(np.uint32).astype(np.uint64)
-    u = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000
-    return u.astype(np.uint32).view(np.float32).reshape(x.shape)
-
-
-def hf(x):  # fp16
-    return np.asarray(x, np.float32).astype(np.float16).astype(np.float32)
-
-
-def ident(x):
-    return np.asarray(x, dtype=np.float32)
-
-
-def ln(x, g, b, eps):
-    x = x.astype(np.float64)
-    mu = x.mean(-1, keepdims=True)
-    var = ((x - mu) ** 2).mean(-1, keepdims=True)
-    return ((x - mu) / np.sqrt(var + eps) * g + b).astype(np.float32)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from encoder_rounding_model import bf, hf, ident, mixed, mode, allof, r16, r22, run  # noqa: E402,F401  (the model itself: tests/encoder_rounding_model.py)
 
 
 def report(name, o, ref):
@@ -46,48 +24,6 @@ def report(name, o, ref):
     pair = np.abs(o @ o.T - ref @ ref.T).max()
     print(f"{name:48s} max(1-cos) {1 - cos.min():.2e}   pairwise {pair:.2e}", flush=True)
 
-def r16(x):  # hi + lo bf16 split: 16 significant bits
-    x = np.asarray(x, np.float32); hi = bf(x); return hi + bf(x - hi)
-
-def r22(x):  # fp16 hi + fp16 lo split: 22 significant bits (inside fp16's exponent range)
-    x = np.asarray(x, np.float32); hi = hf(x); return hi + hf(x - hi)
-
-def run(w, cfg, ids, lens, R):
-    """R: dict of rounding fns: res, gout, x_qk (x into q/k proj), w_qk, qk (q,k stored), x_v, w_v, v, p, ctx, w_o, x_f, w_1, h, w_2, final"""
-    g = lambda k: R.get(k, bf)
-    H, nh, L = cfg.hidden, cfg.heads, cfg.layers; dh = H//nh
-    B, S = ids.shape
-    W = {k: np.asarray(v, np.float32) for k, v in w.items()}
-    mask = (np.arange(S)[None, :] < lens[:, None])
-    x = W["embeddings.word_embeddings.weight"][ids] + W["embeddings.position_embeddings.weight"][None, :S] + W["embeddings.token_type_embeddings.weight"][0]
-    x = ln(x, W["embeddings.LayerNorm.weight"], W["embeddings.LayerNorm.bias"], cfg.ln_eps)
-    for l in range(L):
-        p = f"encoder.layer.{l}."
-        def lin(t, name, rw):
-            return (t.reshape(-1, t.shape[-1]).astype(np.float32) @ rw(W[p+name+".weight"]).T + W[p+name+".bias"]).reshape(t.shape[:-1]+(-1,))
-        def heads(t): return t.reshape(B, S, nh, dh).transpose(0, 2, 1, 3)
-        xr = g('res')(x)
-        q = heads(R.get('q', g('qk'))(lin(g('x_qk')(x), "attention.self.query", g('w_qk'))/math.sqrt(dh)))
-        k = heads(R.get('k', g('qk'))(lin(g('x_qk')(x), "attention.self.key", g('w_qk'))))
-        v = heads(g('v')(lin(g('x_v')(x), "attention.self.value", g('w_v'))))
-        s = (q.astype(np.float64) @ k.transpose(0, 1, 3, 2).astype(np.float64))
-        s = np.where(mask[:, None, None, :], s, -1e30)
-        s = s - s.max(-1, keepdims=True)
-        pr = np.exp(s)
-        lsum = pr.sum(-1, keepdims=True)
-        ctx = (g('p')(pr.astype(np.float32)) @ v) / lsum
-        ctx = g('ctx')(ctx.transpose(0, 2, 1, 3).reshape(B, S, H))
-        a = g('gout')(lin(ctx, "attention.output.dense", g('w_o')))
-        x1 = ln(a.astype(np.float32) + xr, W[p+"attention.output.LayerNorm.weight"], W[p+"attention.output.LayerNorm.bias"], cfg.ln_eps)
-        x1r = g('res')(x1)
-        h = lin(g('x_f')(x1), "intermediate.dense", g('w_1')).astype(np.float64)
-        h = g('h')((0.5*h*(1+erf(h/math.sqrt(2)))).astype(np.float32))
-        o = g('gout')(lin(h, "output.dense", g('w_2')))
-        x = ln(o + x1r, W[p+"output.LayerNorm.weight"], W[p+"output.LayerNorm.bias"], cfg.ln_eps)
-    x = g('final')(x)
-    if cfg.pooling == "cls": pooled = x[:, 0, :].astype(np.float64)
-    else: pooled = (x.astype(np.float64)*mask[:, :, None]).sum(1)/lens[:, None]
-    return pooled/np.linalg.norm(pooled, axis=1, keepdims=True)
 
 if __name__ == "__main__":
     pooling = sys.argv[1]; hidden = int(sys.argv[2]); layers = int(sys.argv[3]); seed = int(sys.argv[4])
@@ -99,9 +35,6 @@ if __name__ == "__main__":
     lens = rng.integers(S//2, S+1, B).astype(np.int32); lens[0] = S
     ref = bert_oracle.encode(w, cfg.as_dict(), ids, lens)
     ref = ref/np.linalg.norm(ref, axis=1, keepdims=True)
-    ALL = ['res','gout','x_qk','w_qk','qk','x_v','w_v','v','p','ctx','w_o','x_f','w_1','h','w_2','final']
-    def allof(fn, **over):
-        d = {k: fn for k in ALL}; d.update(over); return d
     R6B = len(sys.argv) > 5 and sys.argv[5] == "r6b"
     if not R6B: report("all bf16", run(w, cfg, ids, lens, allof(bf)), ref)
     if not R6B: report("all 16-bit split (res/gout/final f32)", run(w, cfg, ids, lens, allof(r16, res=ident, gout=ident, final=ident)), ref)
@@ -118,11 +51,6 @@ if __name__ == "__main__":
     if not R6B: report("all f32 (numpy f32 products)", run(w, cfg, ids, lens, allof(ident)), ref)
     # ---- round 6: the TWO-product candidates: one operand of every product carried as a 16-bit pair, the other as
     # ONE 16-bit value; hidden state / GEMM results / output in f32 throughout
-    F32 = dict(res=ident, gout=ident, final=ident)
-    WEIGHTS = ['w_qk', 'w_v', 'w_o', 'w_1', 'w_2']
-    ACTS = ['x_qk', 'x_v', 'ctx', 'x_f', 'h']
-    def mode(wfn, afn, **attn):
-        d = dict(F32); d.update({k: wfn for k in WEIGHTS}); d.update({k: afn for k in ACTS}); d.update(attn); return d
     if not R6B: report("r6 fp16 w x split-fp16 a; attention 16-bit x3", run(w, cfg, ids, lens, mode(hf, r22, qk=r16, p=r16, v=r16)), ref)
     if not R6B: report("r6 fp16 w x split-fp16 a; attention q split-fp16, k/v/p fp16", run(w, cfg, ids, lens, mode(hf, r22, q=r22, k=hf, p=hf, v=hf)), ref)
     if not R6B: report("r6 fp16 w x split-fp16 a; attention all fp16", run(w, cfg, ids, lens, mode(hf, r22, qk=hf, p=hf, v=hf)), ref)
@@ -135,9 +63,6 @@ if __name__ == "__main__":
 
     # ---- round 6, second pass: inside MX_PREC_MIXED as built (three products on the attention block, two in the MLP), which products
     # could drop to ONE?  (`python scripts/encoder_rounding_sim.py <pooling> <hidden> <layers> <seed> r6b` prints only these)
-    MIXED = dict(qk=r16, p=r16, v=r16, w_1=hf, w_2=hf, x_f=r22, h=r22)
-    def mixed(**over):
-        d = mode(r16, r16, **MIXED); d.update(over); return d
     if R6B:
         print("-- r6b: single products inside MX_PREC_MIXED")
         report("r6b MX_PREC_MIXED as built", run(w, cfg, ids, lens, mixed()), ref)
