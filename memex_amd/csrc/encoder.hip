@@ -26,6 +26,7 @@
 #include "encoder_kernels.h"
 #include "mx_common.h"
 #include "mx_debug.h"
+#include "mx_owned.h"
 
 using namespace mx;
 
@@ -49,7 +50,7 @@ struct Layer {
     bf16_t *wo2 = nullptr;   // [H, F]
     bf16_t *wf = nullptr;    // wo, wi and wo2 once more, as tail_kernel's per-wave fragment streams (fused tail only)
     float *bo2 = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-    // MX_PREC_BF16X3: the same four matrices with k tripled, [hi | hi | lo] (upload_weight3); the bf16 ones above stay null
+    // MX_PREC_BF16X3: the same four matrices with k tripled, [hi | hi | lo] (upload_weight3); the four bf16 ones above stay null
     bf16_t *wqkv3 = nullptr, *wo3 = nullptr, *wi3 = nullptr, *wo23 = nullptr;
     // MX_PREC_MIXED: the attention block as in MX_PREC_BF16X3 (wqkv3, wo3), the MLP's two matrices as fp16 with k DOUBLED,
     // [w | w] against activations split as fp16 [hi | lo] (upload_weight2h); wi3 / wo23 stay null
@@ -63,22 +64,26 @@ bool g_enc_setup_done[64] = {};
 std::mutex g_enc_reg_mu;
 std::map<std::string, mx_encoder *> g_enc_registry;
 
+// the per-row workspace of a pass, grown on demand as a whole (ensure_ws; free_ws releases it by assigning an empty one)
+struct RowWorkspace {
+    Dev<bf16_t> x, x1, q, k, vt, ctx, hbuf;
+    // MX_PREC_BF16X3 workspace: f32 hidden state / QKV / GEMM result, split (3x wide) GEMM operands
+    Dev<float> xf, qkvf, af;
+    Dev<bf16_t> xs, ctxs, hs;
+    Dev<int32_t> tok_seq, tok_pos;
+};
+
 }  // namespace
 
-struct mx_encoder {
+struct mx_encoder : RowWorkspace {
     mx_encoder_cfg cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
-    std::vector<void *> allocs;  // every weight buffer (freed on destroy)
+    std::vector<Dev<void>> allocs;  // every weight buffer and fixed workspace: the pointers below and in `layers` are views of them
     float *word = nullptr, *pos = nullptr, *type0 = nullptr, *eg = nullptr, *eb = nullptr;
     std::vector<Layer> layers;
-    // workspace (grown on demand)
     int ws_rows = 0, ws_seqs = 0, ws_ids = 0;
-    bf16_t *x = nullptr, *x1 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *hbuf = nullptr;
-    // MX_PREC_BF16X3 workspace: f32 hidden state / QKV / GEMM result, split (3x wide) GEMM operands
-    float *xf = nullptr, *qkvf = nullptr, *af = nullptr;
-    bf16_t *xs = nullptr, *ctxs = nullptr, *hs = nullptr;
     bool precise = false;
     bool mixed = false;       // MX_PREC_MIXED / MX_PREC_MIXED1: precise, with the MLP on fp16 products
     bool mlp1 = false;        // MX_PREC_MIXED1: ... ONE fp16 product per product in the MLP (weights, input and GELU output one fp16 value each),
@@ -94,10 +99,10 @@ struct mx_encoder {
     bool small_pass = true;   // MEMEX_HIP_DEBUG small=0: small passes take the large-pass kernels (tests, A/B)
     bool attn_f32 = false;    // MEMEX_HIP_DEBUG attn_f32=1: the bf16x3 mode's attention on the f32 MFMA instead of split bf16 products (tests)
     int small_rows = kSmallRows;  // passes of at most this many packed rows take the small-pass layer (MEMEX_HIP_DEBUG small_rows=N)
-    char *h_io = nullptr;     // pinned, device-mapped page of a query-sized host call: ids | lens | embeddings (mx_encoder_encode)
-    int32_t *cu = nullptr, *tok_seq = nullptr, *tok_pos = nullptr, *lens_dev = nullptr, *ids_dev = nullptr;
-    void *attn_plan = nullptr;  // attention work list of the pass in flight (kAttnPlanBytesPerSeq per sequence)
-    float *out_dev = nullptr;
+    Pin<char> h_io;           // pinned, device-mapped page of a query-sized host call: ids | lens | embeddings (mx_encoder_encode)
+    Dev<int32_t> cu, lens_dev, ids_dev;
+    Dev<void> attn_plan;  // attention work list of the pass in flight (kAttnPlanBytesPerSeq per sequence)
+    Dev<float> out_dev;
     bool profiling = false;
     bool fused_tail = false;  // layer tail as one kernel (hidden 384); MEMEX_HIP_DEBUG unfused_tail=1 keeps the three GEMMs
     bool pgemm = true;        // large passes run their GEMMs on pgemm_kernel (encoder_pgemm.hip); MEMEX_HIP_DEBUG pgemm=0: gemm_kernel
@@ -109,9 +114,19 @@ struct mx_encoder {
 
 namespace {
 
+// `bytes` of device memory owned by e->allocs; *dst views it
+template <class T>
+hipError_t alloc_fixed(mx_encoder *e, T **dst, size_t bytes) {
+    Dev<void> b;
+    const hipError_t he = b.alloc_bytes(bytes);
+    if (he != hipSuccess) return he;
+    *dst = static_cast<T *>(b.get());
+    e->allocs.push_back(std::move(b));
+    return hipSuccess;
+}
+
 int upload_f32(mx_encoder *e, const float *src, size_t n, float **dst) {
-    MX_HIP(hipMalloc(dst, n * sizeof(float)));
-    e->allocs.push_back(*dst);
+    MX_HIP(alloc_fixed(e, dst, n * sizeof(float)));
     MX_HIP(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
     return MX_OK;
 }
@@ -122,8 +137,7 @@ int upload_weight(mx_encoder *e, const float *src, size_t rows, size_t k, bf16_t
     std::vector<uint16_t> tmp(rows * k);
     for (size_t r = 0; r < rows; ++r)
         for (size_t c = 0; c < k; ++c) tmp[((c >> 5) * rows + r) * 32 + (c & 31)] = f32_to_bf16(src[r * k + c]);
-    MX_HIP(hipMalloc(dst, tmp.size() * sizeof(uint16_t)));
-    e->allocs.push_back(*dst);
+    MX_HIP(alloc_fixed(e, dst, tmp.size() * sizeof(uint16_t)));
     MX_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return MX_OK;
 }
@@ -145,8 +159,7 @@ int upload_weight3(mx_encoder *e, const float *src, size_t rows, size_t k, bf16_
             at(r, k + c) = hi;
             at(r, 2 * k + c) = lo;
         }
-    MX_HIP(hipMalloc(dst, tmp.size() * sizeof(uint16_t)));
-    e->allocs.push_back(*dst);
+    MX_HIP(alloc_fixed(e, dst, tmp.size() * sizeof(uint16_t)));
     MX_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return MX_OK;
 }
@@ -166,8 +179,7 @@ int upload_weight2h(mx_encoder *e, const float *src, size_t rows, size_t k, bf16
             at(r, c) = bits;
             if (copies == 2) at(r, k + c) = bits;
         }
-    MX_HIP(hipMalloc(dst, tmp.size() * sizeof(uint16_t)));
-    e->allocs.push_back(*dst);
+    MX_HIP(alloc_fixed(e, dst, tmp.size() * sizeof(uint16_t)));
     MX_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return MX_OK;
 }
@@ -176,21 +188,14 @@ int upload_weight2h(mx_encoder *e, const float *src, size_t rows, size_t k, bf16
 int upload_tail_stream(mx_encoder *e, const float *wo, const float *wi, const float *wo2, size_t F, bf16_t **dst) {
     std::vector<uint16_t> st(tail_stream_elems((int)F));
     tail_stream_layout(wo, wi, wo2, (int)F, st.data(), &f32_to_bf16);
-    MX_HIP(hipMalloc(dst, st.size() * sizeof(uint16_t)));
-    e->allocs.push_back(*dst);
+    MX_HIP(alloc_fixed(e, dst, st.size() * sizeof(uint16_t)));
     MX_HIP(hipMemcpy(*dst, st.data(), st.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return MX_OK;
 }
 
 void free_ws(mx_encoder *e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);  // nothing queued may still use the buffers
-    void *ptrs[] = {e->x, e->x1, e->q, e->k, e->vt, e->ctx, e->hbuf, e->tok_seq, e->tok_pos, e->xf, e->qkvf, e->af, e->xs, e->ctxs, e->hs};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    e->x = e->x1 = e->q = e->k = e->vt = e->ctx = e->hbuf = nullptr;
-    e->xf = e->qkvf = e->af = nullptr;
-    e->xs = e->ctxs = e->hs = nullptr;
-    e->tok_seq = e->tok_pos = nullptr;
+    static_cast<RowWorkspace &>(*e) = RowWorkspace{};
     e->ws_rows = 0;
 }
 
@@ -199,54 +204,41 @@ int ensure_ws(mx_encoder *e, int rows, int seqs, int n_ids) {
     if (rows > e->ws_rows) {
         free_ws(e);
         const size_t r = (size_t)rows;
+        auto zalloc = [&](auto &b, size_t count) -> hipError_t {  // (bf16_t and uint16_t: two bytes each)
+            hipError_t he = b.alloc(count);
+            return he != hipSuccess ? he : hipMemsetAsync(b, 0, count * sizeof(*b.get()), e->stream);
+        };
         if (e->precise) {
-            auto zalloc = [&](void **b, size_t bytes) -> hipError_t {
-                hipError_t he = hipMalloc(b, bytes);
-                return he != hipSuccess ? he : hipMemsetAsync(*b, 0, bytes, e->stream);
-            };
-            MX_HIP(zalloc((void **)&e->xf, r * H * sizeof(float)));
-            MX_HIP(zalloc((void **)&e->qkvf, r * 3 * H * sizeof(float)));
-            MX_HIP(zalloc((void **)&e->af, r * H * sizeof(float)));
-            MX_HIP(zalloc((void **)&e->xs, r * 3 * H * sizeof(uint16_t)));
-            MX_HIP(zalloc((void **)&e->ctxs, r * 3 * H * sizeof(uint16_t)));
-            MX_HIP(zalloc((void **)&e->hs, r * 3 * F * sizeof(uint16_t)));
-        }
-        bf16_t **bufs[] = {&e->x, &e->q, &e->k, &e->vt, &e->ctx};
-        for (bf16_t **b : bufs) {
-            if (e->precise) break;
-            MX_HIP(hipMalloc(b, r * H * sizeof(uint16_t)));
-            MX_HIP(hipMemsetAsync(*b, 0, r * H * sizeof(uint16_t), e->stream));
+            MX_HIP(zalloc(e->xf, r * H));
+            MX_HIP(zalloc(e->qkvf, r * 3 * H));
+            MX_HIP(zalloc(e->af, r * H));
+            MX_HIP(zalloc(e->xs, r * 3 * H));
+            MX_HIP(zalloc(e->ctxs, r * 3 * H));
+            MX_HIP(zalloc(e->hs, r * 3 * F));
+        } else {
+            for (Dev<bf16_t> *b : {&e->x, &e->q, &e->k, &e->vt, &e->ctx}) MX_HIP(zalloc(*b, r * H));
         }
         if (!e->fused_tail && !e->precise) {  // x1 [rows, H] and the [rows, ffn] MLP intermediate only exist GEMM by GEMM:
             // the fused tail kernel keeps both on chip (and is the faster path at every pass size, a
             // single short query included: 0.49 vs 0.58 ms)
-            MX_HIP(hipMalloc(&e->x1, r * H * sizeof(uint16_t)));
-            MX_HIP(hipMemsetAsync(e->x1, 0, r * H * sizeof(uint16_t), e->stream));
-            MX_HIP(hipMalloc(&e->hbuf, r * F * sizeof(uint16_t)));
-            MX_HIP(hipMemsetAsync(e->hbuf, 0, r * F * sizeof(uint16_t), e->stream));
+            MX_HIP(zalloc(e->x1, r * H));
+            MX_HIP(zalloc(e->hbuf, r * F));
         }
-        MX_HIP(hipMalloc(&e->tok_seq, r * sizeof(int32_t)));
-        MX_HIP(hipMalloc(&e->tok_pos, r * sizeof(int32_t)));
+        MX_HIP(e->tok_seq.alloc(r));
+        MX_HIP(e->tok_pos.alloc(r));
         e->ws_rows = rows;
     }
     if (seqs > e->ws_seqs) {
-        if (e->cu) (void)hipFree(e->cu);
-        if (e->lens_dev) (void)hipFree(e->lens_dev);
-        if (e->out_dev) (void)hipFree(e->out_dev);
-        if (e->attn_plan) (void)hipFree(e->attn_plan);
-        e->cu = nullptr; e->lens_dev = nullptr; e->out_dev = nullptr; e->attn_plan = nullptr;
         e->ws_seqs = 0;
-        MX_HIP(hipMalloc(&e->cu, ((size_t)seqs + 1) * sizeof(int32_t)));
-        MX_HIP(hipMalloc(&e->lens_dev, (size_t)seqs * sizeof(int32_t)));
-        MX_HIP(hipMalloc(&e->out_dev, (size_t)seqs * H * sizeof(float)));
-        MX_HIP(hipMalloc(&e->attn_plan, (size_t)seqs * kAttnPlanBytesPerSeq));
+        MX_HIP(e->cu.alloc((size_t)seqs + 1));
+        MX_HIP(e->lens_dev.alloc((size_t)seqs));
+        MX_HIP(e->out_dev.alloc((size_t)seqs * H));
+        MX_HIP(e->attn_plan.alloc_bytes((size_t)seqs * kAttnPlanBytesPerSeq));
         e->ws_seqs = seqs;
     }
     if (n_ids > e->ws_ids) {
-        if (e->ids_dev) (void)hipFree(e->ids_dev);
-        e->ids_dev = nullptr;
         e->ws_ids = 0;
-        MX_HIP(hipMalloc(&e->ids_dev, (size_t)n_ids * sizeof(int32_t)));
+        MX_HIP(e->ids_dev.alloc((size_t)n_ids));
         e->ws_ids = n_ids;
     }
     return MX_OK;
@@ -605,14 +597,14 @@ int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nby
         MX_TRY(upload_f32(e, g1_src, H, &L.ln1g));
         MX_TRY(upload_f32(e, be1_src, H, &L.ln1b));
         const float *wi_src = take(F * H);
-        if (e->precise && !e->mixed) MX_TRY(upload_weight3(e, wi_src, F, H, &L.wi3));
         if (e->mixed) MX_TRY(upload_weight2h(e, wi_src, F, H, &L.wi2h, e->mlp1 ? 1 : 2));
+        else if (e->precise) MX_TRY(upload_weight3(e, wi_src, F, H, &L.wi3));
         else MX_TRY(upload_weight(e, wi_src, F, H, &L.wi));
         const float *b1_src = take(F);
         MX_TRY(upload_f32(e, b1_src, F, &L.bi));
         const float *wo2_src = take(H * F);
-        if (e->precise && !e->mixed) MX_TRY(upload_weight3(e, wo2_src, H, F, &L.wo23));
         if (e->mixed) MX_TRY(upload_weight2h(e, wo2_src, H, F, &L.wo22h, e->mlp1 ? 1 : 2));
+        else if (e->precise) MX_TRY(upload_weight3(e, wo2_src, H, F, &L.wo23));
         else MX_TRY(upload_weight(e, wo2_src, H, F, &L.wo2));
         if (e->fused_tail) MX_TRY(upload_tail_stream(e, wo_src, wi_src, wo2_src, F, &L.wf));
         const float *b2_src = take(H), *g2_src = take(H), *be2_src = take(H);
@@ -623,34 +615,20 @@ int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nby
     if (!e->fused_tail && !e->precise && H == 768) {
         e->split_small = debug_flag("splitk", 1) != 0 && debug_flag("small", 1) != 0;  // (small=0: one kernel set at every pass size)
         if (e->split_small) {
-            void *pp = nullptr, *pz = nullptr;
-            if (hipMalloc(&pp, (size_t)kSplitMax * kSplitRows * H * sizeof(float)) != hipSuccess || hipMalloc(&pz, (size_t)3 * H * sizeof(float)) != hipSuccess ||
-                hipMemset(pz, 0, (size_t)3 * H * sizeof(float)) != hipSuccess) {
-                if (pp) (void)hipFree(pp);
-                if (pz) (void)hipFree(pz);
+            if (alloc_fixed(e, &e->sk_part, (size_t)kSplitMax * kSplitRows * H * sizeof(float)) != hipSuccess ||
+                alloc_fixed(e, &e->sk_zero, (size_t)3 * H * sizeof(float)) != hipSuccess ||
+                hipMemset(e->sk_zero, 0, (size_t)3 * H * sizeof(float)) != hipSuccess)
                 return bail(fail(MX_ENOMEM, "hipMalloc(split-k workspace) failed"));
-            }
-            e->allocs.push_back(pp);
-            e->allocs.push_back(pz);
-            e->sk_part = static_cast<float *>(pp);
-            e->sk_zero = static_cast<float *>(pz);
         }
     }
     if (e->small_pass) {
-        void *px = nullptr, *pp = nullptr;
         {   // where the small-pass layer hands over to the bulk kernels (a multiple of 64)
             const int v = debug_flag("small_rows", 0);
             if (v >= 64 && v <= 16384) e->small_rows = v / 64 * 64;
         }
-        if (hipMalloc(&px, (size_t)e->small_rows * H * sizeof(uint16_t)) != hipSuccess ||
-            hipMalloc(&pp, (size_t)(F / 128) * e->small_rows * H * sizeof(float)) != hipSuccess) {
-            if (px) (void)hipFree(px);
+        if (alloc_fixed(e, &e->sp_x1, (size_t)e->small_rows * H * sizeof(uint16_t)) != hipSuccess ||
+            alloc_fixed(e, &e->sp_part, (size_t)(F / 128) * e->small_rows * H * sizeof(float)) != hipSuccess)
             return bail(fail(MX_ENOMEM, "hipMalloc(small-pass workspace) failed"));
-        }
-        e->allocs.push_back(px);
-        e->allocs.push_back(pp);
-        e->sp_x1 = static_cast<bf16_t *>(px);
-        e->sp_part = static_cast<float *>(pp);
     }
 #undef MX_TRY
     *out = e;
@@ -663,18 +641,12 @@ static void destroy_impl(mx_encoder *e) {
     if (!e) return;
     DeviceGuard g(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (void *p : e->allocs) (void)hipFree(p);
-    free_ws(e);
-    void *ptrs[] = {e->cu, e->lens_dev, e->ids_dev, e->out_dev, e->attn_plan};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->ev_done) (void)hipEventDestroy(e->ev_done);
     if (e->ev_wait) (void)hipEventDestroy(e->ev_wait);
     if (e->stream) (void)hipStreamDestroy(e->stream);
-    if (e->h_io) (void)hipHostFree(e->h_io);
-    delete e;
+    delete e;  // (the buffers go as members, this device current)
 }
 
 void mx_encoder_destroy(mx_encoder *e) {
@@ -770,11 +742,11 @@ int mx_encoder_encode(mx_encoder *e, const int32_t *ids, const int32_t *lens, in
     // D2H copy behind the last one were ~40 us of a 0.27 ms call.
     if ((size_t)B * S <= kIoIds && B <= kIoSeqs) {
         if (!e->h_io) {
-            MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->h_io), kIoBytes(e->cfg.hidden), hipHostMallocMapped | hipHostMallocCoherent));
+            MX_HIP(e->h_io.alloc(kIoBytes(e->cfg.hidden), hipHostMallocMapped | hipHostMallocCoherent));
         }
         rc = ensure_ws(e, 0, B, 0);
         if (rc != MX_OK) return rc;
-        int32_t *io_ids = reinterpret_cast<int32_t *>(e->h_io), *io_lens = io_ids + kIoIds;
+        int32_t *io_ids = reinterpret_cast<int32_t *>(e->h_io.get()), *io_lens = io_ids + kIoIds;
         float *io_out = reinterpret_cast<float *>(io_lens + kIoSeqs);
         memcpy(io_ids, ids, (size_t)B * S * sizeof(int32_t));
         memcpy(io_lens, lens, (size_t)B * sizeof(int32_t));

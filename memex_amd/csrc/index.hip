@@ -45,6 +45,7 @@
 #include "mx_common.h"
 #include "mx_debug.h"
 #include "mx_filter_bits.h"
+#include "mx_owned.h"
 #include "shard_pool.h"
 
 namespace mx {
@@ -70,45 +71,45 @@ constexpr int kAutoI8MaxDim = 1024;  // filter copy of an f32 corpus: int8 (scan
 constexpr int kSumWords = 5;  // max overflow code, candidates, any bad query, e1 of query 0, seq
 
 struct Scratch {
-    void *qfrag = nullptr;
-    float *qpad = nullptr;
-    double *qnorm2 = nullptr;
-    float *theta = nullptr, *theta_retry = nullptr;
-    uint32_t *todo = nullptr;
-    uint32_t *dev_flags = nullptr;   // [kFlagWords]
-    uint32_t *host_flags = nullptr;  // pinned mirror of dev_flags [kFlagWords] (D2H copy, rare)
-    uint32_t *host_sum = nullptr;    // pinned, device-visible [kSumWords]: written by finish_kernel's last workgroup
+    Dev<void> qfrag;
+    Dev<float> qpad;
+    Dev<double> qnorm2;
+    Dev<float> theta, theta_retry;
+    Dev<uint32_t> todo;
+    Dev<uint32_t> dev_flags;   // [kFlagWords]
+    Pin<uint32_t> host_flags;  // pinned mirror of dev_flags [kFlagWords] (D2H copy, rare)
+    Pin<uint32_t> host_sum;    // pinned, device-visible [kSumWords]: written by finish_kernel's last workgroup
     bool out_on_host = false;        // this batch's output pointers are mapped host memory (run_combined)
-    uint32_t *done_ctr = nullptr;    // finish_kernel's workgroup counter
+    Dev<uint32_t> done_ctr;    // finish_kernel's workgroup counter
     uint32_t flag_seq = 0;           // sequence number of the last finish launch
     uint32_t *overflow = nullptr, *cand_cnt = nullptr, *qflags = nullptr;  // views into dev_flags
     float *e1 = nullptr;
-    float *lane_rec = nullptr;       // records of the collect launch (ScanParams)
+    float *lane_rec = nullptr;       // records of the collect launch (ScanParams); leased (LaneLease), like the four below
     uint32_t *lane_tile = nullptr;
     uint32_t *lane_cnt = nullptr;
     float *lane_max = nullptr;
     uint32_t *lane_arg = nullptr;    // the row behind each lane maximum (sample launch of the plain int8 copy)
-    float *qstage = nullptr;       // [256, dim] host->device query staging
-    float *qscale = nullptr;       // [256] quantisation step of each query (8-bit filter copy)
-    float *qa = nullptr, *qb = nullptr;  // [256] a row's filter-score bound is qa + qb * residual (launch_prep_queries)
-    float *qmean = nullptr;        // [256] a_q of the centred bf16 copy
-    uint64_t *out_ids = nullptr;   // [256, kcap] device outputs for the host API
-    float *out_scores = nullptr;
-    float *out_dists = nullptr;
-    int32_t *out_nfound = nullptr;
+    Dev<float> qstage;       // [256, dim] host->device query staging
+    Dev<float> qscale;       // [256] quantisation step of each query (8-bit filter copy)
+    Dev<float> qa, qb;       // [256] a row's filter-score bound is qa + qb * residual (launch_prep_queries)
+    Dev<float> qmean;        // [256] a_q of the centred bf16 copy
+    Dev<uint64_t> out_ids;   // [256, kcap] device outputs for the host API
+    Dev<float> out_scores;
+    Dev<float> out_dists;
+    Dev<int32_t> out_nfound;
     int kcap = 0;
-    void *exact_scratch = nullptr;  // EXACT path: distances of a query group, selection state (exact_group_scratch_bytes)
+    Dev<void> exact_scratch;  // EXACT path: distances of a query group, selection state (exact_group_scratch_bytes)
     size_t exact_bytes = 0;
-    float *max_err = nullptr;
+    Dev<float> max_err;
     // pinned staging of the host API: queries in, results out (one H2D / D2H per combined batch)
-    float *h_q = nullptr;
-    uint64_t *h_ids = nullptr;
-    float *h_scores = nullptr, *h_dists = nullptr;
-    int32_t *h_nf = nullptr;
+    Pin<float> h_q;
+    Pin<uint64_t> h_ids;
+    Pin<float> h_scores, h_dists;
+    Pin<int32_t> h_nf;
     // range search (range_batch): per-query dist bound, device and pinned counts
-    uint32_t *rlim = nullptr;      // [kMaxBatch] dlim of the batch (launch_range_theta)
-    uint64_t *out_nrange = nullptr;  // [kMaxBatch] device n_in_range of a combined sharded pass
-    uint64_t *h_nr = nullptr;      // [kMaxBatch] pinned, mapped: n_in_range of a combined pass
+    Dev<uint32_t> rlim;        // [kMaxBatch] dlim of the batch (launch_range_theta)
+    Dev<uint64_t> out_nrange;  // [kMaxBatch] device n_in_range of a combined sharded pass
+    Pin<uint64_t> h_nr;        // [kMaxBatch] pinned, mapped: n_in_range of a combined pass
     bool ready = false;
 };
 
@@ -192,9 +193,9 @@ struct mx_index {
     std::deque<SearchReq *> pending;
     bool leader = false;
     hipStream_t stream = nullptr;
-    float *x = nullptr;
-    float *scale = nullptr;
-    void *xh = nullptr;          // bf16 filter copy (fragment order), cap/32 tiles; null = not kept
+    Dev<float> x;
+    Dev<float> scale;
+    Dev<void> xh;          // bf16 filter copy (fragment order), cap/32 tiles; null = not kept
     bool want_filter = true;     // keep a filter copy when HBM allows (mx_index_set_filter_copy)
     // 8-bit filter copy (scan8.hip): xh holds int8 fragments in 64-row tiles, tsc one quantisation step per 32-row
     // half tile.  An f32 corpus only; the compressed corpus keeps its bf16 rows.
@@ -206,27 +207,27 @@ struct mx_index {
                                    // that started small, or off a cone, is looked at again once it has doubled (add_device_locked)
     uint64_t demoted_at_rows = 0;  // rows the index held when an automatic int8 copy was demoted to bf16 (0: never); the
                                    // int8 copy gets another try once the collection has doubled (add_device_locked)
-    float *tsc = nullptr;
+    Dev<float> tsc;
     // centred bf16 copy (f32 corpus, up to kMaxKC slots; launch_shadow): `amean` lives with every such copy, `centred` says
     // whether it was built around `mean` (a full rebuild of a populated index: a demotion, mx_index_set_filter_copy)
-    float *amean = nullptr;      // [cap] a_c = (c/|c|) . mean
-    float *mean = nullptr;       // [ds] unit direction; msum: [ds] scratch of its computation
-    float *msum = nullptr;
+    Dev<float> amean;      // [cap] a_c = (c/|c|) . mean
+    Dev<float> mean;       // [ds] unit direction; msum: [ds] scratch of its computation
+    Dev<float> msum;
     bool centred = false;
     // compressed corpus (mx_index_set_corpus_mode): xh is the ONLY copy of the rows; x / scale are not
     // allocated, appends pass through the small f32 staging window xs / ss
     bool compressed = false;
     bool raw_ingest = false;     // rows being appended are stored values coming back from disk: no renormalisation
-    float *xs = nullptr, *ss = nullptr;
+    Dev<float> xs, ss;
     uint64_t xs_rows = 0;
     uint64_t n = 0, cap = 0;
     IdMap idmap{0, 0, 1, 0};
-    uint32_t *flags = nullptr;  // device: [0] non-finite rows, [1] out-of-range-norm rows (last add), [2] ec_max (float bits), [3] zero-norm rows, [4] listed out-of-range-norm rows,
+    Dev<uint32_t> flags;  // device: [0] non-finite rows, [1] out-of-range-norm rows (last add), [2] ec_max (float bits), [3] zero-norm rows, [4] listed out-of-range-norm rows,
                                 // [5] rc_max (float bits): max |r_c| of a centred int8 copy
     uint64_t wild_rows = 0;         // rows with a norm outside [1e-15, 1e15] (a compressed corpus answers on the EXACT path then)
-    uint32_t *zero_rows = nullptr;  // device: [kZeroCap] local rows with zero norm, ascending (finish_kernel adds them to every query)
+    Dev<uint32_t> zero_rows;  // device: [kZeroCap] local rows with zero norm, ascending (finish_kernel adds them to every query)
     uint64_t n_zero = 0;            // zero-norm rows in the index; more than kZeroCap -> EXACT path
-    uint32_t *wild_list = nullptr;  // device: [kWildCap] local rows with a norm outside [1e-15, 1e15] (f32 corpus), ascending
+    Dev<uint32_t> wild_list;  // device: [kWildCap] local rows with a norm outside [1e-15, 1e15] (f32 corpus), ascending
     uint64_t n_wild = 0;            // ... how many; more than kWildCap -> EXACT path
     int mode = MX_SEARCH_AUTO;
     bool profiling = false;
@@ -245,7 +246,7 @@ struct mx_index {
     // removed rows (mx_index_remove): tombstones, ids stay.  A plain index (or shard) keeps one dead-row word per 64-row scan tile
     // on the device ([cap / 64], allocated at the first removal, grown with the capacity) and its host copy; the scans and
     // finish_kernel see the device mask only while n_dead > 0, so an index without removals runs the kernels it always ran
-    uint64_t *dead = nullptr;
+    Dev<uint64_t> dead;
     std::vector<uint64_t> dead_h;
     uint64_t n_dead = 0;            // rows removed (a composite: over its shards)
     std::vector<uint64_t> dead_log;  // the handle's removals in the order made, global rows without id offset (vectors.mxdead)
@@ -257,11 +258,11 @@ struct mx_index {
     // filtered search (mx_index_search_filtered): the per-call mask -- dead words | rows outside the filter, [cap / 64]
     // words, reallocated when the capacity grows past it and rewritten by filter_mask_kernel before every masked pass -- the
     // device copy of the local ranges it is built from, and the row list of the subset kernel ([kSubsetCap])
-    uint64_t *filt = nullptr;
+    Dev<uint64_t> filt;
     size_t filt_words = 0;
-    uint64_t *filt_ranges = nullptr;
+    Dev<uint64_t> filt_ranges;
     size_t filt_ranges_cap = 0;     // pairs
-    uint32_t *subset_rows = nullptr;
+    Dev<uint32_t> subset_rows;
     bool last_subset = false;       // the last search_batch answered on the subset kernel
     // resident filters (mx_filter).  row_epoch (the handle's): how many times the rows were renumbered or replaced
     // (clear, load, a compaction that dropped rows) -- a filter made before the last one is stale.  dead_ver (every plain index or
@@ -272,32 +273,32 @@ struct mx_index {
     // row list of a gather launch and -- the handle's own index, or a shard on another device than shards[0] -- the block the
     // gathered rows go to (at most kMmrStageBytes).  The index that owns the stream (shards[0] of a composite) also holds the
     // candidate stage's lists [kMaxBatch, mmr_fcap], their pinned mirrors and the candidates' positions in the block.
-    uint32_t *mmr_rows = nullptr;
-    float *mmr_stage = nullptr;
+    Dev<uint32_t> mmr_rows;
+    Dev<float> mmr_stage;
     size_t mmr_stage_bytes = 0;
-    uint64_t *mmr_ids = nullptr, *mmr_h_ids = nullptr;
-    float *mmr_scores = nullptr, *mmr_dists = nullptr;
-    int32_t *mmr_nf = nullptr, *mmr_h_nf = nullptr;
-    uint32_t *mmr_pos = nullptr;
+    Dev<uint64_t> mmr_ids; Pin<uint64_t> mmr_h_ids;
+    Dev<float> mmr_scores, mmr_dists;
+    Dev<int32_t> mmr_nf; Pin<int32_t> mmr_h_nf;
+    Dev<uint32_t> mmr_pos;
     int mmr_fcap = 0;
     // search by stored row (mx_index_search_by_id), allocated at the first such call.  Every plain index or shard: the
     // row list of a gather launch [kMaxBatch] and -- a shard on another device than shards[0] -- the block its rows go to before the
     // peer copy [kMaxBatch, dim].  The index that owns the stream also holds the query block [kMaxBatch, dim], the pass's own lists
     // [kMaxBatch, byid_cap] with their counts, and per query its place in them, its id and its dist bound.
-    uint32_t *byid_rows = nullptr;
-    float *byid_stage = nullptr;
-    float *byid_q = nullptr;
-    uint64_t *byid_ids = nullptr, *byid_nr = nullptr, *byid_own = nullptr;
-    float *byid_scores = nullptr, *byid_dists = nullptr;
-    int32_t *byid_nf = nullptr;
-    uint32_t *byid_src = nullptr, *byid_dlim = nullptr;
+    Dev<uint32_t> byid_rows;
+    Dev<float> byid_stage;
+    Dev<float> byid_q;
+    Dev<uint64_t> byid_ids, byid_nr, byid_own;
+    Dev<float> byid_scores, byid_dists;
+    Dev<int32_t> byid_nf;
+    Dev<uint32_t> byid_src, byid_dlim;
     int byid_cap = 0;
     // fused search (mx_index_search_fused), allocated at the first such call on the index that owns the stream: a
     // chunk's weights [kMaxBatch] and, for the host-pointer variant, best_sub and fused [kMaxBatch, kFuseMaxFetch].  The candidate
     // lists are the diversified search's (mmr_ids ...).
-    float *fuse_w = nullptr;
-    int32_t *fuse_best = nullptr;
-    double *fuse_val = nullptr;
+    Dev<float> fuse_w;
+    Dev<int32_t> fuse_best;
+    Dev<double> fuse_val;
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -309,13 +310,14 @@ struct mx_index {
     uint64_t total = 0;
     bool use_rccl = false;
     std::vector<void *> comms;       // ncclComm_t per shard (RCCL exchange)
-    std::vector<void *> sh_block;    // per shard, on its device: packed result block [ids | dists]
-    std::vector<void *> sh_gather;   // per shard, on its device: [G] packed blocks (RCCL recv); [0] is the merge input
-    std::vector<float *> sh_q, sh_scores;
-    std::vector<int32_t *> sh_nf;
+    std::vector<Dev<void>> sh_block;    // per shard, on its device: packed result block [ids | dists]
+    std::vector<Dev<void>> sh_gather;   // per shard, on its device: [G] packed blocks (RCCL recv); [0] is the merge input
+    std::vector<Dev<float>> sh_q, sh_scores;
+    std::vector<Dev<int32_t>> sh_nf;
     int sh_kcap = 0;
     std::unique_ptr<ShardPool> pool;  // helper threads for shards 1 .. G-1 (shards on distinct devices only)
     bool composite() const { return !shards.empty(); }
+    ~mx_index();  // with `device` current (free_index, open_plain); the buffers go as members, after the stream is idle
 };
 
 // A resident filter: one allow bit per row, kept on every plain index or shard of the handle it was made for,
@@ -323,12 +325,12 @@ struct mx_index {
 // edits a filter holds the handle's mutex.
 struct FilterShard {
     int device = 0;                  // where the shard's rows live
-    uint64_t *bits = nullptr;        // device: [words], bit r & 63 of word r >> 6 = local row r is in the set
+    Dev<uint64_t> bits;        // device: [words], bit r & 63 of word r >> 6 = local row r is in the set
     size_t words = 0;                // grows to the index's capacity words at the next edit; rows past it are not in the set
     std::vector<uint64_t> bits_h;    // host mirror [words]
-    uint64_t *stage = nullptr;       // device: the ranges or ids of the edit in progress
+    Dev<uint64_t> stage;       // device: the ranges or ids of the edit in progress
     size_t stage_words = 0;
-    uint32_t *list = nullptr;        // device: [kSubsetCap] the live allowed rows, ascending (launch_filter_list), while list_ok
+    Dev<uint32_t> list;        // device: [kSubsetCap] the live allowed rows, ascending (launch_filter_list), while list_ok
     // what a search needs, valid while `cached` and cached_dead == the index's dead_ver
     bool cached = false, list_ok = false;
     uint64_t cached_dead = 0;
@@ -373,18 +375,36 @@ bool load_rccl() {
 void free_composite_buffers(mx_index *idx) {
     for (size_t g = 0; g < idx->shards.size(); ++g) {
         DeviceGuard dg(idx->shards[g]->device);
-        auto F = [](void *p) {
-            if (p) (void)hipFree(p);
-        };
-        if (g < idx->sh_block.size()) F(idx->sh_block[g]);
-        if (g < idx->sh_gather.size()) F(idx->sh_gather[g]);
-        if (g < idx->sh_q.size()) F(idx->sh_q[g]);
-        if (g < idx->sh_scores.size()) F(idx->sh_scores[g]);
-        if (g < idx->sh_nf.size()) F(idx->sh_nf[g]);
+        if (g < idx->sh_block.size()) idx->sh_block[g].reset();
+        if (g < idx->sh_gather.size()) idx->sh_gather[g].reset();
+        if (g < idx->sh_q.size()) idx->sh_q[g].reset();
+        if (g < idx->sh_scores.size()) idx->sh_scores[g].reset();
+        if (g < idx->sh_nf.size()) idx->sh_nf[g].reset();
     }
     idx->sh_block.clear(); idx->sh_gather.clear(); idx->sh_q.clear(); idx->sh_scores.clear(); idx->sh_nf.clear();
     idx->sh_kcap = 0;
 }
+
+}  // namespace
+
+mx_index::~mx_index() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (ev_wait) (void)hipEventDestroy(ev_wait);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (pooled && device >= 0 && device < kMaxDevices) {  // the last index on the device takes the lane-buffer pool with it
+        LanePool &lp = g_lanes[device];
+        std::lock_guard<std::mutex> lk(lp.mu);
+        if (--lp.open_indexes <= 0) {
+            lp.open_indexes = 0;
+            for (LaneBufs &b : lp.idle) lane_free(b);
+            lp.idle.clear();
+        }
+    }
+}
+
+namespace {
 
 int free_index(mx_index *idx) {
     {   // nobody may still be inside a call on this handle (a combined search holds idx->mu)
@@ -403,43 +423,14 @@ int free_index(mx_index *idx) {
         idx->shards.clear();
     }
     DeviceGuard g(idx->device);
-    if (idx->stream) (void)hipStreamSynchronize(idx->stream);
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    F(idx->x); F(idx->scale); F(idx->xh); F(idx->tsc); F(idx->flags); F(idx->xs); F(idx->ss); F(idx->zero_rows); F(idx->wild_list);
-    F(idx->amean); F(idx->mean); F(idx->msum); F(idx->dead); F(idx->filt); F(idx->filt_ranges); F(idx->subset_rows);
-    F(idx->mmr_rows); F(idx->mmr_stage); F(idx->mmr_ids); F(idx->mmr_scores); F(idx->mmr_dists); F(idx->mmr_nf); F(idx->mmr_pos);
-    if (idx->mmr_h_ids) (void)hipHostFree(idx->mmr_h_ids);
-    if (idx->mmr_h_nf) (void)hipHostFree(idx->mmr_h_nf);
-    F(idx->byid_rows); F(idx->byid_stage); F(idx->byid_q); F(idx->byid_ids); F(idx->byid_nr); F(idx->byid_own); F(idx->byid_scores);
-    F(idx->byid_dists); F(idx->byid_nf); F(idx->byid_src); F(idx->byid_dlim);
-    F(idx->fuse_w); F(idx->fuse_best); F(idx->fuse_val);
-    Scratch &s = idx->s;
-    F(s.qfrag); F(s.qpad); F(s.qnorm2); F(s.theta); F(s.theta_retry); F(s.todo); F(s.dev_flags); F(s.done_ctr);
-    if (s.host_flags) (void)hipHostFree(s.host_flags);
-    if (s.host_sum) (void)hipHostFree(s.host_sum);
-    for (void *hp : {(void *)s.h_q, (void *)s.h_ids, (void *)s.h_scores, (void *)s.h_dists, (void *)s.h_nf, (void *)s.h_nr})
-        if (hp) (void)hipHostFree(hp);
-    F(s.rlim); F(s.out_nrange);
-    F(s.qstage); F(s.qscale); F(s.qa); F(s.qb); F(s.qmean); F(s.out_ids); F(s.out_scores); F(s.out_dists); F(s.out_nfound);
-    F(s.exact_scratch); F(s.max_err);
-    if (idx->ev0) (void)hipEventDestroy(idx->ev0);
-    if (idx->ev1) (void)hipEventDestroy(idx->ev1);
-    if (idx->ev_wait) (void)hipEventDestroy(idx->ev_wait);
-    if (idx->stream) (void)hipStreamDestroy(idx->stream);
-    if (idx->pooled && idx->device >= 0 && idx->device < kMaxDevices) {  // the last index on the device takes the lane-buffer pool with it
-        LanePool &lp = g_lanes[idx->device];
-        std::lock_guard<std::mutex> lk(lp.mu);
-        if (--lp.open_indexes <= 0) {
-            lp.open_indexes = 0;
-            for (LaneBufs &b : lp.idle) lane_free(b);
-            lp.idle.clear();
-        }
-    }
     delete idx;
     return MX_OK;
 }
+
+// a handle under construction: whatever it holds by then (a composite: its shards) goes with it on any failure
+struct IndexCloser {
+    void operator()(mx_index *idx) const { free_index(idx); }
+};
 
 // One set of lane buffers for the duration of a search_batch call (see LanePool).
 struct LaneLease {
@@ -502,36 +493,40 @@ struct LaneLease {
 int ensure_scratch(mx_index *idx) {
     Scratch &s = idx->s;
     if (s.ready) return MX_OK;
+    // a call that failed part-way left some of these allocated (zero-fills maybe still queued): alloc releases what a buffer held,
+    // so nothing leaks, and the set is complete and zero-filled again before `ready` is set
+    if (s.qfrag) MX_HIP(hipStreamSynchronize(idx->stream));
     const size_t ds = (size_t)idx->ds;
-    MX_HIP(hipMalloc(&s.qfrag, (size_t)kMaxBatch * ds * 2));
-    MX_HIP(hipMalloc(&s.qpad, (size_t)kMaxBatch * ds * 4));
-    MX_HIP(hipMalloc(&s.qnorm2, kMaxBatch * sizeof(double)));
-    MX_HIP(hipMalloc(&s.theta, kMaxBatch * sizeof(float)));
-    MX_HIP(hipMalloc(&s.theta_retry, kMaxBatch * sizeof(float)));
-    MX_HIP(hipMalloc(&s.todo, kMaxBatch * sizeof(uint32_t)));
-    MX_HIP(hipMalloc(&s.dev_flags, kFlagWords * sizeof(uint32_t)));
+    const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
+    MX_HIP(s.qfrag.alloc_bytes((size_t)kMaxBatch * ds * 2));
+    MX_HIP(s.qpad.alloc((size_t)kMaxBatch * ds));
+    MX_HIP(s.qnorm2.alloc(kMaxBatch));
+    MX_HIP(s.theta.alloc(kMaxBatch));
+    MX_HIP(s.theta_retry.alloc(kMaxBatch));
+    MX_HIP(s.todo.alloc(kMaxBatch));
+    MX_HIP(s.dev_flags.alloc(kFlagWords));
     MX_HIP(hipMemsetAsync(s.dev_flags, 0, kFlagWords * sizeof(uint32_t), idx->stream));
     s.overflow = s.dev_flags;
     s.cand_cnt = s.dev_flags + kMaxBatch;
     s.e1 = reinterpret_cast<float *>(s.dev_flags + 2 * kMaxBatch);
     s.qflags = s.dev_flags + 3 * kMaxBatch;
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.host_flags), kFlagWords * sizeof(uint32_t), hipHostMallocDefault));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.host_sum), kSumWords * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    MX_HIP(s.host_flags.alloc(kFlagWords, hipHostMallocDefault));
+    MX_HIP(s.host_sum.alloc(kSumWords, mapped));
     memset(s.host_sum, 0, kSumWords * sizeof(uint32_t));
-    MX_HIP(hipMalloc(&s.done_ctr, sizeof(uint32_t)));
+    MX_HIP(s.done_ctr.alloc(1));
     MX_HIP(hipMemsetAsync(s.done_ctr, 0, sizeof(uint32_t), idx->stream));
-    MX_HIP(hipMalloc(&s.qstage, (size_t)kMaxBatch * idx->dim * sizeof(float)));
-    MX_HIP(hipMalloc(&s.qscale, kMaxBatch * sizeof(float)));
-    MX_HIP(hipMalloc(&s.qa, kMaxBatch * sizeof(float)));
-    MX_HIP(hipMalloc(&s.qb, kMaxBatch * sizeof(float)));
-    MX_HIP(hipMalloc(&s.qmean, kMaxBatch * sizeof(float)));
+    MX_HIP(s.qstage.alloc((size_t)kMaxBatch * idx->dim));
+    MX_HIP(s.qscale.alloc(kMaxBatch));
+    MX_HIP(s.qa.alloc(kMaxBatch));
+    MX_HIP(s.qb.alloc(kMaxBatch));
+    MX_HIP(s.qmean.alloc(kMaxBatch));
     MX_HIP(hipMemsetAsync(s.qmean, 0, kMaxBatch * sizeof(float), idx->stream));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_q), (size_t)kMaxBatch * idx->dim * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_nf), kMaxBatch * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
-    MX_HIP(hipMalloc(&s.max_err, sizeof(float)));
-    MX_HIP(hipMalloc(&s.rlim, kMaxBatch * sizeof(uint32_t)));
-    MX_HIP(hipMalloc(&s.out_nrange, kMaxBatch * sizeof(uint64_t)));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_nr), kMaxBatch * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
+    MX_HIP(s.h_q.alloc((size_t)kMaxBatch * idx->dim, mapped));
+    MX_HIP(s.h_nf.alloc(kMaxBatch, mapped));
+    MX_HIP(s.max_err.alloc(1));
+    MX_HIP(s.rlim.alloc(kMaxBatch));
+    MX_HIP(s.out_nrange.alloc(kMaxBatch));
+    MX_HIP(s.h_nr.alloc(kMaxBatch, mapped));
     MX_HIP(hipMemsetAsync(s.max_err, 0, sizeof(float), idx->stream));
     s.ready = true;
     return MX_OK;
@@ -540,23 +535,16 @@ int ensure_scratch(mx_index *idx) {
 int ensure_out(mx_index *idx, int k) {
     Scratch &s = idx->s;
     if (k <= s.kcap) return MX_OK;
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    F(s.out_ids); F(s.out_scores); F(s.out_dists); F(s.out_nfound);
-    s.out_ids = nullptr; s.out_scores = nullptr; s.out_dists = nullptr; s.out_nfound = nullptr;
-    for (void *hp : {(void *)s.h_ids, (void *)s.h_scores, (void *)s.h_dists})
-        if (hp) (void)hipHostFree(hp);
-    s.h_ids = nullptr; s.h_scores = nullptr; s.h_dists = nullptr;
     s.kcap = 0;
     const int kc = std::max(k, 16);
-    MX_HIP(hipMalloc(&s.out_ids, (size_t)kMaxBatch * kc * sizeof(uint64_t)));
-    MX_HIP(hipMalloc(&s.out_scores, (size_t)kMaxBatch * kc * sizeof(float)));
-    MX_HIP(hipMalloc(&s.out_dists, (size_t)kMaxBatch * kc * sizeof(float)));
-    MX_HIP(hipMalloc(&s.out_nfound, kMaxBatch * sizeof(int32_t)));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_ids), (size_t)kMaxBatch * kc * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_scores), (size_t)kMaxBatch * kc * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_dists), (size_t)kMaxBatch * kc * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+    const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
+    MX_HIP(s.out_ids.alloc((size_t)kMaxBatch * kc));
+    MX_HIP(s.out_scores.alloc((size_t)kMaxBatch * kc));
+    MX_HIP(s.out_dists.alloc((size_t)kMaxBatch * kc));
+    MX_HIP(s.out_nfound.alloc(kMaxBatch));
+    MX_HIP(s.h_ids.alloc((size_t)kMaxBatch * kc, mapped));
+    MX_HIP(s.h_scores.alloc((size_t)kMaxBatch * kc, mapped));
+    MX_HIP(s.h_dists.alloc((size_t)kMaxBatch * kc, mapped));
     s.kcap = kc;
     return MX_OK;
 }
@@ -572,18 +560,15 @@ int ensure_exact(mx_index *idx, int k, int *gcap) {
             *gcap = g;
             return MX_OK;
         }
-        if (s.exact_scratch) {
-            MX_HIP(hipStreamSynchronize(idx->stream));
-            (void)hipFree(s.exact_scratch);
-        }
-        s.exact_scratch = nullptr;
+        if (s.exact_scratch) MX_HIP(hipStreamSynchronize(idx->stream));
+        s.exact_scratch.reset();
         s.exact_bytes = 0;
         const size_t want = need + need / 4;  // room for appends before the next reallocation
-        if (hipMalloc(&s.exact_scratch, want) == hipSuccess) {
+        if (s.exact_scratch.alloc_bytes(want) == hipSuccess) {
             s.exact_bytes = want;
         } else {
             (void)hipGetLastError();
-            if (hipMalloc(&s.exact_scratch, need) == hipSuccess) s.exact_bytes = need;
+            if (s.exact_scratch.alloc_bytes(need) == hipSuccess) s.exact_bytes = need;
             else (void)hipGetLastError();
         }
         if (s.exact_bytes >= need) {
@@ -594,31 +579,17 @@ int ensure_exact(mx_index *idx, int k, int *gcap) {
     }
 }
 
-// device buffers being built by ensure_capacity: freed unless handed over
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    void *release() {
-        void *r = p;
-        p = nullptr;
-        return r;
-    }
-};
-
 // the dead-row mask covers `cap` rows (one word per 64-row tile); words past the old size start with no row removed
 int grow_dead(mx_index *idx, uint64_t cap) {
     if (!idx->dead) return MX_OK;  // allocated by the first removal
     const size_t words = (size_t)(cap / kTile8Rows), have = idx->dead_h.size();
     if (words <= have) return MX_OK;
-    DevBuf nd;
-    MX_HIP(hipMalloc(&nd.p, words * sizeof(uint64_t)));
-    MX_HIP(hipMemcpyAsync(nd.p, idx->dead, have * sizeof(uint64_t), hipMemcpyDeviceToDevice, idx->stream));
-    MX_HIP(hipMemsetAsync(static_cast<uint64_t *>(nd.p) + have, 0, (words - have) * sizeof(uint64_t), idx->stream));
+    Dev<uint64_t> nd;
+    MX_HIP(nd.alloc(words));
+    MX_HIP(hipMemcpyAsync(nd, idx->dead, have * sizeof(uint64_t), hipMemcpyDeviceToDevice, idx->stream));
+    MX_HIP(hipMemsetAsync(nd + have, 0, (words - have) * sizeof(uint64_t), idx->stream));
     MX_HIP(hipStreamSynchronize(idx->stream));
-    (void)hipFree(idx->dead);
-    idx->dead = static_cast<uint64_t *>(nd.release());
+    idx->dead = std::move(nd);
     idx->dead_h.resize(words, 0);
     return MX_OK;
 }
@@ -629,23 +600,23 @@ int ensure_capacity(mx_index *idx, uint64_t rows) {
     want = round_up(std::max<uint64_t>(want, 1024), kTile8Rows);
     if (int rc = grow_dead(idx, want); rc != MX_OK) return rc;
     if (idx->compressed) {  // the bf16 copy is the corpus: it must grow, there is nothing to fall back to
-        DevBuf nh2;
+        Dev<void> nh2;
         const size_t hb = (size_t)want * idx->ds * 2;
-        MX_HIP(hipMalloc(&nh2.p, hb));
+        MX_HIP(nh2.alloc_bytes(hb));
         const size_t used = idx->xh ? (size_t)round_up(idx->n, kTileRows) * idx->ds * 2 : 0;
-        if (used) MX_HIP(hipMemcpyAsync(nh2.p, idx->xh, used, hipMemcpyDeviceToDevice, idx->stream));
-        MX_HIP(hipMemsetAsync(static_cast<char *>(nh2.p) + used, 0, hb - used, idx->stream));
+        if (used) MX_HIP(hipMemcpyAsync(nh2, idx->xh, used, hipMemcpyDeviceToDevice, idx->stream));
+        MX_HIP(hipMemsetAsync(static_cast<char *>(nh2.get()) + used, 0, hb - used, idx->stream));
         MX_HIP(hipStreamSynchronize(idx->stream));
-        if (idx->xh) (void)hipFree(idx->xh);
-        idx->xh = nh2.release();
+        idx->xh = std::move(nh2);
         idx->cap = want;
         return MX_OK;
     }
-    DevBuf nx, nsc, nh, nts, nam;
+    Dev<float> nx, nsc, nts, nam;
+    Dev<void> nh;
     const size_t rowb = (size_t)idx->ds * sizeof(float);
-    MX_HIP(hipMalloc(&nx.p, want * rowb));
-    MX_HIP(hipMalloc(&nsc.p, want * sizeof(float)));
-    float *fx = static_cast<float *>(nx.p), *fsc = static_cast<float *>(nsc.p);
+    MX_HIP(nx.alloc(want * (size_t)idx->ds));
+    MX_HIP(nsc.alloc(want));
+    float *fx = nx, *fsc = nsc;
     if (idx->n) {
         MX_HIP(hipMemcpyAsync(fx, idx->x, idx->n * rowb, hipMemcpyDeviceToDevice, idx->stream));
         MX_HIP(hipMemcpyAsync(fsc, idx->scale, idx->n * sizeof(float), hipMemcpyDeviceToDevice, idx->stream));
@@ -657,69 +628,63 @@ int ensure_capacity(mx_index *idx, uint64_t rows) {
         // keeps working on the f32 scan
         const size_t eb = idx->filter_i8 ? 1 : 2;  // bytes per stored element
         const size_t hb = (size_t)want * idx->ds * eb, tb = (size_t)(want / kTile8Rows) * kTscaleFloats * sizeof(float);
-        if (hipMalloc(&nh.p, hb) != hipSuccess || (idx->filter_i8 && hipMalloc(&nts.p, tb) != hipSuccess)) {
+        if (nh.alloc_bytes(hb) != hipSuccess || (idx->filter_i8 && nts.alloc_bytes(tb) != hipSuccess)) {
             (void)hipGetLastError();
-            if (nh.p) (void)hipFree(nh.release());
-            nh.p = nullptr;
+            nh.reset();
         } else {
             const uint64_t used_rows = idx->xh ? round_up(idx->n, kTile8Rows) : 0;
             const size_t used = (size_t)used_rows * idx->ds * eb;
-            if (used) MX_HIP(hipMemcpyAsync(nh.p, idx->xh, used, hipMemcpyDeviceToDevice, idx->stream));
-            MX_HIP(hipMemsetAsync(static_cast<char *>(nh.p) + used, 0, hb - used, idx->stream));
+            if (used) MX_HIP(hipMemcpyAsync(nh, idx->xh, used, hipMemcpyDeviceToDevice, idx->stream));
+            MX_HIP(hipMemsetAsync(static_cast<char *>(nh.get()) + used, 0, hb - used, idx->stream));
             if (idx->filter_i8) {
                 const size_t tused = (size_t)(used_rows / kTile8Rows) * kTscaleFloats * sizeof(float);
-                if (tused) MX_HIP(hipMemcpyAsync(nts.p, idx->tsc, tused, hipMemcpyDeviceToDevice, idx->stream));
-                MX_HIP(hipMemsetAsync(static_cast<char *>(nts.p) + tused, 0, tb - tused, idx->stream));
+                if (tused) MX_HIP(hipMemcpyAsync(nts, idx->tsc, tused, hipMemcpyDeviceToDevice, idx->stream));
+                MX_HIP(hipMemsetAsync(reinterpret_cast<char *>(nts.get()) + tused, 0, tb - tused, idx->stream));
                 if (idx->centred && idx->xh && idx->amean) {
                     // the a_c array of a CENTRED int8 copy grows with it; without room for it the copy is rewritten plain from the rows
-                    if (hipMalloc(&nam.p, want * sizeof(float)) == hipSuccess) {
+                    if (nam.alloc(want) == hipSuccess) {
                         const size_t aused = (size_t)used_rows * sizeof(float);
-                        MX_HIP(hipMemcpyAsync(nam.p, idx->amean, std::min(aused, (size_t)idx->cap * sizeof(float)), hipMemcpyDeviceToDevice, idx->stream));
-                        if (want * sizeof(float) > aused) MX_HIP(hipMemsetAsync(static_cast<char *>(nam.p) + aused, 0, want * sizeof(float) - aused, idx->stream));
+                        MX_HIP(hipMemcpyAsync(nam, idx->amean, std::min(aused, (size_t)idx->cap * sizeof(float)), hipMemcpyDeviceToDevice, idx->stream));
+                        if (want * sizeof(float) > aused) MX_HIP(hipMemsetAsync(reinterpret_cast<char *>(nam.get()) + aused, 0, want * sizeof(float) - aused, idx->stream));
                     } else {
                         (void)hipGetLastError();
                         if (idx->n) {
                             const uint32_t t1c = (uint32_t)((idx->n + kTileRows - 1) / kTileRows);
-                            MX_HIP(launch_shadow8(idx->stream, fx, fsc, idx->ds, 0, (uint32_t)round_up(t1c, 2), idx->n, nh.p, static_cast<float *>(nts.p), idx->flags + 2));
+                            MX_HIP(launch_shadow8(idx->stream, fx, fsc, idx->ds, 0, (uint32_t)round_up(t1c, 2), idx->n, nh, nts, idx->flags + 2));
                         }
                     }
                 }
-            } else if (idx->kc <= kMaxKC && hipMalloc(&nam.p, want * sizeof(float)) == hipSuccess) {
+            } else if (idx->kc <= kMaxKC && nam.alloc(want) == hipSuccess) {
                 // the a_c array of a (possibly centred) bf16 copy grows with it
                 const size_t aused = idx->amean && idx->xh ? (size_t)idx->n * sizeof(float) : 0;
-                if (aused) MX_HIP(hipMemcpyAsync(nam.p, idx->amean, aused, hipMemcpyDeviceToDevice, idx->stream));
-                MX_HIP(hipMemsetAsync(static_cast<char *>(nam.p) + aused, 0, want * sizeof(float) - aused, idx->stream));
+                if (aused) MX_HIP(hipMemcpyAsync(nam, idx->amean, aused, hipMemcpyDeviceToDevice, idx->stream));
+                MX_HIP(hipMemsetAsync(reinterpret_cast<char *>(nam.get()) + aused, 0, want * sizeof(float) - aused, idx->stream));
             } else {
                 (void)hipGetLastError();
                 if (idx->centred && idx->xh && idx->n) {
                     // no room for the a_c array of a CENTRED copy: the fragments just copied hold c/|c| - a_c m and would be
                     // read as c/|c| -- rewrite the copy as a plain one from the rows (rare: 4 bytes per row did not fit)
                     const uint32_t t1c = (uint32_t)((idx->n + kTileRows - 1) / kTileRows);
-                    MX_HIP(launch_shadow(idx->stream, fx, fsc, idx->ds, 0, t1c, nh.p, idx->flags + 2));
+                    MX_HIP(launch_shadow(idx->stream, fx, fsc, idx->ds, 0, t1c, nh, idx->flags + 2));
                 }
             }
             if (!idx->xh && idx->n) {  // (re)enabled on a populated index
                 const uint32_t t1 = (uint32_t)((idx->n + kTileRows - 1) / kTileRows);
                 if (idx->filter_i8)
-                    MX_HIP(launch_shadow8(idx->stream, fx, fsc, idx->ds, 0, t1, idx->n, nh.p, static_cast<float *>(nts.p), idx->flags + 2));
+                    MX_HIP(launch_shadow8(idx->stream, fx, fsc, idx->ds, 0, t1, idx->n, nh, nts, idx->flags + 2));
                 else
-                    MX_HIP(launch_shadow(idx->stream, fx, fsc, idx->ds, 0, t1, nh.p, idx->flags + 2));
+                    MX_HIP(launch_shadow(idx->stream, fx, fsc, idx->ds, 0, t1, nh, idx->flags + 2));
             }
         }
     }
     MX_HIP(hipStreamSynchronize(idx->stream));
-    if (idx->x) (void)hipFree(idx->x);
-    if (idx->scale) (void)hipFree(idx->scale);
     // (a centred copy stays centred only if its a_c array came along: a copy built afresh above is a plain one)
-    const bool keep_centre = idx->centred && idx->xh && idx->amean && nh.p && nam.p;
-    if (idx->xh) (void)hipFree(idx->xh);
-    if (idx->tsc) (void)hipFree(idx->tsc);
-    if (idx->amean) (void)hipFree(idx->amean);
-    idx->x = static_cast<float *>(nx.release());
-    idx->scale = static_cast<float *>(nsc.release());
-    idx->xh = nh.release();
-    idx->tsc = static_cast<float *>(nts.release());
-    idx->amean = static_cast<float *>(nam.release());
+    const bool keep_centre = idx->centred && idx->xh && idx->amean && nh && nam;
+    idx->x = std::move(nx);
+    idx->scale = std::move(nsc);
+    idx->xh = std::move(nh);
+    idx->tsc = std::move(nts);
+    idx->amean = std::move(nam);
     idx->centred = keep_centre;
     idx->cap = want;
     return MX_OK;
@@ -776,8 +741,8 @@ int add_device_locked(mx_index *idx, const float *d_rows, uint64_t n, uint64_t *
         // to the tile of the first new row; rows of that tile that are already stored are not touched.
         constexpr uint64_t kWin = 65536;
         if (!idx->xs) {
-            MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->xs), (size_t)(kWin + kTileRows) * idx->ds * sizeof(float)));
-            MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->ss), (size_t)(kWin + kTileRows) * sizeof(float)));
+            MX_HIP(idx->xs.alloc((size_t)(kWin + kTileRows) * idx->ds));
+            MX_HIP(idx->ss.alloc((size_t)(kWin + kTileRows)));
             idx->xs_rows = kWin + kTileRows;
         }
         uint32_t fl[5] = {0, 0, 0, 0, 0};
@@ -905,18 +870,20 @@ int run_exact(mx_index *idx, const std::vector<int> &qs, int k, uint64_t *d_ids,
 
 // builds the filter copy of kind (i8 ? int8 : bf16) from the f32 rows, complete before it replaces whatever copy is resident
 int build_filter_copy(mx_index *idx, bool i8) {
-    DevBuf nh, nts, nec, nam;
+    Dev<void> nh;
+    Dev<float> nts, nam;
+    Dev<uint32_t> nec;
     const size_t hb = (size_t)idx->cap * idx->ds * (i8 ? 1 : 2), tb = (size_t)(idx->cap / kTile8Rows) * kTscaleFloats * sizeof(float);
-    hipError_t e = hipMalloc(&nh.p, hb);
-    if (e == hipSuccess && i8) e = hipMalloc(&nts.p, tb);
-    if (e == hipSuccess) e = hipMalloc(&nec.p, 2 * sizeof(uint32_t));  // [0] largest residual, [1] longest centred row (int8)
+    hipError_t e = nh.alloc_bytes(hb);
+    if (e == hipSuccess && i8) e = nts.alloc_bytes(tb);
+    if (e == hipSuccess) e = nec.alloc(2);  // [0] largest residual, [1] longest centred row (int8)
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(MX_ENOMEM, "hipMalloc(filter copy, %zu bytes): %s", hb, hipGetErrorString(e));
     }
-    uint32_t *ec = static_cast<uint32_t *>(nec.p);
-    MX_HIP(hipMemsetAsync(nh.p, 0, hb, idx->stream));
-    if (i8) MX_HIP(hipMemsetAsync(nts.p, 0, tb, idx->stream));
+    uint32_t *ec = nec;
+    MX_HIP(hipMemsetAsync(nh, 0, hb, idx->stream));
+    if (i8) MX_HIP(hipMemsetAsync(nts, 0, tb, idx->stream));
     MX_HIP(hipMemsetAsync(ec, 0, 2 * sizeof(uint32_t), idx->stream));
     const uint32_t t1 = (uint32_t)((idx->n + kTileRows - 1) / kTileRows);
     // A copy rebuilt from a populated index is CENTRED on the rows' mean direction (launch_shadow / launch_shadow8): a corpus
@@ -925,11 +892,11 @@ int build_filter_copy(mx_index *idx, bool i8) {
     // the rounding (bf16) or quantisation (int8: round 6) error the scan's certificate has to cover.
     const bool centre_ok = true;
     bool centre = false;
-    if (idx->kc <= kMaxKC && !idx->compressed && hipMalloc(&nam.p, (size_t)idx->cap * sizeof(float)) == hipSuccess) {
-        MX_HIP(hipMemsetAsync(nam.p, 0, (size_t)idx->cap * sizeof(float), idx->stream));
+    if (idx->kc <= kMaxKC && !idx->compressed && nam.alloc((size_t)idx->cap) == hipSuccess) {
+        MX_HIP(hipMemsetAsync(nam, 0, (size_t)idx->cap * sizeof(float), idx->stream));
         if (centre_ok && idx->n >= 256) {
-            if (!idx->mean) MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->mean), (size_t)idx->ds * sizeof(float)));
-            if (!idx->msum) MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->msum), ((size_t)idx->ds + 1) * sizeof(float)));
+            if (!idx->mean) MX_HIP(idx->mean.alloc((size_t)idx->ds));
+            if (!idx->msum) MX_HIP(idx->msum.alloc((size_t)idx->ds + 1));
             MX_HIP(launch_mean_dir(idx->stream, idx->x, idx->scale, idx->n, idx->ds, idx->msum, idx->mean));
             // worth it only for a corpus that does sit in a cone: |mean of the unit rows| = the typical a_c; below 0.3 the
             // centred rows are < 5 % shorter and the scan's extra epilogue work buys nothing
@@ -941,22 +908,19 @@ int build_filter_copy(mx_index *idx, bool i8) {
     } else {
         (void)hipGetLastError();
     }
-    if (i8 && !centre && nam.p) (void)hipFree(nam.release());  // (a plain int8 copy has no use for the a_c array)
+    if (i8 && !centre) nam.reset();  // (a plain int8 copy has no use for the a_c array)
     if (i8)
-        MX_HIP(launch_shadow8(idx->stream, idx->x, idx->scale, idx->ds, 0, (uint32_t)round_up(t1, 2), idx->n, nh.p, static_cast<float *>(nts.p), ec,
-                              centre ? idx->mean : nullptr, centre ? static_cast<float *>(nam.p) : nullptr, centre ? ec + 1 : nullptr));
+        MX_HIP(launch_shadow8(idx->stream, idx->x, idx->scale, idx->ds, 0, (uint32_t)round_up(t1, 2), idx->n, nh, nts, ec,
+                              centre ? idx->mean : nullptr, centre ? nam : nullptr, centre ? ec + 1 : nullptr));
     else
-        MX_HIP(launch_shadow(idx->stream, idx->x, idx->scale, idx->ds, 0, t1, nh.p, ec, 0, 0, ~0ull, centre ? idx->mean : nullptr,
-                             centre ? static_cast<float *>(nam.p) : nullptr));
+        MX_HIP(launch_shadow(idx->stream, idx->x, idx->scale, idx->ds, 0, t1, nh, ec, 0, 0, ~0ull, centre ? idx->mean : nullptr,
+                             centre ? nam : nullptr));
     MX_HIP(hipMemcpyAsync(idx->flags + 2, ec, sizeof(uint32_t), hipMemcpyDeviceToDevice, idx->stream));
     MX_HIP(hipMemcpyAsync(idx->flags + 5, ec + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, idx->stream));
     MX_HIP(hipStreamSynchronize(idx->stream));
-    if (idx->xh) (void)hipFree(idx->xh);
-    if (idx->tsc) (void)hipFree(idx->tsc);
-    if (idx->amean) (void)hipFree(idx->amean);
-    idx->xh = nh.release();
-    idx->tsc = static_cast<float *>(nts.release());
-    idx->amean = static_cast<float *>(nam.release());
+    idx->xh = std::move(nh);
+    idx->tsc = std::move(nts);
+    idx->amean = std::move(nam);
     idx->centred = centre;
     idx->filter_i8 = i8;
     idx->plain_bf16_rows = (!i8 && !centre) ? std::max<uint64_t>(idx->n, 1) : 0;
@@ -1043,11 +1007,9 @@ int build_filter_mask(mx_index *idx, const Ranges &r, std::vector<uint64_t> &fla
     const size_t words = (size_t)(idx->cap / kTile8Rows);
     if (int rc = ensure_mask_words(idx, words); rc != MX_OK) return rc;
     if (idx->filt_ranges_cap < std::max<size_t>(r.size(), 1)) {
-        if (idx->filt_ranges) (void)hipFree(idx->filt_ranges);
-        idx->filt_ranges = nullptr;
         idx->filt_ranges_cap = 0;
         const size_t want = std::max<size_t>(r.size() + r.size() / 2, 64);
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->filt_ranges), want * 2 * sizeof(uint64_t)));
+        MX_HIP(idx->filt_ranges.alloc(want * 2));
         idx->filt_ranges_cap = want;
     }
     flat.resize(2 * r.size());
@@ -1109,10 +1071,8 @@ void refresh_filter_shard(const mx_index *t, FilterShard &fs) {
 // the index-owned mask buffer of a masked pass covers the capacity
 int ensure_mask_words(mx_index *idx, size_t words) {
     if (idx->filt_words >= words) return MX_OK;
-    if (idx->filt) (void)hipFree(idx->filt);  // (every batch before this one is host-synchronised)
-    idx->filt = nullptr;
     idx->filt_words = 0;
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->filt), words * sizeof(uint64_t)));
+    MX_HIP(idx->filt.alloc(words));  // (every batch before this one is host-synchronised)
     idx->filt_words = words;
     return MX_OK;
 }
@@ -1317,8 +1277,7 @@ int fetch_flags(mx_index *idx) {
 // a large exact scratch does not stay behind a fallback batch (the stream is idle)
 void drop_large_exact_scratch(mx_index *idx) {
     if (idx->mode != MX_SEARCH_AUTO || idx->s.exact_bytes <= kExactKeepBytes) return;
-    (void)hipFree(idx->s.exact_scratch);
-    idx->s.exact_scratch = nullptr;
+    idx->s.exact_scratch.reset();
     idx->s.exact_bytes = 0;
 }
 
@@ -1371,7 +1330,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
         std::vector<uint32_t> list;
         const uint32_t *rows_list = nullptr;
         if (res) {  // the filter's own list, compacted on the device and kept until the filter or the removals change
-            if (!res->list) MX_HIP(hipMalloc(reinterpret_cast<void **>(&res->list), (size_t)kSubsetCap * sizeof(uint32_t)));
+            if (!res->list) MX_HIP(res->list.alloc((size_t)kSubsetCap));
             if (!res->list_ok) {
                 MX_HIP(hipMemsetAsync(res->list, 0, (size_t)kSubsetCap * sizeof(uint32_t), st));  // (no entry is ever an arbitrary row)
                 MX_HIP(launch_filter_list(st, idx->n_dead ? idx->dead : nullptr, res->bits, span_lo >> 6, (span_hi + 63) >> 6, res->list,
@@ -1384,7 +1343,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
             for (const auto &x : fr)
                 for (uint64_t r = x.first; r < x.second; ++r)
                     if (!idx->n_dead || !((idx->dead_h[r >> 6] >> (r & 63)) & 1ull)) list.push_back((uint32_t)r);
-            if (!idx->subset_rows) MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->subset_rows), (size_t)kSubsetCap * sizeof(uint32_t)));
+            if (!idx->subset_rows) MX_HIP(idx->subset_rows.alloc((size_t)kSubsetCap));
             MX_HIP(hipMemcpyAsync(idx->subset_rows, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             rows_list = idx->subset_rows;
         }
@@ -1745,15 +1704,15 @@ int ensure_composite_buffers(mx_index *idx, int k) {
     const int kc = std::max(k, 16);
     const size_t G = idx->shards.size();
     const size_t blk = (size_t)kMaxBatch * kc * 12 + kMaxBatch * sizeof(uint64_t);  // [ids | dists] (+ the counts of a range pass)
-    idx->sh_block.assign(G, nullptr); idx->sh_gather.assign(G, nullptr); idx->sh_q.assign(G, nullptr);
-    idx->sh_scores.assign(G, nullptr); idx->sh_nf.assign(G, nullptr);
+    idx->sh_block.resize(G); idx->sh_gather.resize(G); idx->sh_q.resize(G);
+    idx->sh_scores.resize(G); idx->sh_nf.resize(G);
     for (size_t g = 0; g < G; ++g) {
         DeviceGuard dg(idx->shards[g]->device);
-        MX_HIP(hipMalloc(&idx->sh_block[g], blk));
-        if (g == 0 || idx->use_rccl) MX_HIP(hipMalloc(&idx->sh_gather[g], blk * G));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->sh_q[g]), (size_t)kMaxBatch * idx->dim * sizeof(float)));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->sh_scores[g]), (size_t)kMaxBatch * kc * sizeof(float)));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->sh_nf[g]), kMaxBatch * sizeof(int32_t)));
+        MX_HIP(idx->sh_block[g].alloc_bytes(blk));
+        if (g == 0 || idx->use_rccl) MX_HIP(idx->sh_gather[g].alloc_bytes(blk * G));
+        MX_HIP(idx->sh_q[g].alloc((size_t)kMaxBatch * idx->dim));
+        MX_HIP(idx->sh_scores[g].alloc((size_t)kMaxBatch * kc));
+        MX_HIP(idx->sh_nf[g].alloc(kMaxBatch));
     }
     idx->sh_kcap = kc;
     return MX_OK;
@@ -1790,12 +1749,12 @@ void enable_peer_access(mx_index *idx) {
 bool rccl_selftest(mx_index *idx, double seconds) {
     const int G = (int)idx->shards.size();
     std::vector<hipStream_t> st(G, nullptr);
-    std::vector<unsigned char *> snd(G, nullptr), rcv(G, nullptr);
+    std::vector<Dev<unsigned char>> snd(G), rcv(G);
     bool ok = true;
     for (int g = 0; g < G && ok; ++g) {
         DeviceGuard dg(idx->shards[g]->device);
-        ok = hipStreamCreateWithFlags(&st[g], hipStreamNonBlocking) == hipSuccess && hipMalloc(&snd[g], 64) == hipSuccess &&
-             hipMalloc(&rcv[g], 64 * (size_t)G) == hipSuccess && hipMemsetAsync(snd[g], g + 1, 64, st[g]) == hipSuccess &&
+        ok = hipStreamCreateWithFlags(&st[g], hipStreamNonBlocking) == hipSuccess && snd[g].alloc(64) == hipSuccess &&
+             rcv[g].alloc(64 * (size_t)G) == hipSuccess && hipMemsetAsync(snd[g], g + 1, 64, st[g]) == hipSuccess &&
              hipMemsetAsync(rcv[g], 0, 64 * (size_t)G, st[g]) == hipSuccess;
     }
     bool hung = false;
@@ -1831,12 +1790,14 @@ bool rccl_selftest(mx_index *idx, double seconds) {
     }
     if (hung) {
         fprintf(stderr, "memex-hip: the RCCL self-test did not complete within %.0f s; exchanging by peer copies\n", seconds);
-        return false;  // the collective may still own the streams and buffers: leave them
+        // the collective may still own the streams and buffers: leave them (the buffers move to a holder that is never freed)
+        new std::pair<std::vector<Dev<unsigned char>>, std::vector<Dev<unsigned char>>>(std::move(snd), std::move(rcv));
+        return false;
     }
     for (int g = 0; g < G; ++g) {
         DeviceGuard dg(idx->shards[g]->device);
-        if (snd[g]) (void)hipFree(snd[g]);
-        if (rcv[g]) (void)hipFree(rcv[g]);
+        snd[g].reset();
+        rcv[g].reset();
         if (st[g]) (void)hipStreamDestroy(st[g]);
     }
     (void)hipGetLastError();
@@ -1871,11 +1832,11 @@ int exchange_and_merge(mx_index *idx, const float *d_q, int B, int k, size_t blk
         DeviceGuard dg(sh->device);
         auto run = [&]() -> int {
             MX_HIP(hipMemcpyAsync(idx->sh_q[g], d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
-            char *blkp = static_cast<char *>(idx->sh_block[g]);
+            char *blkp = static_cast<char *>(idx->sh_block[g].get());
             int r = local(g, sh, idx->sh_q[g], blkp);
             if (r != MX_OK) return r;
             if (!idx->use_rccl && exchange) {  // peer copy into slot g of the gather area on shards[0]'s device
-                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
+                MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0].get()) + (size_t)g * blk, blkp, blk, hipMemcpyDefault, sh->stream));
                 MX_HIP(hipStreamSynchronize(sh->stream));
             }
             return MX_OK;
@@ -1934,14 +1895,14 @@ int exchange_and_merge(mx_index *idx, const float *d_q, int B, int k, size_t blk
                 idx->stats.exchange_fallbacks += 1;
                 enable_peer_access(idx);
                 for (int g = 0; g < G; ++g)  // (the shards left their blocks in place for the all-gather)
-                    MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0]) + (size_t)g * blk, idx->sh_block[g], blk, hipMemcpyDefault, s0->stream));
+                    MX_HIP(hipMemcpyAsync(static_cast<char *>(idx->sh_gather[0].get()) + (size_t)g * blk, idx->sh_block[g], blk, hipMemcpyDefault, s0->stream));
             }
             // no host wait on shards >= 1: their part of the collective is ordered on their own streams (the
             // next batch's kernels queue behind it), and the merge below follows shard 0's part in stream order
         }
-        const char *gat = static_cast<const char *>(idx->sh_gather[0]);
+        const char *gat = static_cast<const char *>(idx->sh_gather[0].get());
         MX_HIP(launch_merge(s0->stream, gat, blk, gat + ids_bytes, blk, G, B, k, d_ids,
-                            d_dists ? d_dists : reinterpret_cast<float *>(static_cast<char *>(idx->sh_block[0]) + ids_bytes), d_scores));
+                            d_dists ? d_dists : reinterpret_cast<float *>(static_cast<char *>(idx->sh_block[0].get()) + ids_bytes), d_scores));
     }
     MX_HIP(tail(s0->stream));
     MX_HIP(hipStreamSynchronize(s0->stream));
@@ -2027,7 +1988,7 @@ int composite_range_batch(mx_index *idx, const float *d_q, int B, int cap, const
                            idx->sh_nf[g], reinterpret_cast<uint64_t *>(blkp + lists));
     };
     auto tail = [&](hipStream_t st) {
-        return launch_range_sum(st, static_cast<const char *>(idx->sh_gather[0]) + lists, blk, G, B, cap, d_nrange, d_nfound);
+        return launch_range_sum(st, static_cast<const char *>(idx->sh_gather[0].get()) + lists, blk, G, B, cap, d_nrange, d_nfound);
     };
     return exchange_and_merge(idx, d_q, B, cap, blk, true, d_ids, d_scores, d_dists, local, tail);
 }
@@ -2054,23 +2015,15 @@ bool locate_row(const mx_index *idx, uint64_t id, size_t *shard, uint64_t *local
 int ensure_mmr_lists(mx_index *t, int fetch) {
     if (fetch <= t->mmr_fcap) return MX_OK;
     MX_HIP(hipStreamSynchronize(t->stream));
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    F(t->mmr_ids); F(t->mmr_scores); F(t->mmr_dists); F(t->mmr_nf); F(t->mmr_pos);
-    if (t->mmr_h_ids) (void)hipHostFree(t->mmr_h_ids);
-    if (t->mmr_h_nf) (void)hipHostFree(t->mmr_h_nf);
-    t->mmr_ids = nullptr; t->mmr_scores = nullptr; t->mmr_dists = nullptr; t->mmr_nf = nullptr; t->mmr_pos = nullptr;
-    t->mmr_h_ids = nullptr; t->mmr_h_nf = nullptr;
     t->mmr_fcap = 0;
     const size_t fc = (size_t)std::max(fetch, 64);
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_ids), (size_t)kMaxBatch * fc * sizeof(uint64_t)));
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_scores), (size_t)kMaxBatch * fc * sizeof(float)));
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_dists), (size_t)kMaxBatch * fc * sizeof(float)));
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_nf), kMaxBatch * sizeof(int32_t)));
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->mmr_pos), (size_t)kMaxBatch * fc * sizeof(uint32_t)));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->mmr_h_ids), (size_t)kMaxBatch * fc * sizeof(uint64_t), hipHostMallocDefault));
-    MX_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->mmr_h_nf), kMaxBatch * sizeof(int32_t), hipHostMallocDefault));
+    MX_HIP(t->mmr_ids.alloc((size_t)kMaxBatch * fc));
+    MX_HIP(t->mmr_scores.alloc((size_t)kMaxBatch * fc));
+    MX_HIP(t->mmr_dists.alloc((size_t)kMaxBatch * fc));
+    MX_HIP(t->mmr_nf.alloc(kMaxBatch));
+    MX_HIP(t->mmr_pos.alloc((size_t)kMaxBatch * fc));
+    MX_HIP(t->mmr_h_ids.alloc((size_t)kMaxBatch * fc, hipHostMallocDefault));
+    MX_HIP(t->mmr_h_nf.alloc(kMaxBatch, hipHostMallocDefault));
     t->mmr_fcap = (int)fc;
     return MX_OK;
 }
@@ -2079,14 +2032,12 @@ int ensure_mmr_lists(mx_index *t, int fetch) {
 // current device is sh's
 int ensure_mmr_stage(mx_index *sh, size_t bytes) {
     if (!sh->mmr_rows)
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->mmr_rows), kMmrStageBytes / (kChunkFloats * sizeof(float)) * sizeof(uint32_t)));
+        MX_HIP(sh->mmr_rows.alloc(kMmrStageBytes / (kChunkFloats * sizeof(float))));
     if (bytes <= sh->mmr_stage_bytes) return MX_OK;
     MX_HIP(hipStreamSynchronize(sh->stream));
-    if (sh->mmr_stage) (void)hipFree(sh->mmr_stage);
-    sh->mmr_stage = nullptr;
     sh->mmr_stage_bytes = 0;
     const size_t want = std::min(kMmrStageBytes, (bytes + ((size_t)1 << 20) - 1) >> 20 << 20);
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->mmr_stage), want));
+    MX_HIP(sh->mmr_stage.alloc_bytes(want));
     sh->mmr_stage_bytes = want;
     return MX_OK;
 }
@@ -2178,7 +2129,7 @@ int fused_batch(mx_index *idx, const float *d_q, int nreq, int m, const float *w
     mx_index *t = idx->composite() ? idx->shards[0] : idx;
     int rc = ensure_mmr_lists(t, fetch);
     if (rc != MX_OK) return rc;
-    if (!t->fuse_w) MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->fuse_w), kMaxBatch * sizeof(float)));
+    if (!t->fuse_w) MX_HIP(t->fuse_w.alloc(kMaxBatch));
     const int B = nreq * m;
     if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf)) != MX_OK) return rc;
     hipStream_t st = t->stream;
@@ -2198,25 +2149,20 @@ bool row_removed(const mx_index *t, uint64_t r);
 // the pass's own lists, kk wide, and the per-query words on the index that owns the stream (the current device is its device)
 int ensure_byid_lists(mx_index *t, int kk) {
     if (!t->byid_q) {
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_q), (size_t)kMaxBatch * t->dim * sizeof(float)));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_nf), kMaxBatch * sizeof(int32_t)));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_nr), kMaxBatch * sizeof(uint64_t)));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_own), kMaxBatch * sizeof(uint64_t)));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_src), kMaxBatch * sizeof(uint32_t)));
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_dlim), kMaxBatch * sizeof(uint32_t)));
+        MX_HIP(t->byid_q.alloc((size_t)kMaxBatch * t->dim));
+        MX_HIP(t->byid_nf.alloc(kMaxBatch));
+        MX_HIP(t->byid_nr.alloc(kMaxBatch));
+        MX_HIP(t->byid_own.alloc(kMaxBatch));
+        MX_HIP(t->byid_src.alloc(kMaxBatch));
+        MX_HIP(t->byid_dlim.alloc(kMaxBatch));
     }
     if (kk <= t->byid_cap) return MX_OK;
     MX_HIP(hipStreamSynchronize(t->stream));
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    F(t->byid_ids); F(t->byid_scores); F(t->byid_dists);
-    t->byid_ids = nullptr; t->byid_scores = nullptr; t->byid_dists = nullptr;
     t->byid_cap = 0;
     const size_t c = (size_t)std::max(kk, 64);
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_ids), (size_t)kMaxBatch * c * sizeof(uint64_t)));
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_scores), (size_t)kMaxBatch * c * sizeof(float)));
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->byid_dists), (size_t)kMaxBatch * c * sizeof(float)));
+    MX_HIP(t->byid_ids.alloc((size_t)kMaxBatch * c));
+    MX_HIP(t->byid_scores.alloc((size_t)kMaxBatch * c));
+    MX_HIP(t->byid_dists.alloc((size_t)kMaxBatch * c));
     t->byid_cap = (int)c;
     return MX_OK;
 }
@@ -2263,8 +2209,8 @@ int byid_batch(mx_index *idx, const uint64_t *qids, int B, int k, int exclude, c
         if (idx->composite()) lk.lock();  // (a plain index: the caller holds it)
         DeviceGuard dg(sh->device);
         const bool same = sh->device == t->device;
-        if (!sh->byid_rows) MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->byid_rows), kMaxBatch * sizeof(uint32_t)));
-        if (!same && !sh->byid_stage) MX_HIP(hipMalloc(reinterpret_cast<void **>(&sh->byid_stage), (size_t)kMaxBatch * dim * sizeof(float)));
+        if (!sh->byid_rows) MX_HIP(sh->byid_rows.alloc(kMaxBatch));
+        if (!same && !sh->byid_stage) MX_HIP(sh->byid_stage.alloc((size_t)kMaxBatch * dim));
         MX_HIP(hipMemcpyAsync(sh->byid_rows, rows[g].data(), rows[g].size() * sizeof(uint32_t), hipMemcpyHostToDevice, sh->stream));
         float *slot = t->byid_q + first[g] * (size_t)dim;
         MX_HIP(launch_byid_gather(sh->stream, dim, sh->ds, sh->compressed ? nullptr : sh->x, sh->xh, sh->byid_rows, (uint32_t)rows[g].size(),
@@ -2356,10 +2302,8 @@ int composite_add(mx_index *idx, const float *rows, uint64_t n, uint64_t *first_
         DeviceGuard dg(sh->device);
         uint64_t cnt = 0;
         for (auto &sgm : seg[g]) cnt += sgm.second;
-        float *stage = nullptr;
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&stage), (size_t)cnt * rowf * sizeof(float)));
-        DevBuf hold;
-        hold.p = stage;
+        Dev<float> stage;
+        MX_HIP(stage.alloc((size_t)cnt * rowf));
         uint64_t at = 0;
         for (auto &sgm : seg[g]) {
             MX_HIP(hipMemcpyAsync(stage + (size_t)at * rowf, rows + (size_t)sgm.first * rowf, (size_t)sgm.second * rowf * sizeof(float),
@@ -2481,7 +2425,7 @@ int mark_dead_local(mx_index *idx, const std::vector<uint64_t> &rows, std::vecto
     DeviceGuard dg(idx->device);
     if (!idx->dead) {
         const size_t words = (size_t)(idx->cap / kTile8Rows);
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->dead), words * sizeof(uint64_t)));
+        MX_HIP(idx->dead.alloc(words));
         MX_HIP(hipMemsetAsync(idx->dead, 0, words * sizeof(uint64_t), idx->stream));
         idx->dead_h.assign(words, 0);
     }
@@ -2721,8 +2665,8 @@ int add_host_locked(mx_index *idx, const float *rows, uint64_t n, uint64_t *firs
     for (size_t i = 0; i < total; ++i)
         if (!std::isfinite(rows[i])) return fail(MX_EINVAL, "row %zu contains a non-finite value; nothing inserted", i / idx->dim);
     const uint64_t chunk_rows = std::max<uint64_t>(1, (64ull << 20) / ((uint64_t)idx->dim * 4));
-    float *stage = nullptr;
-    MX_HIP(hipMalloc(&stage, (size_t)std::min(chunk_rows, n) * idx->dim * sizeof(float)));
+    Dev<float> stage;  // (add_device_locked returns host-synchronised)
+    MX_HIP(stage.alloc((size_t)std::min(chunk_rows, n) * idx->dim));
     int rc = MX_OK;
     uint64_t first = 0;
     const RowMark mark = mark_rows(idx);
@@ -2738,7 +2682,6 @@ int add_host_locked(mx_index *idx, const float *rows, uint64_t n, uint64_t *firs
         rc = add_device_locked(idx, stage, m, &f);
         if (done == 0) first = f;
     }
-    (void)hipFree(stage);
     if (rc != MX_OK) rollback_rows(idx, mark);  // a later chunk failed: the earlier ones go too
     if (rc == MX_OK && first_id) *first_id = first;
     return rc;
@@ -2795,10 +2738,10 @@ int open_plain(const std::string &k, int dim, int device, mx_index **out) {
     MX_HIP(hipEventCreate(&idx->ev0));
     MX_HIP(hipEventCreate(&idx->ev1));
     MX_HIP(hipEventCreateWithFlags(&idx->ev_wait, hipEventDisableTiming));
-    MX_HIP(hipMalloc(&idx->flags, 6 * sizeof(uint32_t)));
+    MX_HIP(idx->flags.alloc(6));
     MX_HIP(hipMemset(idx->flags, 0, 6 * sizeof(uint32_t)));
-    MX_HIP(hipMalloc(&idx->zero_rows, kZeroCap * sizeof(uint32_t)));
-    MX_HIP(hipMalloc(&idx->wild_list, kWildCap * sizeof(uint32_t)));
+    MX_HIP(idx->zero_rows.alloc(kZeroCap));
+    MX_HIP(idx->wild_list.alloc(kWildCap));
     if (device < kMaxDevices) {
         std::lock_guard<std::mutex> lk(g_lanes[device].mu);
         g_lanes[device].open_indexes += 1;
@@ -2827,11 +2770,11 @@ int release_capacity(mx_index *idx) {
     if (want >= idx->cap) return MX_OK;
     const size_t ds = (size_t)idx->ds;
     const size_t eb = idx->compressed ? 2 : idx->filter_i8 ? 1 : 2;  // bytes per element of the bf16 / int8 copy
-    DevBuf nx, nsc, nh, nts, nam;
-    auto get = [](DevBuf &b, size_t bytes) {
-        if (hipMalloc(&b.p, bytes) == hipSuccess) return true;
+    Dev<float> nx, nsc, nts, nam;
+    Dev<void> nh;
+    auto get = [](auto &b, size_t bytes) {
+        if (b.alloc_bytes(bytes) == hipSuccess) return true;
         (void)hipGetLastError();
-        b.p = nullptr;
         return false;
     };
     bool ok = idx->compressed || (get(nx, want * ds * 4) && get(nsc, want * sizeof(float)));
@@ -2841,32 +2784,24 @@ int release_capacity(mx_index *idx) {
     if (!ok) return MX_OK;
     const uint64_t used = round_up(idx->n, kTile8Rows);  // rows [n, used) were zeroed by the compaction
     hipStream_t st = idx->stream;
-    auto move = [&](DevBuf &b, const void *old, size_t used_bytes, size_t all_bytes) -> hipError_t {
-        hipError_t e = used_bytes ? hipMemcpyAsync(b.p, old, used_bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
-        if (e == hipSuccess && all_bytes > used_bytes) e = hipMemsetAsync(static_cast<char *>(b.p) + used_bytes, 0, all_bytes - used_bytes, st);
+    auto move = [&](void *b, const void *old, size_t used_bytes, size_t all_bytes) -> hipError_t {
+        hipError_t e = used_bytes ? hipMemcpyAsync(b, old, used_bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && all_bytes > used_bytes) e = hipMemsetAsync(static_cast<char *>(b) + used_bytes, 0, all_bytes - used_bytes, st);
         return e;
     };
     if (!idx->compressed) {
         MX_HIP(move(nx, idx->x, used * ds * 4, want * ds * 4));
         MX_HIP(move(nsc, idx->scale, used * sizeof(float), want * sizeof(float)));
     }
-    if (nh.p) MX_HIP(move(nh, idx->xh, used * ds * eb, want * ds * eb));
-    if (nts.p) MX_HIP(move(nts, idx->tsc, (used / kTile8Rows) * kTscaleFloats * sizeof(float), (want / kTile8Rows) * kTscaleFloats * sizeof(float)));
-    if (nam.p) MX_HIP(move(nam, idx->amean, used * sizeof(float), want * sizeof(float)));
+    if (nh) MX_HIP(move(nh, idx->xh, used * ds * eb, want * ds * eb));
+    if (nts) MX_HIP(move(nts, idx->tsc, (used / kTile8Rows) * kTscaleFloats * sizeof(float), (want / kTile8Rows) * kTscaleFloats * sizeof(float)));
+    if (nam) MX_HIP(move(nam, idx->amean, used * sizeof(float), want * sizeof(float)));
     MX_HIP(hipStreamSynchronize(st));
-    auto swap = [](auto *&dst, DevBuf &b) {
-        if (!b.p) return;
-        if (dst) (void)hipFree(dst);
-        dst = static_cast<std::remove_reference_t<decltype(dst)>>(b.release());
-    };
-    swap(idx->x, nx);
-    swap(idx->scale, nsc);
-    if (nh.p) {
-        (void)hipFree(idx->xh);
-        idx->xh = nh.release();
-    }
-    swap(idx->tsc, nts);
-    swap(idx->amean, nam);
+    if (nx) idx->x = std::move(nx);
+    if (nsc) idx->scale = std::move(nsc);
+    if (nh) idx->xh = std::move(nh);
+    if (nts) idx->tsc = std::move(nts);
+    if (nam) idx->amean = std::move(nam);
     idx->cap = want;
     return MX_OK;
 }
@@ -2894,23 +2829,23 @@ int compact_plain(mx_index *idx, bool *moved) {
                                                (unsigned long long)n_live, (unsigned long long)(n - idx->n_dead));
     if (idx->compressed) t_first = 0;  // the bf16 rows are re-ingested from the first: the zero-norm list is rebuilt whole
     const uint32_t nb = compact_count_blocks(tiles);
-    DevBuf tb, bo, stage, wa, wb;
-    MX_HIP(hipMalloc(&tb.p, std::max<uint64_t>(tiles, 1) * sizeof(uint32_t)));
-    MX_HIP(hipMalloc(&bo.p, ((size_t)nb + 1) * sizeof(uint32_t)));
-    uint32_t *tile_base = static_cast<uint32_t *>(tb.p), *blk_off = static_cast<uint32_t *>(bo.p);
+    Dev<uint32_t> tile_base, blk_off;
+    Dev<float> stage, wa, wb;
+    MX_HIP(tile_base.alloc(std::max<uint64_t>(tiles, 1)));
+    MX_HIP(blk_off.alloc((size_t)nb + 1));
     // staging of a chunk whose destination overlaps its source: 64 MiB of rows, a multiple of 64 rows
     const uint64_t stage_tiles = std::max<uint64_t>(1, (64ull << 20) / (kTile8Rows * ds * 4));
     constexpr uint64_t kWinTiles = 16384 / kTile8Rows;  // compressed corpus: rows widened per chunk (the append path's window holds 65536)
     if (idx->compressed) {
-        MX_HIP(hipMalloc(&wa.p, (size_t)kWinTiles * kTile8Rows * idx->dim * sizeof(float)));
-        MX_HIP(hipMalloc(&wb.p, (size_t)kWinTiles * kTile8Rows * idx->dim * sizeof(float)));
+        MX_HIP(wa.alloc((size_t)kWinTiles * kTile8Rows * idx->dim));
+        MX_HIP(wb.alloc((size_t)kWinTiles * kTile8Rows * idx->dim));
         if (!idx->xs) {
-            MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->xs), (size_t)(65536 + kTileRows) * idx->ds * sizeof(float)));
-            MX_HIP(hipMalloc(reinterpret_cast<void **>(&idx->ss), (size_t)(65536 + kTileRows) * sizeof(float)));
+            MX_HIP(idx->xs.alloc((size_t)(65536 + kTileRows) * idx->ds));
+            MX_HIP(idx->ss.alloc((size_t)(65536 + kTileRows)));
             idx->xs_rows = 65536 + kTileRows;
         }
     } else {
-        MX_HIP(hipMalloc(&stage.p, (size_t)stage_tiles * kTile8Rows * (ds + 1) * sizeof(float)));
+        MX_HIP(stage.alloc((size_t)stage_tiles * kTile8Rows * (ds + 1)));
     }
     MX_HIP(launch_compact_prefix(st, idx->dead, n, tile_base, blk_off));
     uint32_t dev_live = 0;
@@ -2921,7 +2856,7 @@ int compact_plain(mx_index *idx, bool *moved) {
 
     *moved = true;  // ---- from here on rows move: an error leaves the index failed
     if (!idx->compressed) {
-        float *sx = static_cast<float *>(stage.p), *ss = sx + stage_tiles * kTile8Rows * ds;
+        float *sx = stage, *ss = sx + stage_tiles * kTile8Rows * ds;
         for (uint64_t t = t_first; t < tiles;) {
             const uint64_t lag = t * kTile8Rows - hp[t];  // rows removed before tile t
             uint64_t c;
@@ -2974,7 +2909,7 @@ int compact_plain(mx_index *idx, bool *moved) {
     } else {
         // the bf16 fragments are the only copy of the rows: per window, widen them (launch_unshadow), keep the live ones, and
         // append those through the raw-ingest path behind the rows already moved -- how mx_index_load reproduces stored rows
-        float *wa_f = static_cast<float *>(wa.p), *wb_f = static_cast<float *>(wb.p);
+        float *wa_f = wa, *wb_f = wb;
         MX_HIP(hipMemsetAsync(idx->flags + 2, 0, 3 * sizeof(uint32_t), st));
         idx->n = 0;
         idx->n_zero = 0;
@@ -3002,8 +2937,7 @@ int compact_plain(mx_index *idx, bool *moved) {
     }
     MX_HIP(hipStreamSynchronize(st));
     // no row is removed any more: the launchers pass a null mask and run the unmasked kernels again
-    (void)hipFree(idx->dead);
-    idx->dead = nullptr;
+    idx->dead.reset();
     idx->dead_h.clear();
     idx->dead_h.shrink_to_fit();
     idx->n_dead = 0;
@@ -3021,20 +2955,13 @@ int compact_plain(mx_index *idx, bool *moved) {
 // only once complete, so a failure leaves the handle as it was.  Costs HBM for both sets of shards and a trip through host memory.
 int compact_composite(mx_index *idx) {
     const uint64_t R = idx->block_rows, G = idx->shards.size(), total = idx->total;
-    std::unique_ptr<mx_index> fresh(new mx_index());  // a composite shell that composite_add fills
+    std::unique_ptr<mx_index, IndexCloser> fresh(new mx_index());  // a composite shell that composite_add fills; frees the shards it ends up with
     fresh->dim = idx->dim;
     fresh->block_rows = R;
-    auto drop_fresh = [&] {
-        for (mx_index *sh : fresh->shards) free_index(sh);
-        fresh->shards.clear();
-    };
     for (uint64_t g = 0; g < G; ++g) {
         mx_index *old = idx->shards[g], *sh = nullptr;
         int rc = open_plain("", idx->dim, old->device, &sh);
-        if (rc != MX_OK) {
-            drop_fresh();
-            return rc;
-        }
+        if (rc != MX_OK) return rc;
         sh->idmap = old->idmap;
         sh->mode = old->mode;
         sh->profiling = old->profiling;
@@ -3064,12 +2991,8 @@ int compact_composite(mx_index *idx) {
         if (rc == MX_OK && k) rc = composite_add(fresh.get(), buf.data(), k, nullptr, false);
     }
     for (mx_index *sh : fresh->shards) sh->raw_ingest = false;
-    if (rc != MX_OK) {
-        drop_fresh();
-        return rc;
-    }
-    std::swap(idx->shards, fresh->shards);
-    drop_fresh();  // (the old shards)
+    if (rc != MX_OK) return rc;
+    std::swap(idx->shards, fresh->shards);  // (the old shards go with `fresh`)
     idx->total = fresh->total;
     idx->n_dead = 0;
     return MX_OK;
@@ -3151,7 +3074,7 @@ int mx_index_open_sharded(const char *key, int dim, int n_dev, const int *device
             return MX_OK;
         }
     }
-    std::unique_ptr<mx_index> idx(new mx_index());
+    std::unique_ptr<mx_index, IndexCloser> idx(new mx_index());  // (shards already opened are freed on any failure, an exception too)
     idx->key = k;
     idx->dim = dim;
     idx->block_rows = round_up(block_rows ? block_rows : 65536, kTileRows);
@@ -3160,10 +3083,7 @@ int mx_index_open_sharded(const char *key, int dim, int n_dev, const int *device
         const int dev = devices ? devices[g] : g;
         mx_index *sh = nullptr;
         int rc = open_plain("", dim, dev, &sh);
-        if (rc != MX_OK) {
-            for (mx_index *s2 : idx->shards) free_index(s2);
-            return rc;
-        }
+        if (rc != MX_OK) return rc;
         sh->idmap = IdMap{0, (uint32_t)idx->block_rows, (uint32_t)n_dev, (uint32_t)g};
         idx->shards.push_back(sh);
         for (int h = 0; h < g; ++h) distinct = distinct && idx->shards[h]->device != dev;
@@ -3220,10 +3140,8 @@ int mx_index_open_sharded(const char *key, int dim, int n_dev, const int *device
             }
         }
         if (!idx->use_rccl) {
-            if (ex) {  // MEMEX_HIP_EXCHANGE=rccl insists
-                for (mx_index *s2 : idx->shards) free_index(s2);
+            if (ex)  // MEMEX_HIP_EXCHANGE=rccl insists
                 return fail(MX_EDEVICE, "MEMEX_HIP_EXCHANGE=rccl: %s", why.c_str());
-            }
             fprintf(stderr, "memex-hip: sharded index '%s' exchanges by peer copies (%s)\n", k.c_str(), why.c_str());
         }
     }
@@ -3733,13 +3651,12 @@ mx_index *filter_target(mx_index *idx, size_t g) { return idx->composite() ? idx
 int ensure_filter_bits(mx_index *t, FilterShard &fs) {
     const size_t words = (size_t)(t->cap / kTile8Rows);
     if (fs.words >= words) return MX_OK;
-    DevBuf nb;
-    MX_HIP(hipMalloc(&nb.p, words * sizeof(uint64_t)));
-    MX_HIP(hipMemsetAsync(nb.p, 0, words * sizeof(uint64_t), t->stream));
-    if (fs.words) MX_HIP(hipMemcpyAsync(nb.p, fs.bits, fs.words * sizeof(uint64_t), hipMemcpyDeviceToDevice, t->stream));
+    Dev<uint64_t> nb;
+    MX_HIP(nb.alloc(words));
+    MX_HIP(hipMemsetAsync(nb, 0, words * sizeof(uint64_t), t->stream));
+    if (fs.words) MX_HIP(hipMemcpyAsync(nb, fs.bits, fs.words * sizeof(uint64_t), hipMemcpyDeviceToDevice, t->stream));
     MX_HIP(hipStreamSynchronize(t->stream));
-    if (fs.bits) (void)hipFree(fs.bits);
-    fs.bits = static_cast<uint64_t *>(nb.release());
+    fs.bits = std::move(nb);
     fs.words = words;
     fs.bits_h.resize(words, 0);
     return MX_OK;
@@ -3747,11 +3664,9 @@ int ensure_filter_bits(mx_index *t, FilterShard &fs) {
 
 int ensure_filter_stage(FilterShard &fs, size_t words) {
     if (fs.stage_words >= words) return MX_OK;
-    if (fs.stage) (void)hipFree(fs.stage);  // (every edit is host-synchronised before it returns)
-    fs.stage = nullptr;
     fs.stage_words = 0;
     const size_t want = std::max<size_t>(words + words / 2, 128);
-    MX_HIP(hipMalloc(reinterpret_cast<void **>(&fs.stage), want * sizeof(uint64_t)));
+    MX_HIP(fs.stage.alloc(want));  // (every edit is host-synchronised before it returns)
     fs.stage_words = want;
     return MX_OK;
 }
@@ -3759,11 +3674,9 @@ int ensure_filter_stage(FilterShard &fs, size_t words) {
 void free_filter_buffers(mx_filter *f) {
     for (FilterShard &fs : f->sh) {
         DeviceGuard dg(fs.device);
-        if (fs.bits) (void)hipFree(fs.bits);
-        if (fs.stage) (void)hipFree(fs.stage);
-        if (fs.list) (void)hipFree(fs.list);
-        fs.bits = fs.stage = nullptr;
-        fs.list = nullptr;
+        fs.bits.reset();
+        fs.stage.reset();
+        fs.list.reset();
     }
 }
 
@@ -4179,8 +4092,8 @@ int mx_index_search_fused(mx_index *idx, const float *q, int R, int m, const flo
     if (rc != MX_OK) return rc;
     if ((rc = ensure_out(t, k)) != MX_OK) return rc;
     if (best_sub && !t->fuse_best)
-        MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->fuse_best), (size_t)kMaxBatch * kFuseMaxFetch * sizeof(int32_t)));
-    if (fused && !t->fuse_val) MX_HIP(hipMalloc(reinterpret_cast<void **>(&t->fuse_val), (size_t)kMaxBatch * kFuseMaxFetch * sizeof(double)));
+        MX_HIP(t->fuse_best.alloc((size_t)kMaxBatch * kFuseMaxFetch));
+    if (fused && !t->fuse_val) MX_HIP(t->fuse_val.alloc((size_t)kMaxBatch * kFuseMaxFetch));
     Scratch &s = t->s;
     const int per = kMaxBatch / m;  // whole requests per pass
     for (int r0 = 0; r0 < R; r0 += per) {
@@ -4336,12 +4249,9 @@ int mx_index_set_filter_copy(mx_index *idx, int on) try {
     auto drop = [&]() -> int {
         if (idx->xh) {
             MX_HIP(hipStreamSynchronize(idx->stream));
-            (void)hipFree(idx->xh);
-            if (idx->tsc) (void)hipFree(idx->tsc);
-            if (idx->amean) (void)hipFree(idx->amean);
-            idx->xh = nullptr;
-            idx->tsc = nullptr;
-            idx->amean = nullptr;
+            idx->xh.reset();
+            idx->tsc.reset();
+            idx->amean.reset();
             idx->centred = false;
         }
         return MX_OK;
@@ -4379,11 +4289,7 @@ int mx_index_set_corpus_mode(mx_index *idx, int mode) try {
         return fail(MX_EUNSUPPORTED, "a compressed corpus supports dim <= %d", kMaxKC16 * kChunkFloats);
     DeviceGuard g(idx->device);
     MX_HIP(hipStreamSynchronize(idx->stream));
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    F(idx->x); F(idx->scale); F(idx->xh); F(idx->tsc); F(idx->amean);
-    idx->x = nullptr; idx->scale = nullptr; idx->xh = nullptr; idx->tsc = nullptr; idx->amean = nullptr;
+    idx->x.reset(); idx->scale.reset(); idx->xh.reset(); idx->tsc.reset(); idx->amean.reset();
     idx->centred = false;
     idx->cap = 0;
     idx->compressed = mode == MX_CORPUS_BF16;
@@ -4598,21 +4504,22 @@ int mx_index_load(mx_index *idx, const char *dir) try {
     const size_t chunk_bytes = (size_t)chunk * idx->dim * sizeof(float);
     mx_index *t0 = idx->composite() ? idx->shards[0] : idx;
     DeviceGuard dg(t0->device);
-    float *pin[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};
+    Pin<float> pin[2];
+    Dev<float> dev[2];
     hipEvent_t ev[2] = {nullptr, nullptr};
     hipStream_t cs = nullptr;
     int rc = MX_OK;
     auto release = [&] {
         for (int i = 0; i < 2; ++i) {
-            if (pin[i]) (void)hipHostFree(pin[i]);
-            if (dev[i]) (void)hipFree(dev[i]);
+            pin[i].reset();
+            dev[i].reset();
             if (ev[i]) (void)hipEventDestroy(ev[i]);
         }
         if (cs) (void)hipStreamDestroy(cs);
     };
     for (int i = 0; i < 2 && rc == MX_OK; ++i) {
-        if (hipHostMalloc(reinterpret_cast<void **>(&pin[i]), chunk_bytes, hipHostMallocDefault) != hipSuccess ||
-            (!idx->composite() && hipMalloc(reinterpret_cast<void **>(&dev[i]), chunk_bytes) != hipSuccess) ||
+        if (pin[i].alloc_bytes(chunk_bytes, hipHostMallocDefault) != hipSuccess ||
+            (!idx->composite() && dev[i].alloc_bytes(chunk_bytes) != hipSuccess) ||
             hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess)
             rc = fail(MX_ENOMEM, "staging buffers for %s", path.c_str());
     }
@@ -4760,5 +4667,15 @@ int mx_topk_merge_packed_async(int device, void *hip_stream, const void *d_packe
 } catch (...) {
     return guard_exception();
 }
+
+#ifdef MEMEX_TESTING
+// libmemex_hip_testing.so only (mx_owned.h): how many device and pinned buffers of this file are alive; fail the n-th next
+// allocation with hipErrorOutOfMemory (0: none) -- returns how many allocations were asked for since the previous call
+long mx_testing_live_buffers(void) { return g_owned_live.load(); }
+long mx_testing_fail_alloc(long n) {
+    g_owned_fail_at.store(n);
+    return g_owned_allocs.exchange(0);
+}
+#endif
 
 }  // extern "C"

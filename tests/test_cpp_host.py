@@ -41,6 +41,16 @@ def test_shard_pool_hand_off(tmp_path):
     assert r.returncode == 0 and "OK shard pool" in r.stdout, r.stdout + r.stderr
 
 
+def test_owned_buffer_type(tmp_path):
+    """mx::Owned (memex_amd/csrc/mx_owned.h), the owning buffer type of the index and encoder hosts, driven with a fake
+    counting policy: alloc / realloc / reset, moves over a held buffer, a vector of buffers, a failed allocation; at
+    the end nothing is live and nothing was released twice.  The generic template includes no HIP header."""
+    exe = str(tmp_path / "test_owned_buf")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "test_owned_buf.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "OK owned buffers" in r.stdout, r.stdout + r.stderr
+
+
 def test_debug_flag_parser(tmp_path):
     """MEMEX_HIP_DEBUG (memex_amd/csrc/mx_debug.h), the library's one kernel-variant switch: re-read when the string
     changes, defaults for absent keys, malformed items ignored, safe from several threads."""
