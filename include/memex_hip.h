@@ -373,6 +373,51 @@ int mx_index_search_fused_device(mx_index *idx, const float *d_queries, int R, i
                                  float rrf_c, uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_best_sub, double *d_fused,
                                  int32_t *d_n_found);
 
+/*
+ * Search by examples: the exact top-k for a BLEND of stored rows -- "more like these segments, less like those" (relevance feedback,
+ * pinned passages, more-like-this for a document of several segments), optionally together with a caller vector.  The example rows
+ * never leave HBM: every shard gathers the rows it owns to devices[0], one kernel blends each request's terms into ONE f32 query in
+ * stated arithmetic, one plain pass runs over those queries, and a last kernel takes the used examples out of each list.
+ * R requests of m example slots each.  example_ids [R, m], example_weights [R, m] (NULL: all 1) and query_weights [R] (NULL: all 1)
+ * are HOST memory on both variants; queries [R, dim] is optional (NULL: no caller term) and is host memory on the first variant,
+ * device memory on the second.  Outputs: ids / scores / dists [R, k], n_found / n_used [R], combined [R, dim]; dists, n_used and
+ * combined may be NULL.
+ *   terms       Let v_i be what mx_index_get_rows returns for the row example_ids[r, i] names (a bf16 corpus: its values widened), id_offset
+ *               applied as for results, and na_i = sum_j (double)fl32(v_ij * v_ij) in ascending j.  Example i is USED when its weight is not
+ *               0, its id names a live (not removed) row and na_i > 0.  A weight of exactly 0 marks an absent slot (the padding of ragged
+ *               requests); a removed row, an id that names no row and a zero row are skipped without error.  The caller vector q =
+ *               queries[r] is a term under the same rule, with weight w_q = query_weights[r]: it is skipped when w_q is 0 or na_q is 0
+ *               (a non-finite vector has a non-finite na_q and is not skipped).
+ *   combined    c_j = +0.0, then c_j += (double)w_q * ((double)q_j / sqrt(na_q)) if the caller term is used, then
+ *               c_j += (double)w_i * ((double)v_ij / sqrt(na_i)) for the used examples in ASCENDING i: IEEE f64 operations, round to nearest,
+ *               a true square root and division, nothing contracted.  combined_j = (float)c_j, round to nearest even.  Results below f32's
+ *               normal range are unspecified.  The value depends on nothing else: not on the shard count, the copy kind or the pass split.
+ *   result      Let E = m when exclude_examples = 1, else 0.  The entries of mx_index_search(combined, k + E) in their (dist, id) order;
+ *               with exclude_examples = 1 every entry whose id is a used example's id of that request is dropped; the list is cut to k and
+ *               n_found follows.  With exclude_examples = 1 that is the EXACT top-k of the live rows other than the used examples: at most
+ *               E entries leave a sorted prefix of k + E, so at least the first k of the others are in it (exact copies of an example are
+ *               other rows and stay).  An id named twice contributes twice and is dropped once.  n_used counts the used examples, the
+ *               caller term not included.
+ *   blank       A request without a used term, or whose combined is all zeros (a row used as positive and negative with equal weight),
+ *               finds nothing: n_found 0, combined zeros, and the call still returns MX_OK.
+ * Unused slots hold id 0, score 0, dist +inf.
+ * Arguments are checked first: R < 0, m < 1, k < 1, exclude_examples not 0 or 1, a weight that is NaN or infinite or whose magnitude is
+ * non-zero and outside [1e-6, 1e6] (the message names it, e.g. example_weights[3]), a NULL example_ids / ids / scores / n_found with
+ * R > 0, query_weights without queries: MX_EINVAL; m > 16 or k + E > 4096: MX_EUNSUPPORTED; then a null index: MX_ESEARCH.  A non-finite
+ * caller vector is rejected as by mx_index_search (MX_EINVAL).  Everything else is the plain pass's: removed rows, the AUTO path and -- for
+ * k + E > 256, like any such k -- the EXACT path, statistics.  Requests go in passes of floor(512 / m) whole requests (at most 512 gathered
+ * rows).  Thread-safe beside every other call.  Concurrent callers are NOT combined into shared passes: each call holds the index from
+ * the translation of its ids to the end of its last kernel, so no append, removal or compaction slips between the stages.  A sharded
+ * handle answers bit for bit what the plain index answers.  Extra HBM, allocated at the first call: two blocks of 512 rows and lists of
+ * 512 x max(k + E, 64) entries on devices[0].
+ */
+int mx_index_search_like(mx_index *idx, const float *queries, const float *query_weights, const uint64_t *example_ids,
+                         const float *example_weights, int R, int m, int k, int exclude_examples, uint64_t *ids, float *scores,
+                         float *dists, int32_t *n_found, int32_t *n_used, float *combined);
+int mx_index_search_like_device(mx_index *idx, const float *d_queries, const float *query_weights, const uint64_t *example_ids,
+                                const float *example_weights, int R, int m, int k, int exclude_examples, uint64_t *d_ids,
+                                float *d_scores, float *d_dists, int32_t *d_n_found, int32_t *d_n_used, float *d_combined);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

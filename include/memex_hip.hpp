@@ -84,6 +84,11 @@ class VectorStore {  // mod.rs:55-66
     virtual void bulk_insert(const std::vector<VectorData> &data) = 0;
     virtual void insert(const VectorData &data) = 0;
     virtual std::vector<VectorSearchResult> search(const std::vector<float> &vec, size_t limit) = 0;
+    // relevance feedback over stored segments (no counterpart in the trait): a store that cannot reach its rows by _id refuses
+    virtual std::vector<VectorSearchResult> search_like(const std::vector<std::string> &, const std::vector<std::string> &, size_t,
+                                                        const std::vector<float> &, float, float, float) {
+        throw VectorStoreError(VectorStoreError::Unsupported, "search_like");
+    }
 };
 
 // ---- storage/local.rs ---------------------------------------------------------------------------
@@ -612,6 +617,54 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // relevance feedback (Rocchio) over segment _ids: more like `positive`, less like `negative`, the named segments themselves left
+    // out.  Every row stored under a named _id is an example (mx_index_search_like: the rows never leave the device), scaled to unit
+    // length and weighted beta / n_pos_rows or -gamma / n_neg_rows; vec (empty: none), the query the feedback is about, weighs alpha.
+    // Unknown _ids are ignored; more than 16 rows in all: std::invalid_argument.  No example row and no vec returns nothing
+    std::vector<VectorSearchResult> search_like(const std::vector<std::string> &positive, const std::vector<std::string> &negative = {},
+                                                size_t limit = 10, const std::vector<float> &vec = {}, float alpha = 1.0f,
+                                                float beta = 0.75f, float gamma = 0.15f) override {
+        std::vector<VectorSearchResult> out;
+        std::vector<uint64_t> ex;
+        size_t n_pos = 0;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0 || _id_map.empty()) return out;
+            build_rows_of();
+            for (const std::vector<std::string> *names : {&positive, &negative}) {
+                for (const std::string &n : *names) {
+                    auto it = rows_of_.find(n);
+                    if (it != rows_of_.end()) ex.insert(ex.end(), it->second.begin(), it->second.end());
+                }
+                if (names == &positive) n_pos = ex.size();
+            }
+        }
+        if (ex.size() > 16) throw std::invalid_argument("more than 16 example rows per request");
+        if (!vec.empty() && vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        if (ex.empty() && vec.empty()) return out;
+        std::vector<float> w;
+        for (size_t i = 0; i < ex.size(); ++i) w.push_back(i < n_pos ? beta / (float)n_pos : -gamma / (float)(ex.size() - n_pos));
+        if (ex.empty()) {  // the caller vector alone: one absent slot
+            ex.push_back(0);
+            w.push_back(0.0f);
+        }
+        const int k = (int)std::min<size_t>(limit, (size_t)INT32_MAX);
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        int32_t nf = 0;
+        int rc = mx_index_search_like(idx_, vec.empty() ? nullptr : vec.data(), vec.empty() ? nullptr : &alpha, ex.data(), w.data(), 1,
+                                      (int)ex.size(), k, 1, found.data(), scores.data(), nullptr, &nf, nullptr, nullptr);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.emplace_back(it->second, scores[j]);
+        }
+        return out;
+    }
+
     struct DuplicatePair {
         std::string a, b;  // the _ids of the two rows, the one with the smaller row id first
         float score;
@@ -767,6 +820,12 @@ class VectorStorage {  // mod.rs:69-93
     std::vector<VectorSearchResult> search(const std::vector<float> &query, size_t limit) {
         std::lock_guard<std::mutex> lk(*mu_);
         return client->search(query, limit);
+    }
+    std::vector<VectorSearchResult> search_like(const std::vector<std::string> &positive, const std::vector<std::string> &negative = {},
+                                                size_t limit = 10, const std::vector<float> &vec = {}, float alpha = 1.0f,
+                                                float beta = 0.75f, float gamma = 0.15f) {
+        std::lock_guard<std::mutex> lk(*mu_);
+        return client->search_like(positive, negative, limit, vec, alpha, beta, gamma);
     }
 
   private:

@@ -32,7 +32,7 @@ EXPORTS = [
     "mx_index_set_id_offset", "mx_index_add", "mx_index_add_device", "mx_index_clear",
     "mx_index_remove", "mx_index_removed", "mx_index_compact",
     "mx_index_search", "mx_index_search_device", "mx_index_search_filtered", "mx_index_search_filtered_device", "mx_index_search_range", "mx_index_search_range_device", "mx_index_search_mmr", "mx_index_search_mmr_device",
-    "mx_index_search_fused", "mx_index_search_fused_device",
+    "mx_index_search_fused", "mx_index_search_fused_device", "mx_index_search_like", "mx_index_search_like_device",
     "mx_filter_create", "mx_filter_destroy", "mx_filter_set_ranges", "mx_filter_set_ids", "mx_filter_count", "mx_filter_get_ranges",
     "mx_index_search_with_filter", "mx_index_search_with_filter_device",
     "mx_index_search_by_id", "mx_index_search_by_id_device", "mx_index_search_range_by_id", "mx_index_search_range_by_id_device",
@@ -140,6 +140,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_index_search_mmr_device": [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp],
         "mx_index_search_fused": [vp, vp, i32, i32, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp, vp, vp],
         "mx_index_search_fused_device": [vp, vp, i32, i32, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_like": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_like_device": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
         "mx_index_search_by_id": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
         "mx_index_search_by_id_device": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
         "mx_index_search_range_by_id": [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp],

@@ -299,6 +299,16 @@ struct mx_index {
     Dev<float> fuse_w;
     Dev<int32_t> fuse_best;
     Dev<double> fuse_val;
+    // search by examples (mx_index_search_like), allocated at the first such call on the index that owns the stream:
+    // the gathered example rows and the combined queries [kMaxBatch, dim] each, the pass's own lists [kMaxBatch, like_cap] with their
+    // counts, and per pass the example ids, weights and places in the gathered block [kMaxBatch], the caller weights, the used-example
+    // masks and their counts [kMaxBatch].  A shard's row list and peer-copy block are the by-id search's (byid_rows, byid_stage).
+    Dev<float> like_rows, like_q;
+    Dev<uint64_t> like_ids, like_own;
+    Dev<float> like_scores, like_dists, like_w, like_wq;
+    Dev<int32_t> like_nf, like_nused;
+    Dev<uint32_t> like_src, like_used;
+    int like_cap = 0;
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -2249,6 +2259,131 @@ int byid_batch(mx_index *idx, const uint64_t *qids, int B, int k, int exclude, c
     p.n_found = d_nfound;
     p.n_in_range = dlim ? d_nrange : nullptr;
     MX_HIP(launch_byid_drop_self(st, p));
+    MX_HIP(hipStreamSynchronize(st));
+    return MX_OK;
+}
+
+// ---- search by examples (mx_index_search_like) ---------------------------------------------------------------
+// the pass's own lists, kk wide, and the per-pass words on the index that owns the stream (the current device is its device)
+int ensure_like_lists(mx_index *t, int kk) {
+    if (!t->like_q) {
+        MX_HIP(t->like_rows.alloc((size_t)kMaxBatch * t->dim));
+        MX_HIP(t->like_q.alloc((size_t)kMaxBatch * t->dim));
+        MX_HIP(t->like_own.alloc(kMaxBatch));
+        MX_HIP(t->like_w.alloc(kMaxBatch));
+        MX_HIP(t->like_wq.alloc(kMaxBatch));
+        MX_HIP(t->like_nf.alloc(kMaxBatch));
+        MX_HIP(t->like_nused.alloc(kMaxBatch));
+        MX_HIP(t->like_src.alloc(kMaxBatch));
+        MX_HIP(t->like_used.alloc(kMaxBatch));
+    }
+    if (kk <= t->like_cap) return MX_OK;
+    MX_HIP(hipStreamSynchronize(t->stream));
+    t->like_cap = 0;
+    const size_t c = (size_t)std::max(kk, 64);
+    MX_HIP(t->like_ids.alloc((size_t)kMaxBatch * c));
+    MX_HIP(t->like_scores.alloc((size_t)kMaxBatch * c));
+    MX_HIP(t->like_dists.alloc((size_t)kMaxBatch * c));
+    t->like_cap = (int)c;
+    return MX_OK;
+}
+
+// One pass of a search by examples: nreq requests of m example slots each (nreq * m <= kMaxBatch), example ids and weights in host
+// memory ([nreq, m]; weights null: all ones), the caller vectors d_q [nreq, dim] (null: none) and the outputs on the device of the
+// index that owns the stream, wq their weights (host, [nreq]; null: all ones), the caller holding idx->mu from here to the end.  Ids ->
+// (shard, local row) while nothing can move them; slots of weight 0 and ids that name no live row are left out; every shard gathers
+// its rows into its slice of one block; like_combine_kernel blends each request's terms into one query; one plain pass at k + (exclude
+// ? m : 0) over the nreq queries into this index's own lists; like_drop_examples_kernel writes the caller's.  d_nused, d_combined: null
+// = not wanted there (the combined queries stay in t->like_q, the counts go to t->like_nused).  Host-synchronised.
+int like_batch(mx_index *idx, const float *d_q, const float *wq, const uint64_t *ex_ids, const float *w, int nreq, int m, int k, int exclude,
+               uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_nfound, int32_t *d_nused, float *d_combined) {
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    const int kk = k + (exclude ? m : 0), dim = idx->dim, S = nreq * m;
+    int rc = ensure_like_lists(t, kk);
+    if (rc != MX_OK) return rc;
+    hipStream_t st = t->stream;
+    const size_t G = idx->composite() ? idx->shards.size() : 1;
+    std::vector<std::vector<uint32_t>> rows(G);  // (alive until the pass is host-synchronised: sources of async uploads)
+    std::vector<uint32_t> src((size_t)S, kLikeNone), owner((size_t)S, 0u);
+    std::vector<float> hw(w ? w : nullptr, w ? w + S : nullptr), hwq(wq ? wq : nullptr, wq ? wq + nreq : nullptr);
+    if (!w) hw.assign((size_t)S, 1.0f);
+    if (!wq) hwq.assign((size_t)nreq, 1.0f);
+    for (int i = 0; i < S; ++i) {
+        if (hw[i] == 0.0f) continue;  // an absent slot
+        const uint64_t id = ex_ids[i];
+        size_t g;
+        uint64_t local;
+        if (!locate_row(idx, id, &g, &local)) continue;  // names no row
+        const mx_index *sh = idx->composite() ? idx->shards[g] : idx;
+        if (local >= sh->n) return fail(MX_ESEARCH, "id %llu names no row of its shard", (unsigned long long)id);
+        if (row_removed(sh, local)) continue;
+        owner[i] = (uint32_t)g;
+        src[i] = (uint32_t)rows[g].size();
+        rows[g].push_back((uint32_t)local);
+    }
+    std::vector<size_t> first(G + 1, 0);
+    for (size_t g = 0; g < G; ++g) first[g + 1] = first[g] + rows[g].size();
+    for (int i = 0; i < S; ++i)
+        if (src[i] != kLikeNone) src[i] += (uint32_t)first[owner[i]];
+    for (size_t g = 0; g < G; ++g) {
+        if (rows[g].empty()) continue;
+        mx_index *sh = idx->composite() ? idx->shards[g] : idx;
+        std::unique_lock<std::mutex> lk(sh->mu, std::defer_lock);
+        if (idx->composite()) lk.lock();  // (a plain index: the caller holds it)
+        DeviceGuard dg(sh->device);
+        const bool same = sh->device == t->device;
+        if (!sh->byid_rows) MX_HIP(sh->byid_rows.alloc(kMaxBatch));
+        if (!same && !sh->byid_stage) MX_HIP(sh->byid_stage.alloc((size_t)kMaxBatch * dim));
+        MX_HIP(hipMemcpyAsync(sh->byid_rows, rows[g].data(), rows[g].size() * sizeof(uint32_t), hipMemcpyHostToDevice, sh->stream));
+        float *slot = t->like_rows + first[g] * (size_t)dim;
+        MX_HIP(launch_byid_gather(sh->stream, dim, sh->ds, sh->compressed ? nullptr : sh->x, sh->xh, sh->byid_rows, (uint32_t)rows[g].size(),
+                                  same ? slot : sh->byid_stage));
+        if (!same)  // peer copy to shards[0]'s device
+            MX_HIP(hipMemcpyAsync(slot, sh->byid_stage, rows[g].size() * (size_t)dim * sizeof(float), hipMemcpyDefault, sh->stream));
+        if (sh != t) MX_HIP(hipStreamSynchronize(sh->stream));
+    }
+    DeviceGuard dg(t->device);
+    MX_HIP(hipMemcpyAsync(t->like_src, src.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    MX_HIP(hipMemcpyAsync(t->like_w, hw.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice, st));
+    MX_HIP(hipMemcpyAsync(t->like_own, ex_ids, (size_t)S * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (d_q) MX_HIP(hipMemcpyAsync(t->like_wq, hwq.data(), (size_t)nreq * sizeof(float), hipMemcpyHostToDevice, st));
+    LikeCombine c{};
+    c.R = nreq;
+    c.m = m;
+    c.dim = dim;
+    c.rows = t->like_rows;
+    c.src = t->like_src;
+    c.w = t->like_w;
+    c.q = d_q;
+    c.wq = t->like_wq;
+    c.out = t->like_q;
+    c.combined = d_combined;
+    c.used = t->like_used;
+    c.n_used = d_nused ? d_nused : t->like_nused.get();
+    MX_HIP(launch_like_combine(st, c));
+    if ((rc = any_batch(idx, t->like_q, nreq, kk, t->like_ids, t->like_scores, t->like_dists, t->like_nf)) != MX_OK) {
+        (void)hipStreamSynchronize(st);  // (the uploads above read this function's vectors)
+        return rc;
+    }
+    LikeDrop p{};
+    p.R = nreq;
+    p.m = m;
+    p.k = k;
+    p.kk = kk;
+    p.exclude = exclude;
+    p.dim = dim;
+    p.own = t->like_own;
+    p.used = t->like_used;
+    p.q = t->like_q;
+    p.in_ids = t->like_ids;
+    p.in_scores = t->like_scores;
+    p.in_dists = t->like_dists;
+    p.in_nfound = t->like_nf;
+    p.ids = d_ids;
+    p.scores = d_scores;
+    p.dists = d_dists;
+    p.n_found = d_nfound;
+    MX_HIP(launch_like_drop_examples(st, p));
     MX_HIP(hipStreamSynchronize(st));
     return MX_OK;
 }
@@ -4227,6 +4362,108 @@ int mx_index_search_range_by_id_device(mx_index *idx, const uint64_t *query_ids,
     std::vector<uint32_t> dlim;
     if (int rc = read_by_id_args(B, cap, exclude_self, true, min_scores, &dlim); rc != MX_OK) return rc;
     return search_by_id(idx, query_ids, B, cap, exclude_self, &dlim, false, d_ids, d_scores, d_dists, d_nfound, d_n_in_range);
+} catch (...) {
+    return guard_exception();
+}
+
+namespace {
+
+// a weight of the search by examples: 0 (absent), or finite with a magnitude in [1e-6, 1e6]
+static bool like_weight_ok(float w) { return w == 0.0f || (std::fabs(w) >= 1e-6f && std::fabs(w) <= 1e6f); }  // (NaN, inf: false)
+
+// arguments of the search-by-examples entry points, checked before the index is looked at (ids and weights: host memory)
+static int read_like_args(const void *q, const float *qw, const uint64_t *ex_ids, const float *ew, int R, int m, int k, int exclude,
+                   const void *ids, const void *scores, const void *n_found) {
+    if (R < 0) return fail(MX_EINVAL, "negative batch");
+    if (m < 1) return fail(MX_EINVAL, "m = %d < 1", m);
+    if (k < 1) return fail(MX_EINVAL, "k = %d < 1", k);
+    if (exclude != 0 && exclude != 1) return fail(MX_EINVAL, "exclude_examples = %d is neither 0 nor 1", exclude);
+    if (qw && !q) return fail(MX_EINVAL, "query_weights without queries");
+    if (ew)
+        for (size_t i = 0; i < (size_t)R * (size_t)m; ++i)
+            if (!like_weight_ok(ew[i]))
+                return fail(MX_EINVAL, "example_weights[%zu] = %g is neither 0 nor a finite value of magnitude 1e-6 .. 1e6", i, (double)ew[i]);
+    if (qw)
+        for (int r = 0; r < R; ++r)
+            if (!like_weight_ok(qw[r]))
+                return fail(MX_EINVAL, "query_weights[%d] = %g is neither 0 nor a finite value of magnitude 1e-6 .. 1e6", r, (double)qw[r]);
+    if (R > 0 && (!ex_ids || !ids || !scores || !n_found)) return fail(MX_EINVAL, "null argument");
+    if (m > kLikeMaxExamples) return fail(MX_EUNSUPPORTED, "m = %d > %d", m, kLikeMaxExamples);
+    if ((long long)k + (exclude ? m : 0) > 4096)
+        return fail(MX_EUNSUPPORTED, "k = %d%s > 4096", k, exclude ? " + m (the examples)" : "");
+    return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_search_like(mx_index *idx, const float *queries, const float *query_weights, const uint64_t *example_ids,
+                         const float *example_weights, int R, int m, int k, int exclude_examples, uint64_t *ids, float *scores, float *dists,
+                         int32_t *n_found, int32_t *n_used, float *combined) try {
+    if (int rc = read_like_args(queries, query_weights, example_ids, example_weights, R, m, k, exclude_examples, ids, scores, n_found);
+        rc != MX_OK)
+        return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (R == 0) return MX_OK;
+    const size_t dim = (size_t)idx->dim;
+    if (queries)
+        for (size_t i = 0; i < (size_t)R * dim; ++i)
+            if (!std::isfinite(queries[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    // not combined with other callers: the call holds the index from the id translation to the end of the drop kernel
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
+    DeviceGuard g(t->device);
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, k)) != MX_OK) return rc;
+    Scratch &s = t->s;
+    const int per = kMaxBatch / m;  // whole requests per pass
+    for (int r0 = 0; r0 < R; r0 += per) {
+        const int nr = std::min(per, R - r0);
+        const size_t o = (size_t)r0 * k, e0 = (size_t)r0 * m;
+        if (queries) {
+            memcpy(s.h_q, queries + (size_t)r0 * dim, (size_t)nr * dim * sizeof(float));
+            MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nr * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        }
+        if ((rc = like_batch(idx, queries ? s.qstage.get() : nullptr, query_weights ? query_weights + r0 : nullptr, example_ids + e0,
+                             example_weights ? example_weights + e0 : nullptr, nr, m, k, exclude_examples, s.out_ids, s.out_scores,
+                             s.out_dists, s.out_nfound, nullptr, nullptr)) != MX_OK)
+            return rc;
+        if (n_used) MX_HIP(hipMemcpyAsync(n_used + r0, t->like_nused, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        if (combined)
+            MX_HIP(hipMemcpyAsync(combined + (size_t)r0 * dim, t->like_q, (size_t)nr * dim * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        if ((rc = copy_out_to_host(t, nr, k, false)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nr, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + r0, nullptr);
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_like_device(mx_index *idx, const float *d_queries, const float *query_weights, const uint64_t *example_ids,
+                                const float *example_weights, int R, int m, int k, int exclude_examples, uint64_t *d_ids, float *d_scores,
+                                float *d_dists, int32_t *d_n_found, int32_t *d_n_used, float *d_combined) try {
+    if (int rc = read_like_args(d_queries, query_weights, example_ids, example_weights, R, m, k, exclude_examples, d_ids, d_scores, d_n_found);
+        rc != MX_OK)
+        return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (R == 0) return MX_OK;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    DeviceGuard g(t->device);
+    const size_t dim = (size_t)idx->dim;
+    const int per = kMaxBatch / m;
+    for (int r0 = 0; r0 < R; r0 += per) {
+        const int nr = std::min(per, R - r0);
+        const size_t o = (size_t)r0 * k, e0 = (size_t)r0 * m;
+        int rc = like_batch(idx, d_queries ? d_queries + (size_t)r0 * dim : nullptr, query_weights ? query_weights + r0 : nullptr,
+                            example_ids + e0, example_weights ? example_weights + e0 : nullptr, nr, m, k, exclude_examples, d_ids + o,
+                            d_scores + o, d_dists ? d_dists + o : nullptr, d_n_found + r0, d_n_used ? d_n_used + r0 : nullptr,
+                            d_combined ? d_combined + (size_t)r0 * dim : nullptr);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
 } catch (...) {
     return guard_exception();
 }

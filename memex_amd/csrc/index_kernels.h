@@ -1,7 +1,7 @@
 // index_kernels.h -- device-side contract of the flat cosine index (launch wrappers + shared
 // constants).  The streaming scans live in scan.hip (f32 rows), scan16.hip / scan16w.hip (bf16 filter
 // copy, with its builder) and scan8.hip (int8 filter copy, with its builder), what they share in
-// scan_common.h; compaction in compact.hip, every other kernel in index_kernels.hip; index.hip holds
+// scan_common.h; compaction in compact.hip, the search by examples in like_kernels.hip, every other kernel in index_kernels.hip; index.hip holds
 // the host logic behind the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -434,5 +434,46 @@ struct FuseArgs {
     int32_t *n_found;
 };
 hipError_t launch_fuse(hipStream_t s, const FuseArgs &p);
+
+// search by examples (mx_index_search_like)
+constexpr int kLikeMaxExamples = 16;             // example slots per request: the used ones fit one 32-bit mask
+constexpr uint32_t kLikeNone = 0xffffffffu;      // LikeCombine::src of a slot that is absent (weight 0) or names no live row
+// One f32 query per request from its terms: the caller vector q[r] (q null: none) under weight wq[r], then example slot i = 0 .. m - 1,
+// gathered row src[r * m + i] of `rows` (launch_byid_gather's block) under weight w[r * m + i].  A term is USED when its weight is not 0,
+// it has a vector (q given / src != kLikeNone) and na != 0 (stored rows: na > 0; a NaN of a non-finite caller vector counts as used), na = the
+// f64 sum in element order of fl32(v_j * v_j).  Per column, from +0.0
+// and in that order over the used terms:  c_j += (double)weight * ((double)v_j / sqrt(na))  (IEEE f64, round to nearest, a true square
+// root and division, nothing contracted); out[r, j] = (float)c_j, also written to combined[r, j] when given.  used[r]: bit i set when
+// example i is used; n_used[r] (may be null) their count.  A request without a used term gets zeros.  1 <= m <= kLikeMaxExamples.
+struct LikeCombine {
+    int R, m, dim;
+    const float *rows;
+    const uint32_t *src;
+    const float *w;
+    const float *q;
+    const float *wq;
+    float *out;
+    float *combined;
+    uint32_t *used;
+    int32_t *n_used;
+};
+hipError_t launch_like_combine(hipStream_t s, const LikeCombine &p);
+// The internal lists [R, kk] of the pass over LikeCombine::out -> the caller's outputs [R, k], k <= kk.  With exclude, every entry whose
+// id is own[r * m + i] for a set bit i of used[r] is dropped and the later ones move up, in order; either way the list is cut to k.  A
+// request whose query q[r] is all zeros (no used term, or terms that cancel) is BLANK: n_found 0.  Unused slots id 0 / score 0 / dist
+// +inf; dists may be null.  Reads the internal lists, writes the caller's: never in place.
+struct LikeDrop {
+    int R, m, k, kk, exclude, dim;
+    const uint64_t *own;
+    const uint32_t *used;
+    const float *q;
+    const uint64_t *in_ids;
+    const float *in_scores, *in_dists;
+    const int32_t *in_nfound;
+    uint64_t *ids;
+    float *scores, *dists;
+    int32_t *n_found;
+};
+hipError_t launch_like_drop_examples(hipStream_t s, const LikeDrop &p);
 
 }  // namespace mx

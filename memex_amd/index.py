@@ -498,6 +498,78 @@ class FlatIndex:
                                                        ctypes.c_void_p(dists.data_ptr()) if dists is not None else None,
                                                        ctypes.c_void_p(n_found.data_ptr()), ctypes.c_void_p(n_in_range.data_ptr())))
 
+    # -- search by examples ----------------------------------------------------------------
+    def _like_args(self, example_ids, weights, queries_shape, query_weights):
+        """-> (example ids u64 [R, m], weights f32 [R, m] or None, query weights f32 [R] or None)"""
+        a = np.asarray(example_ids, dtype=np.uint64)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [R, m] example ids, got {a.shape}")
+        a = np.ascontiguousarray(a)
+        R, m = a.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.ndim == 1 and w.size == m:
+                w = np.ascontiguousarray(np.broadcast_to(w, (R, m)))
+            if w.shape != (R, m):
+                raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [{R}, {m}] weights, got {w.shape}")
+        if queries_shape is not None and tuple(queries_shape) != (R, self.dim):
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [{R}, {self.dim}] queries, got {tuple(queries_shape)}")
+        qw = None
+        if query_weights is not None:
+            if queries_shape is None:
+                raise _lib.MemexHipError(_lib.MX_EINVAL, "query_weights without queries")
+            qw = np.asarray(query_weights, dtype=np.float32)
+            qw = np.ascontiguousarray(np.broadcast_to(qw, (R,)) if qw.ndim == 0 else qw.reshape(-1))
+            if qw.shape != (R,):
+                raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {R} query weights, got {qw.shape}")
+        return a, w, qw
+
+    def search_like(self, example_ids, k: int, weights=None, queries=None, query_weights=None, exclude_examples: bool = True):
+        """More like these rows, less like those (``mx_index_search_like``): per request the exact top-k for the weighted blend of
+        the stored rows ``example_ids`` names -- [R, m], or [m] for one request -- each row scaled to unit length, plus
+        ``query_weights * queries / |queries|`` when ``queries`` [R, dim] is given.  The rows never leave HBM.
+        -> (ids u64 [R,k], scores f32 [R,k], dists f32 [R,k], n_found i32 [R], n_used i32 [R], combined f32 [R,dim]).
+        ``weights`` [R, m] or [m]: positive = more like, negative = less like, 0 = the slot is absent (padding of ragged requests).
+        Removed rows, ids that name no row and zero rows are skipped; ``n_used`` counts the examples that took part and ``combined``
+        is the query that was searched.  ``exclude_examples``: the exact top-k of the live rows OTHER than the used examples (exact
+        copies of them stay).  A request without a term, or whose terms cancel, finds nothing."""
+        q = None
+        if queries is not None:
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            if q.ndim == 1:
+                q = q[None, :]
+        a, w, qw = self._like_args(example_ids, weights, None if q is None else q.shape, query_weights)
+        R, m = a.shape
+        kk = max(int(k), 0)
+        ids = np.zeros((R, kk), dtype=np.uint64)
+        scores = np.zeros((R, kk), dtype=np.float32)
+        dists = np.zeros((R, kk), dtype=np.float32)
+        nf = np.zeros(R, dtype=np.int32)
+        nu = np.zeros(R, dtype=np.int32)
+        comb = np.zeros((R, self.dim), dtype=np.float32)
+        opt = lambda x: _ptr(x) if x is not None and x.size else None  # noqa: E731
+        check(lib().mx_index_search_like(self._h, opt(q), opt(qw), opt(a), opt(w), R, m, int(k), int(exclude_examples), opt(ids),
+                                         opt(scores), opt(dists), _ptr(nf), _ptr(nu), opt(comb)))
+        return ids, scores, dists, nf, nu, comb
+
+    def search_like_device(self, example_ids, k: int, ids, scores, dists, n_found, n_used=None, combined=None, weights=None,
+                           queries=None, query_weights=None, exclude_examples: bool = True) -> None:
+        """``search_like`` on device tensors: queries f32 [R,dim] (or None); ids i64/u64 [R,k]; scores, dists f32 [R,k]; n_found,
+        n_used i32 [R]; combined f32 [R,dim] (dists, n_used and combined may be None).  The example ids and all weights stay on the
+        host.  Blocks until the results are in HBM."""
+        a, w, qw = self._like_args(example_ids, weights, None if queries is None else queries.shape, query_weights)
+        R, m = a.shape
+        st = _caller_stream(queries if queries is not None else ids)
+        if st is not None:
+            self.wait_stream(st)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        opt = lambda x: _ptr(x) if x is not None and x.size else None  # noqa: E731
+        check(lib().mx_index_search_like_device(self._h, dp(queries), opt(qw), opt(a), opt(w), R, m, int(k), int(exclude_examples),
+                                                dp(ids), dp(scores), dp(dists), dp(n_found), dp(n_used), dp(combined)))
+
     def near_duplicates(self, min_score: float, per_row: int = 64, block: int = 512):
         """The exact self-join: every pair of live rows whose score reaches ``min_score``.
         -> (pairs u64 [P, 2] with pairs[:, 0] < pairs[:, 1], sorted by (first id, second id), each pair once; scores f32 [P];

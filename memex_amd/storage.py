@@ -636,6 +636,45 @@ class HipFlatStore(VectorStore):
                 out.append((self._id_map[r], score))
         return out
 
+    def search_like(self, positive: Sequence[str], negative: Sequence[str] = (), limit: int = 10, vec: Sequence[float] | None = None,
+                    alpha: float = 1.0, beta: float = 0.75, gamma: float = 0.15) -> List[VectorSearchResult]:
+        """Relevance feedback (Rocchio) over segment ``_id``s: more like ``positive``, less like ``negative``, as ``(_id, score)``
+        pairs like ``search``, the named segments themselves left out.  Every row stored under a named ``_id`` is an example
+        (``FlatIndex.search_like``: the rows never leave the device), scaled to unit length and weighted ``beta / n_pos_rows``
+        (positive) or ``-gamma / n_neg_rows`` (negative); ``vec``, the query the feedback is about, weighs ``alpha``.  Unknown
+        ``_id``s are ignored; more than 16 rows in all raise ``ValueError``.  No example row and no ``vec`` returns ``[]``.  A row that
+        was removed but not compacted away yet still counts in ``n_pos_rows`` / ``n_neg_rows``; it takes no part in the blend."""
+        with self._lock:
+            idx = self._index
+            if idx is None or limit <= 0 or not self._id_map:
+                return []
+            by_name = self._rows_by_name()
+            pos = [r for n in positive for r in by_name.get(str(n), ())]
+            neg = [r for n in negative for r in by_name.get(str(n), ())]
+        if len(pos) + len(neg) > 16:
+            raise ValueError(f"{len(pos) + len(neg)} example rows: at most 16 per request")
+        q = None
+        if vec is not None:
+            q = np.asarray(vec, dtype=np.float32)
+            if q.shape != (self._dim,):
+                raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        if not pos and not neg and q is None:
+            return []
+        ex = np.array(pos + neg if pos or neg else [0], dtype=np.uint64)
+        w = np.array([beta / len(pos)] * len(pos) + [-gamma / len(neg)] * len(neg) if pos or neg else [0.0], dtype=np.float32)
+        try:
+            ids, scores, _, nf, _, _ = idx.search_like(ex, int(limit), w, q, None if q is None else float(alpha))  # not under the lock, like search
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[VectorSearchResult] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[d_id], float(scores[0, j])))
+        return out
+
     def find_duplicates(self, min_score: float, per_row: int = 64) -> Tuple[List[Tuple[str, str, float]], List[str]]:
         """The rows of the collection that repeat each other: every pair of live rows whose score reaches ``min_score``
         (``FlatIndex.near_duplicates``, an exact self-join on the device) -> (``(_id_a, _id_b, score)`` per pair, in id order;
@@ -701,6 +740,11 @@ class VectorStorage:
                      weights: Sequence[float] | None = None) -> List[VectorSearchResult]:
         with self._mu:
             return self.client.search_fused(queries, limit, mode, fetch, weights)
+
+    def search_like(self, positive: Sequence[str], negative: Sequence[str] = (), limit: int = 10, vec: Sequence[float] | None = None,
+                    alpha: float = 1.0, beta: float = 0.75, gamma: float = 0.15) -> List[VectorSearchResult]:
+        with self._mu:
+            return self.client.search_like(positive, negative, limit, vec, alpha, beta, gamma)
 
 
 def get_vector_storage(uri: str, collection: str, device: int = 0, devices: Sequence[int] | None = None) -> VectorStorage:

@@ -15,6 +15,9 @@ reference                          here
 :func:`search_docs_multi` has no counterpart in the reference: several texts for one request (the phrasings of a question, a question
 and a hypothetical answer, the last turns of a conversation), one ranked list back (``search_fused``).
 
+:func:`search_docs_feedback` has none either: a query (or none) together with the segments marked relevant and irrelevant, one list back
+(``search_like``, Rocchio relevance feedback computed on the device).
+
 The ids are the reference's own (RFC 4122 v5 over the same namespace), so a collection filled through this mirror lines up
 with the rows a memex worker would have written for the same task ids.
 """
@@ -71,3 +74,18 @@ def search_docs_multi(client, embedder, queries: Sequence[str], limit: int = 10,
     if not vectors:
         raise ValueError("Invalid query")
     return client.search_fused(vectors, limit, mode)
+
+
+def search_docs_feedback(client, embedder, query, relevant: Sequence[str], irrelevant: Sequence[str] = (),
+                         limit: int = 10) -> List[Tuple[str, float]]:
+    """``search_docs`` with relevance feedback: the segments the user (or the agent) marked ``relevant`` pull the query towards them,
+    the ``irrelevant`` ones push it away (``client.search_like``, Rocchio weights), and the marked segments are not listed again.
+    ``query`` may be ``None``: more like the relevant segments alone.  ``ValueError("Invalid query")`` where ``search_docs`` raises
+    it: a query that embeds to nothing."""
+    vec = None
+    if query is not None:
+        res = embedder.encode_single(query)
+        if res is None:
+            raise ValueError("Invalid query")
+        vec = res.vector
+    return client.search_like(list(relevant), list(irrelevant), limit, vec)
