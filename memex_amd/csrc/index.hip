@@ -236,6 +236,7 @@ struct mx_index {
     bool exact_theta = true;     // plain int8 copy: the collect threshold also from exact scores of the sample's best rows (launch_theta's
                                  // ThetaExact), and the smaller sample that threshold allows; MEMEX_HIP_EXACT_THETA=0: neither
     int sample_div = 0;          // MEMEX_HIP_DEBUG=sample_div=N as it stood when the index was created (0: the built-in sample sizes)
+    int serial = kSerialAll;     // MEMEX_HIP_DEBUG=serial=N likewise: the kSerial* items of finish_kernel (0: the older forms)
     uint64_t crowded_at_rows = 0;  // rows the index held when a crowded f32 stage last had its plain int8 copy rebuilt (search_batch); 0: never
     bool print_records = false;  // MEMEX_HIP_DEBUG=records=1 (at creation): every batch prints the records of its first collect launch to stderr
     Scratch s;
@@ -1239,6 +1240,7 @@ void fill_finish_params(FinishParams &fp, const mx_index *idx, const BatchPlan &
     fp.k = k;
     fp.ds = idx->ds;
     fp.nwg = pl.nwg;
+    fp.serial = idx->serial;
     fp.x = idx->compressed ? nullptr : idx->x;
     fp.xh = idx->xh;
     fp.scale = idx->scale;
@@ -1440,7 +1442,7 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
             MX_HIP(hipMemcpy(cnt.data(), s.lane_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
             uint64_t rec = 0;
             for (const uint32_t c : cnt) rec += std::min<uint32_t>(c, (uint32_t)kRecCap);
-            fprintf(stderr, "memex_hip: collect records %llu queries %d\n", (unsigned long long)rec, B);
+            fprintf(stderr, "memex_hip: collect records %llu queries %d serial %d\n", (unsigned long long)rec, B, fp.serial);  // (serial: what finish_kernel was given)
         }
         if (timed) {
             float ms = 0.f;
@@ -2867,6 +2869,7 @@ int open_plain(const std::string &k, int dim, int device, mx_index **out) {
         const char *pv = getenv("MEMEX_HIP_EXACT_THETA");
         idx->exact_theta = !(pv && pv[0] == '0');
     }
+    idx->serial = debug_flag("serial", kSerialAll) & kSerialAll;
     idx->sample_div = debug_flag("sample_div", 0);  // read here, not per batch: debug_flag costs a getenv, a mutex and a string compare
     idx->print_records = debug_flag("records", 0) != 0;
     MX_HIP(hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking));
@@ -3103,6 +3106,7 @@ int compact_composite(mx_index *idx) {
         sh->scan8_pair = old->scan8_pair;
         sh->exact_theta = old->exact_theta;
         sh->sample_div = old->sample_div;
+        sh->serial = old->serial;
         sh->print_records = old->print_records;
         sh->want_filter = old->want_filter;
         sh->filter_i8 = old->filter_i8;

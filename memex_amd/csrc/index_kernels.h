@@ -46,6 +46,13 @@ constexpr int kCandCap = 16384;    // candidates finish_kernel holds per query (
 constexpr int kZeroCap = 1024;     // zero-norm rows an index tracks in its list (more: EXACT path)
 constexpr int kWildCap = 64;       // rows with a norm outside [1e-15, 1e15] an f32 index lists (more: EXACT path)
 
+// MEMEX_HIP_DEBUG=serial=N (mx_debug.h): which of the short serial stages of finish_kernel take their newer form, a sum of the
+// items below.  Either item leaves every answer, threshold and candidate set as it is; 0 = the older form throughout
+// (tests/test_serial_stages_gpu.py holds the two against each other).
+constexpr int kSerialPre = 1;      // the first select (the k-th best lower bound) selects among the keys at or above a pivot
+constexpr int kSerialSplit = 2;    // stage 3: two lanes per staged row, one per f64 chain
+constexpr int kSerialAll = 3;
+
 // cosine-unit bounds on |approx - exact| of the bf16 scan.
 //   a priori:  two bf16 roundings (unit roundoff 2^-8 each) of unit vectors, Cauchy-Schwarz:
 //              2^-7 + 2^-16, + kAccSlack for f32 accumulation/normalisation  ->  kApproxErr
@@ -233,6 +240,7 @@ hipError_t launch_theta(hipStream_t s, int B, int k, int nwg, const float *lane_
 // >= 2 = answer on the EXACT path.
 struct FinishParams {
     int k, ds, nwg;
+    int serial;                 // kSerial* items
     const float *x;             // [cap_rows, ds] f32 rows; null = compressed corpus (rows are read from xh)
     const void *xh;             // bf16 filter copy (fragment order)
     const float *scale;         // [cap_rows] 1/|c| (f32 rows only)

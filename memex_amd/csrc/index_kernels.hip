@@ -132,6 +132,118 @@ __device__ __forceinline__ uint32_t block_kth_largest(const uint32_t (&key)[PER]
     return prefix;
 }
 
+// k-th largest of n keys that sit in LDS (ckey, 16-byte aligned; 1 <= k <= n), by rank: the thread that owns a key counts the
+// keys above it with broadcast reads, four per read; the keys with fewer than k above them are the k largest (ties included)
+// and the smallest of those is the answer: a wave minimum, then one LDS atomic per wave into *out, which holds 0xffffffff
+// when the barrier in front of this call is passed.  The caller puts a barrier behind it.  A compare and an add per pair on the
+// SIMDs' 4-cycle cadence: about n^2 / 32 cycles once n keys fill the four SIMDs -- 0.9 us at 256 keys, 3.5 at 512, which is what the
+// radix passes above take (a dozen barriers and 3 * PER LDS atomics per thread, whatever n is): kRankCap.
+constexpr uint32_t kRankCap = 512;
+__device__ __forceinline__ void lds_rank_select(const uint32_t *ckey, uint32_t n, uint32_t k, uint32_t *out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t i0 = threadIdx.x - lane; i0 < n; i0 += blockDim.x) {  // wave-uniform
+        const uint32_t i = i0 + lane;
+        const uint32_t mine = i < n ? ckey[i] : 0u;
+        uint32_t gt = 0, j = 0;
+        for (; j + 4 <= n; j += 4) {
+            const uint4 o = *reinterpret_cast<const uint4 *>(ckey + j);
+            gt += o.x > mine ? 1u : 0u;
+            gt += o.y > mine ? 1u : 0u;
+            gt += o.z > mine ? 1u : 0u;
+            gt += o.w > mine ? 1u : 0u;
+        }
+        for (; j < n; ++j) gt += ckey[j] > mine ? 1u : 0u;
+        uint32_t cand = i < n && gt < k ? mine : 0xffffffffu;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t t = __shfl_xor(cand, o);
+            cand = t < cand ? t : cand;
+        }
+        if (lane == 0 && cand != 0xffffffffu) atomicMin(out, cand);
+    }
+}
+
+// block_kth_largest for a small k among many keys (k <= kPreMaxK): select among the keys at or above a pivot that at least k keys
+// reach.  Every wave takes the kw-th largest of the 64 keys its threads hold in slot 0, kw = ceil(k / nfull) with nfull the waves
+// that nvalid keys could fill; a wave with fewer than kw valid keys there stands aside.  pivot = the smallest of these: each of the c
+// waves that took part holds kw keys >= its own value >= pivot, so c * kw >= k keys reach the pivot, the k-th largest key of all is among
+// them and is their k-th largest.  They are compacted into ckey (LDS, kRankCap words, 16-byte aligned; may be storage whose
+// earlier contents every thread has read before the call: the first barrier here stands in front of the first write) and ranked there.
+// Too few waves took part, or more than kRankCap keys reach the pivot: the radix passes, unchanged.  With keys in no particular
+// order about 5 % of the keys of a 16-wave block reach the pivot at k <= 16.
+// s_pre: nwaves + 2 words.  Requires 1 <= k <= number of valid keys, blockDim a multiple of 64 and <= 1024.
+constexpr uint32_t kPreMaxK = 32;
+template <int PER>
+__device__ __forceinline__ uint32_t block_kth_largest_pre(const uint32_t (&key)[PER], const bool (&valid)[PER], uint32_t k,
+                                                          uint32_t nvalid, uint32_t *ckey, uint32_t *s_pre, uint32_t *hist,
+                                                          uint32_t *s_pick) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, nw = blockDim.x >> 6;
+    uint32_t nfull = nvalid >> 6;
+    nfull = nfull < 1u ? 1u : nfull > nw ? nw : nfull;
+    const uint32_t kw = (k + nfull - 1) / nfull;
+    uint32_t *s_n = s_pre + nw, *s_out = s_pre + nw + 1;
+    {
+        const uint32_t mk = valid[0] ? key[0] : 0u;
+        const uint32_t have = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[0]));
+        uint32_t wp;
+        if (kw == 1) {  // the wave's largest key
+            wp = mk;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const uint32_t t = __shfl_xor(wp, o);
+                wp = t > wp ? t : wp;
+            }
+        } else {  // its kw-th largest: the smallest of the keys with fewer than kw above them
+            uint32_t gt = 0;
+#pragma unroll
+            for (int j = 0; j < 64; ++j) gt += (uint32_t)__builtin_amdgcn_readlane((int)mk, j) > mk ? 1u : 0u;  // (a scalar read per lane: no LDS crossbar)
+            wp = valid[0] && gt < kw ? mk : 0xffffffffu;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const uint32_t t = __shfl_xor(wp, o);
+                wp = t < wp ? t : wp;
+            }
+        }
+        if (lane == 0) s_pre[wave] = have >= kw ? wp : 0xffffffffu;
+        if (tid == 0) *s_n = 0, *s_out = 0xffffffffu;
+    }
+    __syncthreads();
+    uint32_t pivot = 0xffffffffu, took = 0;
+    for (uint32_t w = 0; w < nw; ++w) {
+        const uint32_t wp = s_pre[w];
+        took += wp != 0xffffffffu ? 1u : 0u;  // (a wave whose kw-th key is 0xffffffff, the key of one NaN pattern, stands aside too)
+        pivot = wp < pivot ? wp : pivot;
+    }
+    if (took * kw < k) return block_kth_largest<PER>(key, valid, k, hist, s_pick);  // block-uniform
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) cnt += valid[e] && key[e] >= pivot ? 1u : 0u;
+    uint32_t inc = cnt;  // one LDS atomic per wave, as in finish_kernel's gather
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o);
+        if (lane >= (uint32_t)o) inc += t;
+    }
+    uint32_t wbase = 0;
+    if (lane == 63 && inc) wbase = atomicAdd(s_n, inc);
+    wbase = __shfl(wbase, 63);
+    uint32_t at = wbase + inc - cnt;
+    if (cnt) {
+#pragma unroll
+        for (int e = 0; e < PER; ++e)
+            if (valid[e] && key[e] >= pivot) {
+                if (at < kRankCap) ckey[at] = key[e];
+                ++at;
+            }
+    }
+    __syncthreads();
+    const uint32_t n = *s_n;
+    if (n > kRankCap) return block_kth_largest<PER>(key, valid, k, hist, s_pick);  // block-uniform
+    lds_rank_select(ckey, n, k, s_out);
+    __syncthreads();
+    return *s_out;
+}
+
 // ---------------------------------------------------------------------------------------------
 // ingest: copy rows into the padded store and compute 1/|c|   (replaces hnsw.insert, local.rs:65)
 // ---------------------------------------------------------------------------------------------
@@ -717,6 +829,21 @@ __device__ __forceinline__ float exact_dist_row(const float *__restrict__ qv, co
     return dist_from_sums(dot, na, nb);
 }
 
+// one of exact_dist_row's two chains: sum_i f64(f32(a_i * c_i)) in element order (a = the query: dot; a = c: nb)
+__device__ __forceinline__ double f64_chain(const float *__restrict__ a, const float *__restrict__ c, int ds) {
+    double s = 0.0;
+    const float4 *a4 = reinterpret_cast<const float4 *>(a), *c4 = reinterpret_cast<const float4 *>(c);
+#pragma unroll 8
+    for (int i = 0; i < ds / 4; ++i) {
+        const float4 u = a4[i], v = c4[i];
+        s += (double)__fmul_rn(u.x, v.x);
+        s += (double)__fmul_rn(u.y, v.y);
+        s += (double)__fmul_rn(u.z, v.z);
+        s += (double)__fmul_rn(u.w, v.w);
+    }
+    return s;
+}
+
 constexpr int kFinThreads = 1024;
 constexpr int kFinishTailBytes = 128 + (2 * kMaxScanWGs + 1 + 3) * 4;  // staged row ids [32] + scanned record counts
 constexpr int kFinWaves = kFinThreads / 64;
@@ -757,6 +884,8 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     __shared__ uint32_t s_hist[256];
     __shared__ uint32_t s_pick[2];
     __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_pre[kFinWaves + 2];  // block_kth_largest_pre's
+    __shared__ uint32_t s_err;                 // profiling: the workgroup's largest |s2 - filter score| as float bits
 
     const int q = blockIdx.x;
     const int tid = threadIdx.x;
@@ -858,7 +987,7 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     const uint32_t roff = block_scan_1024(nrec, s_w, &R);
     if (tid < 2 * nwg) s_off[tid] = roff;
     if (tid == 0) s_off[2 * nwg] = R;  // (2 * nwg = kFinThreads with the int8 scan's two-workgroup form)
-    if (tid == 0) s_cnt = 0;
+    if (tid == 0) s_cnt = 0, s_err = 0;
     __syncthreads();
     // (b) one record per thread and trip (all of a query's records are in flight together): find its
     // lane buffer by binary search in the scanned counts, test the 16 scores, append the passing rows
@@ -952,7 +1081,10 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
         }
     }
     {
-        const uint32_t kth = block_kth_largest<kFinPer>(key, valid, (uint32_t)want, s_hist, s_pick);
+        // (every thread holds its entries in registers, so the prefiltered select may compact its keys into ent[]'s storage)
+        const uint32_t kth = (p.serial & kSerialPre) && (uint32_t)want <= kPreMaxK && M >= 64u
+                                 ? block_kth_largest_pre<kFinPer>(key, valid, (uint32_t)want, M, reinterpret_cast<uint32_t *>(fsm), s_pre, s_hist, s_pick)
+                                 : block_kth_largest<kFinPer>(key, valid, (uint32_t)want, s_hist, s_pick);
         const float L1 = key_f32(kth);
         if (tid == 0) s_cnt = 0;
         __syncthreads();  // also: every thread has its entries in registers, ent[] may be overwritten
@@ -1044,9 +1176,11 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
     if (p.max_err) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) err = fmaxf(err, __shfl_xor(err, o));
-        if (lane == 0 && err > 0.0f) atomicMax(reinterpret_cast<unsigned int *>(p.max_err), __float_as_uint(err));
+        // one atomic per workgroup on the batch's word, not one per wave (all on one address)
+        if (lane == 0 && err > 0.0f) atomicMax(&s_err, __float_as_uint(err));
     }
     __syncthreads();
+    if (p.max_err && tid == 0 && s_err) atomicMax(reinterpret_cast<unsigned int *>(p.max_err), s_err);
 
     // ---- k-th best f32 score L; keep [L - 2*e2, +inf); publish the retry threshold
 #pragma unroll
@@ -1140,7 +1274,21 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
             *reinterpret_cast<float4 *>(stage + (size_t)r * pitch + 4 * c4) = row_load4<CMP>(p.x, p.xh, ds, srow[r], (int)c4);
         }
         __syncthreads();
-        if (tid < (int)mt) {
+        if (p.serial & kSerialSplit) {
+            // two lanes per row, one per chain (2 * mt <= 64: one wave): lane 2r sums dot, lane 2r + 1 nb, each in exact_dist_row's
+            // element order, so the sums keep their bits; the even lane fetches nb and finishes the row
+            if (wave == 0) {
+                const uint32_t r = (uint32_t)lane >> 1;
+                const bool second = (lane & 1) != 0;
+                const float *rowp = stage + (size_t)(r < mt ? r : 0u) * pitch;
+                const double acc = r < mt ? f64_chain(second ? rowp : qv, rowp, ds) : 0.0;
+                const double nb = __shfl_down(acc, 1);
+                if (!second && r < mt) {
+                    const float d = dist_from_sums(acc, na, nb);
+                    keys[r] = r >= m2 && is_dead(srow[r]) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | srow[r];  // as below
+                }
+            }
+        } else if (tid < (int)mt) {
             const float d = exact_dist_row(qv, stage + (size_t)tid * pitch, ds, na, nullptr);
             keys[tid] = tid >= (int)m2 && is_dead(srow[tid]) ? ~0ull : ((uint64_t)__float_as_uint(d) << 32) | srow[tid];  // a masked listed row (the candidates are not): last
         }

@@ -17,7 +17,12 @@
 //   sample_div=N          the search's sample pass visits 1/N of the scan tiles (a tuning knob: results do not depend on it); read
 //                         when an index is created, like records: debug_flag costs a getenv, a mutex and a string compare, which
 //                         do not belong on the path of every batch
-//   records=1        [0]  every batch prints the record count of its collect launch to stderr (a measurement aid)
+//   serial=N         [3]  which short serial stages of finish_kernel take their newer form, a sum of 1 (the first select picks
+//                         among the keys at or above a pivot) and 2 (stage 3 gives each staged row two lanes, one per f64
+//                         chain); 0: the older forms.  Bit-identical answers and candidate counts
+//                         (tests/test_serial_stages_gpu.py); read when an index is created, like sample_div
+//   records=1        [0]  every batch prints the record count of its collect launch and the serial value of its finish launch to
+//                         stderr (a measurement aid)
 //   filt_subset=0|1  [by size]  a filtered search of at most 16384 allowed rows always takes the masked scan pipeline / the
 //                         subset kernel (bit-identical answers; tests/test_filtered_gpu.py holds the two against each other)
 // Unknown keys are ignored.  Operational switches (wait mode, exchange, filter copy) are separate, documented in
