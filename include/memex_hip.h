@@ -418,6 +418,40 @@ int mx_index_search_like_device(mx_index *idx, const float *d_queries, const flo
                                 const float *example_weights, int R, int m, int k, int exclude_examples, uint64_t *d_ids,
                                 float *d_scores, float *d_dists, int32_t *d_n_found, int32_t *d_n_used, float *d_combined);
 
+/*
+ * Score named rows: what does this query score against THESE rows?  The exact scores of a candidate list per query -- the hits of a
+ * keyword backend before the two lists are fused, a cached result page after the query changed, a user's own documents, the gold
+ * passage of an evaluation -- and the ranking of each list.  Nothing is scanned and no row leaves HBM: one workgroup per query
+ * translates its ids to rows on the device and runs the exact arithmetic on them.
+ * queries is [B, dim]; cand_ids is [B, m] and is HOST memory on both variants, ids as search returns them (id_offset applied).
+ * Outputs: scores / dists / order [B, m], n_found [B]; dists, order and n_found may be NULL.
+ *   found       Entry (b, j) is FOUND iff mx_index_search(queries[b], k = every live row) would list cand_ids[b, j]: the id names a live
+ *               (not removed) row whose dist is defined (not NaN).  scores[b, j] and dists[b, j] are then bit for bit that list's
+ *               entry for the id: f32 products, sequential f64 sums in element order, then the dist and the score of the plain search,
+ *               on the rows as stored (a bf16 corpus: its values widened).
+ *   blank       An entry that is not found holds score 0 and dist +inf: id 0 (the padding of ragged lists), an id that names no row, a
+ *               removed row, a NaN dist.  The call still returns MX_OK.
+ *   repeats     An id named twice in a list is scored twice.
+ *   n_found     n_found[b] = the found entries of query b.
+ *   order       order[b, r], r < n_found[b], is the position j of the r-th best found entry by (dist ascending, id ascending, position
+ *               j ascending); the slots from n_found[b] on hold -1.  For distinct ids that is the order in which the plain search lists
+ *               them: cand_ids[b, order[b, :k]] is the exact top-k of the list.
+ *   zero query  A zero-norm query has dist 0 against every row, as in mx_index_search.
+ * Arguments are checked first: B < 0, m < 1, a NULL queries / cand_ids / scores with B > 0: MX_EINVAL; m > 4096 (the cap on k):
+ * MX_EUNSUPPORTED; then a null index: MX_ESEARCH; B = 0 is MX_OK.  Non-finite queries are rejected as by mx_index_search.  Rows wider
+ * than 8192 padded dims: MX_EUNSUPPORTED, as for mx_index_search_mmr.  B is split into batches of 512.
+ * Thread-safe beside every other call.  Concurrent callers are NOT combined into shared passes: each call holds the index from its
+ * first upload to the end of its last kernel, so no append, removal or compaction slips in between.  The call touches neither
+ * mx_index_stats nor the filter copy (its kind, its demotion and promotion counts) and does not depend on the search mode.  A sharded
+ * handle answers bit for bit what the plain index answers: every shard scores the pairs whose rows it owns, the dist blocks meet on
+ * devices[0], and the ranking runs once on the combined block.  Extra HBM, allocated at the first call: blocks of 512 x max(m, 64)
+ * entries.
+ */
+int mx_index_score_ids(mx_index *idx, const float *queries, int B, const uint64_t *cand_ids, int m, float *scores, float *dists,
+                       int32_t *order, int32_t *n_found);
+int mx_index_score_ids_device(mx_index *idx, const float *d_queries, int B, const uint64_t *cand_ids, int m, float *d_scores,
+                              float *d_dists, int32_t *d_order, int32_t *d_n_found);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

@@ -89,6 +89,10 @@ class VectorStore {  // mod.rs:55-66
                                                         const std::vector<float> &, float, float, float) {
         throw VectorStoreError(VectorStoreError::Unsupported, "search_like");
     }
+    // exact scores and ranking of named segments (no counterpart in the trait either); limit 0: all of them
+    virtual std::vector<VectorSearchResult> rerank(const std::vector<float> &, const std::vector<std::string> &, size_t) {
+        throw VectorStoreError(VectorStoreError::Unsupported, "rerank");
+    }
 };
 
 // ---- storage/local.rs ---------------------------------------------------------------------------
@@ -665,6 +669,55 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // Score the named segments against vec and rank them: the hits of a keyword backend, a cached result page, a caller's working set,
+    // best first, cut to limit (0: all of them).  Every row stored under a named _id is a candidate (mx_index_score_ids: exact scores,
+    // the rows never leave the device; lists of up to 4096 rows, longer candidate sets go as several lists of one call); a segment is
+    // ranked by its best row in the (dist, id) order search reports and listed once.  Unknown _ids are skipped
+    std::vector<VectorSearchResult> rerank(const std::vector<float> &vec, const std::vector<std::string> &ids, size_t limit = 0) override {
+        std::vector<VectorSearchResult> out;
+        std::vector<uint64_t> rows;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || _id_map.empty()) return out;
+            build_rows_of();
+            std::set<uint64_t> have;
+            for (const std::string &n : ids) {
+                auto it = rows_of_.find(n);
+                if (it == rows_of_.end()) continue;
+                for (uint64_t r : it->second)
+                    if (have.insert(r).second) rows.push_back(r);
+            }
+        }
+        if (rows.empty()) return out;
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        const size_t m = std::min<size_t>(rows.size(), 4096), B = (rows.size() + m - 1) / m;
+        rows.resize(B * m, 0);  // id 0: the padding of the last list
+        std::vector<float> q(B * vec.size());
+        for (size_t b = 0; b < B; ++b) std::copy(vec.begin(), vec.end(), q.begin() + b * vec.size());
+        std::vector<float> scores(B * m), dists(B * m);
+        std::vector<int32_t> order(B * m), nf(B);
+        int rc = mx_index_score_ids(idx_, q.data(), (int)B, rows.data(), (int)m, scores.data(), dists.data(), order.data(), nf.data());
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        std::vector<std::pair<std::pair<float, uint64_t>, float>> ranked;  // ((dist, id), score): the order search reports
+        for (size_t b = 0; b < B; ++b)
+            for (int r = 0; r < nf[b]; ++r) {
+                const size_t at = b * m + (size_t)order[b * m + r];
+                ranked.push_back({{dists[at], rows[at]}, scores[at]});
+            }
+        if (B > 1) std::sort(ranked.begin(), ranked.end());
+        std::set<std::string> seen;
+        std::lock_guard<std::mutex> lk(mu_);
+        for (auto &r : ranked) {
+            auto it = _id_map.find((size_t)r.first.second);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            if (!seen.insert(it->second).second) continue;
+            out.emplace_back(it->second, r.second);
+            if (limit && out.size() >= limit) break;
+        }
+        return out;
+    }
+
     struct DuplicatePair {
         std::string a, b;  // the _ids of the two rows, the one with the smaller row id first
         float score;
@@ -826,6 +879,10 @@ class VectorStorage {  // mod.rs:69-93
                                                 float beta = 0.75f, float gamma = 0.15f) {
         std::lock_guard<std::mutex> lk(*mu_);
         return client->search_like(positive, negative, limit, vec, alpha, beta, gamma);
+    }
+    std::vector<VectorSearchResult> rerank(const std::vector<float> &vec, const std::vector<std::string> &ids, size_t limit = 0) {
+        std::lock_guard<std::mutex> lk(*mu_);
+        return client->rerank(vec, ids, limit);
     }
 
   private:

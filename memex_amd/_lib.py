@@ -33,6 +33,7 @@ EXPORTS = [
     "mx_index_remove", "mx_index_removed", "mx_index_compact",
     "mx_index_search", "mx_index_search_device", "mx_index_search_filtered", "mx_index_search_filtered_device", "mx_index_search_range", "mx_index_search_range_device", "mx_index_search_mmr", "mx_index_search_mmr_device",
     "mx_index_search_fused", "mx_index_search_fused_device", "mx_index_search_like", "mx_index_search_like_device",
+    "mx_index_score_ids", "mx_index_score_ids_device",
     "mx_filter_create", "mx_filter_destroy", "mx_filter_set_ranges", "mx_filter_set_ids", "mx_filter_count", "mx_filter_get_ranges",
     "mx_index_search_with_filter", "mx_index_search_with_filter_device",
     "mx_index_search_by_id", "mx_index_search_by_id_device", "mx_index_search_range_by_id", "mx_index_search_range_by_id_device",
@@ -142,6 +143,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_index_search_fused_device": [vp, vp, i32, i32, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp, vp, vp],
         "mx_index_search_like": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
         "mx_index_search_like_device": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "mx_index_score_ids": [vp, vp, i32, vp, i32, vp, vp, vp, vp],
+        "mx_index_score_ids_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp],
         "mx_index_search_by_id": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
         "mx_index_search_by_id_device": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
         "mx_index_search_range_by_id": [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp],

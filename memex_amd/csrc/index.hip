@@ -310,6 +310,14 @@ struct mx_index {
     Dev<int32_t> like_nf, like_nused;
     Dev<uint32_t> like_src, like_used;
     int like_cap = 0;
+    // scoring of named rows (mx_index_score_ids), allocated at the first such call and sized by kMaxBatch x score_cap.
+    // Every plain index or shard: the id block of a batch.  The index that owns the stream: the outputs of the host-pointer variant.
+    // A shard: its dist block when it lives on another device than shards[0], which holds the gather area of G such blocks.
+    Dev<uint64_t> score_cand;
+    Dev<float> score_scores, score_dists;
+    Dev<int32_t> score_order, score_nf;
+    Dev<uint32_t> score_part, score_gather;
+    int score_cap = 0, score_out_cap = 0, score_part_cap = 0, score_gather_cap = 0;
     // persistence bookkeeping: what vectors.mxflat in `disk_dir` holds, as far as this handle knows
     std::string disk_dir;
     uint64_t disk_rows = 0;
@@ -2390,6 +2398,119 @@ int like_batch(mx_index *idx, const float *d_q, const float *wq, const uint64_t 
     return MX_OK;
 }
 
+// ---- scoring of named rows (mx_index_score_ids) ------------------------------------------------------------
+// The buffers of the call on sh (the current device is its device), each kMaxBatch x m: the id block always; outs: the outputs of the
+// host-pointer variant (the index that owns the stream); part: a shard's own dist block (a shard on another device than shards[0]);
+// gather > 0: the gather area of that many dist blocks (shards[0] of a composite)
+int ensure_score_bufs(mx_index *sh, int m, bool outs, bool part, size_t gather) {
+    if (m <= sh->score_cap && (!outs || m <= sh->score_out_cap) && (!part || m <= sh->score_part_cap) && (!gather || m <= sh->score_gather_cap))
+        return MX_OK;
+    MX_HIP(hipStreamSynchronize(sh->stream));
+    const size_t c = (size_t)std::max(m, 64), n = (size_t)kMaxBatch * c;
+    if (m > sh->score_cap) {
+        sh->score_cap = 0;
+        MX_HIP(sh->score_cand.alloc(n));
+        sh->score_cap = (int)c;
+    }
+    if (outs && m > sh->score_out_cap) {
+        sh->score_out_cap = 0;
+        MX_HIP(sh->score_scores.alloc(n));
+        MX_HIP(sh->score_dists.alloc(n));
+        MX_HIP(sh->score_order.alloc(n));
+        MX_HIP(sh->score_nf.alloc(kMaxBatch));
+        sh->score_out_cap = (int)c;
+    }
+    if (part && m > sh->score_part_cap) {
+        sh->score_part_cap = 0;
+        MX_HIP(sh->score_part.alloc(n));
+        sh->score_part_cap = (int)c;
+    }
+    if (gather && m > sh->score_gather_cap) {
+        sh->score_gather_cap = 0;
+        MX_HIP(sh->score_gather.alloc(n * gather));
+        sh->score_gather_cap = (int)c;
+    }
+    return MX_OK;
+}
+
+// the query block and the id block (host memory, [B, m]) of a batch on sh, whose device is current: qpad / qnorm2 and the non-finite
+// flags as launch_prep_queries leaves them (no filter copy is consulted), and the score kernel's arguments but its outputs
+int score_prepare(mx_index *sh, const float *d_q, int B, const uint64_t *cand, int m, uint64_t total, ScoreIds *p) {
+    Scratch &s = sh->s;
+    MX_HIP(hipMemcpyAsync(sh->score_cand, cand, (size_t)B * m * sizeof(uint64_t), hipMemcpyHostToDevice, sh->stream));
+    MX_HIP(launch_prep_queries(sh->stream, d_q, B, sh->dim, sh->ds, s.qfrag, s.qpad, s.qnorm2, s.theta, s.e1, nullptr, s.overflow, s.qflags,
+                               s.qa, s.qb));
+    *p = ScoreIds{};
+    p->B = B;
+    p->m = m;
+    p->ds = sh->ds;
+    p->x = sh->compressed ? nullptr : sh->x.get();
+    p->xh = sh->xh;
+    p->dead = sh->n_dead ? sh->dead.get() : nullptr;
+    p->n_rows = sh->n;
+    p->total = total;
+    p->idmap = sh->idmap;
+    p->qpad = s.qpad;
+    p->qnorm2 = s.qnorm2;
+    p->cand = sh->score_cand;
+    return MX_OK;
+}
+
+// One batch (B <= kMaxBatch) of a scoring call: the queries d_q [B, dim] and the outputs [B, m] on the device of the index that owns
+// the stream, the ids cand [B, m] in host memory, the caller holding idx->mu from here to the end of the last kernel.  A plain index:
+// one score_ids_kernel launch.  A composite: every shard gets the query block and the id block and scores the pairs whose rows it
+// owns into its dist block (a shard on shards[0]'s device: straight into its slot of the gather area; another: peer-copied there),
+// and score_merge_kernel on shards[0]'s device combines and ranks.  No filter copy, no scan, no counters.  Host-synchronised.
+int score_batch(mx_index *idx, const float *d_q, int B, const uint64_t *cand, int m, float *d_scores, float *d_dists, int32_t *d_order,
+                int32_t *d_nfound) {
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    hipStream_t st = t->stream;
+    const size_t cells = (size_t)B * m;
+    int rc;
+    ScoreIds p;
+    if ((rc = ensure_scratch(t)) != MX_OK) return rc;
+    if (!idx->composite()) {
+        if ((rc = ensure_score_bufs(t, m, false, false, 0)) != MX_OK) return rc;
+        if ((rc = score_prepare(t, d_q, B, cand, m, t->n, &p)) != MX_OK) return rc;
+        p.scores = d_scores;
+        p.dists = d_dists;
+        p.order = d_order;
+        p.n_found = d_nfound;
+        MX_HIP(launch_score_ids(st, p));
+    } else {
+        const size_t G = idx->shards.size();
+        if ((rc = ensure_score_bufs(t, m, false, false, G)) != MX_OK) return rc;
+        MX_HIP(hipStreamSynchronize(st));  // the query block must be complete before other devices read it
+        for (size_t g = 0; g < G; ++g) {
+            mx_index *sh = idx->shards[g];
+            std::lock_guard<std::mutex> lk(sh->mu);
+            DeviceGuard dg(sh->device);
+            const bool same = sh->device == t->device;
+            if ((rc = ensure_scratch(sh)) != MX_OK) return rc;
+            if ((rc = ensure_score_bufs(sh, m, false, !same, sh == t ? G : 0)) != MX_OK) return rc;
+            const float *q = d_q;
+            if (sh != t) {
+                MX_HIP(hipMemcpyAsync(sh->s.qstage, d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDefault, sh->stream));
+                q = sh->s.qstage;
+            }
+            if ((rc = score_prepare(sh, q, B, cand, m, idx->total, &p)) != MX_OK) return rc;
+            uint32_t *slot = t->score_gather + g * cells;
+            p.part = same ? slot : sh->score_part.get();
+            MX_HIP(launch_score_ids(sh->stream, p));
+            if (!same) MX_HIP(hipMemcpyAsync(slot, sh->score_part, cells * sizeof(uint32_t), hipMemcpyDefault, sh->stream));  // peer copy
+            if (sh != t) MX_HIP(hipStreamSynchronize(sh->stream));
+        }
+        DeviceGuard dg(t->device);
+        ScoreMerge mg{B, m, (int)G, t->score_gather, cells, t->score_cand, d_scores, d_dists, d_order, d_nfound};
+        MX_HIP(launch_score_merge(st, mg));
+    }
+    if ((rc = fetch_flags(t)) != MX_OK) return rc;  // (host-synchronised)
+    const uint32_t *h_qfl = t->s.host_flags + 3 * kMaxBatch;
+    for (int b = 0; b < B; ++b)
+        if (h_qfl[b]) return fail(MX_EINVAL, "a query contains non-finite values");
+    return MX_OK;
+}
+
 // what an append can change in a plain index, and how to undo it: an insert is all-or-nothing, also when it
 // spans several shards or several staging chunks and a later part fails (non-finite device rows, HBM)
 struct RowMark {
@@ -4465,6 +4586,79 @@ int mx_index_search_like_device(mx_index *idx, const float *d_queries, const flo
                             example_ids + e0, example_weights ? example_weights + e0 : nullptr, nr, m, k, exclude_examples, d_ids + o,
                             d_scores + o, d_dists ? d_dists + o : nullptr, d_n_found + r0, d_n_used ? d_n_used + r0 : nullptr,
                             d_combined ? d_combined + (size_t)r0 * dim : nullptr);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+namespace {
+
+// arguments of the scoring entry points, checked before the index is looked at
+static int read_score_args(const void *q, int B, const uint64_t *cand_ids, int m, const void *scores) {
+    if (B < 0) return fail(MX_EINVAL, "negative batch");
+    if (m < 1) return fail(MX_EINVAL, "m = %d < 1", m);
+    if (B > 0 && (!q || !cand_ids || !scores)) return fail(MX_EINVAL, "null argument");
+    if (m > kScoreMaxIds) return fail(MX_EUNSUPPORTED, "m = %d > %d", m, kScoreMaxIds);
+    return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_score_ids(mx_index *idx, const float *queries, int B, const uint64_t *cand_ids, int m, float *scores, float *dists,
+                       int32_t *order, int32_t *n_found) try {
+    if (int rc = read_score_args(queries, B, cand_ids, m, scores); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B == 0) return MX_OK;
+    const size_t dim = (size_t)idx->dim;
+    for (size_t i = 0; i < (size_t)B * dim; ++i)
+        if (!std::isfinite(queries[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    // not combined with other callers: the call holds the index from the first upload to the end of its last kernel
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;  // owner of the staging buffers and the stream
+    if (t->ds > kMmrMaxDs) return fail(MX_EUNSUPPORTED, "scoring of named rows supports dim <= %d", kMmrMaxDs);
+    DeviceGuard g(t->device);
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_score_bufs(t, m, true, false, 0)) != MX_OK) return rc;
+    Scratch &s = t->s;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * m, cells = (size_t)nb * m;
+        memcpy(s.h_q, queries + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        if ((rc = score_batch(idx, s.qstage, nb, cand_ids + o, m, t->score_scores, dists ? t->score_dists.get() : nullptr,
+                              order ? t->score_order.get() : nullptr, n_found ? t->score_nf.get() : nullptr)) != MX_OK)
+            return rc;
+        MX_HIP(hipMemcpyAsync(scores + o, t->score_scores, cells * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        if (dists) MX_HIP(hipMemcpyAsync(dists + o, t->score_dists, cells * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        if (order) MX_HIP(hipMemcpyAsync(order + o, t->score_order, cells * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        if (n_found) MX_HIP(hipMemcpyAsync(n_found + b0, t->score_nf, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipStreamSynchronize(t->stream));
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_score_ids_device(mx_index *idx, const float *d_queries, int B, const uint64_t *cand_ids, int m, float *d_scores,
+                              float *d_dists, int32_t *d_order, int32_t *d_n_found) try {
+    if (int rc = read_score_args(d_queries, B, cand_ids, m, d_scores); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    if (B == 0) return MX_OK;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    mx_index *t = idx->composite() ? idx->shards[0] : idx;
+    if (t->ds > kMmrMaxDs) return fail(MX_EUNSUPPORTED, "scoring of named rows supports dim <= %d", kMmrMaxDs);
+    DeviceGuard g(t->device);
+    const size_t dim = (size_t)idx->dim;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * m;
+        int rc = score_batch(idx, d_queries + (size_t)b0 * dim, nb, cand_ids + o, m, d_scores + o, d_dists ? d_dists + o : nullptr,
+                             d_order ? d_order + o : nullptr, d_n_found ? d_n_found + b0 : nullptr);
         if (rc != MX_OK) return rc;
     }
     return MX_OK;

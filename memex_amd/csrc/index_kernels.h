@@ -1,7 +1,7 @@
 // index_kernels.h -- device-side contract of the flat cosine index (launch wrappers + shared
 // constants).  The streaming scans live in scan.hip (f32 rows), scan16.hip / scan16w.hip (bf16 filter
 // copy, with its builder) and scan8.hip (int8 filter copy, with its builder), what they share in
-// scan_common.h; compaction in compact.hip, the search by examples in like_kernels.hip, every other kernel in index_kernels.hip; index.hip holds
+// scan_common.h; compaction in compact.hip, the search by examples in like_kernels.hip, the scoring of named rows in score_kernels.hip, every other kernel in index_kernels.hip; index.hip holds
 // the host logic behind the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -483,5 +483,45 @@ struct LikeDrop {
     int32_t *n_found;
 };
 hipError_t launch_like_drop_examples(hipStream_t s, const LikeDrop &p);
+
+// scoring of named rows (mx_index_score_ids; score_kernels.hip)
+constexpr int kScoreMaxIds = 4096;               // entries per query: their ranking keys (dist bits, id, position) fit 48 KiB of LDS
+constexpr int kScoreThreads = 1024;              // one workgroup per query; thread t owns entries t, t + 1024, ...
+constexpr uint32_t kScoreNotMine = 0xffffffffu;  // ScoreIds::part of an entry whose id names no row of the shard (no dist has these bits:
+constexpr uint32_t kScoreBlank = 0xfffffffeu;    // a NaN dist is blank) | ... of a row of the shard that is removed or has a NaN dist
+// Exact DistCosine (exact_dist_stored: the f64 chain of finish_kernel's stage 3 and of the EXACT path) of query b (qpad / qnorm2 of
+// launch_prep_queries) against the rows its m ids cand[b, 0 .. m) name, B queries.  An id names global row id - id_offset - 1 of the
+// `total` rows of the handle; a shard (idmap.block_rows != 0) holds the rows of its own blocks, as local rows below n_rows.  An entry
+// is FOUND when its id names a row of this index whose bit in `dead` (null: no removals) is clear and whose dist is not NaN.
+// Plain form (part null): scores / dists [B, m] in the caller's order, score 0 and dist +inf where the entry is not found; n_found[b] =
+// the found entries; order[b, r] for r < n_found[b] = the position j of the r-th smallest found entry by (dist bits, id, j), -1 behind
+// them.  dists, order, n_found may be null.  Shard form (part given): the dist bits alone into part[b, j], kScoreNotMine / kScoreBlank
+// otherwise; scores, dists, order, n_found are not touched.  1 <= m <= kScoreMaxIds, ds <= kMmrMaxDs.
+struct ScoreIds {
+    int B, m, ds;
+    const float *x;            // [cap_rows, ds] f32 rows; null = compressed corpus (rows are read from xh)
+    const void *xh;
+    const uint64_t *dead;
+    uint64_t n_rows, total;
+    IdMap idmap;
+    const float *qpad;
+    const double *qnorm2;
+    const uint64_t *cand;
+    uint32_t *part;
+    float *scores, *dists;
+    int32_t *order, *n_found;
+};
+hipError_t launch_score_ids(hipStream_t s, const ScoreIds &p);
+// The G shard blocks of a sharded handle (block g: parts + g * stride words, [B, m] each) -> the outputs of the plain form: entry (b, j)
+// is the one value that is not kScoreNotMine (none: blank), cand[b, j] its id for the ranking.
+struct ScoreMerge {
+    int B, m, G;
+    const uint32_t *parts;
+    size_t stride;
+    const uint64_t *cand;
+    float *scores, *dists;
+    int32_t *order, *n_found;
+};
+hipError_t launch_score_merge(hipStream_t s, const ScoreMerge &p);
 
 }  // namespace mx

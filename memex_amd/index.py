@@ -570,6 +570,60 @@ class FlatIndex:
         check(lib().mx_index_search_like_device(self._h, dp(queries), opt(qw), opt(a), opt(w), R, m, int(k), int(exclude_examples),
                                                 dp(ids), dp(scores), dp(dists), dp(n_found), dp(n_used), dp(combined)))
 
+    # -- scoring of named rows -------------------------------------------------------------
+    @staticmethod
+    def _cand_ids(ids, B: int) -> np.ndarray:
+        """-> candidate ids u64 [B, m]; a list of lists is padded with 0 to its longest list"""
+        if B == 0:
+            return np.zeros((0, 1), dtype=np.uint64)
+        if not isinstance(ids, np.ndarray) and len(ids) and all(hasattr(r, "__len__") for r in ids):
+            m = max(max((len(r) for r in ids), default=0), 1)
+            a = np.zeros((len(ids), m), dtype=np.uint64)
+            for b, r in enumerate(ids):
+                a[b, :len(r)] = np.asarray(r, dtype=np.uint64)
+        else:
+            a = np.asarray(ids, dtype=np.uint64)
+            if a.ndim == 1:
+                a = a[None, :]
+        if a.ndim != 2 or a.shape[0] != B:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [{B}, m] candidate ids, got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def score_ids(self, queries, ids):
+        """What do these queries score against THESE rows (``mx_index_score_ids``): ``ids`` is [B, m], or a list of B lists padded
+        with 0, of ids as ``search`` returns them.  -> (scores f32 [B,m], dists f32 [B,m], order i32 [B,m], n_found i32 [B]).
+        An entry is found when ``search(queries[b], k=len(self))`` would list its id, and then holds that list's score and dist bit
+        for bit; every other entry (id 0, an id that names no row, a removed row) is blank: score 0, dist +inf.  ``order[b, r]``,
+        r < n_found[b], is the position of the r-th best found entry by (dist, id, position), -1 behind them:
+        ``ids[b, order[b, :k]]`` is the exact top-k of the list.  Nothing is scanned and no row leaves HBM."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        B = q.shape[0]
+        a = self._cand_ids(ids, B)
+        m = a.shape[1]
+        scores = np.zeros((B, m), dtype=np.float32)
+        dists = np.full((B, m), np.inf, dtype=np.float32)
+        order = np.full((B, m), -1, dtype=np.int32)
+        nf = np.zeros(B, dtype=np.int32)
+        opt = lambda x: _ptr(x) if x.size else None  # noqa: E731
+        check(lib().mx_index_score_ids(self._h, opt(q), B, opt(a), m, opt(scores), opt(dists), opt(order), opt(nf)))
+        return scores, dists, order, nf
+
+    def score_ids_device(self, q, ids, scores, dists=None, order=None, n_found=None) -> None:
+        """``score_ids`` on device tensors: q f32 [B,dim]; scores, dists f32 [B,m]; order i32 [B,m]; n_found i32 [B] (dists, order and
+        n_found may be None).  The candidate ids stay on the host.  Blocks until the results are in HBM."""
+        B = int(q.shape[0])
+        a = self._cand_ids(ids, B)
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().mx_index_score_ids_device(self._h, dp(q) if B else None, B, _ptr(a) if a.size else None, a.shape[1], dp(scores),
+                                              dp(dists), dp(order), dp(n_found)))
+
     def near_duplicates(self, min_score: float, per_row: int = 64, block: int = 512):
         """The exact self-join: every pair of live rows whose score reaches ``min_score``.
         -> (pairs u64 [P, 2] with pairs[:, 0] < pairs[:, 1], sorted by (first id, second id), each pair once; scores f32 [P];

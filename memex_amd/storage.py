@@ -675,6 +675,47 @@ class HipFlatStore(VectorStore):
                 out.append((self._id_map[d_id], float(scores[0, j])))
         return out
 
+    def rerank(self, vec: Sequence[float], ids: Sequence[str], limit: int | None = None) -> List[VectorSearchResult]:
+        """Score the named segments against ``vec`` and rank them: the hits of a keyword backend, a cached result page, a caller's
+        own working set, as ``(_id, score)`` pairs like ``search``, best first, cut to ``limit`` (None: all of them).  Every row
+        stored under a named ``_id`` is a candidate (``FlatIndex.score_ids``: exact scores, the rows never leave the device); a
+        segment is ranked by its best row, in the (dist, id) order ``search`` reports, and listed once.  Names the store does not
+        know, and segments whose rows were all removed, are skipped."""
+        with self._lock:
+            idx = self._index
+            if idx is None or not self._id_map or (limit is not None and limit <= 0):
+                return []
+            by_name = self._rows_by_name()
+            rows = list(dict.fromkeys(r for n in ids for r in by_name.get(str(n), ())))
+        if not rows:
+            return []
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        cap = 4096                                                    # ids per list: longer candidate sets go as several lists
+        lists = [rows[i:i + cap] for i in range(0, len(rows), cap)]
+        try:
+            scores, dists, order, nf = idx.score_ids(np.broadcast_to(q, (len(lists), self._dim)), lists)  # not under the lock, like search
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        found = [(float(dists[b, j]), lists[b][j], float(scores[b, j])) for b in range(len(lists)) for j in order[b, :int(nf[b])]]
+        if len(lists) > 1:
+            found.sort(key=lambda e: (e[0], e[1]))
+        out: List[VectorSearchResult] = []
+        seen = set()
+        with self._lock:
+            for _, r, score in found:
+                if r not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                name = self._id_map[r]
+                if name in seen:
+                    continue
+                seen.add(name)
+                out.append((name, score))
+                if limit is not None and len(out) >= int(limit):
+                    break
+        return out
+
     def find_duplicates(self, min_score: float, per_row: int = 64) -> Tuple[List[Tuple[str, str, float]], List[str]]:
         """The rows of the collection that repeat each other: every pair of live rows whose score reaches ``min_score``
         (``FlatIndex.near_duplicates``, an exact self-join on the device) -> (``(_id_a, _id_b, score)`` per pair, in id order;
@@ -745,6 +786,10 @@ class VectorStorage:
                     alpha: float = 1.0, beta: float = 0.75, gamma: float = 0.15) -> List[VectorSearchResult]:
         with self._mu:
             return self.client.search_like(positive, negative, limit, vec, alpha, beta, gamma)
+
+    def rerank(self, vec: Sequence[float], ids: Sequence[str], limit: int | None = None) -> List[VectorSearchResult]:
+        with self._mu:
+            return self.client.rerank(vec, ids, limit)
 
 
 def get_vector_storage(uri: str, collection: str, device: int = 0, devices: Sequence[int] | None = None) -> VectorStorage:

@@ -18,6 +18,9 @@ and a hypothetical answer, the last turns of a conversation), one ranked list ba
 :func:`search_docs_feedback` has none either: a query (or none) together with the segments marked relevant and irrelevant, one list back
 (``search_like``, Rocchio relevance feedback computed on the device).
 
+:func:`rerank_docs` has none either: a query and the segments something else found (a keyword backend, a cached result page, the
+caller's own working set), those segments back with their exact scores, best first (``rerank``; nothing is searched).
+
 The ids are the reference's own (RFC 4122 v5 over the same namespace), so a collection filled through this mirror lines up
 with the rows a memex worker would have written for the same task ids.
 """
@@ -89,3 +92,13 @@ def search_docs_feedback(client, embedder, query, relevant: Sequence[str], irrel
             raise ValueError("Invalid query")
         vec = res.vector
     return client.search_like(list(relevant), list(irrelevant), limit, vec)
+
+
+def rerank_docs(client, embedder, query: str, candidates: Sequence[str], limit: int = 10) -> List[Tuple[str, float]]:
+    """Score the ``candidates`` (segment ``_id``s from a keyword backend, a cached page, a working set) against the query and rank
+    them: ``encode_single(query)`` -> ``client.rerank(vector, candidates, limit)`` -> ``(segment _id, score)`` pairs, best first,
+    with the scores ``search_docs`` would report for them.  ``ValueError("Invalid query")`` where ``search_docs`` raises it."""
+    res = embedder.encode_single(query)
+    if res is None:
+        raise ValueError("Invalid query")
+    return client.rerank(res.vector, list(candidates), limit)
