@@ -581,7 +581,9 @@ class HipFlatStore : public VectorStore {
 
     // more like this: the `limit` entries closest to what is stored under _id, the asked _id itself left out.  Every row stored under
     // _id is a query (mx_index_search_by_id: the rows never leave the device, the own row is taken out exactly); the union of their
-    // answers is ranked by best score, each row once.  An unknown _id returns nothing
+    // answers is ranked by best score, each row once.  An unknown _id returns nothing.  Every list must hold limit + (rows under _id)
+    // entries for the answer to be exact (the rows under _id take up places in it and are dropped below), and the library's lists end
+    // at 4095: a larger sum throws Unsupported instead of answering from shortened lists
     std::vector<VectorSearchResult> more_like(const std::string &_id, size_t limit) {
         std::vector<VectorSearchResult> out;
         std::vector<uint64_t> mine;
@@ -593,7 +595,10 @@ class HipFlatStore : public VectorStore {
             if (it != rows_of_.end()) mine.assign(it->second.begin(), it->second.end());
         }
         if (mine.empty()) return out;
-        const size_t k = std::min<size_t>(limit + mine.size(), 4095);  // the rows under _id are the only entries dropped below
+        if (limit > 4095 || limit + mine.size() > 4095)
+            throw VectorStoreError(VectorStoreError::Unsupported, "more_like: limit + the rows under the _id exceeds 4095");
+        const size_t k = limit + mine.size();  // the rows under _id are the only entries dropped below
+        const std::set<uint64_t> own(mine.begin(), mine.end());
         std::vector<uint64_t> found(mine.size() * k);
         std::vector<float> scores(found.size()), dists(found.size());
         std::vector<int32_t> nf(mine.size());
@@ -603,7 +608,7 @@ class HipFlatStore : public VectorStore {
         for (size_t b = 0; b < mine.size(); ++b)
             for (int j = 0; j < nf[b]; ++j) {
                 const uint64_t r = found[b * k + j];
-                if (std::find(mine.begin(), mine.end(), r) != mine.end()) continue;
+                if (own.count(r)) continue;
                 auto it = best.find(r);
                 if (it == best.end() || dists[b * k + j] < it->second.first) best[r] = {dists[b * k + j], scores[b * k + j]};
             }
@@ -624,7 +629,9 @@ class HipFlatStore : public VectorStore {
     // relevance feedback (Rocchio) over segment _ids: more like `positive`, less like `negative`, the named segments themselves left
     // out.  Every row stored under a named _id is an example (mx_index_search_like: the rows never leave the device), scaled to unit
     // length and weighted beta / n_pos_rows or -gamma / n_neg_rows; vec (empty: none), the query the feedback is about, weighs alpha.
-    // Unknown _ids are ignored; more than 16 rows in all: std::invalid_argument.  No example row and no vec returns nothing
+    // Unknown _ids are ignored; more than 16 rows in all: std::invalid_argument.  No example row and no vec returns nothing.
+    // The weights are f32 divisions of the f32 parameters (beta / (float)n_pos_rows): the C ABI takes float weights, and the Python
+    // mirror (memex_amd/storage.py) computes the same bits
     std::vector<VectorSearchResult> search_like(const std::vector<std::string> &positive, const std::vector<std::string> &negative = {},
                                                 size_t limit = 10, const std::vector<float> &vec = {}, float alpha = 1.0f,
                                                 float beta = 0.75f, float gamma = 0.15f) override {

@@ -155,6 +155,15 @@ def evict_resident(storage_path: str | None = None) -> None:
                 st._index = None
 
 
+def _rocchio_weights(beta: float, gamma: float, n_pos: int, n_neg: int) -> np.ndarray:
+    """``search_like``'s example weights, f32 [n_pos + n_neg]: ``beta / n_pos`` then ``-gamma / n_neg``, each ONE f32 division of f32
+    values -- what ``memex::HipFlatStore::search_like`` computes from its ``float`` parameters (a double division rounded afterwards
+    differs from it by an ulp, e.g. for 0.15 / 5)."""
+    pos = np.float32(beta) / np.float32(n_pos) if n_pos else np.float32(0)
+    neg = -np.float32(gamma) / np.float32(n_neg) if n_neg else np.float32(0)
+    return np.array([pos] * n_pos + [neg] * n_neg, dtype=np.float32)
+
+
 class StoreFilter:
     """A resident filter of a ``HipFlatStore``, edited by ``_id`` string (``HipFlatStore.make_filter``)."""
 
@@ -575,7 +584,10 @@ class HipFlatStore(VectorStore):
             idx = self._index
         if idx is None or limit <= 0 or len(vecs) == 0:
             return []
-        q = np.asarray(vecs, dtype=np.float32)
+        try:
+            q = np.asarray(vecs, dtype=np.float32)
+        except ValueError as e:                               # vectors of different lengths: a dimension mismatch like any other
+            raise SearchError(f"query vectors of different dimensions: {e}") from e
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise SearchError(f"query dimension {q.shape} != [m, store dimension {self._dim}]")
         try:
@@ -604,7 +616,8 @@ class HipFlatStore(VectorStore):
         """More like this: the ``limit`` entries closest to what is stored under ``_id``, as ``(_id, score)`` pairs like ``search``,
         the asked ``_id`` itself left out.  Every row stored under ``_id`` is a query (``FlatIndex.search_by_id``: the rows never
         leave the device); the union of their answers is ranked by best score, each row once.  An unknown ``_id``, or one whose
-        rows were all removed, returns ``[]``."""
+        rows were all removed, returns ``[]``.  ``limit`` + the rows under ``_id`` may not exceed 4095 (the lists the device
+        returns hold that many entries and the rows under ``_id`` take up places in them): ``Unsupported`` beyond."""
         with self._lock:
             idx = self._index
             if idx is None or limit <= 0 or not self._id_map:
@@ -612,6 +625,8 @@ class HipFlatStore(VectorStore):
             mine = list(self._rows_by_name().get(str(_id), ()))
         if not mine:
             return []
+        if int(limit) + len(mine) > 4095:
+            raise Unsupported(f"more_like: limit {int(limit)} + {len(mine)} rows under the _id exceeds 4095")
         try:
             # limit + the rows under _id: they are the only entries dropped below, so `limit` others are among them
             ids, scores, dists, nf = idx.search_by_id(mine, int(limit) + len(mine), exclude_self=True)
@@ -643,7 +658,9 @@ class HipFlatStore(VectorStore):
         (``FlatIndex.search_like``: the rows never leave the device), scaled to unit length and weighted ``beta / n_pos_rows``
         (positive) or ``-gamma / n_neg_rows`` (negative); ``vec``, the query the feedback is about, weighs ``alpha``.  Unknown
         ``_id``s are ignored; more than 16 rows in all raise ``ValueError``.  No example row and no ``vec`` returns ``[]``.  A row that
-        was removed but not compacted away yet still counts in ``n_pos_rows`` / ``n_neg_rows``; it takes no part in the blend."""
+        was removed but not compacted away yet still counts in ``n_pos_rows`` / ``n_neg_rows``; it takes no part in the blend.
+        The weights are f32 divisions of the f32 values of ``beta`` and ``gamma`` (``np.float32(beta) / np.float32(n_pos_rows)``): the
+        C ABI takes ``float`` weights and the C++ and Rust callers hold ``f32`` parameters, so every host sends the same bits."""
         with self._lock:
             idx = self._index
             if idx is None or limit <= 0 or not self._id_map:
@@ -661,7 +678,7 @@ class HipFlatStore(VectorStore):
         if not pos and not neg and q is None:
             return []
         ex = np.array(pos + neg if pos or neg else [0], dtype=np.uint64)
-        w = np.array([beta / len(pos)] * len(pos) + [-gamma / len(neg)] * len(neg) if pos or neg else [0.0], dtype=np.float32)
+        w = _rocchio_weights(beta, gamma, len(pos), len(neg)) if pos or neg else np.zeros(1, dtype=np.float32)
         try:
             ids, scores, _, nf, _, _ = idx.search_like(ex, int(limit), w, q, None if q is None else float(alpha))  # not under the lock, like search
         except _lib.MemexHipError as e:

@@ -342,7 +342,8 @@ def test_store_search_like_after_remove_and_compact(lib_built, tmp_path):
     def expect(pos_rows, neg_rows, limit, q=None):
         """the store's Rocchio weights through the index call, ids -> names"""
         ex = np.array(pos_rows + neg_rows, dtype=np.uint64)
-        w = np.array([0.75 / len(pos_rows)] * len(pos_rows) + [-0.15 / len(neg_rows)] * len(neg_rows), np.float32)
+        w = np.array([np.float32(0.75) / np.float32(len(pos_rows))] * len(pos_rows) +       # f32 divisions of the f32 parameters
+                     [-np.float32(0.15) / np.float32(len(neg_rows))] * len(neg_rows), np.float32)
         ids, sc, _, nf, nu, _ = st._index.search_like(ex, limit, w, q, None if q is None else 1.0)
         return [(st._id_map[int(i)], float(s)) for i, s in zip(ids[0, :nf[0]], sc[0, :nf[0]])], int(nu[0])
     got = st.search_like(["s20", "s16", "nobody"], ["s90"], 5)
