@@ -452,6 +452,68 @@ int mx_index_score_ids(mx_index *idx, const float *queries, int B, const uint64_
 int mx_index_score_ids_device(mx_index *idx, const float *d_queries, int B, const uint64_t *cand_ids, int m, float *d_scores,
                               float *d_dists, int32_t *d_order, int32_t *d_n_found);
 
+/*
+ * Grouped search: the k best DOCUMENTS, each represented by its best segment.  A row is one window of a document, and a document is
+ * stored as a run of overlapping windows: a plain top-10 for a question one long document answers well is ten windows of it.
+ *
+ * A GROUPING says which rows belong together: one u32 key per row, kept in HBM on devices[0] and named by handle, like a resident
+ * filter.  Key 0 means "ungrouped": such a row is a group of its own.  A new grouping has key 0 everywhere, and rows appended after
+ * the last edit have key 0 until a call names them.  Nothing is written to the store files and nothing is dealt to shards: the host
+ * that owns the segment -> document mapping builds the grouping, and builds it again after a restart.  4 bytes of HBM per row.
+ *   mx_grouping_create     the all-zero grouping of the rows of `idx`.  The grouping holds a reference on the index, as a filter does;
+ *                          mx_grouping_destroy drops it.
+ *   mx_grouping_set_ranges range i, the ids [ranges[2 i], ranges[2 i + 1]), gets the key keys[i]; a key of 0 un-groups.  The ranges
+ *                          of ONE call must be pairwise disjoint (empty ranges aside): an overlap, lo > hi in any pair, or a NULL
+ *                          ranges / keys with n_ranges > 0 is MX_EINVAL.  They may come in any order.
+ *   mx_grouping_set_ids    ids[i] gets the key keys[i].  Ids may repeat and come in any order; an id named twice in one call with
+ *                          DIFFERENT keys is MX_EINVAL (the same key twice is fine).
+ *   mx_grouping_get_keys   keys[i] = the key of the row ids[i] names; 0 for an id that names no row.
+ *   mx_grouping_count      n_keyed: rows with a non-zero key; n_live_keyed: those of them that are not removed (either may be NULL).
+ * Ids are the ids search returns, id_offset applied at the time of the call; an id outside [id_offset + 1, id_offset + size] at that
+ * time is ignored.  The keys are stored per row: a later mx_index_set_id_offset moves the ids along with the rows.  Removed rows keep
+ * their key and are never listed.  A failing call changes nothing.  mx_index_clear, mx_index_load and an mx_index_compact that dropped
+ * at least one row make every grouping of the index STALE: every call with it except mx_grouping_destroy returns MX_EINVAL with a
+ * message that says so.  A grouping named together with an index it was not made for: MX_EINVAL.  Grouping calls are thread-safe
+ * beside every other call on the index; a search sees a grouping before or after a whole set_* call, never half of one; a grouping
+ * must not be destroyed while a call that names it is running.
+ *
+ *   mx_index_search_grouped[_device]   queries [B, dim]; outputs ids / scores / dists / keys / group_rows [B, k], n_found / complete
+ *                          [B]; dists, keys, group_rows and complete may be NULL.  f may be NULL.  Per query:
+ *   candidates  the list L = what mx_index_search gives with k = fetch, bit for bit -- with f, what mx_index_search_with_filter
+ *               gives: (dist, id) order, removed rows, id_offset, the AUTO path up to fetch = 256 and the EXACT path above, B split
+ *               into batches of 512.  The candidate stage IS a plain search pass: it counts as one in mx_index_stats and in the
+ *               filter copy's heuristics.
+ *   heads       walking L in its order, an entry is a HEAD if its key is 0 or no earlier entry of L has its key.  The first k heads
+ *               are reported, in that order: ids / scores / dists are the entry's, unchanged; keys is its key; group_rows the number
+ *               of entries of L with that key (1 for key 0).  n_found = min(k, heads in L).  Unused slots hold id 0, score 0,
+ *               dist +inf, key 0, group_rows 0.
+ *   complete    complete[b] = 1 iff n_found[b] == k or L holds fewer than fetch entries.
+ * complete = 1 promises the EXACT top-k groups over ALL live rows (all allowed live rows, with f), each with its exact best row and
+ * score; complete = 0 promises the exact grouping of the top-fetch list only, and a larger fetch may find more groups.  (L is a prefix of
+ * all rows in (dist, id) order: with k heads in it, nothing ahead of a head is missing, and every group without a row in L lies behind
+ * its last entry; a list shorter than fetch holds every row.  DESIGN.md 3.16.)  group_rows is always with respect to L.
+ * Arguments are checked first: B < 0, k < 1, fetch < k, a NULL grouping, a NULL queries / ids / scores / n_found with B > 0:
+ * MX_EINVAL; fetch > 4096 (the cap on k): MX_EUNSUPPORTED; then a null index: MX_ESEARCH; then a stale or foreign grouping or filter:
+ * MX_EINVAL.  Non-finite queries are rejected as by mx_index_search.  Thread-safe beside every other call.  Concurrent callers are
+ * NOT combined into shared passes: each call holds the index across its candidate stage and its grouping (both see one snapshot of
+ * the rows and of the keys) and never rides in a plain, filtered or range pass.  A sharded handle merges the candidate lists on
+ * devices[0] as a search does and groups there: the answer equals the plain index's bit for bit.  The grouping step costs
+ * O(fetch^2) key compares per query, independent of dim and of the row count.  Extra HBM, allocated at the first call: the candidate
+ * lists (shared with mx_index_search_mmr) and, for the host-pointer variant, 512 x max(k, 16) keys and counts.
+ */
+typedef struct mx_grouping mx_grouping;
+int mx_grouping_create(mx_index *idx, mx_grouping **out);
+void mx_grouping_destroy(mx_grouping *g);
+int mx_grouping_set_ranges(mx_grouping *g, const uint64_t *ranges, const uint32_t *keys, uint64_t n_ranges);
+int mx_grouping_set_ids(mx_grouping *g, const uint64_t *ids, const uint32_t *keys, uint64_t n_ids);
+int mx_grouping_get_keys(mx_grouping *g, const uint64_t *ids, uint64_t n_ids, uint32_t *keys);
+int mx_grouping_count(mx_grouping *g, uint64_t *n_keyed, uint64_t *n_live_keyed);
+int mx_index_search_grouped(mx_index *idx, mx_grouping *g, mx_filter *f, const float *queries, int B, int k, int fetch, uint64_t *ids,
+                            float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_found, uint8_t *complete);
+int mx_index_search_grouped_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_queries, int B, int k, int fetch,
+                                   uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows,
+                                   int32_t *d_n_found, uint8_t *d_complete);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

@@ -579,6 +579,140 @@ class HipFlatStore : public VectorStore {
         return out;
     }
 
+    // A resident grouping (mx_grouping): which segments belong to which document, one u32 key per row kept in HBM and named in
+    // search_documents().  Every document name gets a key 1, 2, ... the first time it is seen; segments no call names are groups of
+    // their own.  bulk_insert of a document, then assign(document, {its _ids}), is the ingest flow; release() un-groups.  The grouping
+    // is not saved with the store: after compact(), delete_all() or a reload every call but the destructor throws: make a new one.
+    class Grouping {
+      public:
+        Grouping(const Grouping &) = delete;
+        Grouping &operator=(const Grouping &) = delete;
+        Grouping(Grouping &&o) noexcept : store_(o.store_), g_(o.g_), key_of_(std::move(o.key_of_)), name_of_(std::move(o.name_of_)) {
+            o.g_ = nullptr;
+        }
+        ~Grouping() {
+            if (g_) mx_grouping_destroy(g_);
+        }
+        // document name -> the segment _ids under it, in one edit
+        void assign_all(const std::map<std::string, std::vector<std::string>> &documents) {
+            std::lock_guard<std::mutex> lk(store_->mu_);
+            std::vector<std::pair<uint32_t, const std::vector<std::string> *>> pairs;
+            for (auto &kv : documents) pairs.emplace_back(key_of(kv.first), &kv.second);
+            set(pairs);
+        }
+        void assign(const std::string &document, const std::vector<std::string> &ids) { assign_all({{document, ids}}); }
+        void release(const std::vector<std::string> &ids) {
+            std::lock_guard<std::mutex> lk(store_->mu_);
+            set({{0u, &ids}});
+        }
+        // the document name of a key; nothing for key 0 (ungrouped) or a key never handed out
+        std::optional<std::string> document_of(uint32_t key) const {
+            auto it = name_of_.find(key);
+            return it == name_of_.end() ? std::nullopt : std::optional<std::string>(it->second);
+        }
+        // rows under a document, and those of them that are not removed
+        std::pair<uint64_t, uint64_t> count() const {
+            uint64_t a = 0, l = 0;
+            int rc = mx_grouping_count(g_, &a, &l);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            return {a, l};
+        }
+
+      private:
+        friend class HipFlatStore;
+        Grouping(HipFlatStore *store, mx_grouping *g) : store_(store), g_(g) {}
+        uint32_t key_of(const std::string &document) {
+            auto it = key_of_.find(document);
+            if (it != key_of_.end()) return it->second;
+            if (key_of_.size() >= 0xffffffffull) throw VectorStoreError(VectorStoreError::SearchError, "a grouping holds at most 2^32 - 1 documents");
+            const uint32_t key = (uint32_t)key_of_.size() + 1;
+            key_of_[document] = key;
+            name_of_[key] = document;
+            return key;
+        }
+        // (under the store's lock) one mx_grouping_set_ids call for all the pairs
+        void set(const std::vector<std::pair<uint32_t, const std::vector<std::string> *>> &pairs) {
+            store_->build_rows_of();
+            std::vector<uint64_t> rows;
+            std::vector<uint32_t> keys;
+            for (auto &p : pairs) {
+                std::set<std::string> seen;
+                for (auto &id : *p.second) {
+                    if (!seen.insert(id).second) continue;
+                    auto it = store_->rows_of_.find(id);
+                    if (it == store_->rows_of_.end()) continue;
+                    rows.insert(rows.end(), it->second.begin(), it->second.end());
+                    keys.insert(keys.end(), it->second.size(), p.first);
+                }
+            }
+            int rc = mx_grouping_set_ids(g_, rows.empty() ? nullptr : rows.data(), keys.empty() ? nullptr : keys.data(), rows.size());
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        }
+        HipFlatStore *store_;
+        mx_grouping *g_;
+        std::map<std::string, uint32_t> key_of_;
+        std::map<uint32_t, std::string> name_of_;
+    };
+
+    Grouping make_grouping(const std::map<std::string, std::vector<std::string>> &documents = {}) {
+        mx_grouping *g = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_) throw VectorStoreError(VectorStoreError::SearchError, "a grouping needs a store with rows: insert first");
+            int rc = mx_grouping_create(idx_, &g);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        }
+        Grouping out(this, g);
+        if (!documents.empty()) out.assign_all(documents);
+        return out;
+    }
+
+    // one document of a search_documents answer: its name (nothing for an ungrouped segment), its best segment, that segment's score,
+    // and how many of the candidates looked at belong to it
+    struct DocumentHit {
+        std::optional<std::string> document;
+        std::string segment;
+        float score;
+        int32_t group_rows;
+    };
+
+    // the `limit` best DOCUMENTS for vec, each by its best segment (mx_index_search_grouped), best first -> (hits, complete).  complete:
+    // the hits are the exact top documents over the whole store (over flt's rows when given).  The candidates are the top-`fetch` rows
+    // (fetch = 0: the default, 4 * limit clamped to [32, 256] and never below limit); when that answer is not complete the call asks
+    // ONCE more with 4096 candidates
+    std::pair<std::vector<DocumentHit>, bool> search_documents(const std::vector<float> &vec, size_t limit, const Grouping &grouping,
+                                                               size_t fetch = 0, const Filter *flt = nullptr) {
+        std::vector<DocumentHit> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0) return {out, true};
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        if (fetch == 0) fetch = std::min<size_t>(4096, std::max<size_t>(limit, std::min<size_t>(256, std::max<size_t>(32, 4 * limit))));
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        std::vector<uint32_t> keys(limit);
+        std::vector<int32_t> rows(limit);
+        int32_t nf = 0;
+        uint8_t complete = 0;
+        for (int step = 0; step < 2; ++step) {
+            int rc = mx_index_search_grouped(idx_, grouping.g_, flt ? flt->f_ : nullptr, vec.data(), 1, (int)std::min<size_t>(limit, (size_t)INT32_MAX),
+                                             (int)std::min<size_t>(fetch, (size_t)INT32_MAX), found.data(), scores.data(), nullptr, keys.data(),
+                                             rows.data(), &nf, &complete);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            if (complete || fetch >= 4096) break;
+            fetch = 4096;
+        }
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.push_back(DocumentHit{grouping.document_of(keys[j]), it->second, scores[j], rows[j]});
+        }
+        return {out, complete != 0};
+    }
+
     // more like this: the `limit` entries closest to what is stored under _id, the asked _id itself left out.  Every row stored under
     // _id is a query (mx_index_search_by_id: the rows never leave the device, the own row is taken out exactly); the union of their
     // answers is ranked by best score, each row once.  An unknown _id returns nothing.  Every list must hold limit + (rows under _id)
@@ -1435,6 +1569,24 @@ inline std::vector<VectorSearchResult> search_docs_multi(HipFlatStore &store, Se
     }
     if (vectors.empty()) throw std::invalid_argument("Invalid query");
     return store.search_fused(vectors, limit, mode);
+}
+
+// tells a grouping which document the segments of a process_embeddings result belong to: every VectorData goes under its document_id
+// (call it after the vectors were added)
+inline void group_document(HipFlatStore::Grouping &grouping, const std::vector<VectorData> &vectors) {
+    std::map<std::string, std::vector<std::string>> by_doc;
+    for (const VectorData &v : vectors) by_doc[v.document_id].push_back(v._id);
+    if (!by_doc.empty()) grouping.assign_all(by_doc);
+}
+
+// search_docs that answers in DOCUMENTS (no counterpart in the reference, whose handler returns segments): the `limit` best documents,
+// each represented by its best segment (HipFlatStore::search_documents).  std::invalid_argument("Invalid query") where search_docs throws it
+inline std::pair<std::vector<HipFlatStore::DocumentHit>, bool> search_documents(HipFlatStore &store, SentenceEmbedder &embedder,
+                                                                                const HipFlatStore::Grouping &grouping, const std::string &query,
+                                                                                size_t limit = 10) {
+    const std::optional<EmbeddingResult> res = embedder.encode_single(query);
+    if (!res) throw std::invalid_argument("Invalid query");
+    return store.search_documents(res->vector, limit, grouping);
 }
 
 }  // namespace memex

@@ -36,6 +36,8 @@ EXPORTS = [
     "mx_index_score_ids", "mx_index_score_ids_device",
     "mx_filter_create", "mx_filter_destroy", "mx_filter_set_ranges", "mx_filter_set_ids", "mx_filter_count", "mx_filter_get_ranges",
     "mx_index_search_with_filter", "mx_index_search_with_filter_device",
+    "mx_grouping_create", "mx_grouping_destroy", "mx_grouping_set_ranges", "mx_grouping_set_ids", "mx_grouping_get_keys", "mx_grouping_count",
+    "mx_index_search_grouped", "mx_index_search_grouped_device",
     "mx_index_search_by_id", "mx_index_search_by_id_device", "mx_index_search_range_by_id", "mx_index_search_range_by_id_device",
     "mx_index_set_search_mode", "mx_index_set_filter_copy", "mx_index_set_corpus_mode", "mx_index_get_rows",
     "mx_index_save", "mx_index_load", "mx_index_has_store", "mx_index_store_info", "mx_index_remove_files",
@@ -135,6 +137,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_filter_get_ranges": [vp, vp, u64, P(u64)],
         "mx_index_search_with_filter": [vp, vp, vp, i32, i32, vp, vp, vp, vp],
         "mx_index_search_with_filter_device": [vp, vp, vp, i32, i32, vp, vp, vp, vp],
+        "mx_grouping_create": [vp, P(vp)],
+        "mx_grouping_set_ranges": [vp, vp, vp, u64],
+        "mx_grouping_set_ids": [vp, vp, vp, u64],
+        "mx_grouping_get_keys": [vp, vp, u64, vp],
+        "mx_grouping_count": [vp, P(u64), P(u64)],
+        "mx_index_search_grouped": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_grouped_device": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "mx_index_search_range": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_mmr": [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp],
@@ -194,6 +203,8 @@ def _declare(L: ctypes.CDLL) -> None:
     L.mx_index_close.argtypes = [vp]
     L.mx_filter_destroy.restype = None
     L.mx_filter_destroy.argtypes = [vp]
+    L.mx_grouping_destroy.restype = None
+    L.mx_grouping_destroy.argtypes = [vp]
     L.mx_encoder_destroy.restype = None
     L.mx_encoder_destroy.argtypes = [vp]
     L.mx_tokenizer_destroy.restype = None

@@ -362,6 +362,27 @@ struct mx_filter {
     std::vector<FilterShard> sh;     // one per shard; a plain index: one
 };
 
+// A grouping: one u32 key per GLOBAL row (id - id_offset - 1) of the handle it was made for, 0 = ungrouped, in one
+// array on the device of the index that owns the stream (shards[0] of a composite: where the merged lists of a search end up).  No
+// host mirror.  Every call that reads or edits a grouping holds the handle's mutex.
+struct mx_grouping {
+    mx_index *idx = nullptr;
+    uint64_t epoch = 0;              // idx->row_epoch when the grouping was made
+    int device = 0;                  // where the keys live
+    Dev<uint32_t> keys;              // device: [len]; a row at or past len has key 0
+    uint64_t len = 0;
+    Dev<void> stage;                 // device: the ranges or ids of the call in progress and their keys
+    size_t stage_bytes = 0;
+    Dev<uint64_t> part;              // device: [2 * kGroupCountBlocks] the partial sums of a count
+    Dev<uint64_t> dead;              // device: the removal mask by global row a sharded handle's count is taken against
+    size_t dead_words = 0;
+    // outputs of the host-pointer search [kMaxBatch, out_cap] that the index's staging block has no room for
+    Dev<uint32_t> out_keys;
+    Dev<int32_t> out_rows;
+    Dev<uint8_t> out_complete;
+    int out_cap = 0;
+};
+
 namespace {
 
 std::mutex g_reg_mu;
@@ -4391,6 +4412,389 @@ int mx_index_search_fused_device(mx_index *idx, const float *d_q, int R, int m, 
         int rc = fused_batch(idx, d_q + (size_t)r0 * m * idx->dim, nr, m, weights ? weights + (size_t)r0 * m : nullptr, mode, k, fetch, rrf_c,
                              d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr, d_best_sub ? d_best_sub + o : nullptr,
                              d_fused ? d_fused + o : nullptr, d_nfound + r0);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+// ---- grouped search (mx_grouping, mx_index_search_grouped) ----------------------------------------------------------
+namespace {
+
+// the index that owns the stream, the candidate lists and the keys of a grouping
+mx_index *group_owner(mx_index *idx) { return idx->composite() ? idx->shards[0] : idx; }
+
+// a grouping named in a call on idx (under idx->mu): made for this handle, and not older than its rows
+int check_grouping(const mx_index *idx, const mx_grouping *g) {
+    if (g->idx != idx) return fail(MX_EINVAL, "the grouping was made for another index");
+    if (g->epoch != idx->row_epoch)
+        return fail(MX_EINVAL, "the grouping is stale: the index was cleared, loaded or compacted after it was made (destroy it and make a new one)");
+    return MX_OK;
+}
+
+// the key array covers `rows` rows: a new block, the old keys copied, the rest zero (the owner's device is current)
+int ensure_group_keys(mx_grouping *g, mx_index *t, uint64_t rows) {
+    if (rows <= g->len) return MX_OK;
+    const uint64_t want = (rows + 1023) / 1024 * 1024;
+    Dev<uint32_t> nb;
+    MX_HIP(nb.alloc((size_t)want));
+    if (g->len) MX_HIP(hipMemcpyAsync(nb, g->keys, (size_t)g->len * sizeof(uint32_t), hipMemcpyDeviceToDevice, t->stream));
+    MX_HIP(hipMemsetAsync(nb.get() + g->len, 0, (size_t)(want - g->len) * sizeof(uint32_t), t->stream));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    g->keys = std::move(nb);
+    g->len = want;
+    return MX_OK;
+}
+
+int ensure_group_stage(mx_grouping *g, size_t bytes) {
+    if (g->stage_bytes >= bytes) return MX_OK;
+    g->stage_bytes = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
+    MX_HIP(g->stage.alloc_bytes(want));  // (every call is host-synchronised before it returns)
+    g->stage_bytes = want;
+    return MX_OK;
+}
+
+void free_grouping_buffers(mx_grouping *g) {
+    DeviceGuard dg(g->device);
+    g->keys.reset();
+    g->stage.reset();
+    g->part.reset();
+    g->dead.reset();
+    g->out_keys.reset();
+    g->out_rows.reset();
+    g->out_complete.reset();
+}
+
+// the head of every mx_grouping_* call but create and destroy; the caller holds idx->mu
+int grouping_ready(mx_grouping *g) {
+    if (int rc = usable(g->idx); rc != MX_OK) return rc;
+    return check_grouping(g->idx, g);
+}
+
+// arguments of the grouped-search entry points, checked before the index is looked at
+int read_grouped_args(int B, int k, int fetch, const mx_grouping *g, const void *q, const void *ids, const void *scores, const void *n_found) {
+    if (B < 0) return fail(MX_EINVAL, "negative batch");
+    if (k < 1) return fail(MX_EINVAL, "k = %d < 1", k);
+    if (fetch < k) return fail(MX_EINVAL, "fetch = %d < k = %d", fetch, k);
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    if (B > 0 && (!q || !ids || !scores || !n_found)) return fail(MX_EINVAL, "null argument");
+    if (fetch > kGroupMaxFetch) return fail(MX_EUNSUPPORTED, "fetch = %d > %d", fetch, kGroupMaxFetch);
+    return MX_OK;
+}
+
+// One batch (B <= kMaxBatch) of a grouped search, queries and outputs on the device of the index that owns the stream, the caller
+// holding idx->mu across both stages: a plain (or resident-filtered) search pass at k = fetch into that index's lists (the
+// diversified search's: a sharded handle has them merged on devices[0] already, which is where the keys are), one group_heads_kernel
+// launch; host-synchronised.
+int grouped_batch(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int fetch, uint64_t *d_ids, float *d_scores,
+                  float *d_dists, uint32_t *d_keys, int32_t *d_rows, int32_t *d_nfound, uint8_t *d_complete) {
+    mx_index *t = group_owner(idx);
+    int rc = ensure_mmr_lists(t, fetch);
+    if (rc != MX_OK) return rc;
+    const FilterArg fa{nullptr, f, 0};
+    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf, f ? &fa : nullptr)) != MX_OK) return rc;
+    GroupHeads p{B, k, fetch, idx->idmap.id_offset, g->len, g->keys, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf,
+                 d_ids, d_scores, d_dists, d_keys, d_rows, d_nfound, d_complete};
+    MX_HIP(launch_group_heads(t->stream, p));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+}
+
+// handles named in a grouped search (under idx->mu)
+int check_grouped_handles(mx_index *idx, mx_grouping *g, mx_filter *f) {
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (int rc = check_grouping(idx, g); rc != MX_OK) return rc;
+    return f ? check_filter(idx, f) : MX_OK;
+}
+
+}  // namespace
+
+int mx_grouping_create(mx_index *idx, mx_grouping **out) try {
+    if (!out) return fail(MX_EINVAL, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(MX_EINVAL, "null index");
+    {   // the grouping's own reference: the rows stay while it lives, whoever closes the index
+        std::lock_guard<std::mutex> lk(g_reg_mu);
+        idx->refs += 1;
+    }
+    std::unique_ptr<mx_grouping> g(new mx_grouping());
+    int rc = MX_OK;
+    {
+        std::lock_guard<std::mutex> lk(idx->mu);
+        rc = usable(idx);
+        mx_index *t = group_owner(idx);
+        g->idx = idx;
+        g->epoch = idx->row_epoch;
+        g->device = t->device;
+        if (rc == MX_OK) {
+            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+            if (t != idx) l2.lock();
+            DeviceGuard dg(t->device);
+            rc = ensure_group_keys(g.get(), t, rows_of(idx));
+        }
+        if (rc != MX_OK) free_grouping_buffers(g.get());
+    }
+    if (rc != MX_OK) {
+        const std::string keep = last_error_slot();
+        mx_index_close(idx);
+        last_error_slot() = keep;
+        return rc;
+    }
+    *out = g.release();
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+void mx_grouping_destroy(mx_grouping *g) {
+    if (!g) return;
+    mx_index *idx = g->idx;
+    try {
+        std::lock_guard<std::mutex> lk(idx->mu);  // (no search that names the grouping is inside the library)
+        free_grouping_buffers(g);
+    } catch (...) {
+    }
+    delete g;
+    mx_index_close(idx);
+}
+
+int mx_grouping_set_ranges(mx_grouping *g, const uint64_t *ranges, const uint32_t *keys, uint64_t n_ranges) try {
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    if ((!ranges || !keys) && n_ranges) return fail(MX_EINVAL, "null ranges or keys with n_ranges = %llu", (unsigned long long)n_ranges);
+    if (n_ranges > 0x7fffffffull) return fail(MX_EINVAL, "too many ranges");
+    struct Span {
+        uint64_t lo, hi;
+        uint32_t key;
+    };
+    std::vector<Span> sp;
+    sp.reserve((size_t)n_ranges);
+    for (uint64_t i = 0; i < n_ranges; ++i) {
+        if (ranges[2 * i] > ranges[2 * i + 1])
+            return fail(MX_EINVAL, "range %llu is [%llu, %llu): lo > hi; nothing changed", (unsigned long long)i,
+                        (unsigned long long)ranges[2 * i], (unsigned long long)ranges[2 * i + 1]);
+        if (ranges[2 * i] < ranges[2 * i + 1]) sp.push_back({ranges[2 * i], ranges[2 * i + 1], keys[i]});  // (an empty range covers nothing)
+    }
+    std::sort(sp.begin(), sp.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
+    for (size_t i = 1; i < sp.size(); ++i)
+        if (sp[i - 1].hi > sp[i].lo)
+            return fail(MX_EINVAL, "ranges [%llu, %llu) and [%llu, %llu) overlap: the ranges of one call must be disjoint; nothing changed",
+                        (unsigned long long)sp[i - 1].lo, (unsigned long long)sp[i - 1].hi, (unsigned long long)sp[i].lo,
+                        (unsigned long long)sp[i].hi);
+    mx_index *idx = g->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
+    const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
+    std::vector<uint64_t> rows;  // the spans as rows, clipped to the rows of the moment
+    std::vector<uint32_t> rk;
+    for (const Span &s : sp) {
+        const uint64_t lo = s.lo > off ? s.lo - off - 1 : 0, hi = std::min(s.hi > off ? s.hi - off - 1 : 0, total);
+        if (lo >= hi) continue;
+        rows.push_back(lo);
+        rows.push_back(hi);
+        rk.push_back(s.key);
+    }
+    if (rk.empty()) return MX_OK;
+    mx_index *t = group_owner(idx);
+    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+    if (t != idx) l2.lock();
+    DeviceGuard dg(t->device);
+    // every allocation first: a call that fails leaves the keys as they were
+    const size_t rb = rows.size() * sizeof(uint64_t), kb = rk.size() * sizeof(uint32_t);
+    if (int rc = ensure_group_keys(g, t, rows.back()); rc != MX_OK) return rc;
+    if (int rc = ensure_group_stage(g, rb + kb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(g->stage.get());
+    MX_HIP(hipMemcpyAsync(st, rows.data(), rb, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(hipMemcpyAsync(st + rb, rk.data(), kb, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(launch_grouping_range_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + rb),
+                                      (uint32_t)rk.size(), rows.front(), rows.back(), g->keys));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_grouping_set_ids(mx_grouping *g, const uint64_t *ids, const uint32_t *keys, uint64_t n_ids) try {
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    if ((!ids || !keys) && n_ids) return fail(MX_EINVAL, "null ids or keys with n_ids = %llu", (unsigned long long)n_ids);
+    {   // an id with two different keys would make the result depend on which store lands last
+        std::vector<std::pair<uint64_t, uint32_t>> pr((size_t)n_ids);
+        for (uint64_t i = 0; i < n_ids; ++i) pr[i] = {ids[i], keys[i]};
+        std::sort(pr.begin(), pr.end());
+        for (size_t i = 1; i < pr.size(); ++i)
+            if (pr[i - 1].first == pr[i].first && pr[i - 1].second != pr[i].second)
+                return fail(MX_EINVAL, "id %llu is named with the keys %u and %u; nothing changed", (unsigned long long)pr[i].first,
+                            pr[i - 1].second, pr[i].second);
+    }
+    mx_index *idx = g->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
+    const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
+    uint64_t top = 0;  // one past the last row the call names
+    for (uint64_t i = 0; i < n_ids; ++i)
+        if (ids[i] > off && ids[i] - off <= total) top = std::max(top, ids[i] - off);
+    if (top == 0) return MX_OK;
+    mx_index *t = group_owner(idx);
+    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+    if (t != idx) l2.lock();
+    DeviceGuard dg(t->device);
+    const size_t ib = (size_t)n_ids * sizeof(uint64_t), kb = (size_t)n_ids * sizeof(uint32_t);
+    if (int rc = ensure_group_keys(g, t, top); rc != MX_OK) return rc;
+    if (int rc = ensure_group_stage(g, ib + kb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(g->stage.get());
+    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(hipMemcpyAsync(st + ib, keys, kb, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(launch_grouping_id_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + ib), n_ids, off,
+                                   std::min(total, g->len), g->keys));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_grouping_get_keys(mx_grouping *g, const uint64_t *ids, uint64_t n_ids, uint32_t *keys) try {
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    if ((!ids || !keys) && n_ids) return fail(MX_EINVAL, "null ids or keys with n_ids = %llu", (unsigned long long)n_ids);
+    mx_index *idx = g->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
+    if (n_ids == 0) return MX_OK;
+    mx_index *t = group_owner(idx);
+    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+    if (t != idx) l2.lock();
+    DeviceGuard dg(t->device);
+    const size_t ib = (size_t)n_ids * sizeof(uint64_t), kb = (size_t)n_ids * sizeof(uint32_t);
+    if (int rc = ensure_group_stage(g, ib + kb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(g->stage.get());
+    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(launch_grouping_get(t->stream, reinterpret_cast<const uint64_t *>(st), n_ids, idx->idmap.id_offset, std::min(rows_of(idx), g->len),
+                               g->keys, reinterpret_cast<uint32_t *>(st + ib)));
+    MX_HIP(hipMemcpyAsync(keys, st + ib, kb, hipMemcpyDeviceToHost, t->stream));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_grouping_count(mx_grouping *g, uint64_t *n_keyed, uint64_t *n_live_keyed) try {
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    mx_index *idx = g->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
+    const uint64_t n = std::min(rows_of(idx), g->len);
+    uint64_t a = 0, l = 0;
+    if (n) {
+        mx_index *t = group_owner(idx);
+        std::vector<uint64_t> mask;  // a sharded handle: the removal mask by global row, from the shards' host copies
+        if (idx->composite() && idx->n_dead) {
+            mask.assign((size_t)((n + 63) >> 6), 0);
+            const uint64_t R = idx->block_rows, G = idx->shards.size();
+            for (uint64_t s = 0; s < G; ++s) {
+                mx_index *sh = idx->shards[(size_t)s];
+                std::lock_guard<std::mutex> ls(sh->mu);
+                if (!sh->dead) continue;
+                for (size_t w = 0; w < sh->dead_h.size(); ++w) {
+                    for (uint64_t bits = sh->dead_h[w]; bits; bits &= bits - 1) {
+                        const uint64_t loc = (uint64_t)w * 64 + (uint64_t)__builtin_ctzll(bits);
+                        const uint64_t r = ((loc / R) * G + s) * R + loc % R;
+                        if (r < n) mask[(size_t)(r >> 6)] |= 1ull << (r & 63);
+                    }
+                }
+            }
+        }
+        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+        if (t != idx) l2.lock();
+        DeviceGuard dg(t->device);
+        if (!g->part) MX_HIP(g->part.alloc(2 * kGroupCountBlocks));
+        const uint64_t *d_dead = nullptr;
+        if (!mask.empty()) {
+            if (g->dead_words < mask.size()) {
+                g->dead_words = 0;
+                MX_HIP(g->dead.alloc(mask.size()));
+                g->dead_words = mask.size();
+            }
+            MX_HIP(hipMemcpyAsync(g->dead, mask.data(), mask.size() * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+            d_dead = g->dead;
+        } else if (!idx->composite() && idx->n_dead && idx->dead) {
+            d_dead = idx->dead;  // a plain index: its own mask, one word per 64 rows of its capacity
+        }
+        uint64_t part[2 * kGroupCountBlocks];
+        MX_HIP(launch_grouping_count(t->stream, g->keys, n, d_dead, g->part));
+        MX_HIP(hipMemcpyAsync(part, g->part, sizeof(part), hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipStreamSynchronize(t->stream));
+        for (int w = 0; w < kGroupCountBlocks; ++w) {
+            a += part[2 * w];
+            l += part[2 * w + 1];
+        }
+    }
+    if (n_keyed) *n_keyed = a;
+    if (n_live_keyed) *n_live_keyed = l;
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_grouped(mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int fetch, uint64_t *ids,
+                            float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_found, uint8_t *complete) try {
+    if (int rc = read_grouped_args(B, k, fetch, g, q, ids, scores, n_found); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    const size_t dim = (size_t)idx->dim;
+    for (size_t i = 0; i < (size_t)B * dim; ++i)
+        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    // not combined with other callers: the call holds the index across the candidate stage and the grouping, like a device-pointer call
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);  // owner of the staging buffers and the stream
+    DeviceGuard dg(t->device);
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, k)) != MX_OK) return rc;
+    if (k > g->out_cap) {
+        g->out_cap = 0;
+        const size_t kc = (size_t)std::max(k, 16);
+        MX_HIP(g->out_keys.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_rows.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_complete.alloc(kMaxBatch));
+        g->out_cap = (int)kc;
+    }
+    Scratch &s = t->s;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        if ((rc = grouped_batch(idx, g, f, s.qstage, nb, k, fetch, s.out_ids, s.out_scores, s.out_dists, g->out_keys, g->out_rows, s.out_nfound,
+                                g->out_complete)) != MX_OK)
+            return rc;
+        if (keys) MX_HIP(hipMemcpyAsync(keys + o, g->out_keys, (size_t)nb * k * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
+        if (group_rows) MX_HIP(hipMemcpyAsync(group_rows + o, g->out_rows, (size_t)nb * k * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        if (complete) MX_HIP(hipMemcpyAsync(complete + b0, g->out_complete, (size_t)nb, hipMemcpyDeviceToHost, t->stream));
+        if ((rc = copy_out_to_host(t, nb, k, false)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nb, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, nullptr);
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_grouped_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int fetch, uint64_t *d_ids,
+                                   float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows, int32_t *d_nfound,
+                                   uint8_t *d_complete) try {
+    if (int rc = read_grouped_args(B, k, fetch, g, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);
+    DeviceGuard dg(t->device);
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        int rc = grouped_batch(idx, g, f, d_q + (size_t)b0 * idx->dim, nb, k, fetch, d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr,
+                               d_keys ? d_keys + o : nullptr, d_group_rows ? d_group_rows + o : nullptr, d_nfound + b0,
+                               d_complete ? d_complete + b0 : nullptr);
         if (rc != MX_OK) return rc;
     }
     return MX_OK;

@@ -524,4 +524,44 @@ struct ScoreMerge {
 };
 hipError_t launch_score_merge(hipStream_t s, const ScoreMerge &p);
 
+// grouped search (mx_grouping / mx_index_search_grouped; group_kernels.hip)
+constexpr int kGroupThreads = 1024;              // one workgroup per query
+constexpr int kGroupMaxFetch = 4096;             // entries per list (the ABI's cap on k): kGroupMaxFetch / kGroupThreads per thread
+constexpr int kGroupCountBlocks = 256;           // workgroups of the count; each writes its two partial sums
+// The keys of a grouping: one u32 per GLOBAL row (id - id_offset - 1) of the handle, keys[0, len).  Every edit is a plain store of a
+// value the host has made unambiguous (disjoint ranges; no id with two keys): no atomics, nothing depends on thread order.
+// Range edit: one thread per row of [row0, row1); ranges holds n_ranges pairs [lo, hi) of rows sorted by lo and pairwise disjoint,
+// rkeys the key of each; a row some range covers gets that range's key.  row1 <= len.
+hipError_t launch_grouping_range_edit(hipStream_t s, const uint64_t *ranges, const uint32_t *rkeys, uint32_t n_ranges, uint64_t row0,
+                                      uint64_t row1, uint32_t *keys);
+// Id edit: one thread per id; ids outside [id_offset + 1, id_offset + limit] are skipped (limit <= len).
+hipError_t launch_grouping_id_edit(hipStream_t s, const uint64_t *ids, const uint32_t *ikeys, uint64_t n_ids, uint64_t id_offset,
+                                   uint64_t limit, uint32_t *keys);
+// Get: out[i] = the key of the row ids[i] names, 0 for an id outside [id_offset + 1, id_offset + limit] (limit <= len).
+hipError_t launch_grouping_get(hipStream_t s, const uint64_t *ids, uint64_t n_ids, uint64_t id_offset, uint64_t limit, const uint32_t *keys,
+                               uint32_t *out);
+// Count: part[2 w] = rows r < n of workgroup w's share with keys[r] != 0, part[2 w + 1] = those of them whose bit in `dead` (one bit per
+// global row, null: no removals) is clear; kGroupCountBlocks workgroups, the host adds the partial sums.
+hipError_t launch_grouping_count(hipStream_t s, const uint32_t *keys, uint64_t n, const uint64_t *dead, uint64_t *part);
+// One list [B, k] of group heads per query from its candidate list (row b of cand_* [B, fetch], (dist, id) order, cand_nf entries).  The
+// key of an entry is keys[id - id_offset - 1], 0 when that row is not below len.  Entry i is a HEAD when its key is 0 or no entry
+// before it has its key; the first k heads are written in list order with the entry's id, score and dist unchanged, the key, and
+// group_rows = the entries of the list with that key (1 for key 0).  n_found = min(k, heads); the slots behind them hold id 0, score
+// 0, dist +inf, key 0, group_rows 0; complete = n_found == k or the list holds fewer than fetch entries.  dists, out_keys, group_rows
+// and complete may be null.  1 <= k <= fetch <= kGroupMaxFetch.
+struct GroupHeads {
+    int B, k, fetch;
+    uint64_t id_offset, len;
+    const uint32_t *keys;
+    const uint64_t *cand_ids;
+    const float *cand_scores, *cand_dists;
+    const int32_t *cand_nf;
+    uint64_t *ids;
+    float *scores, *dists;
+    uint32_t *out_keys;
+    int32_t *group_rows, *n_found;
+    uint8_t *complete;
+};
+hipError_t launch_group_heads(hipStream_t s, const GroupHeads &p);
+
 }  // namespace mx

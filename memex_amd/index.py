@@ -433,6 +433,59 @@ class FlatIndex:
                                                  self._fused_fetch(k, mode, fetch), float(rrf_c), dp(ids), dp(scores), dp(dists),
                                                  dp(best_sub), dp(fused), dp(n_found)))
 
+    # -- grouped search --------------------------------------------------------------------
+    def make_grouping(self) -> "IndexGrouping":
+        """A grouping (``mx_grouping``): one u32 key per row of this index, kept in HBM and named in ``search_grouped``.  It starts
+        with key 0 (ungrouped) everywhere."""
+        return IndexGrouping(self)
+
+    @staticmethod
+    def _grouped_fetch(k: int, fetch) -> int:
+        if fetch is not None:
+            return int(fetch)
+        return min(4096, max(int(k), min(256, max(32, 4 * int(k)))))
+
+    def search_grouped(self, grouping: "IndexGrouping", queries, k: int, fetch=None, flt: "IndexFilter | None" = None):
+        """The ``k`` best GROUPS (documents), each by its best row (``mx_index_search_grouped``).
+        -> (ids u64 [B,k], scores f32 [B,k], dists f32 [B,k], keys u32 [B,k], group_rows i32 [B,k], n_found i32 [B], complete bool [B]).
+        Per query the top-``fetch`` list of ``search`` (of ``search_with(flt, ...)`` when ``flt`` is given) is walked in its order; a
+        row whose key is 0, or whose key no earlier row of the list has, heads a group, and the first ``k`` heads are reported with
+        their key and the number of rows of the list under that key.  ``complete[b]``: the answer is the exact top-k groups over all
+        rows; otherwise it is exact for the list only and a larger ``fetch`` may find more.  ``fetch=None``: ``4 * k`` clamped to
+        [32, 256] and never below ``k``."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        B = q.shape[0]
+        kk = max(int(k), 0)
+        ids = np.zeros((B, kk), dtype=np.uint64)
+        scores = np.zeros((B, kk), dtype=np.float32)
+        dists = np.zeros((B, kk), dtype=np.float32)
+        keys = np.zeros((B, kk), dtype=np.uint32)
+        rows = np.zeros((B, kk), dtype=np.int32)
+        nf = np.zeros(B, dtype=np.int32)
+        done = np.zeros(B, dtype=np.uint8)
+        p = lambda a: _ptr(a) if a.size else None  # noqa: E731
+        check(lib().mx_index_search_grouped(self._h, grouping._h, flt._h if flt is not None else None, p(q), B, int(k),
+                                            self._grouped_fetch(k, fetch), p(ids), p(scores), p(dists), p(keys), p(rows), p(nf), p(done)))
+        return ids, scores, dists, keys, rows, nf, done.astype(bool)
+
+    def search_grouped_device(self, grouping: "IndexGrouping", q, k: int, ids, scores, dists, keys, group_rows, n_found, complete,
+                              fetch=None, flt: "IndexFilter | None" = None) -> None:
+        """``search_grouped`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,k]; scores, dists f32 [B,k]; keys i32/u32 [B,k];
+        group_rows i32 [B,k]; n_found i32 [B]; complete u8 [B] (dists, keys, group_rows and complete may be None).  Blocks until the
+        results are in HBM."""
+        B = int(q.shape[0])
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().mx_index_search_grouped_device(self._h, grouping._h, flt._h if flt is not None else None, dp(q), B, int(k),
+                                                   self._grouped_fetch(k, fetch), dp(ids), dp(scores), dp(dists), dp(keys),
+                                                   dp(group_rows), dp(n_found), dp(complete)))
+
     # -- search by stored row --------------------------------------------------------------
     @staticmethod
     def _query_ids(ids) -> np.ndarray:
@@ -744,6 +797,74 @@ class IndexFilter:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().mx_filter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class IndexGrouping:
+    """Which rows of one ``FlatIndex`` belong together: one u32 key per row, resident on the index's first device (``mx_grouping``,
+    DESIGN.md 3.16).  Key 0 means ungrouped; rows appended later have key 0 until a call names them.  It holds a reference on the
+    index.  After the index's ``clear``, ``load`` or a ``compact`` that dropped rows every method but ``close`` raises: make a new
+    grouping."""
+
+    def __init__(self, index: FlatIndex):
+        h = ctypes.c_void_p()
+        check(lib().mx_grouping_create(index._h, ctypes.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _keys(keys, n: int) -> np.ndarray:
+        k = np.asarray(keys, dtype=np.uint32)
+        if k.ndim == 0:
+            k = np.full(n, k, dtype=np.uint32)
+        k = np.ascontiguousarray(k.reshape(-1))
+        if k.size != n:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {n} keys, got {k.size}")
+        return k
+
+    def set_ranges(self, ranges, keys) -> None:
+        """Every id of range ``i`` ([m, 2] half-open id ranges, pairwise disjoint, any order) gets ``keys[i]`` (one key per range,
+        or one for all); key 0 un-groups.  Ids that name no row at this moment are ignored."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+        k = self._keys(keys, r.shape[0])
+        check(lib().mx_grouping_set_ranges(self._h, _ptr(r) if r.size else None, _ptr(k) if k.size else None, r.shape[0]))
+
+    def set_ids(self, ids, keys) -> None:
+        """``ids[i]`` gets ``keys[i]`` (one key per id, or one for all).  Ids may repeat and come in any order, but not with two
+        different keys in one call."""
+        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
+        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        k = self._keys(keys, a.size)
+        check(lib().mx_grouping_set_ids(self._h, _ptr(a) if a.size else None, _ptr(k) if k.size else None, a.size))
+
+    def keys_of(self, ids) -> np.ndarray:
+        """-> uint32 [n]: the key of the row each id names, 0 for an id that names no row."""
+        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
+        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        out = np.zeros(a.size, dtype=np.uint32)
+        check(lib().mx_grouping_get_keys(self._h, _ptr(a) if a.size else None, a.size, _ptr(out) if out.size else None))
+        return out
+
+    def count(self):
+        """-> (rows with a non-zero key, those of them that are not removed)."""
+        a, l = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().mx_grouping_count(self._h, ctypes.byref(a), ctypes.byref(l)))
+        return int(a.value), int(l.value)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().mx_grouping_destroy(self._h)
             self._h = None
 
     def __del__(self):

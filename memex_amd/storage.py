@@ -25,7 +25,7 @@ import json
 import os
 import threading
 from dataclasses import dataclass, field
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Mapping, Sequence, Tuple
 from urllib.parse import urlparse
 
 import numpy as np
@@ -196,6 +196,78 @@ class StoreFilter:
 
     def close(self) -> None:
         self._flt.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class StoreGrouping:
+    """Which segments of a ``HipFlatStore`` belong to which document (``HipFlatStore.make_grouping``): a resident grouping of the
+    index, edited by document name and segment ``_id``.  Every document name gets a key 1, 2, ... the first time it is seen.  The
+    grouping is not saved with the store: the host that owns the segment -> document mapping builds it again after a restart, and
+    after ``compact()``, ``delete_all()`` or a reload, when every method but ``close`` raises."""
+
+    def __init__(self, store: "HipFlatStore", grouping):
+        self._store = store
+        self._grp = grouping
+        self._key_of: Dict[str, int] = {}
+        self._name_of: Dict[int, str] = {}
+
+    def key_of(self, document: str) -> int:
+        """The key of a document name, handed out on first use."""
+        name = str(document)
+        key = self._key_of.get(name)
+        if key is None:
+            key = len(self._key_of) + 1
+            if key > 0xFFFFFFFF:
+                raise SearchError("a grouping holds at most 2^32 - 1 documents")
+            self._key_of[name] = key
+            self._name_of[key] = name
+        return key
+
+    def document_of(self, key: int) -> str | None:
+        """The document name of a key; ``None`` for key 0 (ungrouped) or a key never handed out."""
+        return self._name_of.get(int(key))
+
+    def _set(self, pairs) -> None:
+        """pairs: (key, segment _ids) -- one ``set_ids`` call for all of them (under the store's lock)."""
+        rows: List[int] = []
+        keys: List[int] = []
+        for key, ids in pairs:
+            named = self._store._ids_named(ids)
+            rows.extend(named)
+            keys.extend([key] * len(named))
+        try:
+            self._grp.set_ids(np.asarray(rows, dtype=np.uint64), np.asarray(keys, dtype=np.uint32))
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+
+    def assign_all(self, documents) -> None:
+        """``assign`` for a mapping document name -> segment ``_id``s, in one edit."""
+        with self._store._lock:
+            self._set([(self.key_of(doc), ids) for doc, ids in documents.items()])
+
+    def assign(self, document: str, ids) -> None:
+        """Put every row inserted under the given segment ``_id`` strings under ``document`` (ingest); unknown ones add nothing."""
+        self.assign_all({document: ids})
+
+    def release(self, ids) -> None:
+        """Un-group every row inserted under the given segment ``_id`` strings (delete): each is a group of its own again."""
+        with self._store._lock:
+            self._set([(0, ids)])
+
+    def count(self):
+        """-> (rows under a document, those of them that are not removed)."""
+        try:
+            return self._grp.count()
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+
+    def close(self) -> None:
+        self._grp.close()
 
     def __enter__(self):
         return self
@@ -603,6 +675,58 @@ class HipFlatStore(VectorStore):
                 out.append((self._id_map[d_id], float(scores[0, j])))
         return out
 
+    def make_grouping(self, documents: Mapping[str, Sequence[str]] = {}) -> "StoreGrouping":  # noqa: B006 (read only)
+        """A resident grouping (``FlatIndex.make_grouping``) with the segments of ``documents`` -- document name -> the segment
+        ``_id``s under it -- grouped, every other row a group of its own.  Bulk-inserting a document and then
+        ``grouping.assign(document, [its _ids])`` is the ingest flow; ``grouping.release`` takes segments out.  After ``compact()``,
+        ``delete_all()`` or a reload the grouping raises: make a new one.  The store must hold at least one row."""
+        with self._lock:
+            if self._index is None:
+                raise SearchError("a grouping needs a store with rows: insert first")
+            try:
+                grp = StoreGrouping(self, self._index.make_grouping())
+            except _lib.MemexHipError as e:
+                _raise_from(e, SearchError)
+            try:
+                if documents:
+                    grp.assign_all(documents)
+            except Exception:
+                grp.close()
+                raise
+        return grp
+
+    def search_documents(self, vec: Sequence[float], limit: int, grouping: "StoreGrouping", fetch: int | None = None,
+                         flt: "StoreFilter | None" = None) -> Tuple[List[Tuple[str | None, str, float, int]], bool]:
+        """The ``limit`` best DOCUMENTS for ``vec``, each by its best segment (``FlatIndex.search_grouped``) -> ``(hits, complete)``.
+        Each hit is ``(document name or None for an ungrouped segment, best segment _id, score, group_rows)``, best first;
+        ``group_rows`` counts the document's segments among the candidates looked at.  ``complete``: the hits are the exact top
+        documents over the whole store (over ``flt``'s rows when given).  The candidates are the top-``fetch`` rows; when that
+        answer is not complete the call asks ONCE more with 4096 candidates, so ``complete`` is false only for a store where even
+        those hold fewer than ``limit`` documents.  Removed rows never appear."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0:
+            return [], True
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        f = flt._flt if flt is not None else None
+        first = FlatIndex._grouped_fetch(int(limit), fetch)
+        try:
+            ids, scores, _, keys, rows, nf, done = idx.search_grouped(grouping._grp, q, int(limit), first, f)  # not under the lock
+            if not done[0] and first < 4096:
+                ids, scores, _, keys, rows, nf, done = idx.search_grouped(grouping._grp, q, int(limit), 4096, f)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[Tuple[str | None, str, float, int]] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((grouping.document_of(int(keys[0, j])), self._id_map[d_id], float(scores[0, j]), int(rows[0, j])))
+        return out, bool(done[0])
+
     def _rows_by_name(self) -> Dict[str, List[int]]:
         """(under the lock) ``_id`` -> the ids stored under it: built once per store, kept on insert."""
         if self._rows_of is None:
@@ -798,6 +922,11 @@ class VectorStorage:
                      weights: Sequence[float] | None = None) -> List[VectorSearchResult]:
         with self._mu:
             return self.client.search_fused(queries, limit, mode, fetch, weights)
+
+    def search_documents(self, query: Sequence[float], limit: int, grouping: "StoreGrouping", fetch: int | None = None,
+                         flt: "StoreFilter | None" = None):
+        with self._mu:
+            return self.client.search_documents(query, limit, grouping, fetch, flt)
 
     def search_like(self, positive: Sequence[str], negative: Sequence[str] = (), limit: int = 10, vec: Sequence[float] | None = None,
                     alpha: float = 1.0, beta: float = 0.75, gamma: float = 0.15) -> List[VectorSearchResult]:

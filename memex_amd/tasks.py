@@ -21,6 +21,10 @@ and a hypothetical answer, the last turns of a conversation), one ranked list ba
 :func:`rerank_docs` has none either: a query and the segments something else found (a keyword backend, a cached result page, the
 caller's own working set), those segments back with their exact scores, best first (``rerank``; nothing is searched).
 
+:func:`search_documents` has none either: ``search_docs`` returns segments despite its name, and so does the reference's handler; this
+one returns the best DOCUMENTS, each by its best segment (``search_documents`` of the store, over a grouping that
+:func:`group_document` fills from a ``process_embeddings`` result).
+
 The ids are the reference's own (RFC 4122 v5 over the same namespace), so a collection filled through this mirror lines up
 with the rows a memex worker would have written for the same task ids.
 """
@@ -92,6 +96,27 @@ def search_docs_feedback(client, embedder, query, relevant: Sequence[str], irrel
             raise ValueError("Invalid query")
         vec = res.vector
     return client.search_like(list(relevant), list(irrelevant), limit, vec)
+
+
+def group_document(grouping, vectors: Sequence[VectorData]) -> None:
+    """Tell a grouping (``HipFlatStore.make_grouping``) which document the segments of a ``process_embeddings`` result belong to:
+    every ``VectorData`` goes under its ``document_id``.  Call it after the vectors were added."""
+    by_doc = {}
+    for v in vectors:
+        by_doc.setdefault(v.document_id, []).append(v._id)
+    for doc, ids in by_doc.items():
+        grouping.assign(doc, ids)
+
+
+def search_documents(client, embedder, grouping, query: str, limit: int = 10):
+    """``search_docs`` that answers in DOCUMENTS: ``encode_single(query)`` -> ``client.search_documents(vector, limit, grouping)`` ->
+    ``(hits, complete)``, each hit ``(document id or None, best segment _id, score, group_rows)`` -- the ``limit`` best documents,
+    each represented by its best segment, where ``search_docs`` may return ``limit`` windows of one document.
+    ``ValueError("Invalid query")`` where ``search_docs`` raises it."""
+    res = embedder.encode_single(query)
+    if res is None:
+        raise ValueError("Invalid query")
+    return client.search_documents(res.vector, limit, grouping)
 
 
 def rerank_docs(client, embedder, query: str, candidates: Sequence[str], limit: int = 10) -> List[Tuple[str, float]]:
