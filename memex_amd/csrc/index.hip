@@ -2556,7 +2556,7 @@ void rollback_rows(mx_index *idx, const RowMark &m) {
 // append host rows to a composite: global row r -> block b = r / R, shard b % G
 int composite_add(mx_index *idx, const float *rows, uint64_t n, uint64_t *first_id, bool on_device) {
     const uint64_t R = idx->block_rows, G = idx->shards.size();
-    if (first_id) *first_id = idx->total + 1;
+    if (first_id) *first_id = idx->idmap.id_offset + idx->total + 1;  // the id a search reports for the row, as on a plain index
     if (n == 0) return MX_OK;
     const size_t rowf = (size_t)idx->dim;
     // per shard: the (contiguous in the source) segments it receives, in order

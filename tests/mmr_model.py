@@ -56,18 +56,27 @@ def mmr_model(oracle, rows, Q, k, fetch=None, lam=0.5, alive=None, id_offset=0):
     fetch = default_fetch(k) if fetch is None else fetch
     live = np.arange(rows.shape[0]) if alive is None else np.flatnonzero(alive)
     ci, cd, cs, cnf = oracle.search(rows[live], Q, fetch)
-    B = Q.shape[0]
+    for b in range(Q.shape[0]):                                           # positions among the live rows -> ids
+        m = int(cnf[b])
+        ci[b, :m] = live[ci[b, :m].astype(np.int64) - 1].astype(np.uint64) + np.uint64(1 + id_offset)
+    return select_from_lists(oracle, rows, ci, cs, cd, cnf, k, lam, id_offset)
+
+
+def select_from_lists(oracle, rows, ci, cs, cd, cnf, k, lam=0.5, id_offset=0):
+    """the selection stage on candidate lists [B, fetch] as a search returns them (ids under id_offset, (dist, id) order) ->
+    (ids, scores, dists, n_found) in selection order"""
+    B = ci.shape[0]
     ids = np.zeros((B, k), np.uint64)
     sc = np.zeros((B, k), np.float32)
     di = np.full((B, k), np.inf, np.float32)
     nf = np.zeros(B, np.int32)
     for b in range(B):
         m = int(cnf[b])
-        cand = live[ci[b, :m].astype(np.int64) - 1]                       # 0-based stored rows, (dist, id) order
+        cand = ci[b, :m].astype(np.int64) - 1 - id_offset                 # 0-based stored rows, (dist, id) order
         n_pick = min(k, m)
         order = greedy(oracle, rows[cand], cs[b, :m], n_pick, lam)
         nf[b] = n_pick
-        ids[b, :n_pick] = cand[order].astype(np.uint64) + np.uint64(1 + id_offset)
+        ids[b, :n_pick] = ci[b, order]
         sc[b, :n_pick] = cs[b, order]
         di[b, :n_pick] = cd[b, order]
     return ids, sc, di, nf

@@ -8,6 +8,7 @@ import threading
 import numpy as np
 import pytest
 
+from by_id_model import blank, drop_own
 from conftest import bits
 from mmr_model import near_copy_corpus
 from test_mmr_gpu import _KINDS
@@ -24,11 +25,6 @@ def corpus(d=384, clusters=150):
     return _CACHE[key]
 
 
-def blank(B, k, counts=False):
-    out = [np.zeros((B, k), np.uint64), np.zeros((B, k), np.float32), np.full((B, k), np.inf, np.float32), np.zeros(B, np.int32)]
-    return out + [np.zeros(B, np.uint64)] if counts else out
-
-
 def stored_rows(idx, qids, off=0):
     """-> (the stored rows of the ids that name a row [B, dim] (zeros elsewhere), mask of those ids)"""
     qids = np.asarray(qids, dtype=np.int64)
@@ -37,20 +33,6 @@ def stored_rows(idx, qids, off=0):
     for b in np.flatnonzero(ok):
         rows[b] = idx.get_rows(int(qids[b]) - off - 1, 1)[0]
     return rows, ok
-
-
-def drop_own(lists, qids, ok, k, e, counts=None):
-    """the contract's last three steps on the plain call's lists: drop the own id, cut to k, count"""
-    ids, sc, di, nf = lists
-    out = blank(len(qids), k, counts is not None)
-    for b in np.flatnonzero(ok):
-        keep = [j for j in range(int(nf[b])) if not (e and int(ids[b, j]) == int(qids[b]))]
-        if counts is not None:                                  # (everything in range is listed: membership is "it is in the list")
-            assert counts[b] == nf[b], "the model's cap does not list everything in range"
-            out[4][b] = len(keep)
-        keep = keep[:k]
-        out[0][b, :len(keep)], out[1][b, :len(keep)], out[2][b, :len(keep)], out[3][b] = ids[b, keep], sc[b, keep], di[b, keep], len(keep)
-    return out
 
 
 def topk_model(idx, qids, k, e, off=0, dead=()):

@@ -7,29 +7,10 @@ import numpy as np
 import pytest
 
 from conftest import bits
+from filtered_model import allowed_mask, subset_oracle
 from test_remove_gpu import corpus
 
 pytestmark = pytest.mark.gpu
-
-
-def allowed_mask(n, ranges, off=0):
-    a = np.zeros(n, dtype=bool)
-    for lo, hi in np.asarray(ranges, dtype=np.int64).reshape(-1, 2):
-        lo, hi = max(lo - off - 1, 0), min(hi - off - 1, n)
-        if lo < hi:
-            a[lo:hi] = True
-    return a
-
-
-def subset_oracle(oracle, rows, keep, Q, k, off=0):
-    """-> (ids, scores, dists, n_found), the order FlatIndex.search returns them in"""
-    ids = np.flatnonzero(keep).astype(np.uint64) + 1 + off
-    if ids.size == 0:  # nothing allowed: every slot empty
-        B = Q.shape[0]
-        return (np.zeros((B, k), np.uint64), np.zeros((B, k), np.float32), np.full((B, k), np.inf, np.float32), np.zeros(B, np.int32))
-    oi, od, os_, onf = oracle.search(rows[keep], Q, k)
-    mapped = np.where(oi > 0, ids[np.maximum(oi.astype(np.int64) - 1, 0)], 0).astype(np.uint64)
-    return mapped, os_, od, onf
 
 
 def same(got, want, what):

@@ -8,23 +8,13 @@ import time
 import numpy as np
 import pytest
 
-from test_filtered_gpu import allowed_mask, same, shapes, subset_oracle
+from filtered_model import allowed_mask, ids_of, model_ranges, subset_oracle
+from test_filtered_gpu import same, shapes
 from test_remove_gpu import corpus
 
 pytestmark = pytest.mark.gpu
 
 D, N = 384, 20037                      # deliberately no multiple of 64
-
-
-def model_ranges(a, off=0):
-    """bool [n] -> the normalised id ranges mx_filter_get_ranges must report"""
-    e = np.flatnonzero(np.diff(np.r_[0, a.astype(np.int8), 0]))
-    return (e.reshape(-1, 2) + 1 + off).astype(np.uint64)
-
-
-def ids_of(ranges):
-    r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
-    return np.concatenate([np.arange(lo, hi) for lo, hi in r] + [np.zeros(0, np.int64)]).astype(np.uint64)
 
 
 def check_set(flt, model, alive, what, off=0):

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import bits
 from mmr_model import near_copy_corpus
+from score_ids_model import from_plain_lists
 from test_mmr_gpu import _KINDS
 
 pytestmark = pytest.mark.gpu
@@ -53,28 +54,11 @@ def expected(idx, Q, ids, off=0):
     key = (Q.tobytes(), off, len(idx), idx.removed)
     if key not in cache:
         cache[key] = idx.search(Q, len(idx))
-    pi, ps, pd, pnf = cache[key]
+    pnf = cache[key][3]
     n = len(idx)
-    B, m = ids.shape
-    sc = np.zeros((B, m), np.float32)
-    di = np.full((B, m), np.inf, np.float32)
-    order = np.full((B, m), -1, np.int32)
-    nf = np.zeros(B, np.int32)
-    for b in range(B):
+    for b in range(ids.shape[0]):
         assert pnf[b] == n - idx.removed                                   # every live row has a defined dist in these corpora
-        place = np.full(n + 1, -1, np.int64)                               # row (1-based, offset taken off) -> place in the plain list
-        place[(pi[b, :pnf[b]] - np.uint64(off)).astype(np.int64)] = np.arange(pnf[b])
-        c = ids[b]
-        ok = (c > np.uint64(off)) & (c <= np.uint64(off + n))
-        p = np.where(ok, place[np.where(ok, c - np.uint64(off), 0).astype(np.int64)], -1)
-        found = p >= 0
-        sc[b, found] = ps[b, p[found]]
-        di[b, found] = pd[b, p[found]]
-        js = np.flatnonzero(found)
-        js = js[np.lexsort((js, p[js]))]
-        order[b, :len(js)] = js
-        nf[b] = len(js)
-    return sc, di, order, nf
+    return from_plain_lists(cache[key], n, ids, off)
 
 
 def same(got, want, what):

@@ -56,6 +56,21 @@ def test_logical_shards_equal_unsharded(G, block_rows, oracle, lib_built, tmp_pa
         _same(idx, X[:100], Q, 10, oracle)
 
 
+def test_add_reports_the_first_id_under_the_id_offset(lib_built):
+    """mx_index_add's first_id is the id a search reports for rows[0]: id_offset applies on a sharded handle as on a plain one
+    (found by tests/test_feature_random_ops_gpu.py; the composite returned total + 1)"""
+    from memex_amd.index import FlatIndex
+    X = np.random.default_rng(3).standard_normal((150, 64), dtype=np.float32)
+    with FlatIndex(64) as plain, FlatIndex(64, devices=[0, 0], block_rows=64) as sh:
+        for idx in (plain, sh):
+            idx.set_id_offset(1000)
+            assert idx.add(X[:100]) == 1001
+            assert idx.add(X[100:]) == 1101
+            assert idx.search(X[100:101], 1)[0][0, 0] == 1101
+            idx.set_id_offset(0)
+            assert idx.add(X[:1]) == 151
+
+
 def test_sharded_device_api_and_small_shards(oracle, lib_built):
     """Device-pointer API on a composite; fewer rows than shards * k."""
     import torch
