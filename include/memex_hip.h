@@ -514,6 +514,68 @@ int mx_index_search_grouped_device(mx_index *idx, mx_grouping *g, mx_filter *f, 
                                    uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows,
                                    int32_t *d_n_found, uint8_t *d_complete);
 
+/*
+ * Boosted search: relevance plus something the vectors do not carry -- how recent a segment is, how important the host has marked it,
+ * how trusted its source is.  Rows are ranked by score + weight * prior, exactly, and the answer says whether a row outside the
+ * candidates could have won.
+ *
+ * A PRIOR is one f32 per row, kept in HBM on devices[0] and named by handle, like a grouping.  A new prior is 0 everywhere, and rows
+ * appended after the last edit read 0 until a call names them.  Negative values are a penalty.  Nothing is written to the store files
+ * and nothing is dealt to shards; there is no host copy of the values.  4 bytes of HBM per row.
+ *   mx_prior_create      the all-zero prior of the rows of `idx`.  It holds a reference on the index; mx_prior_destroy drops it.
+ *   mx_prior_set_ranges  range i, the ids [ranges[2 i], ranges[2 i + 1]), gets values[i].  The ranges of ONE call must be pairwise
+ *                        disjoint (empty ranges aside): an overlap, lo > hi in any pair, or a NULL ranges / values with n_ranges > 0
+ *                        is MX_EINVAL.  They may come in any order.
+ *   mx_prior_set_ids     ids[i] gets values[i].  Ids may repeat and come in any order; an id named twice in one call with values of
+ *                        DIFFERENT bits is MX_EINVAL (the same bits twice are fine).
+ *                        Both: a value that is NaN or +-inf is MX_EINVAL, and nothing is written.
+ *   mx_prior_get         values[i] = the value of the row ids[i] names; 0 for an id that names no row.
+ *   mx_prior_bound       *hi = an upper bound of every value in the array, the one the certificate below uses.  It starts at 0 (rows
+ *                        nobody set read 0), every successful edit raises it to the largest value the call was handed, and no edit
+ *                        lowers it.  refresh = 1 first replaces it by the exact maximum of 0 and the values of the rows that are not
+ *                        removed (one reduction over the array): the remedy after large values were overwritten with small ones.
+ *                        refresh other than 0 or 1: MX_EINVAL.  hi may be NULL.
+ * Ids, id_offset, removed rows, failing calls, staleness after mx_index_clear / mx_index_load / a compaction that dropped rows
+ * (MX_EINVAL, "stale" in the message), a foreign index (MX_EINVAL), threads and destruction: as for a grouping, above.
+ *
+ *   mx_index_search_boosted[_device]   queries [B, dim]; weights f32 [B] in HOST memory on both variants, NULL = 1.0 for every query;
+ *                        outputs ids / scores / dists / priors f32 [B, k], combined f64 [B, k], n_found / complete [B]; dists, priors,
+ *                        combined and complete may be NULL.  f may be NULL.  Per query b, with w = weights[b]:
+ *   candidates  the list L = what mx_index_search gives with k = fetch, bit for bit -- with f, what mx_index_search_with_filter
+ *               gives; m entries.  As for grouped search the candidate stage IS a plain search pass.
+ *   combined    c_j = (double)score_j + (double)w * (double)prior_j for entry j: the f32 score L reports, the row's prior.  The product
+ *               is exact in f64, so c_j is rounded once: the same bits as that expression anywhere else.
+ *   order       by c descending, then by position in L (its (dist, id) order).  The first min(k, m) entries are reported: ids / scores /
+ *               dists are the entry's, unchanged; priors and combined are prior_j and c_j.  n_found = min(k, m).  Unused slots hold
+ *               id 0, score 0, dist +inf, prior 0, combined 0.
+ *   complete    complete[b] = 1 iff m < fetch, or the k-th reported c is strictly greater than
+ *               U = (double)score_last + (double)w * (double)hi, score_last the score of L's last entry, hi as mx_prior_bound(p, 0).
+ * complete = 1 promises the EXACT top-k of ALL live rows (all allowed live rows, with f) by (c descending, dist, id); complete = 0
+ * promises the exact re-ranking of L only, and a larger fetch (or a refreshed bound) may change the answer.  (Every live row outside
+ * L scores at most score_last and has a prior of at most hi, so with w >= 0 its c is at most U.  DESIGN.md 3.17.)  The test is
+ * sufficient, not necessary: at w = 0 with equal scores at the end of L it reports 0 for an answer that is right.
+ * Arguments are checked first: B < 0, k < 1, fetch < k, a NULL prior, a NULL queries / ids / scores / n_found with B > 0, a weight
+ * that is negative, NaN or infinite: MX_EINVAL; then fetch > 4096: MX_EUNSUPPORTED; then a null index: MX_ESEARCH; then a stale or
+ * foreign prior or filter: MX_EINVAL.  Non-finite queries are rejected as by mx_index_search.  B is split into batches of 512.
+ * Thread-safe beside every other call; NOT combined with other callers, as grouped search.  A sharded handle merges the candidate
+ * lists on devices[0] as a search does and re-ranks there: the answer equals the plain index's bit for bit.  The re-ranking costs
+ * O(fetch^2) f64 compares per query, independent of dim and of the row count.  Extra HBM, allocated at the first call: the candidate
+ * lists (shared with mx_index_search_mmr) and, for the host-pointer variant, 512 x max(k, 16) priors and combined values.
+ */
+typedef struct mx_prior mx_prior;
+int mx_prior_create(mx_index *idx, mx_prior **out);
+void mx_prior_destroy(mx_prior *p);
+int mx_prior_set_ranges(mx_prior *p, const uint64_t *ranges, const float *values, uint64_t n_ranges);
+int mx_prior_set_ids(mx_prior *p, const uint64_t *ids, const float *values, uint64_t n_ids);
+int mx_prior_get(mx_prior *p, const uint64_t *ids, uint64_t n_ids, float *values);
+int mx_prior_bound(mx_prior *p, int refresh, float *hi);
+int mx_index_search_boosted(mx_index *idx, mx_prior *p, mx_filter *f, const float *queries, const float *weights, int B, int k, int fetch,
+                            uint64_t *ids, float *scores, float *dists, float *priors, double *combined, int32_t *n_found,
+                            uint8_t *complete);
+int mx_index_search_boosted_device(mx_index *idx, mx_prior *p, mx_filter *f, const float *d_queries, const float *weights, int B, int k,
+                                   int fetch, uint64_t *d_ids, float *d_scores, float *d_dists, float *d_priors, double *d_combined,
+                                   int32_t *d_n_found, uint8_t *d_complete);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

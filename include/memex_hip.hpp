@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <deque>
@@ -713,6 +714,106 @@ class HipFlatStore : public VectorStore {
         return {out, complete != 0};
     }
 
+    // A resident prior (mx_prior): what the vectors do not say about a segment -- how recent, how important, how trusted -- one f32 per
+    // row kept in HBM and added to the score by search_boosted().  Segments nobody set read 0.  bulk_insert of a document, then
+    // set_document({its _ids}, value), is the ingest flow.  The prior is not saved with the store: after compact(), delete_all() or a
+    // reload every call but the destructor throws: make a new one.
+    class Prior {
+      public:
+        Prior(const Prior &) = delete;
+        Prior &operator=(const Prior &) = delete;
+        Prior(Prior &&o) noexcept : store_(o.store_), p_(o.p_) { o.p_ = nullptr; }
+        ~Prior() {
+            if (p_) mx_prior_destroy(p_);
+        }
+        // every row inserted under ids[i] gets values[i]; unknown _ids add nothing.  One mx_prior_set_ids call for all of them
+        void set(const std::vector<std::string> &ids, const std::vector<float> &values) {
+            if (ids.size() != values.size()) throw VectorStoreError(VectorStoreError::SearchError, "one value per _id");
+            std::lock_guard<std::mutex> lk(store_->mu_);
+            store_->build_rows_of();
+            std::vector<uint64_t> rows;
+            std::vector<float> vals;
+            for (size_t i = 0; i < ids.size(); ++i) {
+                auto it = store_->rows_of_.find(ids[i]);
+                if (it == store_->rows_of_.end()) continue;
+                rows.insert(rows.end(), it->second.begin(), it->second.end());
+                vals.insert(vals.end(), it->second.size(), values[i]);
+            }
+            int rc = mx_prior_set_ids(p_, rows.empty() ? nullptr : rows.data(), vals.empty() ? nullptr : vals.data(), rows.size());
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        }
+        // one value for all the segments of a document
+        void set_document(const std::vector<std::string> &document_ids, float value) {
+            set(document_ids, std::vector<float>(document_ids.size(), value));
+        }
+        // the upper bound of the values that `complete` is decided with; refresh: recomputed over the rows that are not removed
+        float bound(bool refresh = false) const {
+            float hi = 0.0f;
+            int rc = mx_prior_bound(p_, refresh ? 1 : 0, &hi);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            return hi;
+        }
+
+      private:
+        friend class HipFlatStore;
+        Prior(HipFlatStore *store, mx_prior *p) : store_(store), p_(p) {}
+        HipFlatStore *store_;
+        mx_prior *p_;
+    };
+
+    Prior make_prior() {
+        mx_prior *p = nullptr;
+        std::lock_guard<std::mutex> lk(mu_);
+        if (!idx_) throw VectorStoreError(VectorStoreError::SearchError, "a prior needs a store with rows: insert first");
+        int rc = mx_prior_create(idx_, &p);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        return Prior(this, p);
+    }
+
+    // one segment of a search_boosted answer: its _id, its score, its prior, and combined = (double)score + (double)weight * (double)prior
+    struct BoostedHit {
+        std::string _id;
+        float score;
+        float prior;
+        double combined;
+    };
+
+    // the `limit` best segments for vec by score + weight * prior (mx_index_search_boosted), best first -> (hits, complete).  complete:
+    // the hits are the exact top segments over the whole store (over flt's rows when given).  The candidates are the top-`fetch` rows
+    // (fetch = 0: the default, 4 * limit clamped to [32, 256] and never below limit); when that answer is not complete the call asks
+    // ONCE more with 4096 candidates
+    std::pair<std::vector<BoostedHit>, bool> search_boosted(const std::vector<float> &vec, size_t limit, const Prior &prior, float weight = 1.0f,
+                                                            size_t fetch = 0, const Filter *flt = nullptr) {
+        std::vector<BoostedHit> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0) return {out, true};
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        if (fetch == 0) fetch = std::min<size_t>(4096, std::max<size_t>(limit, std::min<size_t>(256, std::max<size_t>(32, 4 * limit))));
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit), priors(limit);
+        std::vector<double> combined(limit);
+        int32_t nf = 0;
+        uint8_t complete = 0;
+        for (int step = 0; step < 2; ++step) {
+            int rc = mx_index_search_boosted(idx_, prior.p_, flt ? flt->f_ : nullptr, vec.data(), &weight, 1,
+                                             (int)std::min<size_t>(limit, (size_t)INT32_MAX), (int)std::min<size_t>(fetch, (size_t)INT32_MAX),
+                                             found.data(), scores.data(), nullptr, priors.data(), combined.data(), &nf, &complete);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            if (complete || fetch >= 4096) break;
+            fetch = 4096;
+        }
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.push_back(BoostedHit{it->second, scores[j], priors[j], combined[j]});
+        }
+        return {out, complete != 0};
+    }
+
     // more like this: the `limit` entries closest to what is stored under _id, the asked _id itself left out.  Every row stored under
     // _id is a query (mx_index_search_by_id: the rows never leave the device, the own row is taken out exactly); the union of their
     // answers is ranked by best score, each row once.  An unknown _id returns nothing.  Every list must hold limit + (rows under _id)
@@ -1024,6 +1125,15 @@ class VectorStorage {  // mod.rs:69-93
     std::vector<VectorSearchResult> rerank(const std::vector<float> &vec, const std::vector<std::string> &ids, size_t limit = 0) {
         std::lock_guard<std::mutex> lk(*mu_);
         return client->rerank(vec, ids, limit);
+    }
+    // (a prior belongs to a HipFlatStore: any other client is Unsupported)
+    std::pair<std::vector<HipFlatStore::BoostedHit>, bool> search_boosted(const std::vector<float> &query, size_t limit,
+                                                                          const HipFlatStore::Prior &prior, float weight = 1.0f,
+                                                                          size_t fetch = 0, const HipFlatStore::Filter *flt = nullptr) {
+        std::lock_guard<std::mutex> lk(*mu_);
+        auto store = std::dynamic_pointer_cast<HipFlatStore>(client);
+        if (!store) throw VectorStoreError(VectorStoreError::Unsupported, "search_boosted needs a HipFlatStore");
+        return store->search_boosted(query, limit, prior, weight, fetch, flt);
     }
 
   private:
@@ -1587,6 +1697,27 @@ inline std::pair<std::vector<HipFlatStore::DocumentHit>, bool> search_documents(
     const std::optional<EmbeddingResult> res = embedder.encode_single(query);
     if (!res) throw std::invalid_argument("Invalid query");
     return store.search_documents(res->vector, limit, grouping);
+}
+
+// ingest side of search_docs_recent: the segments of a process_embeddings result, written at time t, get the prior
+// exp2((t - t0) / half_life).  The value is an f32: about 120 half-lives after t0 the epoch must be moved and the values written again
+inline void stamp_document(HipFlatStore::Prior &prior, const std::vector<VectorData> &vectors, double t, double half_life, double t0) {
+    const float value = (float)std::exp2((t - t0) / half_life);
+    if (!std::isfinite(value)) throw std::invalid_argument("t is too far from t0 for an f32 prior: move t0 and stamp the documents again");
+    std::vector<std::string> ids;
+    for (const VectorData &v : vectors) ids.push_back(v._id);
+    if (!ids.empty()) prior.set_document(ids, value);
+}
+
+// search_docs that prefers recent segments: a segment stamped at t is ranked by score + weight * exp2(-(now - t) / half_life).  The
+// decay is folded into the query's weight, weight * exp2(-(now - t0) / half_life): the resident values are never rewritten
+inline std::pair<std::vector<HipFlatStore::BoostedHit>, bool> search_docs_recent(HipFlatStore &store, SentenceEmbedder &embedder,
+                                                                                 const HipFlatStore::Prior &prior, const std::string &query,
+                                                                                 size_t limit, double now, double half_life, double t0,
+                                                                                 double weight) {
+    const std::optional<EmbeddingResult> res = embedder.encode_single(query);
+    if (!res) throw std::invalid_argument("Invalid query");
+    return store.search_boosted(res->vector, limit, prior, (float)(weight * std::exp2(-(now - t0) / half_life)));
 }
 
 }  // namespace memex

@@ -38,6 +38,8 @@ EXPORTS = [
     "mx_index_search_with_filter", "mx_index_search_with_filter_device",
     "mx_grouping_create", "mx_grouping_destroy", "mx_grouping_set_ranges", "mx_grouping_set_ids", "mx_grouping_get_keys", "mx_grouping_count",
     "mx_index_search_grouped", "mx_index_search_grouped_device",
+    "mx_prior_create", "mx_prior_destroy", "mx_prior_set_ranges", "mx_prior_set_ids", "mx_prior_get", "mx_prior_bound",
+    "mx_index_search_boosted", "mx_index_search_boosted_device",
     "mx_index_search_by_id", "mx_index_search_by_id_device", "mx_index_search_range_by_id", "mx_index_search_range_by_id_device",
     "mx_index_set_search_mode", "mx_index_set_filter_copy", "mx_index_set_corpus_mode", "mx_index_get_rows",
     "mx_index_save", "mx_index_load", "mx_index_has_store", "mx_index_store_info", "mx_index_remove_files",
@@ -144,6 +146,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_grouping_count": [vp, P(u64), P(u64)],
         "mx_index_search_grouped": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "mx_index_search_grouped_device": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "mx_prior_create": [vp, P(vp)],
+        "mx_prior_set_ranges": [vp, vp, vp, u64],
+        "mx_prior_set_ids": [vp, vp, vp, u64],
+        "mx_prior_get": [vp, vp, u64, vp],
+        "mx_prior_bound": [vp, i32, P(ctypes.c_float)],
+        "mx_index_search_boosted": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_boosted_device": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "mx_index_search_range": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_mmr": [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp],
@@ -205,6 +214,8 @@ def _declare(L: ctypes.CDLL) -> None:
     L.mx_filter_destroy.argtypes = [vp]
     L.mx_grouping_destroy.restype = None
     L.mx_grouping_destroy.argtypes = [vp]
+    L.mx_prior_destroy.restype = None
+    L.mx_prior_destroy.argtypes = [vp]
     L.mx_encoder_destroy.restype = None
     L.mx_encoder_destroy.argtypes = [vp]
     L.mx_tokenizer_destroy.restype = None

@@ -383,6 +383,29 @@ struct mx_grouping {
     int out_cap = 0;
 };
 
+// A prior: one f32 per GLOBAL row of the handle it was made for, 0 where nothing was set, kept where a grouping's
+// keys are and under the same rules.  hi >= every value of the array at all times: edits raise it on the host, a refresh replaces it
+// by the exact maximum over the live rows and 0.
+struct mx_prior {
+    mx_index *idx = nullptr;
+    uint64_t epoch = 0;              // idx->row_epoch when the prior was made
+    int device = 0;                  // where the values live
+    Dev<float> vals;                 // device: [len]; a row at or past len has prior 0
+    uint64_t len = 0;
+    float hi = 0.0f;
+    Dev<void> stage;                 // device: the ranges or ids of the call in progress and their values
+    size_t stage_bytes = 0;
+    Dev<float> part;                 // device: [kBoostMaxBlocks] the partial maxima of a refresh
+    Dev<uint64_t> dead;              // device: the removal mask by global row a sharded handle's refresh is taken against
+    size_t dead_words = 0;
+    Dev<float> weights;              // device: [kMaxBatch] the weights of the batch in progress
+    // outputs of the host-pointer search [kMaxBatch, out_cap] that the index's staging block has no room for
+    Dev<float> out_priors;
+    Dev<double> out_combined;
+    Dev<uint8_t> out_complete;
+    int out_cap = 0;
+};
+
 namespace {
 
 std::mutex g_reg_mu;
@@ -4467,6 +4490,105 @@ void free_grouping_buffers(mx_grouping *g) {
     g->out_complete.reset();
 }
 
+// ---- host checks of the per-row edits (a grouping's keys, a prior's values: 32-bit words either way) -----------------------------------
+struct WordSpan {
+    uint64_t lo, hi;
+    uint32_t word;
+};
+
+// the non-empty ranges of a set_ranges call sorted by lo, each with its word; lo > hi in a pair or an overlap: MX_EINVAL
+int read_word_spans(const uint64_t *ranges, const uint32_t *words, uint64_t n_ranges, std::vector<WordSpan> *out) {
+    if (n_ranges > 0x7fffffffull) return fail(MX_EINVAL, "too many ranges");
+    std::vector<WordSpan> &sp = *out;
+    sp.clear();
+    sp.reserve((size_t)n_ranges);
+    for (uint64_t i = 0; i < n_ranges; ++i) {
+        if (ranges[2 * i] > ranges[2 * i + 1])
+            return fail(MX_EINVAL, "range %llu is [%llu, %llu): lo > hi; nothing changed", (unsigned long long)i,
+                        (unsigned long long)ranges[2 * i], (unsigned long long)ranges[2 * i + 1]);
+        if (ranges[2 * i] < ranges[2 * i + 1]) sp.push_back({ranges[2 * i], ranges[2 * i + 1], words[i]});  // (an empty range covers nothing)
+    }
+    std::sort(sp.begin(), sp.end(), [](const WordSpan &a, const WordSpan &b) { return a.lo < b.lo; });
+    for (size_t i = 1; i < sp.size(); ++i)
+        if (sp[i - 1].hi > sp[i].lo)
+            return fail(MX_EINVAL, "ranges [%llu, %llu) and [%llu, %llu) overlap: the ranges of one call must be disjoint; nothing changed",
+                        (unsigned long long)sp[i - 1].lo, (unsigned long long)sp[i - 1].hi, (unsigned long long)sp[i].lo,
+                        (unsigned long long)sp[i].hi);
+    return MX_OK;
+}
+
+// the spans as pairs of rows clipped to the `total` rows of the moment, and the word of each span that is left
+void spans_to_rows(const std::vector<WordSpan> &sp, uint64_t off, uint64_t total, std::vector<uint64_t> *rows, std::vector<uint32_t> *words) {
+    for (const WordSpan &s : sp) {
+        const uint64_t lo = s.lo > off ? s.lo - off - 1 : 0, hi = std::min(s.hi > off ? s.hi - off - 1 : 0, total);
+        if (lo >= hi) continue;
+        rows->push_back(lo);
+        rows->push_back(hi);
+        words->push_back(s.word);
+    }
+}
+
+// an id with two different words in one set_ids call would make the result depend on which store lands last
+int check_id_words(const uint64_t *ids, const uint32_t *words, uint64_t n_ids, const char *what) {
+    std::vector<std::pair<uint64_t, uint32_t>> pr((size_t)n_ids);
+    for (uint64_t i = 0; i < n_ids; ++i) pr[i] = {ids[i], words[i]};
+    std::sort(pr.begin(), pr.end());
+    for (size_t i = 1; i < pr.size(); ++i)
+        if (pr[i - 1].first == pr[i].first && pr[i - 1].second != pr[i].second)
+            return fail(MX_EINVAL, "id %llu is named with the %s 0x%08x and 0x%08x; nothing changed", (unsigned long long)pr[i].first, what,
+                        pr[i - 1].second, pr[i].second);
+    return MX_OK;
+}
+
+// one past the last row a set_ids call names; 0: it names none
+uint64_t top_row_named(const uint64_t *ids, uint64_t n_ids, uint64_t off, uint64_t total) {
+    uint64_t top = 0;
+    for (uint64_t i = 0; i < n_ids; ++i)
+        if (ids[i] > off && ids[i] - off <= total) top = std::max(top, ids[i] - off);
+    return top;
+}
+
+// a sharded handle's removal mask by global row, rows [0, n), from the shards' host copies (under idx->mu); empty: a plain index, or
+// nothing removed
+void composite_dead_mask(mx_index *idx, uint64_t n, std::vector<uint64_t> *out) {
+    std::vector<uint64_t> &mask = *out;
+    mask.clear();
+    if (!idx->composite() || !idx->n_dead) return;
+    mask.assign((size_t)((n + 63) >> 6), 0);
+    const uint64_t R = idx->block_rows, G = idx->shards.size();
+    for (uint64_t s = 0; s < G; ++s) {
+        mx_index *sh = idx->shards[(size_t)s];
+        std::lock_guard<std::mutex> ls(sh->mu);
+        if (!sh->dead) continue;
+        for (size_t w = 0; w < sh->dead_h.size(); ++w) {
+            for (uint64_t bits = sh->dead_h[w]; bits; bits &= bits - 1) {
+                const uint64_t loc = (uint64_t)w * 64 + (uint64_t)__builtin_ctzll(bits);
+                const uint64_t r = ((loc / R) * G + s) * R + loc % R;
+                if (r < n) mask[(size_t)(r >> 6)] |= 1ull << (r & 63);
+            }
+        }
+    }
+}
+
+// *d_dead = the removal mask by global row that a reduction over the rows of idx is taken against on t's device (current, t->mu
+// held): `mask` copied into buf on t's stream, a plain index's own mask, or null when nothing is removed
+int dead_mask_on_device(mx_index *idx, mx_index *t, const std::vector<uint64_t> &mask, Dev<uint64_t> &buf, size_t &buf_words,
+                        const uint64_t **d_dead) {
+    *d_dead = nullptr;
+    if (!mask.empty()) {
+        if (buf_words < mask.size()) {
+            buf_words = 0;
+            MX_HIP(buf.alloc(mask.size()));
+            buf_words = mask.size();
+        }
+        MX_HIP(hipMemcpyAsync(buf, mask.data(), mask.size() * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+        *d_dead = buf;
+    } else if (!idx->composite() && idx->n_dead && idx->dead) {
+        *d_dead = idx->dead;  // a plain index: its own mask, one word per 64 rows of its capacity
+    }
+    return MX_OK;
+}
+
 // the head of every mx_grouping_* call but create and destroy; the caller holds idx->mu
 int grouping_ready(mx_grouping *g) {
     if (int rc = usable(g->idx); rc != MX_OK) return rc;
@@ -4563,38 +4685,14 @@ void mx_grouping_destroy(mx_grouping *g) {
 int mx_grouping_set_ranges(mx_grouping *g, const uint64_t *ranges, const uint32_t *keys, uint64_t n_ranges) try {
     if (!g) return fail(MX_EINVAL, "null grouping");
     if ((!ranges || !keys) && n_ranges) return fail(MX_EINVAL, "null ranges or keys with n_ranges = %llu", (unsigned long long)n_ranges);
-    if (n_ranges > 0x7fffffffull) return fail(MX_EINVAL, "too many ranges");
-    struct Span {
-        uint64_t lo, hi;
-        uint32_t key;
-    };
-    std::vector<Span> sp;
-    sp.reserve((size_t)n_ranges);
-    for (uint64_t i = 0; i < n_ranges; ++i) {
-        if (ranges[2 * i] > ranges[2 * i + 1])
-            return fail(MX_EINVAL, "range %llu is [%llu, %llu): lo > hi; nothing changed", (unsigned long long)i,
-                        (unsigned long long)ranges[2 * i], (unsigned long long)ranges[2 * i + 1]);
-        if (ranges[2 * i] < ranges[2 * i + 1]) sp.push_back({ranges[2 * i], ranges[2 * i + 1], keys[i]});  // (an empty range covers nothing)
-    }
-    std::sort(sp.begin(), sp.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
-    for (size_t i = 1; i < sp.size(); ++i)
-        if (sp[i - 1].hi > sp[i].lo)
-            return fail(MX_EINVAL, "ranges [%llu, %llu) and [%llu, %llu) overlap: the ranges of one call must be disjoint; nothing changed",
-                        (unsigned long long)sp[i - 1].lo, (unsigned long long)sp[i - 1].hi, (unsigned long long)sp[i].lo,
-                        (unsigned long long)sp[i].hi);
+    std::vector<WordSpan> sp;
+    if (int rc = read_word_spans(ranges, keys, n_ranges, &sp); rc != MX_OK) return rc;
     mx_index *idx = g->idx;
     std::lock_guard<std::mutex> lk(idx->mu);
     if (int rc = grouping_ready(g); rc != MX_OK) return rc;
-    const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
-    std::vector<uint64_t> rows;  // the spans as rows, clipped to the rows of the moment
+    std::vector<uint64_t> rows;
     std::vector<uint32_t> rk;
-    for (const Span &s : sp) {
-        const uint64_t lo = s.lo > off ? s.lo - off - 1 : 0, hi = std::min(s.hi > off ? s.hi - off - 1 : 0, total);
-        if (lo >= hi) continue;
-        rows.push_back(lo);
-        rows.push_back(hi);
-        rk.push_back(s.key);
-    }
+    spans_to_rows(sp, idx->idmap.id_offset, rows_of(idx), &rows, &rk);
     if (rk.empty()) return MX_OK;
     mx_index *t = group_owner(idx);
     std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
@@ -4618,22 +4716,12 @@ int mx_grouping_set_ranges(mx_grouping *g, const uint64_t *ranges, const uint32_
 int mx_grouping_set_ids(mx_grouping *g, const uint64_t *ids, const uint32_t *keys, uint64_t n_ids) try {
     if (!g) return fail(MX_EINVAL, "null grouping");
     if ((!ids || !keys) && n_ids) return fail(MX_EINVAL, "null ids or keys with n_ids = %llu", (unsigned long long)n_ids);
-    {   // an id with two different keys would make the result depend on which store lands last
-        std::vector<std::pair<uint64_t, uint32_t>> pr((size_t)n_ids);
-        for (uint64_t i = 0; i < n_ids; ++i) pr[i] = {ids[i], keys[i]};
-        std::sort(pr.begin(), pr.end());
-        for (size_t i = 1; i < pr.size(); ++i)
-            if (pr[i - 1].first == pr[i].first && pr[i - 1].second != pr[i].second)
-                return fail(MX_EINVAL, "id %llu is named with the keys %u and %u; nothing changed", (unsigned long long)pr[i].first,
-                            pr[i - 1].second, pr[i].second);
-    }
+    if (int rc = check_id_words(ids, keys, n_ids, "keys"); rc != MX_OK) return rc;
     mx_index *idx = g->idx;
     std::lock_guard<std::mutex> lk(idx->mu);
     if (int rc = grouping_ready(g); rc != MX_OK) return rc;
     const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
-    uint64_t top = 0;  // one past the last row the call names
-    for (uint64_t i = 0; i < n_ids; ++i)
-        if (ids[i] > off && ids[i] - off <= total) top = std::max(top, ids[i] - off);
+    const uint64_t top = top_row_named(ids, n_ids, off, total);
     if (top == 0) return MX_OK;
     mx_index *t = group_owner(idx);
     std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
@@ -4686,39 +4774,14 @@ int mx_grouping_count(mx_grouping *g, uint64_t *n_keyed, uint64_t *n_live_keyed)
     uint64_t a = 0, l = 0;
     if (n) {
         mx_index *t = group_owner(idx);
-        std::vector<uint64_t> mask;  // a sharded handle: the removal mask by global row, from the shards' host copies
-        if (idx->composite() && idx->n_dead) {
-            mask.assign((size_t)((n + 63) >> 6), 0);
-            const uint64_t R = idx->block_rows, G = idx->shards.size();
-            for (uint64_t s = 0; s < G; ++s) {
-                mx_index *sh = idx->shards[(size_t)s];
-                std::lock_guard<std::mutex> ls(sh->mu);
-                if (!sh->dead) continue;
-                for (size_t w = 0; w < sh->dead_h.size(); ++w) {
-                    for (uint64_t bits = sh->dead_h[w]; bits; bits &= bits - 1) {
-                        const uint64_t loc = (uint64_t)w * 64 + (uint64_t)__builtin_ctzll(bits);
-                        const uint64_t r = ((loc / R) * G + s) * R + loc % R;
-                        if (r < n) mask[(size_t)(r >> 6)] |= 1ull << (r & 63);
-                    }
-                }
-            }
-        }
+        std::vector<uint64_t> mask;
+        composite_dead_mask(idx, n, &mask);
         std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
         if (t != idx) l2.lock();
         DeviceGuard dg(t->device);
         if (!g->part) MX_HIP(g->part.alloc(2 * kGroupCountBlocks));
         const uint64_t *d_dead = nullptr;
-        if (!mask.empty()) {
-            if (g->dead_words < mask.size()) {
-                g->dead_words = 0;
-                MX_HIP(g->dead.alloc(mask.size()));
-                g->dead_words = mask.size();
-            }
-            MX_HIP(hipMemcpyAsync(g->dead, mask.data(), mask.size() * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
-            d_dead = g->dead;
-        } else if (!idx->composite() && idx->n_dead && idx->dead) {
-            d_dead = idx->dead;  // a plain index: its own mask, one word per 64 rows of its capacity
-        }
+        if (int rc = dead_mask_on_device(idx, t, mask, g->dead, g->dead_words, &d_dead); rc != MX_OK) return rc;
         uint64_t part[2 * kGroupCountBlocks];
         MX_HIP(launch_grouping_count(t->stream, g->keys, n, d_dead, g->part));
         MX_HIP(hipMemcpyAsync(part, g->part, sizeof(part), hipMemcpyDeviceToHost, t->stream));
@@ -4795,6 +4858,359 @@ int mx_index_search_grouped_device(mx_index *idx, mx_grouping *g, mx_filter *f, 
         int rc = grouped_batch(idx, g, f, d_q + (size_t)b0 * idx->dim, nb, k, fetch, d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr,
                                d_keys ? d_keys + o : nullptr, d_group_rows ? d_group_rows + o : nullptr, d_nfound + b0,
                                d_complete ? d_complete + b0 : nullptr);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+// ---- boosted search (mx_prior, mx_index_search_boosted) -------------------------------------------------------------
+namespace {
+
+// a prior named in a call on idx (under idx->mu): made for this handle, and not older than its rows
+int check_prior(const mx_index *idx, const mx_prior *p) {
+    if (p->idx != idx) return fail(MX_EINVAL, "the prior was made for another index");
+    if (p->epoch != idx->row_epoch)
+        return fail(MX_EINVAL, "the prior is stale: the index was cleared, loaded or compacted after it was made (destroy it and make a new one)");
+    return MX_OK;
+}
+
+// the value array covers `rows` rows: a new block, the old values copied, the rest zero (the owner's device is current)
+int ensure_prior_vals(mx_prior *p, mx_index *t, uint64_t rows) {
+    if (rows <= p->len) return MX_OK;
+    const uint64_t want = (rows + 1023) / 1024 * 1024;
+    Dev<float> nb;
+    MX_HIP(nb.alloc((size_t)want));
+    if (p->len) MX_HIP(hipMemcpyAsync(nb, p->vals, (size_t)p->len * sizeof(float), hipMemcpyDeviceToDevice, t->stream));
+    MX_HIP(hipMemsetAsync(nb.get() + p->len, 0, (size_t)(want - p->len) * sizeof(float), t->stream));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    p->vals = std::move(nb);
+    p->len = want;
+    return MX_OK;
+}
+
+int ensure_prior_stage(mx_prior *p, size_t bytes) {
+    if (p->stage_bytes >= bytes) return MX_OK;
+    p->stage_bytes = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
+    MX_HIP(p->stage.alloc_bytes(want));  // (every call is host-synchronised before it returns)
+    p->stage_bytes = want;
+    return MX_OK;
+}
+
+void free_prior_buffers(mx_prior *p) {
+    DeviceGuard dg(p->device);
+    p->vals.reset();
+    p->stage.reset();
+    p->part.reset();
+    p->dead.reset();
+    p->weights.reset();
+    p->out_priors.reset();
+    p->out_combined.reset();
+    p->out_complete.reset();
+}
+
+// the head of every mx_prior_* call but create and destroy; the caller holds idx->mu
+int prior_ready(mx_prior *p) {
+    if (int rc = usable(p->idx); rc != MX_OK) return rc;
+    return check_prior(p->idx, p);
+}
+
+// the values of an edit as the words the edit kernels store; *top = the largest of them.  A value that is not finite: MX_EINVAL
+int read_prior_values(const float *values, uint64_t n, std::vector<uint32_t> *words, float *top) {
+    words->resize((size_t)n);
+    *top = -INFINITY;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!std::isfinite(values[i])) return fail(MX_EINVAL, "value %llu is not finite; nothing changed", (unsigned long long)i);
+        *top = std::max(*top, values[i]);
+    }
+    if (n) memcpy(words->data(), values, (size_t)n * sizeof(uint32_t));
+    return MX_OK;
+}
+
+// arguments of the boosted-search entry points, checked before the index is looked at
+int read_boosted_args(int B, int k, int fetch, const mx_prior *p, const float *weights, const void *q, const void *ids, const void *scores,
+                      const void *n_found) {
+    if (B < 0) return fail(MX_EINVAL, "negative batch");
+    if (k < 1) return fail(MX_EINVAL, "k = %d < 1", k);
+    if (fetch < k) return fail(MX_EINVAL, "fetch = %d < k = %d", fetch, k);
+    if (!p) return fail(MX_EINVAL, "null prior");
+    if (B > 0 && (!q || !ids || !scores || !n_found)) return fail(MX_EINVAL, "null argument");
+    for (int b = 0; weights && b < B; ++b)
+        if (!std::isfinite(weights[b]) || weights[b] < 0.0f)
+            return fail(MX_EINVAL, "weights[%d] = %g: a weight is finite and not negative", b, (double)weights[b]);
+    if (fetch > kBoostMaxFetch) return fail(MX_EUNSUPPORTED, "fetch = %d > %d", fetch, kBoostMaxFetch);
+    return MX_OK;
+}
+
+// One batch (B <= kMaxBatch) of a boosted search, as grouped_batch: a plain (or resident-filtered) search pass at k = fetch into the
+// owner's lists, one boost_rank_kernel launch; host-synchronised.  weights: host memory [B] or null.
+int boosted_batch(mx_index *idx, mx_prior *p, mx_filter *f, const float *d_q, const float *weights, int B, int k, int fetch, uint64_t *d_ids,
+                  float *d_scores, float *d_dists, float *d_priors, double *d_combined, int32_t *d_nfound, uint8_t *d_complete) {
+    mx_index *t = group_owner(idx);
+    int rc = ensure_mmr_lists(t, fetch);
+    if (rc != MX_OK) return rc;
+    if (weights && !p->weights) MX_HIP(p->weights.alloc(kMaxBatch));
+    const FilterArg fa{nullptr, f, 0};
+    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf, f ? &fa : nullptr)) != MX_OK) return rc;
+    if (weights) MX_HIP(hipMemcpyAsync(p->weights, weights, (size_t)B * sizeof(float), hipMemcpyHostToDevice, t->stream));
+    BoostRank a{B, k, fetch, idx->idmap.id_offset, p->len, p->vals, weights ? p->weights.get() : nullptr, p->hi, t->mmr_ids, t->mmr_scores,
+                t->mmr_dists, t->mmr_nf, d_ids, d_scores, d_dists, d_priors, d_combined, d_nfound, d_complete};
+    MX_HIP(launch_boost_rank(t->stream, a));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+}
+
+// handles named in a boosted search (under idx->mu)
+int check_boosted_handles(mx_index *idx, mx_prior *p, mx_filter *f) {
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (int rc = check_prior(idx, p); rc != MX_OK) return rc;
+    return f ? check_filter(idx, f) : MX_OK;
+}
+
+}  // namespace
+
+int mx_prior_create(mx_index *idx, mx_prior **out) try {
+    if (!out) return fail(MX_EINVAL, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(MX_EINVAL, "null index");
+    {   // the prior's own reference: the rows stay while it lives, whoever closes the index
+        std::lock_guard<std::mutex> lk(g_reg_mu);
+        idx->refs += 1;
+    }
+    std::unique_ptr<mx_prior> p(new mx_prior());
+    int rc = MX_OK;
+    {
+        std::lock_guard<std::mutex> lk(idx->mu);
+        rc = usable(idx);
+        mx_index *t = group_owner(idx);
+        p->idx = idx;
+        p->epoch = idx->row_epoch;
+        p->device = t->device;
+        if (rc == MX_OK) {
+            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+            if (t != idx) l2.lock();
+            DeviceGuard dg(t->device);
+            rc = ensure_prior_vals(p.get(), t, rows_of(idx));
+        }
+        if (rc != MX_OK) free_prior_buffers(p.get());
+    }
+    if (rc != MX_OK) {
+        const std::string keep = last_error_slot();
+        mx_index_close(idx);
+        last_error_slot() = keep;
+        return rc;
+    }
+    *out = p.release();
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+void mx_prior_destroy(mx_prior *p) {
+    if (!p) return;
+    mx_index *idx = p->idx;
+    try {
+        std::lock_guard<std::mutex> lk(idx->mu);  // (no search that names the prior is inside the library)
+        free_prior_buffers(p);
+    } catch (...) {
+    }
+    delete p;
+    mx_index_close(idx);
+}
+
+int mx_prior_set_ranges(mx_prior *p, const uint64_t *ranges, const float *values, uint64_t n_ranges) try {
+    if (!p) return fail(MX_EINVAL, "null prior");
+    if ((!ranges || !values) && n_ranges) return fail(MX_EINVAL, "null ranges or values with n_ranges = %llu", (unsigned long long)n_ranges);
+    std::vector<uint32_t> words;
+    float top = 0.0f;
+    if (int rc = read_prior_values(values, n_ranges, &words, &top); rc != MX_OK) return rc;
+    std::vector<WordSpan> sp;
+    if (int rc = read_word_spans(ranges, words.data(), n_ranges, &sp); rc != MX_OK) return rc;
+    mx_index *idx = p->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = prior_ready(p); rc != MX_OK) return rc;
+    std::vector<uint64_t> rows;
+    std::vector<uint32_t> rw;
+    spans_to_rows(sp, idx->idmap.id_offset, rows_of(idx), &rows, &rw);
+    if (rw.empty()) {
+        p->hi = std::max(p->hi, top);  // (hi follows what the call was handed, whether or not a row took it)
+        return MX_OK;
+    }
+    mx_index *t = group_owner(idx);
+    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+    if (t != idx) l2.lock();
+    DeviceGuard dg(t->device);
+    // every allocation first: a call that fails leaves the values as they were
+    const size_t rb = rows.size() * sizeof(uint64_t), wb = rw.size() * sizeof(uint32_t);
+    if (int rc = ensure_prior_vals(p, t, rows.back()); rc != MX_OK) return rc;
+    if (int rc = ensure_prior_stage(p, rb + wb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(p->stage.get());
+    MX_HIP(hipMemcpyAsync(st, rows.data(), rb, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(hipMemcpyAsync(st + rb, rw.data(), wb, hipMemcpyHostToDevice, t->stream));
+    p->hi = std::max(p->hi, top);  // (before the store is queued: hi is never below a value of the array)
+    MX_HIP(launch_grouping_range_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + rb),
+                                      (uint32_t)rw.size(), rows.front(), rows.back(), reinterpret_cast<uint32_t *>(p->vals.get())));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_prior_set_ids(mx_prior *p, const uint64_t *ids, const float *values, uint64_t n_ids) try {
+    if (!p) return fail(MX_EINVAL, "null prior");
+    if ((!ids || !values) && n_ids) return fail(MX_EINVAL, "null ids or values with n_ids = %llu", (unsigned long long)n_ids);
+    std::vector<uint32_t> words;
+    float top = 0.0f;
+    if (int rc = read_prior_values(values, n_ids, &words, &top); rc != MX_OK) return rc;
+    if (int rc = check_id_words(ids, words.data(), n_ids, "value bits"); rc != MX_OK) return rc;
+    mx_index *idx = p->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = prior_ready(p); rc != MX_OK) return rc;
+    const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
+    const uint64_t last = top_row_named(ids, n_ids, off, total);
+    if (last == 0) {
+        p->hi = std::max(p->hi, top);
+        return MX_OK;
+    }
+    mx_index *t = group_owner(idx);
+    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+    if (t != idx) l2.lock();
+    DeviceGuard dg(t->device);
+    const size_t ib = (size_t)n_ids * sizeof(uint64_t), wb = (size_t)n_ids * sizeof(uint32_t);
+    if (int rc = ensure_prior_vals(p, t, last); rc != MX_OK) return rc;
+    if (int rc = ensure_prior_stage(p, ib + wb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(p->stage.get());
+    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(hipMemcpyAsync(st + ib, words.data(), wb, hipMemcpyHostToDevice, t->stream));
+    p->hi = std::max(p->hi, top);
+    MX_HIP(launch_grouping_id_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + ib), n_ids, off,
+                                   std::min(total, p->len), reinterpret_cast<uint32_t *>(p->vals.get())));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_prior_get(mx_prior *p, const uint64_t *ids, uint64_t n_ids, float *values) try {
+    if (!p) return fail(MX_EINVAL, "null prior");
+    if ((!ids || !values) && n_ids) return fail(MX_EINVAL, "null ids or values with n_ids = %llu", (unsigned long long)n_ids);
+    mx_index *idx = p->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = prior_ready(p); rc != MX_OK) return rc;
+    if (n_ids == 0) return MX_OK;
+    mx_index *t = group_owner(idx);
+    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+    if (t != idx) l2.lock();
+    DeviceGuard dg(t->device);
+    const size_t ib = (size_t)n_ids * sizeof(uint64_t), wb = (size_t)n_ids * sizeof(uint32_t);
+    if (int rc = ensure_prior_stage(p, ib + wb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(p->stage.get());
+    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(launch_grouping_get(t->stream, reinterpret_cast<const uint64_t *>(st), n_ids, idx->idmap.id_offset, std::min(rows_of(idx), p->len),
+                               reinterpret_cast<const uint32_t *>(p->vals.get()), reinterpret_cast<uint32_t *>(st + ib)));
+    MX_HIP(hipMemcpyAsync(values, st + ib, wb, hipMemcpyDeviceToHost, t->stream));  // (the word 0 of an id that names no row is +0.0f)
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_prior_bound(mx_prior *p, int refresh, float *hi) try {
+    if (!p) return fail(MX_EINVAL, "null prior");
+    if (refresh != 0 && refresh != 1) return fail(MX_EINVAL, "refresh = %d is neither 0 nor 1", refresh);
+    mx_index *idx = p->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = prior_ready(p); rc != MX_OK) return rc;
+    if (refresh) {
+        const uint64_t n = std::min(rows_of(idx), p->len);
+        float top = 0.0f;
+        if (n) {
+            mx_index *t = group_owner(idx);
+            std::vector<uint64_t> mask;
+            composite_dead_mask(idx, n, &mask);
+            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+            if (t != idx) l2.lock();
+            DeviceGuard dg(t->device);
+            if (!p->part) MX_HIP(p->part.alloc(kBoostMaxBlocks));
+            const uint64_t *d_dead = nullptr;
+            if (int rc = dead_mask_on_device(idx, t, mask, p->dead, p->dead_words, &d_dead); rc != MX_OK) return rc;
+            float part[kBoostMaxBlocks];
+            MX_HIP(launch_prior_max(t->stream, p->vals, n, d_dead, p->part));
+            MX_HIP(hipMemcpyAsync(part, p->part, sizeof(part), hipMemcpyDeviceToHost, t->stream));
+            MX_HIP(hipStreamSynchronize(t->stream));
+            for (int w = 0; w < kBoostMaxBlocks; ++w) top = std::max(top, part[w]);
+        }
+        p->hi = top;
+    }
+    if (hi) *hi = p->hi;
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_boosted(mx_index *idx, mx_prior *p, mx_filter *f, const float *q, const float *weights, int B, int k, int fetch,
+                            uint64_t *ids, float *scores, float *dists, float *priors, double *combined, int32_t *n_found,
+                            uint8_t *complete) try {
+    if (int rc = read_boosted_args(B, k, fetch, p, weights, q, ids, scores, n_found); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    const size_t dim = (size_t)idx->dim;
+    for (size_t i = 0; i < (size_t)B * dim; ++i)
+        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    // not combined with other callers: the call holds the index across the candidate stage and the re-ranking, like a device-pointer call
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_boosted_handles(idx, p, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);  // owner of the staging buffers and the stream
+    DeviceGuard dg(t->device);
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, k)) != MX_OK) return rc;
+    if (k > p->out_cap) {
+        p->out_cap = 0;
+        const size_t kc = (size_t)std::max(k, 16);
+        MX_HIP(p->out_priors.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(p->out_combined.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(p->out_complete.alloc(kMaxBatch));
+        p->out_cap = (int)kc;
+    }
+    Scratch &s = t->s;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        if ((rc = boosted_batch(idx, p, f, s.qstage, weights ? weights + b0 : nullptr, nb, k, fetch, s.out_ids, s.out_scores, s.out_dists,
+                                p->out_priors, p->out_combined, s.out_nfound, p->out_complete)) != MX_OK)
+            return rc;
+        if (priors) MX_HIP(hipMemcpyAsync(priors + o, p->out_priors, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+        if (combined) MX_HIP(hipMemcpyAsync(combined + o, p->out_combined, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+        if (complete) MX_HIP(hipMemcpyAsync(complete + b0, p->out_complete, (size_t)nb, hipMemcpyDeviceToHost, t->stream));
+        if ((rc = copy_out_to_host(t, nb, k, false)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nb, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, nullptr);
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_boosted_device(mx_index *idx, mx_prior *p, mx_filter *f, const float *d_q, const float *weights, int B, int k, int fetch,
+                                   uint64_t *d_ids, float *d_scores, float *d_dists, float *d_priors, double *d_combined,
+                                   int32_t *d_nfound, uint8_t *d_complete) try {
+    if (int rc = read_boosted_args(B, k, fetch, p, weights, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_boosted_handles(idx, p, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);
+    DeviceGuard dg(t->device);
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        int rc = boosted_batch(idx, p, f, d_q + (size_t)b0 * idx->dim, weights ? weights + b0 : nullptr, nb, k, fetch, d_ids + o, d_scores + o,
+                               d_dists ? d_dists + o : nullptr, d_priors ? d_priors + o : nullptr, d_combined ? d_combined + o : nullptr,
+                               d_nfound + b0, d_complete ? d_complete + b0 : nullptr);
         if (rc != MX_OK) return rc;
     }
     return MX_OK;

@@ -564,4 +564,36 @@ struct GroupHeads {
 };
 hipError_t launch_group_heads(hipStream_t s, const GroupHeads &p);
 
+// boosted search (mx_prior / mx_index_search_boosted; boost_kernels.hip)
+constexpr int kBoostThreads = 1024;              // one workgroup per query
+constexpr int kBoostMaxFetch = 4096;             // entries per list (the ABI's cap on k): kBoostMaxFetch / kBoostThreads per thread
+constexpr int kBoostMaxBlocks = 256;             // workgroups of the maximum; each writes its partial maximum
+// The values of a prior: one f32 per GLOBAL row (id - id_offset - 1) of the handle, vals[0, len).  They are edited and read back by
+// the grouping's edit and get kernels, as their 32 bits.
+// Maximum: part[w] = the largest of 0 and vals[r] over the rows r < n of workgroup w's share whose bit in `dead` (one bit per global
+// row, null: no removals) is clear; kBoostMaxBlocks workgroups, the host folds the partial maxima.
+hipError_t launch_prior_max(hipStream_t s, const float *vals, uint64_t n, const uint64_t *dead, float *part);
+// One re-ranked list [B, k] per query from its candidate list (row b of cand_* [B, fetch], (dist, id) order, cand_nf = m entries).
+// Entry j has prior vals[id - id_offset - 1] (0 when that row is not below len) and c_j = (double)score_j + (double)w * (double)prior_j
+// with w = weights[b] (device memory; null: 1).  The entries are ranked by (c descending, j ascending) and the first min(k, m) written
+// in that order: id, score and dist unchanged, the prior, and c.  n_found = min(k, m); the slots behind hold id 0, score 0, dist +inf,
+// prior 0, combined 0.  complete = m < fetch, or the k-th reported c > (double)score_{m-1} + (double)w * (double)hi.  dists, priors,
+// combined and complete may be null.  1 <= k <= fetch <= kBoostMaxFetch.
+struct BoostRank {
+    int B, k, fetch;
+    uint64_t id_offset, len;
+    const float *vals;
+    const float *weights;
+    float hi;
+    const uint64_t *cand_ids;
+    const float *cand_scores, *cand_dists;
+    const int32_t *cand_nf;
+    uint64_t *ids;
+    float *scores, *dists, *priors;
+    double *combined;
+    int32_t *n_found;
+    uint8_t *complete;
+};
+hipError_t launch_boost_rank(hipStream_t s, const BoostRank &p);
+
 }  // namespace mx

@@ -486,6 +486,70 @@ class FlatIndex:
                                                    self._grouped_fetch(k, fetch), dp(ids), dp(scores), dp(dists), dp(keys),
                                                    dp(group_rows), dp(n_found), dp(complete)))
 
+    # -- boosted search --------------------------------------------------------------------
+    def make_prior(self) -> "IndexPrior":
+        """A prior (``mx_prior``): one f32 per row of this index, kept in HBM and named in ``search_boosted``.  It starts at 0
+        everywhere."""
+        return IndexPrior(self)
+
+    @staticmethod
+    def _boost_weights(weight, B: int):
+        """-> f32 [B], or None for weight 1.0 everywhere."""
+        w = np.asarray(weight, dtype=np.float32)
+        if w.ndim == 0:
+            if float(w) == 1.0:
+                return None
+            w = np.full(B, w, dtype=np.float32)
+        w = np.ascontiguousarray(w.reshape(-1))
+        if w.size != B:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {B} weights, got {w.size}")
+        return w
+
+    def search_boosted(self, prior: "IndexPrior", queries, k: int, weight=1.0, fetch=None, flt: "IndexFilter | None" = None):
+        """The ``k`` best rows by ``score + weight * prior`` (``mx_index_search_boosted``).
+        -> (ids u64 [B,k], scores f32 [B,k], dists f32 [B,k], priors f32 [B,k], combined f64 [B,k], n_found i32 [B], complete bool [B]).
+        Per query the top-``fetch`` list of ``search`` (of ``search_with(flt, ...)`` when ``flt`` is given) is re-ranked by
+        ``combined = float64(score) + float64(weight) * float64(prior)``, descending, ties in the list's order.  ``weight`` is a
+        scalar or one value per query, finite and not negative.  ``complete[b]``: the answer is the exact top-k over all rows;
+        otherwise it is exact for the list only and a larger ``fetch`` may change it.  ``fetch=None``: ``4 * k`` clamped to
+        [32, 256] and never below ``k``."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        B = q.shape[0]
+        w = self._boost_weights(weight, B)
+        kk = max(int(k), 0)
+        ids = np.zeros((B, kk), dtype=np.uint64)
+        scores = np.zeros((B, kk), dtype=np.float32)
+        dists = np.zeros((B, kk), dtype=np.float32)
+        priors = np.zeros((B, kk), dtype=np.float32)
+        combined = np.zeros((B, kk), dtype=np.float64)
+        nf = np.zeros(B, dtype=np.int32)
+        done = np.zeros(B, dtype=np.uint8)
+        p = lambda a: _ptr(a) if a is not None and a.size else None  # noqa: E731
+        check(lib().mx_index_search_boosted(self._h, prior._h, flt._h if flt is not None else None, p(q), p(w), B, int(k),
+                                            self._grouped_fetch(k, fetch), p(ids), p(scores), p(dists), p(priors), p(combined), p(nf),
+                                            p(done)))
+        return ids, scores, dists, priors, combined, nf, done.astype(bool)
+
+    def search_boosted_device(self, prior: "IndexPrior", q, k: int, ids, scores, dists, priors, combined, n_found, complete,
+                              weight=1.0, fetch=None, flt: "IndexFilter | None" = None) -> None:
+        """``search_boosted`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,k]; scores, dists, priors f32 [B,k]; combined f64
+        [B,k]; n_found i32 [B]; complete u8 [B] (dists, priors, combined and complete may be None).  ``weight`` stays on the host.
+        Blocks until the results are in HBM."""
+        B = int(q.shape[0])
+        w = self._boost_weights(weight, B)
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().mx_index_search_boosted_device(self._h, prior._h, flt._h if flt is not None else None, dp(q),
+                                                   _ptr(w) if w is not None and w.size else None, B, int(k),
+                                                   self._grouped_fetch(k, fetch), dp(ids), dp(scores), dp(dists), dp(priors),
+                                                   dp(combined), dp(n_found), dp(complete)))
+
     # -- search by stored row --------------------------------------------------------------
     @staticmethod
     def _query_ids(ids) -> np.ndarray:
@@ -865,6 +929,75 @@ class IndexGrouping:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().mx_grouping_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class IndexPrior:
+    """What the vectors do not carry, per row of one ``FlatIndex``: one f32 per row, resident on the index's first device
+    (``mx_prior``), added to the score by ``search_boosted``.  Rows nobody set, and rows appended later, read 0.  It
+    holds a reference on the index.  After the index's ``clear``, ``load`` or a ``compact`` that dropped rows every method but
+    ``close`` raises: make a new prior."""
+
+    def __init__(self, index: FlatIndex):
+        h = ctypes.c_void_p()
+        check(lib().mx_prior_create(index._h, ctypes.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _values(values, n: int) -> np.ndarray:
+        v = np.asarray(values, dtype=np.float32)
+        if v.ndim == 0:
+            v = np.full(n, v, dtype=np.float32)
+        v = np.ascontiguousarray(v.reshape(-1))
+        if v.size != n:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {n} values, got {v.size}")
+        return v
+
+    def set_ranges(self, ranges, values) -> None:
+        """Every id of range ``i`` ([m, 2] half-open id ranges, pairwise disjoint, any order) gets ``values[i]`` (one value per
+        range, or one for all).  Values are finite; a negative one is a penalty.  Ids that name no row at this moment are ignored."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+        v = self._values(values, r.shape[0])
+        check(lib().mx_prior_set_ranges(self._h, _ptr(r) if r.size else None, _ptr(v) if v.size else None, r.shape[0]))
+
+    def set_ids(self, ids, values) -> None:
+        """``ids[i]`` gets ``values[i]`` (one value per id, or one for all).  Ids may repeat and come in any order, but not with two
+        different values in one call."""
+        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
+        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        v = self._values(values, a.size)
+        check(lib().mx_prior_set_ids(self._h, _ptr(a) if a.size else None, _ptr(v) if v.size else None, a.size))
+
+    def values_of(self, ids) -> np.ndarray:
+        """-> float32 [n]: the value of the row each id names, 0 for an id that names no row."""
+        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
+        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        out = np.zeros(a.size, dtype=np.float32)
+        check(lib().mx_prior_get(self._h, _ptr(a) if a.size else None, a.size, _ptr(out) if out.size else None))
+        return out
+
+    def bound(self, refresh: bool = False) -> float:
+        """The upper bound of the values that ``search_boosted``'s ``complete`` is decided with: never below a value of the array,
+        raised by every edit, lowered only by ``refresh=True``, which recomputes the maximum of 0 and the live rows' values."""
+        hi = ctypes.c_float(0.0)
+        check(lib().mx_prior_bound(self._h, 1 if refresh else 0, ctypes.byref(hi)))
+        return float(hi.value)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().mx_prior_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -276,6 +276,57 @@ class StoreGrouping:
         self.close()
 
 
+class StorePrior:
+    """What a ``HipFlatStore``'s vectors do not say about its segments (``HipFlatStore.make_prior``): a resident prior of the index,
+    edited by segment ``_id``, added to the score by ``search_boosted``.  Segments nobody set read 0.  The prior is not saved with
+    the store: the host that owns the values builds it again after a restart, and after ``compact()``, ``delete_all()`` or a
+    reload, when every method but ``close`` raises."""
+
+    def __init__(self, store: "HipFlatStore", prior):
+        self._store = store
+        self._pri = prior
+
+    def set(self, ids, values) -> None:
+        """Every row inserted under segment ``ids[i]`` gets ``values[i]`` (one value per ``_id``, or one for all); unknown ``_id``s
+        add nothing.  One ``set_ids`` call for all of them."""
+        names = [ids] if isinstance(ids, str) else [str(i) for i in ids]
+        vals = np.asarray(values, dtype=np.float32)
+        vals = np.full(len(names), vals, dtype=np.float32) if vals.ndim == 0 else vals.reshape(-1)
+        if vals.size != len(names):
+            raise SearchError(f"expected {len(names)} values, got {vals.size}")
+        rows: List[int] = []
+        out: List[float] = []
+        with self._store._lock:
+            for name, v in zip(names, vals):
+                named = self._store._ids_named([name])
+                rows.extend(named)
+                out.extend([v] * len(named))
+            try:
+                self._pri.set_ids(np.asarray(rows, dtype=np.uint64), np.asarray(out, dtype=np.float32))
+            except _lib.MemexHipError as e:
+                _raise_from(e, SearchError)
+
+    def set_document(self, document_ids, value) -> None:
+        """One value for all the segments of a document: ``set(document_ids, value)``."""
+        self.set(list(document_ids), float(value))
+
+    def bound(self, refresh: bool = False) -> float:
+        """The upper bound of the values that ``complete`` is decided with (``IndexPrior.bound``)."""
+        try:
+            return self._pri.bound(refresh)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+
+    def close(self) -> None:
+        self._pri.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 @dataclass
 class HipFlatStore(VectorStore):
     """Drop-in for ``HnswStore``: same id map, same score formula, exact search on the GPU."""
@@ -727,6 +778,48 @@ class HipFlatStore(VectorStore):
                 out.append((grouping.document_of(int(keys[0, j])), self._id_map[d_id], float(scores[0, j]), int(rows[0, j])))
         return out, bool(done[0])
 
+    def make_prior(self) -> "StorePrior":
+        """A resident prior (``FlatIndex.make_prior``), 0 for every segment.  Bulk-inserting a document and then
+        ``prior.set_document([its _ids], value)`` is the ingest flow.  After ``compact()``, ``delete_all()`` or a reload the prior
+        raises: make a new one.  The store must hold at least one row."""
+        with self._lock:
+            if self._index is None:
+                raise SearchError("a prior needs a store with rows: insert first")
+            try:
+                return StorePrior(self, self._index.make_prior())
+            except _lib.MemexHipError as e:
+                _raise_from(e, SearchError)
+
+    def search_boosted(self, vec: Sequence[float], limit: int, prior: "StorePrior", weight: float = 1.0, fetch: int | None = None,
+                       flt: "StoreFilter | None" = None) -> Tuple[List[Tuple[str, float, float, float]], bool]:
+        """The ``limit`` best segments for ``vec`` by ``score + weight * prior`` (``FlatIndex.search_boosted``) -> ``(hits,
+        complete)``.  Each hit is ``(segment _id, score, prior, combined)``, best first.  ``complete``: the hits are the exact top
+        segments over the whole store (over ``flt``'s rows when given).  The candidates are the top-``fetch`` rows; when that answer
+        is not complete the call asks ONCE more with 4096 candidates.  Removed rows never appear."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0:
+            return [], True
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        f = flt._flt if flt is not None else None
+        first = FlatIndex._grouped_fetch(int(limit), fetch)
+        try:
+            ids, scores, _, priors, comb, nf, done = idx.search_boosted(prior._pri, q, int(limit), weight, first, f)  # not under the lock
+            if not done[0] and first < 4096:
+                ids, scores, _, priors, comb, nf, done = idx.search_boosted(prior._pri, q, int(limit), weight, 4096, f)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[Tuple[str, float, float, float]] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((self._id_map[d_id], float(scores[0, j]), float(priors[0, j]), float(comb[0, j])))
+        return out, bool(done[0])
+
     def _rows_by_name(self) -> Dict[str, List[int]]:
         """(under the lock) ``_id`` -> the ids stored under it: built once per store, kept on insert."""
         if self._rows_of is None:
@@ -927,6 +1020,11 @@ class VectorStorage:
                          flt: "StoreFilter | None" = None):
         with self._mu:
             return self.client.search_documents(query, limit, grouping, fetch, flt)
+
+    def search_boosted(self, query: Sequence[float], limit: int, prior: "StorePrior", weight: float = 1.0, fetch: int | None = None,
+                       flt: "StoreFilter | None" = None):
+        with self._mu:
+            return self.client.search_boosted(query, limit, prior, weight, fetch, flt)
 
     def search_like(self, positive: Sequence[str], negative: Sequence[str] = (), limit: int = 10, vec: Sequence[float] | None = None,
                     alpha: float = 1.0, beta: float = 0.75, gamma: float = 0.15) -> List[VectorSearchResult]:

@@ -25,6 +25,10 @@ caller's own working set), those segments back with their exact scores, best fir
 one returns the best DOCUMENTS, each by its best segment (``search_documents`` of the store, over a grouping that
 :func:`group_document` fills from a ``process_embeddings`` result).
 
+:func:`search_docs_recent` has none either: relevance plus recency.  :func:`stamp_document` stores ``exp2((t - t0) / half_life)`` for
+a document's segments once, at ingest; a query at time ``now`` multiplies its weight by ``exp2(-(now - t0) / half_life)``, so the
+boost a segment gets is ``weight * exp2(-(now - t) / half_life)`` and the resident values are never rewritten as time passes.
+
 The ids are the reference's own (RFC 4122 v5 over the same namespace), so a collection filled through this mirror lines up
 with the rows a memex worker would have written for the same task ids.
 """
@@ -32,6 +36,8 @@ from __future__ import annotations
 
 import uuid
 from typing import List, Sequence, Tuple
+
+import numpy as np
 
 from .storage import VectorData
 
@@ -117,6 +123,38 @@ def search_documents(client, embedder, grouping, query: str, limit: int = 10):
     if res is None:
         raise ValueError("Invalid query")
     return client.search_documents(res.vector, limit, grouping)
+
+
+def stamp_document(prior, vectors: Sequence[VectorData], t: float, half_life: float, t0: float) -> None:
+    """Ingest side of :func:`search_docs_recent`: the segments of a ``process_embeddings`` result, written at time ``t``, get the
+    prior ``exp2((t - t0) / half_life)`` (``StorePrior.set_document``).  Call it after the vectors were added.  The value is an f32:
+    it overflows about 127 half-lives after ``t0`` (``ValueError``), and a query's folded weight underflows about as far out, so
+    after roughly 120 half-lives ``t0`` must be moved and the values written again."""
+    with np.errstate(over="ignore"):
+        value = float(np.float32(np.exp2((np.float64(t) - np.float64(t0)) / np.float64(half_life))))
+    if not np.isfinite(value):
+        raise ValueError("t is too far from t0 for an f32 prior: move t0 and stamp the documents again")
+    ids = [v._id for v in vectors]
+    if ids:
+        prior.set_document(ids, value)
+
+
+def recency_weight(weight: float, now: float, half_life: float, t0: float) -> float:
+    """The weight a query at time ``now`` carries: ``weight * exp2(-(now - t0) / half_life)``, as an f32."""
+    return float(np.float32(np.float64(weight) * np.exp2(-(np.float64(now) - np.float64(t0)) / np.float64(half_life))))
+
+
+def search_docs_recent(client, embedder, prior, query: str, limit: int = 10, now: float = 0.0, half_life: float = 1.0, t0: float = 0.0,
+                       weight: float = 1.0):
+    """``search_docs`` that prefers recent segments: ``encode_single(query)`` -> ``client.search_boosted(vector, limit, prior,
+    recency_weight(weight, now, half_life, t0))`` -> ``(hits, complete)``, each hit ``(segment _id, score, prior, combined)``.  With
+    the priors of :func:`stamp_document` a segment written at ``t`` is ranked by ``score + weight * exp2(-(now - t) / half_life)``:
+    ``weight`` is the boost of a segment written this instant, halved every ``half_life``.  ``ValueError("Invalid query")`` where
+    ``search_docs`` raises it."""
+    res = embedder.encode_single(query)
+    if res is None:
+        raise ValueError("Invalid query")
+    return client.search_boosted(res.vector, limit, prior, recency_weight(weight, now, half_life, t0))
 
 
 def rerank_docs(client, embedder, query: str, candidates: Sequence[str], limit: int = 10) -> List[Tuple[str, float]]:
