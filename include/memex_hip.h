@@ -576,6 +576,39 @@ int mx_index_search_boosted_device(mx_index *idx, mx_prior *p, mx_filter *f, con
                                    int fetch, uint64_t *d_ids, float *d_scores, float *d_dists, float *d_priors, double *d_combined,
                                    int32_t *d_n_found, uint8_t *d_complete);
 
+/*
+ * Filters from row attributes: a resident filter built from what the rows already carry in HBM -- a predicate on a prior's values
+ * ("only segments stamped after T", "only sources trusted >= 0.8"), membership of the row's grouping key in a list ("only these 300
+ * documents") -- and the set algebra of filters that exist (tenant AND tag AND NOT already-shown).  No id is enumerated on the host
+ * and none is uploaded: the device decides the set in one pass over 4 bytes per row.  The result is an ordinary
+ * mx_filter: mx_index_search_with_filter, grouped search and boosted search take it as they take any other, and mx_filter_count,
+ * mx_filter_get_ranges and every search behave exactly as after an mx_filter_set_ids with the same rows.
+ *   mx_filter_set_where  the selection S is the rows r in [0, size) at the time of the call with lo <= v_r && v_r <= hi, v_r the value
+ *                        of row r in `p`: 0 for a row at or past the prior's length, exactly as mx_prior_get reads it.  The comparison
+ *                        is plain IEEE f32, so a stored -0.0 matches [0, 0].  allow = 1 adds S to the set, allow = 0 takes S away (any
+ *                        other value: MX_EINVAL).  +-inf bounds are allowed and make a one-sided predicate; lo > hi selects nothing
+ *                        and returns MX_OK; a NaN bound is MX_EINVAL.  Removed rows are selected like any other row: they stay in the
+ *                        set and are never returned.  n_selected may be NULL; it receives |S|, not the change of the set.
+ *   mx_filter_set_keys   the same with S = the rows whose key in `g` is one of keys[0 .. n_keys).  Keys may repeat and come in any
+ *                        order.  Key 0 may be listed: it names the ungrouped rows, those past the grouping's length included.
+ *                        n_keys = 0 is a no-op (S is empty).  NULL keys with n_keys > 0: MX_EINVAL; n_keys > 2^20: MX_EUNSUPPORTED.
+ *   mx_filter_combine    dst = a op b, bitwise over the rows; MX_FILTER_ANDNOT is a and not b.  dst may be a or b, and a may be b.  An
+ *                        op outside the enum: MX_EINVAL.  The operands hold no row at or past size, so the result holds none either.
+ *   mx_filter_invert     the complement within [0, size) at the time of the call; rows appended later are outside the set, as for
+ *                        every filter.
+ * All four: a NULL handle is MX_EINVAL ("null filter", "null prior", "null grouping") before anything else; objects of different
+ * indexes: MX_EINVAL; a stale filter, prior or grouping: MX_EINVAL with "stale" in the message.  A failing call changes nothing.  The
+ * calls hold the handle's mutex as mx_filter_set_ids does: a search sees the filter before or after a whole call, never half of one.
+ * A sharded handle evaluates the predicate on devices[0], where priors and groupings live, and deals the selected rows to the shards'
+ * bitmaps; combine and invert run shard by shard.  Its filters equal a plain index's bit for bit.  One selection bitmap (1 bit per
+ * row) crosses to the host per set_where / set_keys call: the host mirror of the filter is taken from the kernel's own output.
+ */
+enum { MX_FILTER_AND = 0, MX_FILTER_OR = 1, MX_FILTER_ANDNOT = 2, MX_FILTER_XOR = 3 };
+int mx_filter_set_where(mx_filter *f, mx_prior *p, float lo, float hi, int allow, uint64_t *n_selected);
+int mx_filter_set_keys(mx_filter *f, mx_grouping *g, const uint32_t *keys, uint64_t n_keys, int allow, uint64_t *n_selected);
+int mx_filter_combine(mx_filter *dst, mx_filter *a, mx_filter *b, int op);
+int mx_filter_invert(mx_filter *f);
+
 /* Search strategy (testing / diagnostics).  AUTO = low-precision MFMA streaming scan (int8 or bf16
  * filter copy, or the f32 rows) that certifies a candidate superset, f32 then exact f64 rescoring of the
  * candidates, per-query fallback to EXACT when a candidate buffer overflows twice.  EXACT = f64 arithmetic on every row (slow, always available). */

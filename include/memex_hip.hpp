@@ -416,6 +416,8 @@ class HipFlatStore : public VectorStore {
     // A resident filter (mx_filter): the rows inserted under some _id strings -- one tenant's, one ACL group's, one tag's documents --
     // kept as a bitmap next to the rows and named in search_in().  bulk_insert of a document, then allow({its _ids}), is the
     // tenant-ingest flow.  After compact(), delete_all() or a reload every call but the destructor throws: make a new one.
+    class Grouping;
+    class Prior;
     class Filter {
       public:
         Filter(const Filter &) = delete;
@@ -426,6 +428,19 @@ class HipFlatStore : public VectorStore {
         }
         void allow(const std::vector<std::string> &ids) { edit(ids, 1); }
         void deny(const std::vector<std::string> &ids) { edit(ids, 0); }
+        // the rows whose value in `prior` lies in [lo, hi] join / leave the set (mx_filter_set_where): the device decides, the host
+        // needs no copy of the values; rows nobody set read 0.  -> rows selected
+        uint64_t allow_where(const Prior &prior, float lo = -INFINITY, float hi = INFINITY) { return where(prior, lo, hi, 1); }
+        uint64_t deny_where(const Prior &prior, float lo = -INFINITY, float hi = INFINITY) { return where(prior, lo, hi, 0); }
+        // every segment `grouping` holds under one of the document names joins / leaves the set (mx_filter_set_keys); unknown names
+        // add nothing and no key is handed out for them.  -> rows selected
+        uint64_t allow_documents(const Grouping &grouping, const std::vector<std::string> &documents) { return keys(grouping, documents, 1); }
+        uint64_t deny_documents(const Grouping &grouping, const std::vector<std::string> &documents) { return keys(grouping, documents, 0); }
+        // the complement within the rows the store holds at this moment (mx_filter_invert)
+        void invert() {
+            int rc = mx_filter_invert(f_);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+        }
         // rows in the set, and those of them that are not removed
         std::pair<uint64_t, uint64_t> count() const {
             uint64_t a = 0, l = 0;
@@ -437,6 +452,26 @@ class HipFlatStore : public VectorStore {
       private:
         friend class HipFlatStore;
         Filter(HipFlatStore *store, mx_filter *f) : store_(store), f_(f) {}
+        uint64_t where(const Prior &prior, float lo, float hi, int allow) {
+            uint64_t n = 0;
+            int rc = mx_filter_set_where(f_, prior.p_, lo, hi, allow, &n);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            return n;
+        }
+        uint64_t keys(const Grouping &grouping, const std::vector<std::string> &documents, int allow) {
+            std::vector<uint32_t> ks;
+            {
+                std::lock_guard<std::mutex> lk(store_->mu_);
+                for (auto &d : documents) {
+                    auto it = grouping.key_of_.find(d);
+                    if (it != grouping.key_of_.end()) ks.push_back(it->second);
+                }
+            }
+            uint64_t n = 0;
+            int rc = mx_filter_set_keys(f_, grouping.g_, ks.empty() ? nullptr : ks.data(), ks.size(), allow, &n);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            return n;
+        }
         void edit(const std::vector<std::string> &ids, int allow) {
             std::lock_guard<std::mutex> lk(store_->mu_);
             if (!store_->rows_of_built_) {
@@ -465,6 +500,18 @@ class HipFlatStore : public VectorStore {
         }
         Filter out(this, f);
         out.allow(ids);
+        return out;
+    }
+
+    // out = a op b over the rows (mx_filter_combine), op one of MX_FILTER_AND, MX_FILTER_OR, MX_FILTER_ANDNOT (a and not b), MX_FILTER_XOR;
+    // out may be a or b.  The three-argument form makes a new filter
+    void combine_filters(const Filter &a, const Filter &b, int op, Filter &out) {
+        int rc = mx_filter_combine(out.f_, a.f_, b.f_, op);
+        if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+    }
+    Filter combine_filters(const Filter &a, const Filter &b, int op) {
+        Filter out = make_filter({});
+        combine_filters(a, b, op, out);
         return out;
     }
 
@@ -621,6 +668,7 @@ class HipFlatStore : public VectorStore {
 
       private:
         friend class HipFlatStore;
+        friend class Filter;
         Grouping(HipFlatStore *store, mx_grouping *g) : store_(store), g_(g) {}
         uint32_t key_of(const std::string &document) {
             auto it = key_of_.find(document);
@@ -756,6 +804,7 @@ class HipFlatStore : public VectorStore {
 
       private:
         friend class HipFlatStore;
+        friend class Filter;
         Prior(HipFlatStore *store, mx_prior *p) : store_(store), p_(p) {}
         HipFlatStore *store_;
         mx_prior *p_;

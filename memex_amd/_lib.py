@@ -21,6 +21,7 @@ MX_OK = 0
 MX_EINVAL, MX_EDEVICE, MX_EINSERT, MX_ESEARCH, MX_EIO, MX_EUNSUPPORTED, MX_ENOMEM = -1, -2, -3, -4, -5, -6, -7
 MX_SEARCH_AUTO, MX_SEARCH_EXACT = 0, 1
 MX_FUSE_MAX, MX_FUSE_RRF = 0, 1
+MX_FILTER_AND, MX_FILTER_OR, MX_FILTER_ANDNOT, MX_FILTER_XOR = 0, 1, 2, 3
 MX_CORPUS_F32, MX_CORPUS_BF16 = 0, 1
 MX_POOL_MEAN, MX_POOL_CLS = 0, 1
 MX_PREC_BF16, MX_PREC_BF16X3, MX_PREC_MIXED, MX_PREC_MIXED1 = 0, 1, 2, 3
@@ -40,6 +41,7 @@ EXPORTS = [
     "mx_index_search_grouped", "mx_index_search_grouped_device",
     "mx_prior_create", "mx_prior_destroy", "mx_prior_set_ranges", "mx_prior_set_ids", "mx_prior_get", "mx_prior_bound",
     "mx_index_search_boosted", "mx_index_search_boosted_device",
+    "mx_filter_set_where", "mx_filter_set_keys", "mx_filter_combine", "mx_filter_invert",
     "mx_index_search_by_id", "mx_index_search_by_id_device", "mx_index_search_range_by_id", "mx_index_search_range_by_id_device",
     "mx_index_set_search_mode", "mx_index_set_filter_copy", "mx_index_set_corpus_mode", "mx_index_get_rows",
     "mx_index_save", "mx_index_load", "mx_index_has_store", "mx_index_store_info", "mx_index_remove_files",
@@ -153,6 +155,10 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_prior_bound": [vp, i32, P(ctypes.c_float)],
         "mx_index_search_boosted": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "mx_index_search_boosted_device": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "mx_filter_set_where": [vp, vp, ctypes.c_float, ctypes.c_float, i32, P(u64)],
+        "mx_filter_set_keys": [vp, vp, vp, u64, i32, P(u64)],
+        "mx_filter_combine": [vp, vp, vp, i32],
+        "mx_filter_invert": [vp],
         "mx_index_search_range": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
         "mx_index_search_mmr": [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp, vp],

@@ -34,6 +34,7 @@
 #include <ctime>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -5212,6 +5213,220 @@ int mx_index_search_boosted_device(mx_index *idx, mx_prior *p, mx_filter *f, con
                                d_dists ? d_dists + o : nullptr, d_priors ? d_priors + o : nullptr, d_combined ? d_combined + o : nullptr,
                                d_nfound + b0, d_complete ? d_complete + b0 : nullptr);
         if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+// ---- filters from row attributes (mx_filter_set_where / set_keys / combine / invert) ---------------------------------
+namespace {
+
+constexpr uint64_t kWhereMaxKeys = 1ull << 20;
+
+// An edit by predicate, under idx->mu.  The predicate kernel (launch(stream, rows, d_sel, d_extra)) runs on the device of the column,
+// the owner's, and leaves a selection bitmap over the handle's GLOBAL rows at the head of the column's staging buffer, which
+// stage(bytes, &ptr) grows; `extra` (extra_bytes of host memory, the sorted keys) is uploaded behind it.  The selection comes to the
+// host, where it is counted and folded into the mirrors, and goes into every shard's words by filter_words_kernel: a plain index reads
+// it where it lies (global rows are its local rows), a shard gets its own rows of it, dealt as filter_edit_ids deals ids (global block
+// b: local block b / G of shard b % G), through its stage.  Every allocation comes first: a call that fails leaves the set as it was.
+using WhereStage = std::function<int(size_t, char **)>;
+using WhereLaunch = std::function<hipError_t(hipStream_t, uint64_t, uint64_t *, const char *)>;
+int filter_edit_selected(mx_filter *f, const void *extra, size_t extra_bytes, const WhereStage &stage, const WhereLaunch &launch, bool allow,
+                         uint64_t *n_selected) {
+    mx_index *idx = f->idx;
+    const size_t G = f->sh.size();
+    const uint64_t rows = rows_of(idx), R = idx->block_rows;
+    const size_t sw = (size_t)((rows + 63) >> 6), sb = sw * sizeof(uint64_t);
+    std::vector<size_t> lw(G);  // the words of shard g that hold its rows
+    for (size_t g = 0; g < G; ++g) {
+        mx_index *t = filter_target(idx, g);
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        DeviceGuard dg(t->device);
+        FilterShard &fs = f->sh[g];
+        if (int rc = ensure_filter_bits(t, fs); rc != MX_OK) return rc;
+        lw[g] = (size_t)((t->n + 63) >> 6);
+        if (lw[g] > fs.words) return fail(MX_EDEVICE, "filter bitmap shorter than the rows");
+        if (idx->composite())
+            if (int rc = ensure_filter_stage(fs, lw[g]); rc != MX_OK) return rc;
+    }
+    if (rows == 0) {
+        if (n_selected) *n_selected = 0;
+        return MX_OK;
+    }
+    std::vector<uint64_t> sel_h(sw);
+    const uint64_t *d_sel = nullptr;
+    {
+        mx_index *t = group_owner(idx);
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        DeviceGuard dg(t->device);
+        char *st = nullptr;
+        if (int rc = stage(sb + extra_bytes, &st); rc != MX_OK) return rc;
+        if (extra_bytes) MX_HIP(hipMemcpyAsync(st + sb, extra, extra_bytes, hipMemcpyHostToDevice, t->stream));
+        MX_HIP(launch(t->stream, rows, reinterpret_cast<uint64_t *>(st), st + sb));
+        MX_HIP(hipMemcpyAsync(sel_h.data(), st, sb, hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipStreamSynchronize(t->stream));
+        d_sel = reinterpret_cast<const uint64_t *>(st);
+    }
+    uint64_t count = 0;
+    for (uint64_t w : sel_h) count += (uint64_t)__builtin_popcountll(w);
+    const int op = allow ? kFilterOr : kFilterAndNot;
+    std::vector<uint64_t> loc;
+    for (size_t g = 0; g < G && count; ++g) {
+        mx_index *t = filter_target(idx, g);
+        FilterShard &fs = f->sh[g];
+        if (lw[g] == 0) continue;
+        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
+        if (t != idx) lk.lock();
+        DeviceGuard dg(t->device);
+        const std::vector<uint64_t> *src = &sel_h;
+        if (idx->composite()) {
+            loc.assign(lw[g], 0);
+            for (uint64_t b = g; b * R < rows; b += G) {
+                const uint64_t n = std::min(R, rows - b * R), lo = (b / G) * R;
+                if (lo + n > (uint64_t)lw[g] * 64) return fail(MX_EDEVICE, "shard %zu holds fewer rows than its blocks", g);
+                copy_bits(loc, lo, sel_h, b * R, n);
+            }
+            MX_HIP(hipMemcpyAsync(fs.stage, loc.data(), lw[g] * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+            src = &loc;
+        }
+        fs.cached = false;
+        fs.list_ok = false;
+        MX_HIP(launch_filter_words(t->stream, fs.bits, fs.bits, idx->composite() ? fs.stage.get() : d_sel, lw[g], op, 0));
+        for (size_t w = 0; w < lw[g]; ++w) fs.bits_h[w] = combine_word(op, fs.bits_h[w], (*src)[w]);
+        MX_HIP(hipStreamSynchronize(t->stream));
+    }
+    if (n_selected) *n_selected = count;
+    return MX_OK;
+}
+
+// the handles of a predicate edit or a combination (under idx->mu, idx the filter's own index)
+int where_ready(mx_filter *f) {
+    if (int rc = usable(f->idx); rc != MX_OK) return rc;
+    return check_filter(f->idx, f);
+}
+
+}  // namespace
+
+int mx_filter_set_where(mx_filter *f, mx_prior *p, float lo, float hi, int allow, uint64_t *n_selected) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    if (!p) return fail(MX_EINVAL, "null prior");
+    if (allow != 0 && allow != 1) return fail(MX_EINVAL, "allow = %d: 1 adds the selected rows to the set, 0 takes them away", allow);
+    if (std::isnan(lo) || std::isnan(hi)) return fail(MX_EINVAL, "a bound is NaN; nothing changed");
+    mx_index *idx = f->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = where_ready(f); rc != MX_OK) return rc;
+    if (int rc = check_prior(idx, p); rc != MX_OK) return rc;
+    return filter_edit_selected(
+        f, nullptr, 0,
+        [&](size_t bytes, char **st) {
+            const int rc = ensure_prior_stage(p, bytes);
+            *st = static_cast<char *>(p->stage.get());
+            return rc;
+        },
+        [&](hipStream_t s, uint64_t rows, uint64_t *sel, const char *) { return launch_where_range(s, p->vals, p->len, rows, lo, hi, sel); },
+        allow == 1, n_selected);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_filter_set_keys(mx_filter *f, mx_grouping *g, const uint32_t *keys, uint64_t n_keys, int allow, uint64_t *n_selected) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    if (allow != 0 && allow != 1) return fail(MX_EINVAL, "allow = %d: 1 adds the selected rows to the set, 0 takes them away", allow);
+    if (!keys && n_keys) return fail(MX_EINVAL, "null keys with n_keys = %llu", (unsigned long long)n_keys);
+    if (n_keys > kWhereMaxKeys)
+        return fail(MX_EUNSUPPORTED, "n_keys = %llu > %llu", (unsigned long long)n_keys, (unsigned long long)kWhereMaxKeys);
+    std::vector<uint32_t> sorted(keys, keys + n_keys);
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    mx_index *idx = f->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = where_ready(f); rc != MX_OK) return rc;
+    if (int rc = check_grouping(idx, g); rc != MX_OK) return rc;
+    if (sorted.empty()) {
+        if (n_selected) *n_selected = 0;
+        return MX_OK;
+    }
+    return filter_edit_selected(
+        f, sorted.data(), sorted.size() * sizeof(uint32_t),
+        [&](size_t bytes, char **st) {
+            const int rc = ensure_group_stage(g, bytes);
+            *st = static_cast<char *>(g->stage.get());
+            return rc;
+        },
+        [&](hipStream_t s, uint64_t rows, uint64_t *sel, const char *extra) {
+            return launch_where_keys(s, g->keys, g->len, rows, reinterpret_cast<const uint32_t *>(extra), (uint32_t)sorted.size(), sel);
+        },
+        allow == 1, n_selected);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_filter_combine(mx_filter *dst, mx_filter *a, mx_filter *b, int op) try {
+    if (!dst || !a || !b) return fail(MX_EINVAL, "null filter");
+    if (op != MX_FILTER_AND && op != MX_FILTER_OR && op != MX_FILTER_ANDNOT && op != MX_FILTER_XOR)
+        return fail(MX_EINVAL, "op = %d is none of MX_FILTER_AND, MX_FILTER_OR, MX_FILTER_ANDNOT, MX_FILTER_XOR", op);
+    mx_index *idx = dst->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = where_ready(dst); rc != MX_OK) return rc;
+    if (int rc = check_filter(idx, a); rc != MX_OK) return rc;
+    if (int rc = check_filter(idx, b); rc != MX_OK) return rc;
+    const size_t G = dst->sh.size();
+    for (size_t g = 0; g < G; ++g) {  // every allocation first: the three bitmaps cover the shard's capacity, missing words are zeros
+        mx_index *t = filter_target(idx, g);
+        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+        if (t != idx) l2.lock();
+        DeviceGuard dg(t->device);
+        for (mx_filter *x : {dst, a, b})
+            if (int rc = ensure_filter_bits(t, x->sh[g]); rc != MX_OK) return rc;
+    }
+    for (size_t g = 0; g < G; ++g) {
+        mx_index *t = filter_target(idx, g);
+        FilterShard &d = dst->sh[g];
+        const FilterShard &x = a->sh[g], &y = b->sh[g];
+        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+        if (t != idx) l2.lock();
+        DeviceGuard dg(t->device);
+        const size_t words = std::min(d.words, std::min(x.words, y.words));  // (equal: the capacity's)
+        d.cached = false;
+        d.list_ok = false;
+        MX_HIP(launch_filter_words(t->stream, d.bits, x.bits, y.bits, words, op, 0));
+        for (size_t w = 0; w < words; ++w) d.bits_h[w] = combine_word(op, x.bits_h[w], y.bits_h[w]);
+        MX_HIP(hipStreamSynchronize(t->stream));
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_filter_invert(mx_filter *f) try {
+    if (!f) return fail(MX_EINVAL, "null filter");
+    mx_index *idx = f->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = where_ready(f); rc != MX_OK) return rc;
+    const size_t G = f->sh.size();
+    for (size_t g = 0; g < G; ++g) {
+        mx_index *t = filter_target(idx, g);
+        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+        if (t != idx) l2.lock();
+        DeviceGuard dg(t->device);
+        if (int rc = ensure_filter_bits(t, f->sh[g]); rc != MX_OK) return rc;
+    }
+    for (size_t g = 0; g < G; ++g) {  // a shard's rows are [0, n) of its own: the complement within the handle's rows, shard by shard
+        mx_index *t = filter_target(idx, g);
+        FilterShard &fs = f->sh[g];
+        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+        if (t != idx) l2.lock();
+        DeviceGuard dg(t->device);
+        const size_t words = std::min(fs.words, (size_t)((t->n + 63) >> 6));
+        fs.cached = false;
+        fs.list_ok = false;
+        MX_HIP(launch_filter_words(t->stream, fs.bits, fs.bits, nullptr, words, kFilterXor, t->n));
+        for (size_t w = 0; w < words; ++w) fs.bits_h[w] ^= rows_below_word(t->n, w);
+        MX_HIP(hipStreamSynchronize(t->stream));
     }
     return MX_OK;
 } catch (...) {

@@ -596,4 +596,19 @@ struct BoostRank {
 };
 hipError_t launch_boost_rank(hipStream_t s, const BoostRank &p);
 
+// filters from row attributes (mx_filter_set_where / set_keys / combine / invert; where_kernels.hip)
+constexpr int kWhereThreads = 256;               // four waves; each wave and step owns one 64-row word of the selection
+constexpr int kWhereMaxBlocks = 2048;            // workgroups of a predicate kernel: they stride over the rows
+constexpr int kFilterAnd = 0, kFilterOr = 1, kFilterAndNot = 2, kFilterXor = 3;  // MX_FILTER_AND ... of the C ABI
+// Range predicate: sel[w], w < (rows + 63) / 64, bit r & 63 of word r >> 6 = lo <= v_r && v_r <= hi (IEEE f32) for the GLOBAL row
+// r < rows, v_r = vals[r] below len and 0 from there on.  Bits at or past `rows` are 0.  sel holds (rows + 63) / 64 words.
+hipError_t launch_where_range(hipStream_t s, const float *vals, uint64_t len, uint64_t rows, float lo, float hi, uint64_t *sel);
+// Key predicate: the same with "the key of row r (keys[r] below len, 0 from there on) is in sorted[0, n_sorted)", a device array in
+// ascending order without repeats, n_sorted >= 1.
+hipError_t launch_where_keys(hipStream_t s, const uint32_t *keys, uint64_t len, uint64_t rows, const uint32_t *sorted, uint32_t n_sorted,
+                             uint64_t *sel);
+// dst[w] = a[w] OP b[w] for w < words, OP one of kFilterAnd ... kFilterXor (kFilterAndNot: a & ~b); b null: b is the pattern that has
+// one bit for every row below `size`.  One thread per word, no atomics; dst may be a or b, a may be b.
+hipError_t launch_filter_words(hipStream_t s, uint64_t *dst, const uint64_t *a, const uint64_t *b, uint64_t words, int op, uint64_t size);
+
 }  // namespace mx

@@ -43,4 +43,33 @@ inline void append_runs(const std::vector<uint64_t> &bits, uint64_t lo, uint64_t
     }
 }
 
+// the n <= 64 bits of src from bit position s on, as the low bits of a word (s + n <= 64 * src.size())
+inline uint64_t get_bits(const std::vector<uint64_t> &src, uint64_t s, unsigned n) {
+    if (n == 0) return 0;
+    const unsigned o = (unsigned)(s & 63);
+    uint64_t v = src[s >> 6] >> o;
+    if (o + n > 64) v |= src[(s >> 6) + 1] << (64 - o);  // (o > 0 here)
+    return n == 64 ? v : v & ((1ull << n) - 1ull);
+}
+
+// the bits src[s, s + n) replace dst[d, d + n), at any two alignments (a selection over global rows dealt to a shard's local rows)
+inline void copy_bits(std::vector<uint64_t> &dst, uint64_t d, const std::vector<uint64_t> &src, uint64_t s, uint64_t n) {
+    while (n) {
+        const unsigned o = (unsigned)(d & 63), take = (unsigned)std::min<uint64_t>(64 - o, n);
+        const uint64_t m = (take == 64 ? ~0ull : (1ull << take) - 1ull) << o;
+        dst[d >> 6] = (dst[d >> 6] & ~m) | (get_bits(src, s, take) << o);
+        d += take;
+        s += take;
+        n -= take;
+    }
+}
+
+// word w of the set "every row below size"
+inline uint64_t rows_below_word(uint64_t size, uint64_t w) {
+    return size >= (w + 1) * 64 ? ~0ull : size <= w * 64 ? 0ull : (1ull << (size - w * 64)) - 1ull;
+}
+
+// one word of mx_filter_combine: op 0 AND, 1 OR, 2 ANDNOT (x and not y), 3 XOR -- what filter_words_kernel computes
+inline uint64_t combine_word(int op, uint64_t x, uint64_t y) { return op == 0 ? x & y : op == 1 ? x | y : op == 2 ? x & ~y : x ^ y; }
+
 }  // namespace mx

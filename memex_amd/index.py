@@ -260,6 +260,23 @@ class FlatIndex:
             raise
         return f
 
+    _FILTER_OPS = {"and": _lib.MX_FILTER_AND, "or": _lib.MX_FILTER_OR, "andnot": _lib.MX_FILTER_ANDNOT, "xor": _lib.MX_FILTER_XOR}
+
+    def combine_filters(self, a: "IndexFilter", b: "IndexFilter", op, out: "IndexFilter | None" = None) -> "IndexFilter":
+        """``out = a op b`` over the rows, on the device (``mx_filter_combine``): ``op`` is "and", "or", "andnot" (``a`` and not
+        ``b``), "xor" or the ``MX_FILTER_*`` number.  ``out`` may be ``a`` or ``b``; None makes a new filter.  -> ``out``."""
+        code = self._FILTER_OPS.get(op, op) if isinstance(op, str) else op
+        if isinstance(code, str):
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"unknown filter op {op!r}: and, or, andnot, xor")
+        dst = out if out is not None else IndexFilter(self)
+        try:
+            check(lib().mx_filter_combine(dst._h, a._h, b._h, int(code)))
+        except Exception:
+            if out is None:
+                dst.close()
+            raise
+        return dst
+
     def search_with(self, flt: "IndexFilter", queries, k: int):
         """``search`` restricted to the rows of a resident filter: what ``search_filtered(queries, k, ranges=flt.ranges())``
         returns, bit for bit, without the per-call set-up."""
@@ -822,6 +839,7 @@ class IndexFilter:
         h = ctypes.c_void_p()
         check(lib().mx_filter_create(index._h, ctypes.byref(h)))
         self._h = h
+        self._index = index
 
     def _edit(self, ranges, ids, allow: int) -> None:
         if ranges is None and ids is None:
@@ -842,6 +860,52 @@ class IndexFilter:
     def deny(self, ranges=None, ids=None) -> None:
         """Take ids away from the set."""
         self._edit(ranges, ids, 0)
+
+    def _where(self, prior: "IndexPrior", lo, hi, allow: int) -> int:
+        n = ctypes.c_uint64(0)
+        check(lib().mx_filter_set_where(self._h, prior._h, float(lo), float(hi), allow, ctypes.byref(n)))
+        return int(n.value)
+
+    def allow_where(self, prior: "IndexPrior", lo: float = -np.inf, hi: float = np.inf) -> int:
+        """Add the rows whose value in ``prior`` lies in ``[lo, hi]`` (IEEE f32 compares; rows the prior does not reach read 0)
+        -- decided on the device, no ids pass through the host (``mx_filter_set_where``).  -> rows selected."""
+        return self._where(prior, lo, hi, 1)
+
+    def deny_where(self, prior: "IndexPrior", lo: float = -np.inf, hi: float = np.inf) -> int:
+        """Take the rows whose value in ``prior`` lies in ``[lo, hi]`` away from the set.  -> rows selected."""
+        return self._where(prior, lo, hi, 0)
+
+    def _keys(self, grouping: "IndexGrouping", keys, allow: int) -> int:
+        k = keys if isinstance(keys, np.ndarray) else np.fromiter(keys, dtype=np.uint32)
+        k = np.ascontiguousarray(k.astype(np.uint32, copy=False).reshape(-1))
+        n = ctypes.c_uint64(0)
+        check(lib().mx_filter_set_keys(self._h, grouping._h, _ptr(k) if k.size else None, k.size, allow, ctypes.byref(n)))
+        return int(n.value)
+
+    def allow_keys(self, grouping: "IndexGrouping", keys) -> int:
+        """Add the rows whose key in ``grouping`` is one of ``keys`` (any order, repeats allowed, at most 2^20; key 0 names the
+        ungrouped rows) -- ``mx_filter_set_keys``.  -> rows selected."""
+        return self._keys(grouping, keys, 1)
+
+    def deny_keys(self, grouping: "IndexGrouping", keys) -> int:
+        """Take the rows whose key in ``grouping`` is one of ``keys`` away from the set.  -> rows selected."""
+        return self._keys(grouping, keys, 0)
+
+    def invert(self) -> None:
+        """Replace the set by its complement within the rows the index holds at this moment (``mx_filter_invert``)."""
+        check(lib().mx_filter_invert(self._h))
+
+    def __and__(self, other: "IndexFilter") -> "IndexFilter":
+        return self._index.combine_filters(self, other, "and")
+
+    def __or__(self, other: "IndexFilter") -> "IndexFilter":
+        return self._index.combine_filters(self, other, "or")
+
+    def __sub__(self, other: "IndexFilter") -> "IndexFilter":
+        return self._index.combine_filters(self, other, "andnot")
+
+    def __xor__(self, other: "IndexFilter") -> "IndexFilter":
+        return self._index.combine_filters(self, other, "xor")
 
     def count(self):
         """-> (rows in the set, those of them that are not removed)."""

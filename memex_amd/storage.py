@@ -187,6 +187,46 @@ class StoreFilter:
         """Take every row inserted under the given ``_id`` strings out of the set."""
         self._edit(ids, False)
 
+    def _where(self, prior: "StorePrior", lo, hi, allow: bool) -> int:
+        try:
+            return (self._flt.allow_where if allow else self._flt.deny_where)(prior._pri, lo, hi)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+
+    def allow_where(self, prior: "StorePrior", lo: float = -np.inf, hi: float = np.inf) -> int:
+        """Add every row whose value in ``prior`` lies in ``[lo, hi]`` (``IndexFilter.allow_where``): the device decides, the host
+        needs no copy of the values.  Rows nobody set read 0.  -> rows selected."""
+        return self._where(prior, lo, hi, True)
+
+    def deny_where(self, prior: "StorePrior", lo: float = -np.inf, hi: float = np.inf) -> int:
+        """Take every row whose value in ``prior`` lies in ``[lo, hi]`` out of the set.  -> rows selected."""
+        return self._where(prior, lo, hi, False)
+
+    def _documents(self, grouping: "StoreGrouping", documents, allow: bool) -> int:
+        names = [documents] if isinstance(documents, str) else [str(d) for d in documents]
+        with self._store._lock:  # a lookup only: an unknown name selects nothing and no key is handed out for it
+            keys = [grouping._key_of[n] for n in dict.fromkeys(names) if n in grouping._key_of]
+        try:
+            return (self._flt.allow_keys if allow else self._flt.deny_keys)(grouping._grp, np.asarray(keys, dtype=np.uint32))
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+
+    def allow_documents(self, grouping: "StoreGrouping", documents) -> int:
+        """Add every segment ``grouping`` holds under one of the document names (``IndexFilter.allow_keys``): the host names
+        documents, not their segments.  Unknown names add nothing.  -> rows selected."""
+        return self._documents(grouping, documents, True)
+
+    def deny_documents(self, grouping: "StoreGrouping", documents) -> int:
+        """Take every segment ``grouping`` holds under one of the document names out of the set.  -> rows selected."""
+        return self._documents(grouping, documents, False)
+
+    def invert(self) -> None:
+        """Replace the set by its complement within the rows the store holds at this moment (``IndexFilter.invert``)."""
+        try:
+            self._flt.invert()
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+
     def count(self):
         """-> (rows in the set, those of them that are not removed)."""
         try:
@@ -626,6 +666,19 @@ class HipFlatStore(VectorStore):
             except _lib.MemexHipError as e:
                 _raise_from(e, SearchError)
         return flt
+
+    def combine_filters(self, a: "StoreFilter", b: "StoreFilter", op, out: "StoreFilter | None" = None) -> "StoreFilter":
+        """``out = a op b`` over the rows (``FlatIndex.combine_filters``): ``op`` is "and", "or", "andnot" (``a`` and not ``b``) or
+        "xor".  ``out`` may be ``a`` or ``b``; None makes a new filter.  -> ``out``."""
+        with self._lock:
+            idx = self._index
+        if idx is None:
+            raise SearchError("a filter needs a store with rows: insert first")
+        try:
+            res = idx.combine_filters(a._flt, b._flt, op, out._flt if out is not None else None)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        return out if out is not None else StoreFilter(self, res)
 
     def search_in(self, vec: Sequence[float], limit: int, flt: "StoreFilter") -> List[VectorSearchResult]:
         """``search`` restricted to the rows of a resident filter (``FlatIndex.search_with``), as ``(_id, score)`` pairs."""

@@ -130,13 +130,19 @@ def stamp_document(prior, vectors: Sequence[VectorData], t: float, half_life: fl
     prior ``exp2((t - t0) / half_life)`` (``StorePrior.set_document``).  Call it after the vectors were added.  The value is an f32:
     it overflows about 127 half-lives after ``t0`` (``ValueError``), and a query's folded weight underflows about as far out, so
     after roughly 120 half-lives ``t0`` must be moved and the values written again."""
+    value = _stamp_value(t, half_life, t0)
+    ids = [v._id for v in vectors]
+    if ids:
+        prior.set_document(ids, value)
+
+
+def _stamp_value(t: float, half_life: float, t0: float) -> float:
+    """The f32 prior of a segment written at ``t``: ``exp2((t - t0) / half_life)``; ``ValueError`` when it overflows."""
     with np.errstate(over="ignore"):
         value = float(np.float32(np.exp2((np.float64(t) - np.float64(t0)) / np.float64(half_life))))
     if not np.isfinite(value):
         raise ValueError("t is too far from t0 for an f32 prior: move t0 and stamp the documents again")
-    ids = [v._id for v in vectors]
-    if ids:
-        prior.set_document(ids, value)
+    return value
 
 
 def recency_weight(weight: float, now: float, half_life: float, t0: float) -> float:
@@ -155,6 +161,23 @@ def search_docs_recent(client, embedder, prior, query: str, limit: int = 10, now
     if res is None:
         raise ValueError("Invalid query")
     return client.search_boosted(res.vector, limit, prior, recency_weight(weight, now, half_life, t0))
+
+
+def search_docs_since(client, embedder, prior, flt, query: str, limit: int = 10, t_min: float = 0.0, half_life: float = 1.0,
+                      t0: float = 0.0, now: float = 0.0, weight: float = 0.0):
+    """``search_docs`` over the segments stamped at or after ``t_min`` only: ``flt.allow_where(prior, lo=v)`` with ``v`` the value
+    :func:`stamp_document` stores for ``t_min`` -- the device picks the rows out of the prior, no id list is built on the host -- then
+    ``encode_single(query)`` -> ``client.search_boosted(vector, limit, prior, recency_weight(weight, now, half_life, t0), None, flt)``
+    -> ``(hits, complete)`` as :func:`search_docs_recent`.  ``flt`` is a filter of the store (``HipFlatStore.make_filter()``), empty
+    or already allowing other rows: the recent segments are added to it, and it can serve later queries with the same ``t_min``
+    through ``search_boosted`` directly.  The stored values rise with ``t`` and f32 rounding keeps the order, so a segment stamped at
+    ``t >= t_min`` is in the set; segments nobody stamped read 0 and are not.  ``weight = 0`` (the default) ranks by relevance alone.
+    ``ValueError("Invalid query")`` where ``search_docs`` raises it."""
+    res = embedder.encode_single(query)
+    if res is None:
+        raise ValueError("Invalid query")
+    flt.allow_where(prior, lo=_stamp_value(t_min, half_life, t0))
+    return client.search_boosted(res.vector, limit, prior, recency_weight(weight, now, half_life, t0), None, flt)
 
 
 def rerank_docs(client, embedder, query: str, candidates: Sequence[str], limit: int = 10) -> List[Tuple[str, float]]:
