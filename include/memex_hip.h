@@ -730,9 +730,9 @@ enum { MX_POOL_MEAN = 0, MX_POOL_CLS = 1 };
 
 typedef struct mx_encoder_cfg {
     int32_t layers;     /* 6  (all-MiniLM-L6-v2) / 12 (all-MiniLM-L12-v2, bge-base-en)      */
-    int32_t hidden;     /* 384 / 768; multiple of 64                                         */
-    int32_t heads;      /* 12; hidden/heads must be 32 or 64                                 */
-    int32_t ffn;        /* 1536 / 3072; multiple of 64                                       */
+    int32_t hidden;     /* 384 / 768: nothing else (see "What mx_encoder_create accepts" below) */
+    int32_t heads;      /* 12; hidden/heads must be 32 or 64: 12 or 6 heads at 384, 24 or 12 at 768 */
+    int32_t ffn;        /* 1536 / 3072; any multiple of 384                                  */
     int32_t vocab;      /* 30522                                                              */
     int32_t max_pos;    /* rows of the position table: 512 (BERT) / 514 (RoBERTa); sequences <= 512 tokens */
     int32_t type_vocab; /* 2                                                                  */
@@ -780,6 +780,26 @@ size_t mx_encoder_cfg_size(void);
  */
 size_t mx_encoder_weight_bytes(const mx_encoder_cfg *cfg);
 
+/*
+ * What mx_encoder_create accepts -- and whatever it accepts encodes every batch of B >= 1 sequences of
+ * 1 <= S <= min(512, max_pos - pos_offset) tokens, in every precision mode (tests/test_encoder_lattice_gpu.py):
+ *   layers    1 ... 48                                              else MX_EUNSUPPORTED
+ *   hidden    384 or 768                                            else MX_EUNSUPPORTED
+ *   heads     must divide hidden                                    else MX_EINVAL
+ *             hidden / heads = 32 or 64: 12 or 6 heads at hidden 384, 24 or 12 at hidden 768   else MX_EUNSUPPORTED
+ *             (24 heads are as good as 12: the attention work list is sized by the head count of the configuration)
+ *   ffn       any multiple of 384, no upper limit                   else MX_EUNSUPPORTED
+ *   vocab, type_vocab >= 1; 1 <= max_pos <= 8192; 0 <= pos_offset < max_pos; ln_eps >= 0; pooling and precision one of
+ *   their enumerators                                               else MX_EINVAL
+ * Every accepted shape computes the same function; the ffn width decides which kernels do (MX_PREC_BF16 only):
+ *   hidden 384, ffn <= 1536 (384, 768, 1152, 1536)   the layer tail as ONE kernel (out-projection, Add&Norm, MLP, Add&Norm) and,
+ *                                                    in passes of <= 2048 packed rows, the small-pass kernels (query latency)
+ *   hidden 384, ffn > 1536                           neither: GEMM by GEMM at every pass size
+ *   hidden 768                                       GEMM by GEMM; passes of <= 4096 packed rows split the two Add&Norm GEMMs
+ *                                                    over k, W2 into min(8, ffn / 384) chunks where those are whole k-tiles of 32
+ *   passes of >= 32768 packed rows                   the 256 x 256-tile GEMM where N is a multiple of 256 (f32 outputs of the
+ *                                                    split-operand modes: also a last half tile), the 64-row GEMM otherwise
+ */
 /* Replaces SentenceEmbeddingsBuilder::remote(..).create_model() (embedding.rs:99-100). */
 int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nbytes, int device,
                       mx_encoder **out);

@@ -101,7 +101,7 @@ struct mx_encoder : RowWorkspace {
     int small_rows = kSmallRows;  // passes of at most this many packed rows take the small-pass layer (MEMEX_HIP_DEBUG small_rows=N)
     Pin<char> h_io;           // pinned, device-mapped page of a query-sized host call: ids | lens | embeddings (mx_encoder_encode)
     Dev<int32_t> cu, lens_dev, ids_dev;
-    Dev<void> attn_plan;  // attention work list of the pass in flight (kAttnPlanBytesPerSeq per sequence)
+    Dev<void> attn_plan;  // attention work list of the pass in flight (attention_plan_bytes(heads) per sequence)
     Dev<float> out_dev;
     bool profiling = false;
     bool fused_tail = false;  // layer tail as one kernel (hidden 384); MEMEX_HIP_DEBUG unfused_tail=1 keeps the three GEMMs
@@ -233,7 +233,7 @@ int ensure_ws(mx_encoder *e, int rows, int seqs, int n_ids) {
         MX_HIP(e->cu.alloc((size_t)seqs + 1));
         MX_HIP(e->lens_dev.alloc((size_t)seqs));
         MX_HIP(e->out_dev.alloc((size_t)seqs * H));
-        MX_HIP(e->attn_plan.alloc_bytes((size_t)seqs * kAttnPlanBytesPerSeq));
+        MX_HIP(e->attn_plan.alloc_bytes((size_t)seqs * attention_plan_bytes(e->cfg.heads)));
         e->ws_seqs = seqs;
     }
     if (n_ids > e->ws_ids) {
@@ -285,7 +285,6 @@ int encode_pass(mx_encoder *e, const int32_t *d_ids, const int32_t *h_lens, cons
     int rc = ensure_ws(e, t_pad, B, 0);
     if (rc != MX_OK) return rc;
     hipStream_t st = e->stream;
-    if ((size_t)attention_groups(heads, dh, max_len, B) * 16 > kAttnPlanBytesPerSeq) return fail(MX_EINVAL, "more than 16 head groups per sequence");
     MX_HIP(launch_token_map(st, d_lens, B, S, e->cu, e->tok_seq, e->tok_pos, t_pad, heads, dh, max_len, e->attn_plan));
     if (e->precise) {
         // MX_PREC_BF16X3 (encoder_precise.hip): split operands through the unchanged GEMM loops with k tripled (pgemm_kernel for

@@ -122,9 +122,10 @@ hipError_t launch_embed_ln(hipStream_t s, const int32_t *ids, int S, const int32
                            const float *gamma, const float *beta, float eps, int vocab, bf16_t *x);
 
 // softmax(q k^T + mask) v per (sequence, head); q is pre-scaled by 1/sqrt(d)*log2(e)
-// `plan`: kAttnPlanBytesPerSeq bytes per sequence, written by launch_token_map once per pass (the work list: one
-// item per (sequence, head group), longest sequences first) and read by every layer's launch_attention
-constexpr size_t kAttnPlanBytesPerSeq = 16 * 16;
+// `plan`: attention_plan_bytes(heads) bytes per sequence, written by launch_token_map once per pass (the work list: one
+// 16-byte item per (sequence, head group), longest sequences first) and read by every layer's launch_attention.  A pass has
+// at most `heads` groups per sequence (attention_groups: heads, or heads / 2 in the paired form), whatever its lengths.
+constexpr size_t attention_plan_bytes(int heads) { return (size_t)heads * 16; }
 int attention_groups(int heads, int d_head, int max_len, int B);
 hipError_t launch_attention(hipStream_t s, const bf16_t *q, const bf16_t *k, const bf16_t *vt, int ldvt, const void *plan, int B,
                             int heads, int d_head, int hidden, int max_len, bf16_t *ctx);

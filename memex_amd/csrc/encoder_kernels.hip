@@ -509,6 +509,7 @@ hipError_t launch_gemm(hipStream_t s, int epi, const GemmParams &p) {
 struct AttnItem {
     int32_t tok0, len, group, pad;
 };
+static_assert(sizeof(AttnItem) * 2 == attention_plan_bytes(2), "the plan is allocated in items of this size (encoder.hip)");
 
 __global__ __launch_bounds__(1024) void token_map_kernel(const int32_t *__restrict__ lens, int B, int S, int32_t *cu,
                                                          int32_t *tok_seq, int32_t *tok_pos, int t_pad, int groups,

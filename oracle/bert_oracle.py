@@ -60,6 +60,8 @@ DEVIATIONS = {
     "swap_v_heads": "(layer, h0, h1): the value projections of two heads change places",
     "drop_ln": "'gain' | 'bias': the last Add&Norm of the last layer applies no gain / no bias",
     "pool_div": "'S': mean pooling divides by the padded width S, not by the length (visible with normalize=False only)",
+    "ffn_tail": "n: in the last layer the last n intermediate features add nothing to the MLP output (a final chunk dropped)",
+    "head_last": "n: in the last layer the context of the last n heads is zero (a head group never scheduled)",
 }
 _BIAS_NAMES = {"query": "attention.self.query", "value": "attention.self.value", "attn_out": "attention.output.dense",
                "intermediate": "intermediate.dense", "mlp_out": "output.dense"}
@@ -100,6 +102,8 @@ def encode(weights: dict, cfg: dict, ids: np.ndarray, lens: np.ndarray, dtype=np
     gelu = gelu_tanh if dev.get("gelu") == "tanh" else gelu_erf
     if dev.get("gelu", "tanh") != "tanh" or dev.get("drop_ln", "gain") not in ("gain", "bias") or dev.get("pool_div", "S") != "S":
         raise ValueError(f"unknown value in {dev}")
+    if dev.get("ffn_tail", 1) < 1 or not 1 <= dev.get("head_last", 1) <= nh:
+        raise ValueError(f"unknown value in {dev}")
 
     x = (W["embeddings.word_embeddings.weight"][ids]
          + W["embeddings.position_embeddings.weight"][None, pos0:pos0 + S]
@@ -135,10 +139,14 @@ def encode(weights: dict, cfg: dict, ids: np.ndarray, lens: np.ndarray, dtype=np
         pr = np.exp(s)
         pr = pr / pr.sum(axis=-1, keepdims=True)
         ctx = (pr @ v).transpose(0, 2, 1, 3).reshape(B, S, H)
+        if "head_last" in dev and l == L - 1:
+            ctx[..., H - dev["head_last"] * dh:] = 0.0
         a = lin(ctx, "attention.output.dense")
         x = layer_norm(a + x, W[p + "attention.output.LayerNorm.weight"],
                        W[p + "attention.output.LayerNorm.bias"], eps)
         h = gelu(lin(x, "intermediate.dense"))
+        if "ffn_tail" in dev and l == L - 1:
+            h[..., h.shape[-1] - dev["ffn_tail"]:] = 0.0
         o = lin(h, "output.dense")
         g2, b2 = W[p + "output.LayerNorm.weight"], W[p + "output.LayerNorm.bias"]
         if "drop_ln" in dev and l == L - 1:

@@ -40,6 +40,8 @@ DEVIATIONS = {
     "ln_gain":    (dict(drop_ln="gain"), ("mlp",)),
     "ln_bias":    (dict(drop_ln="bias"), ("mlp",)),
     "pool_div":   (dict(pool_div="S"), ("pooling",)),
+    "ffn_tail":   (dict(ffn_tail=128), ("mlp",)),            # the last 128-feature chunk of the last layer's MLP dropped
+    "head_last":  (dict(head_last=1), ("attention",)),       # the last head of the last layer never scheduled
 }
 SUBTLE = ("eps", "gelu", "scale")     # at most these may stay unseen on routes with bf16 operands
 FAMILIES = ("embed_ln", "qkv", "attention", "out_ln", "mlp", "pooling")
@@ -56,6 +58,7 @@ class Case:
     held: int = 0                  # > 0: only the first `held` sequences are held to the oracle (large passes); they are ragged
     claims: tuple = ()             # ((precision, (deviation, ...)), ...): what test_encoder_bars_model.py proves separable
     routes: tuple = ()             # ((precision, (route, ...)), ...): see test_encoder_bars_gpu.ROUTES
+    lens: tuple = ()               # the lengths themselves instead of drawn ones (tests/test_encoder_lattice_gpu.py)
 
     def cfg(self, precision="bf16"):
         return EncoderConfig(**dict(self.kw), precision=precision)
@@ -97,7 +100,13 @@ def inputs(case):
     token exists), the first one longer than one token; large passes fill up with full-length rows behind them."""
     cfg = case.cfg()
     rng = np.random.default_rng(case.seed)
-    ids = rng.integers(1000, cfg.vocab, size=(case.B, case.S)).astype(np.int32)
+    ids = rng.integers(1000 if cfg.vocab > 1000 else 0, cfg.vocab, size=(case.B, case.S)).astype(np.int32)
+    if case.lens:
+        lens = np.asarray(case.lens, dtype=np.int32)
+        assert lens.shape == (case.B,) and not case.held
+        ids.setflags(write=False)
+        lens.setflags(write=False)
+        return ids, lens
     n = case.held or case.B
     lens = np.full(case.B, case.S, dtype=np.int32)
     lens[:n] = rng.integers(max(2, case.S // 3), case.S, size=n)
@@ -280,6 +289,65 @@ CASES = (
          routes=_routes(bf16=("default", "pgemm=0"), bf16x3=("default",))),
 )
 
+# ---- the shape axis: every kind of ffn width and head count that mx_encoder_create accepts and the cases above do not reach.
+# Each claims ffn_tail and head_last (the mistakes a chunk count or a head-group count invites) on every precision it routes,
+# and the members of _COARSE and _BIASES that reach the 1.5 ratio there.
+_SHAPE = ("ffn_tail", "head_last")
+
+
+def _m384(ffn, heads=12):
+    return _kw(layers=2, hidden=384, heads=heads, ffn=ffn, vocab=3000)
+
+
+def _b768(ffn, heads=12):
+    return _kw(layers=2, hidden=768, heads=heads, ffn=ffn, vocab=3000)
+
+
+_BIG = ("default", "pgemm=0")
+_ALL = _SHAPE + _COARSE + _BIASES
+
+
+def _all(*precisions, bf16_not=()):
+    """_SHAPE, _COARSE and _BIASES on bf16 and the named further precisions; `bf16_not`: the members below the 1.5 ratio on bf16
+    (tests/ENCODER_BARS.md has every ratio; on the other precisions the smallest ratio of these cases is 138)"""
+    return _claims(tuple(n for n in _ALL if n not in bf16_not), **{p: _ALL for p in precisions})
+
+
+SHAPE_CASES = (
+    # hidden 384, the fused tail and the small-pass MLP at odd chunk counts: 3 and 9 chunks of 128 ffn features
+    Case("m384_f384_s33", _m384(384), 5, 33, 31, claims=_all("bf16x3", "mixed", "mixed1"),
+         routes=_routes(bf16=("default", "small=0", "unfused_tail"), bf16x3=("default",), mixed=("default",), mixed1=("default",))),
+    Case("m384_f1152_s33", _m384(1152), 5, 33, 32, claims=_all("bf16x3", "mixed", "mixed1", bf16_not=("bias_int",)),
+         routes=_routes(bf16=("default", "small=0", "unfused_tail"), bf16x3=("default",), mixed=("default",), mixed1=("default",))),
+    # hidden 384 past the fused tail (ffn > 1536): gemm_kernel serves the small pass; 1920 = 7 x 256 + 128
+    Case("m384_f1920_s33", _m384(1920), 5, 33, 33, claims=_all("bf16x3", "mixed", "mixed1"),
+         routes=_routes(bf16=("default", "attn_safe=1"), bf16x3=("default",), mixed=("default",), mixed1=("default",))),
+    Case("m384_f3072_s33", _m384(3072), 5, 33, 34, claims=_all("bf16x3"), routes=_routes(bf16=("default",), bf16x3=("default",))),
+    # head dim 64 at hidden 384 on the staged attention kernel with two stages of keys
+    Case("m384_d64_s300", _m384(1536, heads=6), 4, 300, 35, claims=_all("bf16x3"),
+         routes=_routes(bf16=("default", "small=0", "attn_safe=1"), bf16x3=_RX3)),
+    # hidden 768, split-k over ns_2 = min(8, ffn / 384) chunks: 1 (W2 not split, the out-projection is), 3, 5, 8 chunks that do
+    # not divide into k-tiles (3456 / 8 = 432: the fused GEMM instead), 8 chunks of 480 columns
+    Case("b768_f384_s33", _b768(384), 5, 33, 36, claims=_all("bf16x3", bf16_not=("bias_int",)), routes=_routes(bf16=("default", "splitk=0"), bf16x3=("default",))),
+    Case("b768_f1152_s33", _b768(1152), 5, 33, 37, claims=_all("bf16x3", "mixed", bf16_not=("bias_int",)),
+         routes=_routes(bf16=("default", "splitk=0"), bf16x3=("default",), mixed=("default",))),
+    Case("b768_f1920_s33", _b768(1920), 5, 33, 38, claims=_all("mixed1", bf16_not=("bias_int",)), routes=_routes(bf16=("default", "splitk=0"), mixed1=("default",))),
+    Case("b768_f3456_s33", _b768(3456), 5, 33, 39, claims=_all("bf16x3"), routes=_routes(bf16=("default", "splitk=0"), bf16x3=("default",))),
+    Case("b768_f3840_s33", _b768(3840), 5, 33, 40, claims=_all(), routes=_routes(bf16=("default", "splitk=0"))),
+    # hidden 768 with 24 heads of 32: 24 head groups per sequence in the short and the one-head form, 12 in the paired one
+    Case("b768_h24_s33", _b768(3072, heads=24), 5, 33, 41, claims=_all("bf16x3"),
+         routes=_routes(bf16=("default", "attn_short=0", "attn_safe=1"), bf16x3=_RX3)),
+    Case("b768_h24_s130", _b768(3072, heads=24), 6, 130, 42, claims=_all("bf16x3"),
+         routes=_routes(bf16=("default", "attn_pair=1", "attn_pair=0"), bf16x3=("default",))),
+    Case("b768_h24_s300", _b768(3072, heads=24), 4, 300, 43, claims=_all("mixed", bf16_not=("keys_extra",)), routes=_routes(bf16=("default",), mixed=("default",))),
+    # large passes: N = 1152 / 1920 end in a half tile of pgemm_kernel (the f32 epilogues take it, the bf16 W1 goes to gemm_kernel)
+    Case("big384_f1152_s130", _m384(1152), 244, 130, 44, held=4, claims=_all("bf16x3", "mixed"),
+         routes=_routes(bf16=_BIG + ("unfused_tail",), bf16x3=_BIG, mixed=_BIG)),
+    Case("big384_f1920_s130", _m384(1920), 244, 130, 45, held=4, claims=_all("bf16x3", "mixed1"), routes=_routes(bf16=_BIG, bf16x3=_BIG, mixed1=_BIG)),
+    Case("big768_h24_s130", _b768(3072, heads=24), 244, 130, 46, held=4, claims=_all("bf16x3"), routes=_routes(bf16=_BIG, bf16x3=("default",))),
+)
+CASES = CASES + SHAPE_CASES
+
 # The pairs no case claims, with the reason (tests/ENCODER_BARS.md repeats them).  The cap of the issue: at most eps, gelu and
 # the 1 % scale, and only on routes with a bf16 operand -- the mixed modes keep P as one bf16 value and their MLP operands as
 # one fp16 value (11 bits), so the GELU variant stays below their floor as well.
@@ -319,7 +387,9 @@ def relation(case, precision, route):
     if route == "default":
         return None
     if route == "held_alone":
-        return ("default", "differs")       # bf16 only: small-pass kernels / split-k against the large pass's
+        # bf16 only: small-pass kernels / split-k against the large pass's.  Hidden 384 past the fused tail (ffn > 1536) has no
+        # small-pass kernels: gemm_kernel at every pass size, and pgemm_kernel's Q / K of the large pass carry gemm_kernel's bits
+        return ("default", "differs" if cfg.hidden == 768 or cfg.ffn <= 1536 else "same")
     if route == "small=0":
         return ("default", "differs")
     if route == "unfused_tail":

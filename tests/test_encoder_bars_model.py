@@ -129,6 +129,28 @@ def test_every_family_is_covered_on_every_precision():
             assert bool(case.routed(precision)) == bool(case.claimed(precision)), (case.name, precision)
 
 
+def test_shape_cases_claim_the_shape_deviations():
+    """every case of the shape axis claims a dropped last ffn chunk and an unscheduled last head on every precision it routes
+    (test_bar_separates_every_claimed_deviation then proves the 2 x), and follows the file's rule for the rest: the members of
+    _COARSE and _BIASES with a ratio of at least 1.5 are claimed, the others are not"""
+    assert len(C.SHAPE_CASES) == 16 and set(C.SHAPE_CASES) <= set(C.CASES)
+    for case in C.SHAPE_CASES:
+        assert dict(case.kw)["layers"] == 2 and dict(case.kw)["vocab"] == 3000
+        ids, lens = C.inputs(case)
+        assert lens[:case.held or case.B].min() < case.S, "ragged"
+        for precision in C.PRECISIONS:
+            if not case.routed(precision):
+                continue
+            claimed = set(case.claimed(precision))
+            assert {"ffn_tail", "head_last"} <= claimed, (case.name, precision)
+            b = C.bar(case, precision)
+            for name in C._COARSE + C._BIASES:
+                ratio = C.distance(case, name) / 2 / b            # (another BLAS moves a floor in its second digit: 20 % either way)
+                assert ratio >= 1.5 / 1.2 if name in claimed else ratio < 1.5 * 1.2, (case.name, precision, name, ratio)
+    for name in ("ffn_tail", "head_last"):
+        assert C.deviation(C.SHAPE_CASES[0], name) == {name: 128 if name == "ffn_tail" else 1}
+
+
 def test_rounding_functions():
     x = np.float32([1.0, 1.00390625, 1.0 + 2.0 ** -9, 3.14159274, -2.71828175, 65504.0, 1e-3])
     np.testing.assert_array_equal(M.bf(x)[:2], np.float32([1.0, 1.0]))           # 1 + 2^-8 is a tie: to even

@@ -49,6 +49,51 @@ def test_padding_is_ignored_and_mask_semantics():
     assert np.abs(a[1] - c[0]).max() < 1e-6
 
 
+def test_shape_deviations_move_the_output_and_the_default_does_not():
+    """deviate=ffn_tail / head_last: the last 128 intermediate features / the last head's context of the LAST layer count for
+    nothing.  Each moves the output, each is what its words say (stated here a second way, through the weights), neither
+    touches an earlier layer, and without a deviation the oracle returns the bits it returned before it knew them."""
+    from memex_amd.weights import EncoderConfig, synthetic_weights
+    from oracle import bert_oracle
+    for name, cfg, w, ids, lens, gold in golden_cases():                      # the default: the committed vectors, and one call = another
+        a = bert_oracle.encode(w, cfg.as_dict(), ids, lens)
+        assert np.abs(a - gold).max() < 1e-9, name
+    cfg = EncoderConfig(layers=2, hidden=384, heads=12, ffn=384, vocab=300)
+    w = synthetic_weights(cfg, 4)
+    rng = np.random.default_rng(4)
+    ids = rng.integers(5, 300, size=(3, 20)).astype(np.int32)
+    lens = np.array([20, 7, 1], dtype=np.int32)
+    enc = lambda w_, **dev: bert_oracle.encode(w_, cfg.as_dict(), ids, lens, deviate=dev or None)
+    base = enc(w)
+    np.testing.assert_array_equal(base, bert_oracle.encode(w, cfg.as_dict(), ids, lens))
+    np.testing.assert_array_equal(base, bert_oracle.encode(w, cfg.as_dict(), ids, lens, deviate={}))
+    cos = lambda a, b: 1.0 - (a * b).sum(1) / np.linalg.norm(a, axis=1) / np.linalg.norm(b, axis=1)
+    last = "encoder.layer.1."
+    # ffn_tail = W2's last 128 columns of the last layer are zero
+    w2 = dict(w)
+    w2[last + "output.dense.weight"] = w[last + "output.dense.weight"].copy()
+    w2[last + "output.dense.weight"][:, -128:] = 0.0
+    tail = enc(w, ffn_tail=128)
+    assert cos(tail, base).min() > 1e-6                                       # every row moves, the one-token row included
+    np.testing.assert_allclose(tail, enc(w2), rtol=0, atol=1e-14)
+    assert cos(enc(w, ffn_tail=256), base).min() > cos(tail, base).min()
+    # head_last = the out-projection's last 32 columns of the last layer are zero
+    w3 = dict(w)
+    w3[last + "attention.output.dense.weight"] = w[last + "attention.output.dense.weight"].copy()
+    w3[last + "attention.output.dense.weight"][:, -32:] = 0.0
+    head = enc(w, head_last=1)
+    assert cos(head, base).min() > 1e-6
+    np.testing.assert_allclose(head, enc(w3), rtol=0, atol=1e-14)
+    # the first layer is untouched: with its own last chunk / head zeroed in the weights the outputs differ from the deviations'
+    w4 = dict(w)
+    w4["encoder.layer.0.output.dense.weight"] = w["encoder.layer.0.output.dense.weight"].copy()
+    w4["encoder.layer.0.output.dense.weight"][:, -128:] = 0.0
+    assert cos(enc(w4), tail).min() > 1e-6
+    for bad in (dict(ffn_tail=0), dict(head_last=0), dict(head_last=13), dict(ffn_tail=128, head_last=1)):
+        with pytest.raises(ValueError):
+            enc(w, **bad)
+
+
 def test_weight_packing_layout(lib_built):
     from memex_amd.encoder import Encoder
     from memex_amd.weights import ALL_MINILM_L6_V2, BGE_BASE_EN, EncoderConfig, pack_weights, synthetic_weights, tensor_order
