@@ -1307,6 +1307,8 @@ void fill_finish_params(FinishParams &fp, const mx_index *idx, const BatchPlan &
     fp.terr = pl.filt8 ? idx->tsc : nullptr;
     fp.e2 = (float)(idx->ds + 8) * 5.9604645e-8f + 1e-6f;  // f32 fma dot of <= ds terms of unit vectors, any order
     fp.lane_rec = s.lane_rec;
+    fp.rec_int = pl.filt8 ? 1 : 0;
+    fp.qscale = s.qscale;
     fp.lane_tile = s.lane_tile;
     fp.lane_cnt = s.lane_cnt;
     fp.theta = s.theta;

@@ -95,7 +95,8 @@ struct ScanParams {
                                 // (two query groups per wave: one bit per group of 32, 16 bits)
     // collect launch: a lane whose 16 scores of a tile contain one >= theta stores ALL 16 (one record =
     // 64 bytes + the tile index); finish_kernel picks the passing rows.  No per-row code on the stream.
-    float *lane_rec;         // [512][nwg][kRecCap][16]  (thread-in-workgroup major; [1024] with two query groups per wave)
+    float *lane_rec;         // [512][nwg][kRecCap][16]  (thread-in-workgroup major; [1024] with two query groups per wave);
+                             // scan8_kernel stores 16 int32 sums per record in place of the floats (FinishParams::rec_int)
     uint32_t *lane_tile;     // [512][nwg][kRecCap] tile index of each record
     uint32_t *lane_cnt;      // [512][nwg] records written
     float *lane_max;         // [512][nwg] sample mode: running maximum of each lane
@@ -253,6 +254,8 @@ struct FinishParams {
     const float *terr;          // the 8-bit copy's tscale array (residual of row r: [kTscaleFloats * (r / 64) + 2 + (r / 32 & 1)]); null: 0
     float e2;                   // bound on |f32 rescoring - cosine|
     const float *lane_rec;      // records of the collect launch (ScanParams)
+    int rec_int;                // the records hold the int8 scan's integer sums: a score is ((float)sum * s_h) * qscale[q], s_h = terr[kTscaleFloats * (r / 64) + (r / 32 & 1)]
+    const float *qscale;        // [256] the batch's query steps (ScanParams::qscale); read only with rec_int
     const uint32_t *lane_tile;
     const uint32_t *lane_cnt;
     const float *theta;         // [256] the collect launch's pass threshold

@@ -827,6 +827,14 @@ __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t *lds_w,
     return base + inc - v;
 }
 
+// A record of the int8 scan (FinishParams::rec_int) holds the lane's 16 integer sums, loaded here as float bits: each becomes the
+// score scan8_kernel tested, ((float)sum * s_h) * s_q -- two multiplications in this order (this file is built without FMA
+// contraction, and there is no addition to contract with), so the bits are those the scan compared with the threshold.
+__device__ __forceinline__ void int_record_scores(float (&v)[16], float s_h, float s_q) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = ((float)__float_as_int(v[r]) * s_h) * s_q;
+}
+
 template <bool CMP>
 __device__ __forceinline__ void finish_query(const FinishParams &p) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];
@@ -974,6 +982,7 @@ __device__ __forceinline__ void finish_query(const FinishParams &p) {
             const f32x4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = a[r], v[4 + r] = b[r], v[8 + r] = c[r], v[12 + r] = d[r];
+            if (p.rec_int) int_record_scores(v, p.terr[kTscaleFloats * (size_t)(t32 >> 1) + (t32 & 1u)], p.qscale[q]);
             const float er = resid(rowb);                  // one half tile per record
             const float thr = fmaf(-qb, er, th), eb = fmaf(qb, er, qa);
 #pragma unroll
@@ -2134,6 +2143,7 @@ __device__ __forceinline__ void range_query(const RangeParams &rp) {
             const f32x4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = a[r], v[4 + r] = b[r], v[8 + r] = c[r], v[12 + r] = d[r];
+            if (p.rec_int) int_record_scores(v, p.terr[kTscaleFloats * (size_t)(t32 >> 1) + (t32 & 1u)], p.qscale[q]);
             const float er = resid(rowb);
             const float thr = fmaf(-qb, er, th), eb = fmaf(qb, er, qa);
 #pragma unroll

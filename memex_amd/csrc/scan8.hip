@@ -36,8 +36,10 @@
 // on two 4-wave workgroups per CU, each with an 8-slot ring (NW = 4, RING = 8).  A wave none of whose
 // queries is wanted (small batches, retry passes: ScanParams::wave_mask) skips its MFMAs.
 // Tile epilogue, per half: integer max over the lane's 16 sums, one conversion, two multiplications (s_h, s_q),
-// one FMA (theta - qb * e_h), one compare; a passing lane stores its 16 scores as floats -- the record format of
-// scan16_kernel with the 32-row tile index 2T + u, so theta_kernel and finish_kernel do not know which scan ran.
+// one FMA (theta - qb * e_h), one compare; a passing lane stores its 16 integer sums as they are (a removed row's: INT_MIN) --
+// the record slot of scan16_kernel with the 32-row tile index 2T + u.  finish_kernel and range_finish_kernel rebuild a row's
+// score, ((float)sum * s_h) * s_q, from the tscale entry they read the residual from and the query's step (FinishParams::rec_int):
+// the same two roundings as the test above, on the threads that hold a record and not on the whole wave here.
 #include "mx_rotate.h"
 #include "scan_common.h"
 
@@ -287,6 +289,9 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
                              : "memory");
             }
         } else {
+            // (Reading the entry at the top of the tile's last slot instead, and waiting here only until the fragment reads issued
+            // behind it are all that is outstanding -- so that the wait below no longer drains the next tile's first fragments -- was
+            // built and measured: the collect launch did not move, profiles/int_records_ab.txt.)
             const uint32_t sa = kSbase + (ti & (SRING - 1)) * SENTRY;
             asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(shs) : "v"(sa) : "memory");
         }
@@ -321,7 +326,7 @@ __global__ __launch_bounds__(NW * 64, 2) void scan8_kernel(const ScanParams p) {
                         if ((cnt[g] & 0x7fffffffu) < (uint32_t)kRecCap) {
                             store_record(p.lane_rec, p.lane_tile, (size_t)mylane(g) * kRecCap + (cnt[g] & 0x7fffffffu),
                                          [&] { return 2 * tile + u; },  // 32-row tile index, as finish_kernel counts them
-                                         [&](int r) { return ((float)ac[r] * sh) * sq[g]; });
+                                         ac);                           // the sums themselves: the readers scale them
                             ++cnt[g];
                         } else {
                             cnt[g] |= 0x80000000u;

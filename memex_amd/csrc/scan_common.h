@@ -79,11 +79,14 @@ __device__ __forceinline__ TileSpan tile_span(const ScanParams &p) {
 // ---- tile epilogue --------------------------------------------------------------------------------------------------------
 // With A = corpus rows and B = queries, an MFMA lane ends a 32-row tile holding the 16 scores of ONE query (column lane & 31)
 // against rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  Lane buffers are laid out [thread-in-workgroup][workgroup], so everything
-// one query ever receives (2 lanes x all workgroups) is contiguous for the gathers of theta_kernel and finish_kernel, which do
-// not know which scan ran.
+// one query ever receives (2 lanes x all workgroups) is contiguous for the gathers of theta_kernel and finish_kernel, which know
+// of the scan that ran only whether its records hold floats or integers.
 //   MODE 1 (collect): a lane whose maximum reaches the query's pass threshold (one wave-uniform ballot branch, taken by a few
 //     percent of the tiles) stores ALL 16 scores as one record -- 4 x f32x4 in lane_rec plus the 32-row tile index in lane_tile
-//     -- and counts it in lane_cnt; which rows pass is sorted out by finish_kernel, so the stream carries no per-row code.  A
+//     -- and counts it in lane_cnt; which rows pass is sorted out by finish_kernel, so the stream carries no per-row code.  The
+//     int8 scan (scan8_kernel) stores its 16 integer sums instead, in the same 64 bytes (INT_MIN for a removed row): the
+//     readers, finish_kernel and range_finish_kernel, turn a sum into ((float)sum * s_h) * s_q -- the value the scan compared
+//     with the threshold -- on the threads that hold a record (FinishParams::rec_int), so the wave-wide branch here is stores only.  A
 //     lane has room for kRecCap records; one more sets overflow[query].  The count and the overflow flag are a kernel's own
 //     registers: scan_kernel and scan16_kernel keep them apart, next to the lane's two buffer addresses; scan16w_kernel and
 //     scan8_kernel are short of registers, keep the flag in bit 31 of the count and rebuild the addresses where a record is stored.
@@ -119,7 +122,8 @@ __device__ __forceinline__ auto max16(const V &v) {
 }
 
 // Record number `at` of the buffers rec (floats or f32x4) / tiles: score(0) .. score(15), then the 32-row tile index tile().
-// `at` is a number, or a function of none where the kernel rebuilds the number at each use.
+// `at` is a number, or a function of none where the kernel rebuilds the number at each use.  `score` is a function of r, or the
+// lane's 16 integer sums as a vector (scan8_kernel), which go out as they are.
 template <class R, class A, class T, class F>
 __device__ __forceinline__ void store_record(R *rec, uint32_t *tiles, A at, T tile, F score) {
     constexpr int k = 64 / sizeof(R);  // a record in units of R
@@ -127,7 +131,10 @@ __device__ __forceinline__ void store_record(R *rec, uint32_t *tiles, A at, T ti
     if constexpr (std::is_invocable_v<A &>) dst = reinterpret_cast<f32x4 *>(rec + at() * k);
     else dst = reinterpret_cast<f32x4 *>(rec + at * k);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) dst[i] = f32x4{score(4 * i), score(4 * i + 1), score(4 * i + 2), score(4 * i + 3)};
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (std::is_invocable_v<F &, int>) dst[i] = f32x4{score(4 * i), score(4 * i + 1), score(4 * i + 2), score(4 * i + 3)};
+        else reinterpret_cast<i32x4 *>(dst)[i] = i32x4{score[4 * i], score[4 * i + 1], score[4 * i + 2], score[4 * i + 3]};
+    }
     if constexpr (std::is_invocable_v<A &>) tiles[at()] = tile();
     else tiles[at] = tile();
 }
