@@ -515,6 +515,61 @@ int mx_index_search_grouped_device(mx_index *idx, mx_grouping *g, mx_filter *f, 
                                    int32_t *d_n_found, uint8_t *d_complete);
 
 /*
+ * Grouped search with members: the k best documents, each with its n best segments -- or a flat top-k in which no document supplies
+ * more than per_key segments.  Both forms read the candidate list L of mx_index_search_grouped (same candidates, same heads, same
+ * path choice, statistics and batches of 512) and a grouping; key 0 is "ungrouped", a group of its own.
+ *
+ *   mx_index_search_group_rows[_device]   queries [B, dim]; outputs ids / scores / dists [B, k, n]; keys / group_rows / n_members /
+ *                          members_complete [B, k]; n_found / complete [B].  dists, keys, group_rows, n_members, members_complete
+ *                          and complete may be NULL.  f may be NULL.  Per query:
+ *   heads       as in mx_index_search_grouped: the first k heads of L in list order; n_found = min(k, heads in L).
+ *   members     for head j with key K != 0, slot [j, r] holds the r-th entry of L with key K, in list order, r < n: the entry's id,
+ *               score and dist unchanged.  Slot [j, 0] is the head itself.  A key-0 head has itself as its only member.
+ *               group_rows[j] = the entries of L under K (1 for key 0); n_members[j] = min(n, group_rows[j]).  Unused slots hold id 0,
+ *               score 0, dist +inf; behind the heads found keys, group_rows, n_members and members_complete are 0.
+ *   complete    complete[b] = 1 iff n_found[b] == k or L holds fewer than fetch entries: the heads are the exact top-k groups.
+ *   members_complete   [j] = 1 iff n_members[j] == n, or L holds fewer than fetch entries, or the key is 0.
+ * The listed members of a group are ALWAYS its exact best n_members live (with f: allowed live) rows over all rows, in (dist, id)
+ * order: L is a prefix of that order, so a row of the group outside L lies behind every listed one.  members_complete = 1 adds that
+ * the group has no further member that belongs in its first n.  Where it is 0, mx_grouping_key_counts settles it: a group whose
+ * n_members equals its live row count is fully listed (with or without f: the allowed rows are a subset of the live ones).  With
+ * n = 1, ids, scores, dists, keys, group_rows, n_found and complete equal those of mx_index_search_grouped bit for bit.
+ *
+ *   mx_index_search_capped[_device]   outputs ids / scores / dists / keys [B, k]; n_found / complete [B]; dists, keys and complete
+ *                          may be NULL.  Walking L in its order, an entry is ACCEPTED if its key is 0 or fewer than per_key earlier
+ *                          entries of L have its key.  The first k accepted entries are reported unchanged, with their key; unused
+ *                          slots hold id 0, score 0, dist +inf, key 0.  complete[b] = 1 iff n_found[b] == k or L holds fewer than fetch
+ *                          entries; then the answer is the exact capped top-k over all rows (acceptance depends only on the entries
+ *                          ahead of an entry, so the walk over the prefix equals the walk over everything).  per_key = 1 gives the
+ *                          heads of mx_index_search_grouped bit for bit; per_key >= fetch gives mx_index_search at k.
+ *
+ *   mx_grouping_key_counts for each of keys[0, n_keys): n_rows[i] = the rows of the index under that key, n_live[i] = those of them not
+ *                          removed (either may be NULL).  Key 0 counts the ungrouped rows, those appended after the last edit
+ *                          included.  Keys may repeat and come in any order.  A NULL keys with n_keys > 0: MX_EINVAL; n_keys > 2^20:
+ *                          MX_EUNSUPPORTED.  One pass over the keys of all rows; a sharded handle counts against the removal masks
+ *                          of all shards, as mx_grouping_count does.
+ *
+ * Arguments are checked first: B < 0, k < 1, n < 1, per_key < 1, fetch < k, a NULL grouping, a NULL queries / ids / scores / n_found
+ * with B > 0: MX_EINVAL; fetch > 4096, n > 16 or k * n > 4096: MX_EUNSUPPORTED; then a null index: MX_ESEARCH; then a stale or foreign
+ * grouping or filter: MX_EINVAL.  Non-finite queries are rejected as by mx_index_search.  Thread-safe beside every other call; as
+ * with mx_index_search_grouped, concurrent callers are NOT combined into shared passes, and a sharded handle merges the lists on
+ * devices[0] and answers as the plain index does, bit for bit.  O(fetch^2) key compares per query.  Extra HBM, allocated at the
+ * first call: the candidate lists, the result staging at width k * n, and 512 x max(k, 16) per-head words on the grouping.
+ */
+int mx_index_search_group_rows(mx_index *idx, mx_grouping *g, mx_filter *f, const float *queries, int B, int k, int n, int fetch,
+                               uint64_t *ids, float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_members,
+                               uint8_t *members_complete, int32_t *n_found, uint8_t *complete);
+int mx_index_search_group_rows_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_queries, int B, int k, int n, int fetch,
+                                      uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows,
+                                      int32_t *d_n_members, uint8_t *d_members_complete, int32_t *d_n_found, uint8_t *d_complete);
+int mx_index_search_capped(mx_index *idx, mx_grouping *g, mx_filter *f, const float *queries, int B, int k, int per_key, int fetch,
+                           uint64_t *ids, float *scores, float *dists, uint32_t *keys, int32_t *n_found, uint8_t *complete);
+int mx_index_search_capped_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_queries, int B, int k, int per_key,
+                                  int fetch, uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_n_found,
+                                  uint8_t *d_complete);
+int mx_grouping_key_counts(mx_grouping *g, const uint32_t *keys, uint64_t n_keys, uint64_t *n_rows, uint64_t *n_live);
+
+/*
  * Boosted search: relevance plus something the vectors do not carry -- how recent a segment is, how important the host has marked it,
  * how trusted its source is.  Rows are ranked by score + weight * prior, exactly, and the answer says whether a row outside the
  * candidates could have won.

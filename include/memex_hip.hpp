@@ -762,6 +762,101 @@ class HipFlatStore : public VectorStore {
         return {out, complete != 0};
     }
 
+    // one document of a search_document_passages answer: its name (nothing for an ungrouped segment), its best segments as (_id, score)
+    // pairs, best first, and whether it has no further segment that belongs among them
+    struct DocumentPassages {
+        std::optional<std::string> document;
+        std::vector<VectorSearchResult> passages;
+        bool members_complete;
+    };
+
+    // the `limit` best DOCUMENTS for vec, each with its `passages` best segments (mx_index_search_group_rows) -> (hits, complete).  The
+    // passages of a hit are always the exact best ones of their document.  fetch = 0: the default, 4 * limit * passages clamped to
+    // [32, 256] and never below limit; when the answer is not complete the call asks ONCE more with 4096 candidates
+    std::pair<std::vector<DocumentPassages>, bool> search_document_passages(const std::vector<float> &vec, size_t limit, const Grouping &grouping,
+                                                                            size_t passages = 3, size_t fetch = 0,
+                                                                            const Filter *flt = nullptr) {
+        std::vector<DocumentPassages> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0 || passages == 0) return {out, true};
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        const int k = (int)std::min<size_t>(limit, (size_t)INT32_MAX), n = (int)std::min<size_t>(passages, (size_t)INT32_MAX);
+        if (fetch == 0)
+            fetch = std::min<size_t>(4096, std::max<size_t>(limit, std::min<size_t>(256, std::max<size_t>(32, 4 * (size_t)k * (size_t)n))));
+        const size_t width = n <= 16 && (size_t)k * (size_t)n <= 4096 ? (size_t)k * (size_t)n : 1;  // (past the caps the call is refused)
+        std::vector<uint64_t> found(width);
+        std::vector<float> scores(width);
+        std::vector<uint32_t> keys(limit);
+        std::vector<int32_t> members(limit);
+        std::vector<uint8_t> mdone(limit);
+        int32_t nf = 0;
+        uint8_t complete = 0;
+        for (int step = 0; step < 2; ++step) {
+            int rc = mx_index_search_group_rows(idx_, grouping.g_, flt ? flt->f_ : nullptr, vec.data(), 1, k, n,
+                                                (int)std::min<size_t>(fetch, (size_t)INT32_MAX), found.data(), scores.data(), nullptr,
+                                                keys.data(), nullptr, members.data(), mdone.data(), &nf, &complete);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            if (complete || fetch >= 4096) break;
+            fetch = 4096;
+        }
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            DocumentPassages hit{grouping.document_of(keys[j]), {}, mdone[j] != 0};
+            for (int r = 0; r < members[j]; ++r) {
+                auto it = _id_map.find((size_t)found[(size_t)j * n + r]);
+                if (it == _id_map.end())
+                    throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+                hit.passages.push_back({it->second, scores[(size_t)j * n + r]});
+            }
+            out.push_back(std::move(hit));
+        }
+        return {out, complete != 0};
+    }
+
+    // one segment of a search_spread answer: its document (nothing for an ungrouped segment), its _id and score
+    struct SpreadHit {
+        std::optional<std::string> document;
+        std::string segment;
+        float score;
+    };
+
+    // the `limit` best segments for vec with at most `per_document` segments of any one document (mx_index_search_capped), a flat
+    // list, best first -> (hits, complete).  fetch = 0: the default of search_documents; when the answer is not complete the call asks
+    // ONCE more with 4096 candidates
+    std::pair<std::vector<SpreadHit>, bool> search_spread(const std::vector<float> &vec, size_t limit, const Grouping &grouping,
+                                                          size_t per_document = 2, size_t fetch = 0, const Filter *flt = nullptr) {
+        std::vector<SpreadHit> out;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!idx_ || limit == 0 || per_document == 0) return {out, true};
+        }
+        if (vec.size() != (size_t)dim_) throw VectorStoreError(VectorStoreError::SearchError, "query dimension mismatch");
+        if (fetch == 0) fetch = std::min<size_t>(4096, std::max<size_t>(limit, std::min<size_t>(256, std::max<size_t>(32, 4 * limit))));
+        std::vector<uint64_t> found(limit);
+        std::vector<float> scores(limit);
+        std::vector<uint32_t> keys(limit);
+        int32_t nf = 0;
+        uint8_t complete = 0;
+        for (int step = 0; step < 2; ++step) {
+            int rc = mx_index_search_capped(idx_, grouping.g_, flt ? flt->f_ : nullptr, vec.data(), 1, (int)std::min<size_t>(limit, (size_t)INT32_MAX),
+                                            (int)std::min<size_t>(per_document, (size_t)INT32_MAX), (int)std::min<size_t>(fetch, (size_t)INT32_MAX),
+                                            found.data(), scores.data(), nullptr, keys.data(), &nf, &complete);
+            if (rc != MX_OK) throw from_status(rc, VectorStoreError::SearchError);
+            if (complete || fetch >= 4096) break;
+            fetch = 4096;
+        }
+        std::lock_guard<std::mutex> lk(mu_);
+        for (int j = 0; j < nf; ++j) {
+            auto it = _id_map.find((size_t)found[j]);
+            if (it == _id_map.end())
+                throw VectorStoreError(VectorStoreError::SearchError, "Internal inconsistency. Id from vector store not mapped.");
+            out.push_back(SpreadHit{grouping.document_of(keys[j]), it->second, scores[j]});
+        }
+        return {out, complete != 0};
+    }
+
     // A resident prior (mx_prior): what the vectors do not say about a segment -- how recent, how important, how trusted -- one f32 per
     // row kept in HBM and added to the score by search_boosted().  Segments nobody set read 0.  bulk_insert of a document, then
     // set_document({its _ids}, value), is the ingest flow.  The prior is not saved with the store: after compact(), delete_all() or a

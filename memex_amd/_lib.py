@@ -39,6 +39,8 @@ EXPORTS = [
     "mx_index_search_with_filter", "mx_index_search_with_filter_device",
     "mx_grouping_create", "mx_grouping_destroy", "mx_grouping_set_ranges", "mx_grouping_set_ids", "mx_grouping_get_keys", "mx_grouping_count",
     "mx_index_search_grouped", "mx_index_search_grouped_device",
+    "mx_index_search_group_rows", "mx_index_search_group_rows_device", "mx_index_search_capped", "mx_index_search_capped_device",
+    "mx_grouping_key_counts",
     "mx_prior_create", "mx_prior_destroy", "mx_prior_set_ranges", "mx_prior_set_ids", "mx_prior_get", "mx_prior_bound",
     "mx_index_search_boosted", "mx_index_search_boosted_device",
     "mx_filter_set_where", "mx_filter_set_keys", "mx_filter_combine", "mx_filter_invert",
@@ -148,6 +150,11 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_grouping_count": [vp, P(u64), P(u64)],
         "mx_index_search_grouped": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "mx_index_search_grouped_device": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_group_rows": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_group_rows_device": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_capped": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "mx_index_search_capped_device": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "mx_grouping_key_counts": [vp, vp, u64, vp, vp],
         "mx_prior_create": [vp, P(vp)],
         "mx_prior_set_ranges": [vp, vp, vp, u64],
         "mx_prior_set_ids": [vp, vp, vp, u64],

@@ -382,6 +382,10 @@ struct mx_grouping {
     Dev<int32_t> out_rows;
     Dev<uint8_t> out_complete;
     int out_cap = 0;
+    // the further per-head outputs of mx_index_search_group_rows [kMaxBatch, members_cap]
+    Dev<int32_t> out_members;
+    Dev<uint8_t> out_members_complete;
+    int members_cap = 0;
 };
 
 // A prior: one f32 per GLOBAL row of the handle it was made for, 0 where nothing was set, kept where a grouping's
@@ -4491,6 +4495,8 @@ void free_grouping_buffers(mx_grouping *g) {
     g->out_keys.reset();
     g->out_rows.reset();
     g->out_complete.reset();
+    g->out_members.reset();
+    g->out_members_complete.reset();
 }
 
 // ---- host checks of the per-row edits (a grouping's keys, a prior's values: 32-bit words either way) -----------------------------------
@@ -4862,6 +4868,204 @@ int mx_index_search_grouped_device(mx_index *idx, mx_grouping *g, mx_filter *f, 
                                d_keys ? d_keys + o : nullptr, d_group_rows ? d_group_rows + o : nullptr, d_nfound + b0,
                                d_complete ? d_complete + b0 : nullptr);
         if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+// ---- grouped search with members (mx_index_search_group_rows, mx_index_search_capped, mx_grouping_key_counts) -------
+namespace {
+
+// arguments of the group-rows and capped entry points, checked before the index is looked at; per: n or per_key, `what` its name,
+// per_cap: the most the kernel takes (0: no cap)
+int read_group_rows_args(int B, int k, int per, const char *what, int per_cap, int fetch, const mx_grouping *g, const void *q, const void *ids,
+                         const void *scores, const void *n_found) {
+    if (B < 0) return fail(MX_EINVAL, "negative batch");
+    if (k < 1) return fail(MX_EINVAL, "k = %d < 1", k);
+    if (per < 1) return fail(MX_EINVAL, "%s = %d < 1", what, per);
+    if (fetch < k) return fail(MX_EINVAL, "fetch = %d < k = %d", fetch, k);
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    if (B > 0 && (!q || !ids || !scores || !n_found)) return fail(MX_EINVAL, "null argument");
+    if (fetch > kGroupMaxFetch) return fail(MX_EUNSUPPORTED, "fetch = %d > %d", fetch, kGroupMaxFetch);
+    if (per_cap && per > per_cap) return fail(MX_EUNSUPPORTED, "%s = %d > %d", what, per, per_cap);
+    if (per_cap && (long long)k * per > kGroupMaxFetch) return fail(MX_EUNSUPPORTED, "k * %s = %lld > %d", what, (long long)k * per, kGroupMaxFetch);
+    return MX_OK;
+}
+
+// One batch (B <= kMaxBatch), as grouped_batch: the same candidate stage into the owner's lists, one group_rows_kernel launch;
+// host-synchronised.  per_key == 0: the group-rows form at n; otherwise the capped form (n = 1).
+int group_rows_batch(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int n, int per_key, int fetch,
+                     uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_rows, int32_t *d_members,
+                     uint8_t *d_mcomplete, int32_t *d_nfound, uint8_t *d_complete) {
+    mx_index *t = group_owner(idx);
+    int rc = ensure_mmr_lists(t, fetch);
+    if (rc != MX_OK) return rc;
+    const FilterArg fa{nullptr, f, 0};
+    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf, f ? &fa : nullptr)) != MX_OK) return rc;
+    GroupRows p{B, k, n, per_key, fetch, idx->idmap.id_offset, g->len, g->keys, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf,
+                d_ids, d_scores, d_dists, d_keys, d_rows, d_members, d_mcomplete, d_nfound, d_complete};
+    MX_HIP(launch_group_rows(t->stream, p));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+}
+
+// the per-head staging of the host-pointer variants covers k heads per query (the owner's device is current)
+int ensure_group_rows_out(mx_grouping *g, int k) {
+    const size_t kc = (size_t)std::max(k, 16);
+    if (k > g->out_cap) {
+        g->out_cap = 0;
+        MX_HIP(g->out_keys.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_rows.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_complete.alloc(kMaxBatch));
+        g->out_cap = (int)kc;
+    }
+    if (k > g->members_cap) {
+        g->members_cap = 0;
+        MX_HIP(g->out_members.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_members_complete.alloc((size_t)kMaxBatch * kc));
+        g->members_cap = (int)kc;
+    }
+    return MX_OK;
+}
+
+// the host-pointer variants: queries staged per batch of kMaxBatch, results through the owner's staging block (width k * n) and the
+// grouping's per-head arrays.  Not combined with other callers, like mx_index_search_grouped.
+int group_rows_host(mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int n, int per_key, int fetch, uint64_t *ids,
+                    float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_members, uint8_t *members_complete,
+                    int32_t *n_found, uint8_t *complete) {
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    const size_t dim = (size_t)idx->dim;
+    for (size_t i = 0; i < (size_t)B * dim; ++i)
+        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);  // owner of the staging buffers and the stream
+    DeviceGuard dg(t->device);
+    const int width = k * n;
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, width)) != MX_OK) return rc;
+    if ((rc = ensure_group_rows_out(g, k)) != MX_OK) return rc;
+    Scratch &s = t->s;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k;
+        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        if ((rc = group_rows_batch(idx, g, f, s.qstage, nb, k, n, per_key, fetch, s.out_ids, s.out_scores, s.out_dists, g->out_keys, g->out_rows,
+                                   g->out_members, g->out_members_complete, s.out_nfound, g->out_complete)) != MX_OK)
+            return rc;
+        if (keys) MX_HIP(hipMemcpyAsync(keys + o, g->out_keys, (size_t)nb * k * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
+        if (group_rows) MX_HIP(hipMemcpyAsync(group_rows + o, g->out_rows, (size_t)nb * k * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        if (n_members) MX_HIP(hipMemcpyAsync(n_members + o, g->out_members, (size_t)nb * k * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+        if (members_complete)
+            MX_HIP(hipMemcpyAsync(members_complete + o, g->out_members_complete, (size_t)nb * k, hipMemcpyDeviceToHost, t->stream));
+        if (complete) MX_HIP(hipMemcpyAsync(complete + b0, g->out_complete, (size_t)nb, hipMemcpyDeviceToHost, t->stream));
+        if ((rc = copy_out_to_host(t, nb, width, false)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nb, width, ids + o * n, scores + o * n, dists ? dists + o * n : nullptr, n_found + b0, nullptr);
+    }
+    return MX_OK;
+}
+
+int group_rows_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int n, int per_key, int fetch,
+                      uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows, int32_t *d_members,
+                      uint8_t *d_mcomplete, int32_t *d_nfound, uint8_t *d_complete) {
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);
+    DeviceGuard dg(t->device);
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * k, w = o * n;
+        int rc = group_rows_batch(idx, g, f, d_q + (size_t)b0 * idx->dim, nb, k, n, per_key, fetch, d_ids + w, d_scores + w,
+                                  d_dists ? d_dists + w : nullptr, d_keys ? d_keys + o : nullptr, d_group_rows ? d_group_rows + o : nullptr,
+                                  d_members ? d_members + o : nullptr, d_mcomplete ? d_mcomplete + o : nullptr, d_nfound + b0,
+                                  d_complete ? d_complete + b0 : nullptr);
+        if (rc != MX_OK) return rc;
+    }
+    return MX_OK;
+}
+
+}  // namespace
+
+int mx_index_search_group_rows(mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int n, int fetch, uint64_t *ids,
+                               float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_members,
+                               uint8_t *members_complete, int32_t *n_found, uint8_t *complete) try {
+    if (int rc = read_group_rows_args(B, k, n, "n", kGroupMaxMembers, fetch, g, q, ids, scores, n_found); rc != MX_OK) return rc;
+    return group_rows_host(idx, g, f, q, B, k, n, 0, fetch, ids, scores, dists, keys, group_rows, n_members, members_complete, n_found, complete);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_group_rows_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int n, int fetch,
+                                      uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows,
+                                      int32_t *d_n_members, uint8_t *d_members_complete, int32_t *d_nfound, uint8_t *d_complete) try {
+    if (int rc = read_group_rows_args(B, k, n, "n", kGroupMaxMembers, fetch, g, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
+    return group_rows_device(idx, g, f, d_q, B, k, n, 0, fetch, d_ids, d_scores, d_dists, d_keys, d_group_rows, d_n_members,
+                             d_members_complete, d_nfound, d_complete);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_capped(mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int per_key, int fetch, uint64_t *ids,
+                           float *scores, float *dists, uint32_t *keys, int32_t *n_found, uint8_t *complete) try {
+    if (int rc = read_group_rows_args(B, k, per_key, "per_key", 0, fetch, g, q, ids, scores, n_found); rc != MX_OK) return rc;
+    return group_rows_host(idx, g, f, q, B, k, 1, per_key, fetch, ids, scores, dists, keys, nullptr, nullptr, nullptr, n_found, complete);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_index_search_capped_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int per_key, int fetch,
+                                  uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_nfound,
+                                  uint8_t *d_complete) try {
+    if (int rc = read_group_rows_args(B, k, per_key, "per_key", 0, fetch, g, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
+    return group_rows_device(idx, g, f, d_q, B, k, 1, per_key, fetch, d_ids, d_scores, d_dists, d_keys, nullptr, nullptr, nullptr, d_nfound,
+                             d_complete);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_grouping_key_counts(mx_grouping *g, const uint32_t *keys, uint64_t n_keys, uint64_t *n_rows, uint64_t *n_live) try {
+    if (!g) return fail(MX_EINVAL, "null grouping");
+    if (!keys && n_keys) return fail(MX_EINVAL, "null keys with n_keys = %llu", (unsigned long long)n_keys);
+    if (n_keys > kGroupMaxCountKeys)
+        return fail(MX_EUNSUPPORTED, "n_keys = %llu > %llu", (unsigned long long)n_keys, (unsigned long long)kGroupMaxCountKeys);
+    std::vector<uint32_t> sorted(keys, keys + n_keys);
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    mx_index *idx = g->idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
+    if (n_keys == 0) return MX_OK;
+    const uint64_t rows = rows_of(idx);
+    std::vector<uint64_t> counts(2 * sorted.size(), 0);
+    if (rows) {
+        mx_index *t = group_owner(idx);
+        std::vector<uint64_t> mask;
+        composite_dead_mask(idx, rows, &mask);
+        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
+        if (t != idx) l2.lock();
+        DeviceGuard dg(t->device);
+        const uint64_t *d_dead = nullptr;
+        if (int rc = dead_mask_on_device(idx, t, mask, g->dead, g->dead_words, &d_dead); rc != MX_OK) return rc;
+        const size_t cb = counts.size() * sizeof(uint64_t), kb = sorted.size() * sizeof(uint32_t);  // the counters first: 8-byte aligned
+        if (int rc = ensure_group_stage(g, cb + kb); rc != MX_OK) return rc;
+        char *st = static_cast<char *>(g->stage.get());
+        MX_HIP(hipMemsetAsync(st, 0, cb, t->stream));
+        MX_HIP(hipMemcpyAsync(st + cb, sorted.data(), kb, hipMemcpyHostToDevice, t->stream));
+        MX_HIP(launch_grouping_key_counts(t->stream, g->keys, g->len, rows, d_dead, reinterpret_cast<const uint32_t *>(st + cb),
+                                          (uint32_t)sorted.size(), reinterpret_cast<uint64_t *>(st)));
+        MX_HIP(hipMemcpyAsync(counts.data(), st, cb, hipMemcpyDeviceToHost, t->stream));
+        MX_HIP(hipStreamSynchronize(t->stream));
+    }
+    for (uint64_t i = 0; i < n_keys; ++i) {
+        const size_t at = (size_t)(std::lower_bound(sorted.begin(), sorted.end(), keys[i]) - sorted.begin());
+        if (n_rows) n_rows[i] = counts[2 * at];
+        if (n_live) n_live[i] = counts[2 * at + 1];
     }
     return MX_OK;
 } catch (...) {

@@ -567,6 +567,40 @@ struct GroupHeads {
 };
 hipError_t launch_group_heads(hipStream_t s, const GroupHeads &p);
 
+// grouped search with members (mx_index_search_group_rows / mx_index_search_capped / mx_grouping_key_counts, DESIGN.md section 3.19;
+// group_rows_kernels.hip).  Lists, keys and heads as for GroupHeads.
+constexpr int kGroupMaxMembers = 16;             // n: rows reported per group; k * n <= kGroupMaxFetch
+constexpr uint64_t kGroupMaxCountKeys = 1ull << 20;
+// per_key == 0, the GROUP-ROWS form: the first k heads in list order, each with the first n entries of the list under its key (a key-0
+// head: itself alone) in list order: ids, scores, dists [B, k, n], unused slots id 0 / score 0 / dist +inf; per head [B, k] the key,
+// group_rows = the entries of the list under the key (1 for key 0), n_members = min(n, group_rows), members_complete = n_members == n
+// or the list holds fewer than fetch entries or the key is 0; all four 0 behind the heads found.  1 <= n <= kGroupMaxMembers.
+// per_key >= 1, the CAPPED form (n = 1): an entry is accepted when its key is 0 or fewer than per_key entries before it have its key;
+// the first k accepted entries unchanged with their key, [B, k]; group_rows, n_members and members_complete are not written.
+// Both: n_found = min(k, heads or accepted entries); complete = n_found == k or the list holds fewer than fetch entries.  dists,
+// out_keys, group_rows, n_members, members_complete and complete may be null.  1 <= k <= fetch <= kGroupMaxFetch.
+struct GroupRows {
+    int B, k, n, per_key, fetch;
+    uint64_t id_offset, len;
+    const uint32_t *keys;
+    const uint64_t *cand_ids;
+    const float *cand_scores, *cand_dists;
+    const int32_t *cand_nf;
+    uint64_t *ids;
+    float *scores, *dists;
+    uint32_t *out_keys;
+    int32_t *group_rows, *n_members;
+    uint8_t *members_complete;
+    int32_t *n_found;
+    uint8_t *complete;
+};
+hipError_t launch_group_rows(hipStream_t s, const GroupRows &p);
+// Key counts: counts[2 i] += the rows r < rows whose key (keys[r], 0 at or past len) is sorted[i], counts[2 i + 1] += those of them
+// whose bit in `dead` (one bit per global row, null: no removals) is clear.  sorted: n_sorted distinct keys, ascending; the caller
+// zeroes counts [2 * n_sorted] first.  One thread per row, a binary search, global integer adds.
+hipError_t launch_grouping_key_counts(hipStream_t s, const uint32_t *keys, uint64_t len, uint64_t rows, const uint64_t *dead,
+                                      const uint32_t *sorted, uint32_t n_sorted, uint64_t *counts);
+
 // boosted search (mx_prior / mx_index_search_boosted; boost_kernels.hip)
 constexpr int kBoostThreads = 1024;              // one workgroup per query
 constexpr int kBoostMaxFetch = 4096;             // entries per list (the ABI's cap on k): kBoostMaxFetch / kBoostThreads per thread

@@ -503,6 +503,105 @@ class FlatIndex:
                                                    self._grouped_fetch(k, fetch), dp(ids), dp(scores), dp(dists), dp(keys),
                                                    dp(group_rows), dp(n_found), dp(complete)))
 
+    # -- grouped search with members -------------------------------------------------------
+    @staticmethod
+    def _group_rows_fetch(k: int, n: int, fetch) -> int:
+        if fetch is not None:
+            return int(fetch)
+        return min(4096, max(int(k), min(256, max(32, 4 * int(k) * int(n)))))
+
+    def _grouped_queries(self, queries) -> np.ndarray:
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected [B, {self.dim}] queries, got {q.shape}")
+        return q
+
+    def search_group_rows(self, grouping: "IndexGrouping", queries, k: int, n: int, fetch=None, flt: "IndexFilter | None" = None,
+                          settle: bool = False):
+        """The ``k`` best GROUPS (documents), each with its ``n`` best rows (``mx_index_search_group_rows``).
+        -> (ids u64 [B,k,n], scores f32 [B,k,n], dists f32 [B,k,n], keys u32 [B,k], group_rows i32 [B,k], n_members i32 [B,k],
+        members_complete bool [B,k], n_found i32 [B], complete bool [B]).
+        The heads are those of ``search_grouped``; slot ``[b, j, r]`` is the r-th row of the top-``fetch`` list under head j's key
+        (slot 0 the head itself; a key-0 head has itself only), unused slots id 0 / score 0 / dist +inf.  The listed members are
+        always the exact best ``n_members`` rows of their group; ``members_complete[b, j]`` adds that the group has no further row
+        that belongs in its first ``n``.  ``settle=True`` asks ``grouping.key_counts`` about the reported keys whose flag is 0 and
+        raises it where ``n_members`` equals the key's live rows (one more pass over the keys, only when some flag is 0).
+        ``fetch=None``: ``4 * k * n`` clamped to [32, 256] and never below ``k``."""
+        q = self._grouped_queries(queries)
+        B = q.shape[0]
+        kk, nn = max(int(k), 0), max(int(n), 0)
+        ids = np.zeros((B, kk, nn), dtype=np.uint64)
+        scores = np.zeros((B, kk, nn), dtype=np.float32)
+        dists = np.zeros((B, kk, nn), dtype=np.float32)
+        keys = np.zeros((B, kk), dtype=np.uint32)
+        rows = np.zeros((B, kk), dtype=np.int32)
+        members = np.zeros((B, kk), dtype=np.int32)
+        mdone = np.zeros((B, kk), dtype=np.uint8)
+        nf = np.zeros(B, dtype=np.int32)
+        done = np.zeros(B, dtype=np.uint8)
+        p = lambda a: _ptr(a) if a.size else None  # noqa: E731
+        check(lib().mx_index_search_group_rows(self._h, grouping._h, flt._h if flt is not None else None, p(q), B, int(k), int(n),
+                                               self._group_rows_fetch(k, n, fetch), p(ids), p(scores), p(dists), p(keys), p(rows),
+                                               p(members), p(mdone), p(nf), p(done)))
+        mdone = mdone.astype(bool)
+        if settle:
+            open_ = ~mdone & (np.arange(kk)[None, :] < nf[:, None])
+            if open_.any():
+                asked = np.unique(keys[open_])
+                live = grouping.key_counts(asked)[1]
+                at = np.searchsorted(asked, keys[open_])
+                mdone[open_] = members[open_].astype(np.uint64) == live[at]
+        return ids, scores, dists, keys, rows, members, mdone, nf, done.astype(bool)
+
+    def search_group_rows_device(self, grouping: "IndexGrouping", q, k: int, n: int, ids, scores, dists, keys, group_rows, n_members,
+                                 members_complete, n_found, complete, fetch=None, flt: "IndexFilter | None" = None) -> None:
+        """``search_group_rows`` on device tensors: q f32 [B,dim]; ids i64/u64, scores, dists f32 [B,k,n]; keys i32/u32, group_rows
+        i32, n_members i32, members_complete u8 [B,k]; n_found i32 [B]; complete u8 [B] (dists, keys, group_rows, n_members,
+        members_complete and complete may be None).  Blocks until the results are in HBM."""
+        B = int(q.shape[0])
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().mx_index_search_group_rows_device(self._h, grouping._h, flt._h if flt is not None else None, dp(q), B, int(k), int(n),
+                                                      self._group_rows_fetch(k, n, fetch), dp(ids), dp(scores), dp(dists), dp(keys),
+                                                      dp(group_rows), dp(n_members), dp(members_complete), dp(n_found), dp(complete)))
+
+    def search_capped(self, grouping: "IndexGrouping", queries, k: int, per_key: int, fetch=None, flt: "IndexFilter | None" = None):
+        """The top-``k`` rows with at most ``per_key`` rows of any one group (``mx_index_search_capped``).
+        -> (ids u64 [B,k], scores f32 [B,k], dists f32 [B,k], keys u32 [B,k], n_found i32 [B], complete bool [B]).
+        The top-``fetch`` list is walked in its order; a row is accepted when its key is 0 or fewer than ``per_key`` earlier rows of
+        the list have its key.  ``complete[b]``: the answer is the exact capped top-k over all rows.  ``fetch=None``: as
+        ``search_grouped``."""
+        q = self._grouped_queries(queries)
+        B = q.shape[0]
+        kk = max(int(k), 0)
+        ids = np.zeros((B, kk), dtype=np.uint64)
+        scores = np.zeros((B, kk), dtype=np.float32)
+        dists = np.zeros((B, kk), dtype=np.float32)
+        keys = np.zeros((B, kk), dtype=np.uint32)
+        nf = np.zeros(B, dtype=np.int32)
+        done = np.zeros(B, dtype=np.uint8)
+        p = lambda a: _ptr(a) if a.size else None  # noqa: E731
+        check(lib().mx_index_search_capped(self._h, grouping._h, flt._h if flt is not None else None, p(q), B, int(k), int(per_key),
+                                           self._grouped_fetch(k, fetch), p(ids), p(scores), p(dists), p(keys), p(nf), p(done)))
+        return ids, scores, dists, keys, nf, done.astype(bool)
+
+    def search_capped_device(self, grouping: "IndexGrouping", q, k: int, per_key: int, ids, scores, dists, keys, n_found, complete,
+                             fetch=None, flt: "IndexFilter | None" = None) -> None:
+        """``search_capped`` on device tensors: q f32 [B,dim]; ids i64/u64, scores, dists f32, keys i32/u32 [B,k]; n_found i32 [B];
+        complete u8 [B] (dists, keys and complete may be None).  Blocks until the results are in HBM."""
+        B = int(q.shape[0])
+        st = _caller_stream(q)
+        if st is not None:
+            self.wait_stream(st)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().mx_index_search_capped_device(self._h, grouping._h, flt._h if flt is not None else None, dp(q), B, int(k),
+                                                  int(per_key), self._grouped_fetch(k, fetch), dp(ids), dp(scores), dp(dists), dp(keys),
+                                                  dp(n_found), dp(complete)))
+
     # -- boosted search --------------------------------------------------------------------
     def make_prior(self) -> "IndexPrior":
         """A prior (``mx_prior``): one f32 per row of this index, kept in HBM and named in ``search_boosted``.  It starts at 0
@@ -989,6 +1088,16 @@ class IndexGrouping:
         a, l = ctypes.c_uint64(0), ctypes.c_uint64(0)
         check(lib().mx_grouping_count(self._h, ctypes.byref(a), ctypes.byref(l)))
         return int(a.value), int(l.value)
+
+    def key_counts(self, keys):
+        """-> (uint64 [n] rows of the index under each key, uint64 [n] those of them that are not removed) -- ``mx_grouping_key_counts``.
+        Key 0 counts the ungrouped rows; keys may repeat; at most 2^20."""
+        k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint32).reshape(-1))
+        rows = np.zeros(k.size, dtype=np.uint64)
+        live = np.zeros(k.size, dtype=np.uint64)
+        check(lib().mx_grouping_key_counts(self._h, _ptr(k) if k.size else None, k.size, _ptr(rows) if k.size else None,
+                                           _ptr(live) if k.size else None))
+        return rows, live
 
     def close(self) -> None:
         if getattr(self, "_h", None):

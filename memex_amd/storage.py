@@ -831,6 +831,75 @@ class HipFlatStore(VectorStore):
                 out.append((grouping.document_of(int(keys[0, j])), self._id_map[d_id], float(scores[0, j]), int(rows[0, j])))
         return out, bool(done[0])
 
+    def _one_query(self, vec: Sequence[float]) -> np.ndarray:
+        q = np.asarray(vec, dtype=np.float32)
+        if q.shape != (self._dim,):
+            raise SearchError(f"query dimension {q.shape} != store dimension {self._dim}")
+        return q
+
+    def search_document_passages(self, vec: Sequence[float], limit: int, grouping: "StoreGrouping", passages: int = 3,
+                                 fetch: int | None = None, flt: "StoreFilter | None" = None
+                                 ) -> Tuple[List[Tuple[str | None, List[VectorSearchResult], bool]], bool]:
+        """The ``limit`` best DOCUMENTS for ``vec``, each with its ``passages`` best segments (``FlatIndex.search_group_rows``) ->
+        ``(hits, complete)``.  Each hit is ``(document name or None for an ungrouped segment, [(segment _id, score), ...] best first,
+        members_complete)``; the first passage is the segment ``search_documents`` reports.  The passages of a hit are always the
+        exact best ones of their document; ``members_complete`` says the document has no further segment that belongs among its
+        first ``passages``.  ``complete``: the documents are the exact top documents over the whole store (over ``flt``'s rows when
+        given).  When that is false the call asks ONCE more with 4096 candidates, as ``search_documents`` does."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0 or passages <= 0:
+            return [], True
+        q = self._one_query(vec)
+        f = flt._flt if flt is not None else None
+        k, n = int(limit), int(passages)
+        first = FlatIndex._group_rows_fetch(k, n, fetch)
+        try:
+            ids, scores, _, keys, _, mem, mdone, nf, done = idx.search_group_rows(grouping._grp, q, k, n, first, f)  # not under the lock
+            if not done[0] and first < 4096:
+                ids, scores, _, keys, _, mem, mdone, nf, done = idx.search_group_rows(grouping._grp, q, k, n, 4096, f)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[Tuple[str | None, List[VectorSearchResult], bool]] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                rows: List[VectorSearchResult] = []
+                for r in range(int(mem[0, j])):
+                    d_id = int(ids[0, j, r])
+                    if d_id not in self._id_map:
+                        raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                    rows.append((self._id_map[d_id], float(scores[0, j, r])))
+                out.append((grouping.document_of(int(keys[0, j])), rows, bool(mdone[0, j])))
+        return out, bool(done[0])
+
+    def search_spread(self, vec: Sequence[float], limit: int, grouping: "StoreGrouping", per_document: int = 2,
+                      fetch: int | None = None, flt: "StoreFilter | None" = None) -> Tuple[List[Tuple[str | None, str, float]], bool]:
+        """The ``limit`` best segments for ``vec`` with at most ``per_document`` segments of any one document
+        (``FlatIndex.search_capped``) -> ``(hits, complete)``.  Each hit is ``(document name or None, segment _id, score)``, best
+        first: a flat list.  ``complete``: the hits are the exact capped top segments over the whole store (over ``flt``'s rows when
+        given); when that is false the call asks ONCE more with 4096 candidates, as ``search_documents`` does."""
+        with self._lock:
+            idx = self._index
+        if idx is None or limit <= 0 or per_document <= 0:
+            return [], True
+        q = self._one_query(vec)
+        f = flt._flt if flt is not None else None
+        first = FlatIndex._grouped_fetch(int(limit), fetch)
+        try:
+            ids, scores, _, keys, nf, done = idx.search_capped(grouping._grp, q, int(limit), int(per_document), first, f)  # not under the lock
+            if not done[0] and first < 4096:
+                ids, scores, _, keys, nf, done = idx.search_capped(grouping._grp, q, int(limit), int(per_document), 4096, f)
+        except _lib.MemexHipError as e:
+            _raise_from(e, SearchError)
+        out: List[Tuple[str | None, str, float]] = []
+        with self._lock:
+            for j in range(int(nf[0])):
+                d_id = int(ids[0, j])
+                if d_id not in self._id_map:
+                    raise SearchError("Internal inconsistency. Id from vector store not mapped.")
+                out.append((grouping.document_of(int(keys[0, j])), self._id_map[d_id], float(scores[0, j])))
+        return out, bool(done[0])
+
     def make_prior(self) -> "StorePrior":
         """A resident prior (``FlatIndex.make_prior``), 0 for every segment.  Bulk-inserting a document and then
         ``prior.set_document([its _ids], value)`` is the ingest flow.  After ``compact()``, ``delete_all()`` or a reload the prior
@@ -1073,6 +1142,16 @@ class VectorStorage:
                          flt: "StoreFilter | None" = None):
         with self._mu:
             return self.client.search_documents(query, limit, grouping, fetch, flt)
+
+    def search_document_passages(self, query: Sequence[float], limit: int, grouping: "StoreGrouping", passages: int = 3,
+                                 fetch: int | None = None, flt: "StoreFilter | None" = None):
+        with self._mu:
+            return self.client.search_document_passages(query, limit, grouping, passages, fetch, flt)
+
+    def search_spread(self, query: Sequence[float], limit: int, grouping: "StoreGrouping", per_document: int = 2,
+                      fetch: int | None = None, flt: "StoreFilter | None" = None):
+        with self._mu:
+            return self.client.search_spread(query, limit, grouping, per_document, fetch, flt)
 
     def search_boosted(self, query: Sequence[float], limit: int, prior: "StorePrior", weight: float = 1.0, fetch: int | None = None,
                        flt: "StoreFilter | None" = None):

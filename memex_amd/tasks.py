@@ -25,6 +25,9 @@ caller's own working set), those segments back with their exact scores, best fir
 one returns the best DOCUMENTS, each by its best segment (``search_documents`` of the store, over a grouping that
 :func:`group_document` fills from a ``process_embeddings`` result).
 
+:func:`search_document_passages` and :func:`search_docs_spread` go one step further: the best documents with their few best segments
+each, and a flat list in which no document supplies more than a few segments -- what a caller that assembles context asks for.
+
 :func:`search_docs_recent` has none either: relevance plus recency.  :func:`stamp_document` stores ``exp2((t - t0) / half_life)`` for
 a document's segments once, at ingest; a query at time ``now`` multiplies its weight by ``exp2(-(now - t0) / half_life)``, so the
 boost a segment gets is ``weight * exp2(-(now - t) / half_life)`` and the resident values are never rewritten as time passes.
@@ -123,6 +126,26 @@ def search_documents(client, embedder, grouping, query: str, limit: int = 10):
     if res is None:
         raise ValueError("Invalid query")
     return client.search_documents(res.vector, limit, grouping)
+
+
+def search_document_passages(client, embedder, grouping, query: str, limit: int = 10, passages: int = 3):
+    """``search_documents`` with context to assemble: ``client.search_document_passages(vector, limit, grouping, passages)`` ->
+    ``(hits, complete)``, each hit ``(document id or None, [(segment _id, score), ...], members_complete)`` -- the ``limit`` best
+    documents, each with its ``passages`` best segments.  ``ValueError("Invalid query")`` where ``search_docs`` raises it."""
+    res = embedder.encode_single(query)
+    if res is None:
+        raise ValueError("Invalid query")
+    return client.search_document_passages(res.vector, limit, grouping, passages)
+
+
+def search_docs_spread(client, embedder, grouping, query: str, limit: int = 10, per_document: int = 2):
+    """``search_docs`` in which no document supplies more than ``per_document`` segments: ``client.search_spread(vector, limit,
+    grouping, per_document)`` -> ``(hits, complete)``, each hit ``(document id or None, segment _id, score)``, a flat list best
+    first.  ``ValueError("Invalid query")`` where ``search_docs`` raises it."""
+    res = embedder.encode_single(query)
+    if res is None:
+        raise ValueError("Invalid query")
+    return client.search_spread(res.vector, limit, grouping, per_document)
 
 
 def stamp_document(prior, vectors: Sequence[VectorData], t: float, half_life: float, t0: float) -> None:
