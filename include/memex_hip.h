@@ -72,8 +72,17 @@ typedef struct mx_index mx_index;
  * Replaces HnswStore::new / the per-request construction in get_vector_storage
  * (storage/mod.rs:95-121, storage/local.rs:95-108): callers there build a store per request, so
  * a second open of the same key returns the SAME resident index (ref-counted, O(1)).
- * key == NULL or "" creates a private, unregistered index.  dim >= 1 (any; rows are padded
- * internally).  device = HIP device ordinal.
+ * key == NULL or "" creates a private, unregistered index.  device = HIP device ordinal.
+ * 1 <= dim <= 65536, else MX_EINVAL (also mx_index_open_sharded).  Every accepted dim can be added to, searched by every form below but
+ * the two named here, removed from, compacted, saved and loaded, and answers bit-exactly.  Rows are padded internally to a multiple
+ * of 128 dims up to 768 and of 256 above; the padded width decides what runs:
+ *   padded dim <= 768    every filter copy (int8, bf16) and the f32 scan
+ *   padded dim <= 1536   the int8 and bf16 filter copies (chosen automatically: int8 up to 1024, bf16 above); no f32 scan: without
+ *                        a copy every search is answered on the EXACT path
+ *   padded dim >  1536   no filter copy (mx_index_set_filter_copy returns MX_OK and keeps none): every form is answered on the
+ *                        EXACT path; mx_index_set_corpus_mode(MX_CORPUS_BF16) is MX_EUNSUPPORTED
+ *   padded dim >  8192   mx_index_search_mmr and mx_index_score_ids (and their _device forms) are MX_EUNSUPPORTED; nothing is
+ *                        written to their outputs
  */
 int mx_index_open(const char *key, int dim, int device, mx_index **out);
 void mx_index_close(mx_index *idx); /* drops one reference; frees HBM when the last one goes */

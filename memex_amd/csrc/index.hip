@@ -1444,6 +1444,9 @@ int search_batch(mx_index *idx, const float *d_q, int B, int k, uint64_t *d_ids,
     FinishParams fp;
     fill_finish_params(fp, idx, pl, B, k, mask, n_live, d_ids, d_scores, d_dists, d_nfound);
     if (trivial) fp.n_rows = fp.n_live = 0;
+    // (nothing to find: finish_kernel writes the blanks and leaves before it stages the query, so rows wider than every scan ask for the
+    // widest query the kernel's LDS limit was raised for, not for their own)
+    if (trivial) fp.ds = std::min(fp.ds, kMaxKC16 * kChunkFloats);
     fp.max_err = idx->profiling ? s.max_err : nullptr;
     // finish + completion: the kernel's last workgroup writes the batch summary into pinned host memory and
     // stores the launch's sequence number behind it; the host spins on that word (no D2H copy command and no
@@ -1713,7 +1716,7 @@ int range_batch(mx_index *idx, const float *d_q, int B, int cap, const uint32_t 
             MX_HIP(hipMemsetAsync(s.rlim, 0, (size_t)B * sizeof(uint32_t), st));
             RangeParams rp{};
             rp.f.k = cap;
-            rp.f.ds = idx->ds;
+            rp.f.ds = std::min(idx->ds, kMaxKC16 * kChunkFloats);  // (the blanks alone: the query is never staged, as in search_batch)
             rp.f.x = idx->x;
             rp.f.ids = d_ids;
             rp.f.scores = d_scores;
@@ -3342,7 +3345,7 @@ int mx_device_count(int *n) try {
 int mx_index_open(const char *key, int dim, int device, mx_index **out) try {
     if (!out) return fail(MX_EINVAL, "out is null");
     *out = nullptr;
-    if (dim < 1 || dim > (1 << 16)) return fail(MX_EINVAL, "dim %d out of range", dim);
+    if (dim < 1 || dim > (1 << 16)) return fail(MX_EINVAL, "dim %d out of range: 1 <= dim <= %d", dim, 1 << 16);
     const std::string k = key ? key : "";
     std::lock_guard<std::mutex> lk(g_reg_mu);
     if (!k.empty()) {
@@ -3370,7 +3373,7 @@ int mx_index_open(const char *key, int dim, int device, mx_index **out) try {
 int mx_index_open_sharded(const char *key, int dim, int n_dev, const int *devices, uint64_t block_rows, mx_index **out) try {
     if (!out) return fail(MX_EINVAL, "out is null");
     *out = nullptr;
-    if (dim < 1 || dim > (1 << 16)) return fail(MX_EINVAL, "dim %d out of range", dim);
+    if (dim < 1 || dim > (1 << 16)) return fail(MX_EINVAL, "dim %d out of range: 1 <= dim <= %d", dim, 1 << 16);
     if (n_dev < 1 || n_dev > 64) return fail(MX_EINVAL, "n_dev %d out of range", n_dev);
     const std::string k = key ? key : "";
     std::lock_guard<std::mutex> lk(g_reg_mu);

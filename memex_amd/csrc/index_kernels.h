@@ -216,6 +216,10 @@ hipError_t launch_prep_queries(hipStream_t s, const float *q, int B, int d, int 
 // one residual for all rows get qa = e1, qb = 0
 // filt8: fragments for the 8-bit filter copy (scan8.hip: int8 [8 waves][ds/32][64 lanes][16]) and qscale[256] = the
 // query's quantisation step (0 for an unusable query); ec_max then is that copy's residual word (required)
+// ds > kMaxKC16 * kChunkFloats (no scan, no filter copy: filt8 false and ec_max null, anything else is hipErrorInvalidValue): the
+// call goes to launch_prep_queries_wide, which stages the query through LDS in fixed chunks and leaves qfrag alone.
+hipError_t launch_prep_queries_wide(hipStream_t s, const float *q, int B, int d, int ds, float *qpad, double *qnorm2, float *theta,
+                                    float *e1, uint32_t *overflow, uint32_t *flags, float *qa, float *qb);
 
 // theta[q] = (k-th largest of query q's lane maxima) - 2*e1[q]
 // raw: the lane maxima are plain scores (theta = k-th - 2 * qa); otherwise they are lower bounds of cosines already

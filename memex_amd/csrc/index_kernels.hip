@@ -493,6 +493,10 @@ hipError_t launch_prep_queries(hipStream_t s, const float *q, int B, int d, int 
                                double *qnorm2, float *theta, float *e1, const uint32_t *ec_max, uint32_t *overflow,
                                uint32_t *flags, float *qa, float *qb, bool filt8, float *qscale, const float *mean, float *qmean,
                                const uint32_t *rc_max) {
+    if (ds > kMaxKC16 * kChunkFloats) {
+        if (filt8 || ec_max) return hipErrorInvalidValue;  // no filter copy exists at this width (index.hip, build_filter_copy)
+        return launch_prep_queries_wide(s, q, B, d, ds, qpad, qnorm2, theta, e1, overflow, flags, qa, qb);  // prep_wide.hip
+    }
     if (!qmean) mean = nullptr;
     // one block per query slot: 256 slots (a pass computes all of them), 512 for a batch of more than 256
     hipLaunchKernelGGL(prep_queries_kernel, dim3(B > kPassBatch ? kMaxBatch : kPassBatch), dim3(256),
