@@ -912,6 +912,70 @@ typedef struct mx_encoder_stats {
 int mx_encoder_set_profiling(mx_encoder *enc, int on);
 int mx_encoder_get_stats(mx_encoder *enc, mx_encoder_stats *out);
 int mx_encoder_reset_stats(mx_encoder *enc);
+int mx_encoder_get_cfg(mx_encoder *enc, mx_encoder_cfg *out); /* precision = the mode the handle runs */
+
+/*
+ * Calibrated open: which precision mode holds the score bar is a property of the loaded WEIGHTS, not of the model's shape
+ * (profiles/r6_precision_modes_over_seeds.txt: bf16 misses north_star's 1e-3 on several draws of the MiniLM-L6 shape where
+ * MX_PREC_MIXED1 reads <= 2.6e-4; on the CLS-pooled bge-base shape only MX_PREC_BF16X3 holds on every draw).  So measure at
+ * load time, on the weights that were loaded, and open the cheapest mode that holds.
+ *
+ * The rule.  The f32 blob is uploaded ONCE; every mode's weight images are built from it in HBM (bit for bit what
+ * mx_encoder_create's host routines lay out; only the fused tail's fragment stream is still laid out on the host).  The
+ * MX_PREC_BF16X3 encoder is built as the reference and encodes a probe batch.  Then the candidates in order of cost --
+ * MX_PREC_BF16, MX_PREC_MIXED1, MX_PREC_MIXED -- are built, encode the same probe, and are compared with the reference on
+ * the device, in f64:  pair_dev = max_{i<j} |cos_mode(i, j) - cos_bf16x3(i, j)|,  row_dev = max_i 1 - cos(e_mode_i, e_bf16x3_i).
+ * The first candidate with pair_dev <= bar is chosen, MX_PREC_BF16X3 if none is.  cfg->precision on entry is ignored.
+ * Without MX_CALIBRATE_ALL the measurement stops at the chosen mode.  A reference that gives non-finite (or zero) embeddings
+ * on the probe is an error (MX_EINVAL, text in mx_last_error), not a choice.
+ *
+ * The bar.  MX_CALIBRATE_BAR = 4e-4 = north_star's 1e-3 minus the 6.0e-4 that MX_PREC_BF16X3 itself is from the f64 oracle at
+ * worst (seed 4, profiles/r6_precision_modes_over_seeds.txt section 2).  bar must be finite and > 0, else MX_EINVAL.
+ *
+ * The probe.  ids NULL = mx_encoder_default_probe: 16 sequences, lengths spread evenly over [n/2, n], n = min(200, max_pos -
+ * pos_offset), ids from a counter hash (splitmix64) modulo vocab -- about 2400 packed rows at n = 200, so a hidden-384
+ * MX_PREC_BF16 candidate is measured on its bulk kernels (above the 2048-row small pass) and a hidden-768 one in its <= 4096-row
+ * form (the pass-size regimes round at the same points, see mx_encoder_encode).  A caller who wants the >= 32768-row regime
+ * measured passes a probe of 64 x 512.  A caller's probe needs 2 <= B <= 64, 1 <= S <= min(512, max_pos - pos_offset) and
+ * lens[b] in [1, S], else MX_EINVAL.
+ */
+typedef struct mx_encoder_calibration {
+    int32_t chosen;          /* MX_PREC_* */
+    int32_t tried;           /* bit (1 << MX_PREC_*) per mode that was run */
+    int32_t probe_seqs, probe_tokens;
+    double  bar;
+    double  pair_dev[4];     /* by MX_PREC_*: max |cos_mode(i,j) - cos_bf16x3(i,j)|; 0 for BF16X3; NaN where not tried */
+    double  row_dev[4];      /* by MX_PREC_*: max 1 - cos(e_mode_i, e_bf16x3_i) */
+    double  ms;              /* wall time of the calibration */
+} mx_encoder_calibration;
+size_t mx_encoder_calibration_size(void);                 /* same handshake as mx_encoder_cfg_size */
+#define MX_CALIBRATE_BAR 4e-4
+enum { MX_CALIBRATE_ALL = 1 };                            /* measure every mode even after one has passed */
+
+/* host only.  ids [16 x S] and lens [16] may both be NULL (B and S only); S <= 200. */
+int mx_encoder_default_probe(const mx_encoder_cfg *cfg, int32_t *ids, int32_t *lens, int *B, int *S);
+/* the report alone: nothing stays resident */
+int mx_encoder_calibrate(const mx_encoder_cfg *cfg, const void *weights, size_t nbytes, int device,
+                         const int32_t *ids, const int32_t *lens, int B, int S,   /* NULL ids = the default probe */
+                         double bar, int flags, mx_encoder_calibration *out);
+/*
+ * Calibrates and returns the encoder that was chosen -- the one that was measured, not a rebuilt one; the f32 blob in HBM,
+ * the other encoders and the probe buffers are released before return, and the handle's mx_encoder_stats start at zero.
+ * report may be NULL.  Keyed form: the first open of `key` calibrates and registers the handle with its report; later opens
+ * return the same handle and the stored report in O(1) when every field of cfg except `precision` matches (a resident handle
+ * that mx_encoder_open created reports its precision as chosen and tried = 0).  mx_encoder_open(key, cfg ...) on a calibrated
+ * resident handle keeps its strict comparison: a caller who names a precision gets that precision or MX_EINVAL.
+ */
+int mx_encoder_open_calibrated(const char *key, const mx_encoder_cfg *cfg, const void *weights, size_t nbytes, int device,
+                               const int32_t *ids, const int32_t *lens, int B, int S, double bar, int flags,
+                               mx_encoder **out, mx_encoder_calibration *report);
+
+/* For tests.  The K-blocked image [k'/32][rows][32] of a Linear weight w [rows, k] (k a multiple of 32) in one of the four
+ * forms.  form: MX_PREC_*; via_device = 0 host routine, 1 the kernel.  out: rows * k * {1, 3, 2, 1} uint16, sized by the form. */
+int mx_encoder_weight_image(const float *w, int rows, int k, int form, int via_device, int device, uint16_t *out);
+/* For tests.  d_a, d_b: [B, H] f32 on the current device, complete (the caller's streams synchronised); 2 <= B <= 64, H 384 /
+ * 768.  pair / row as in mx_encoder_calibration; both +inf on a non-finite value or a zero row. */
+int mx_embeddings_deviation_device(const float *d_a, const float *d_b, int B, int H, double *pair, double *row);
 
 /* =====================================================================================
  * WordPiece / byte-level BPE tokenizer + sliding-window segmenter (host code; replaces the `tokenizers` crate

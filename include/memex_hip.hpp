@@ -1526,11 +1526,17 @@ inline std::vector<std::string> segment_text(const ModelConfig &mc, const std::s
     return WhitespaceHashTokenizer{}.windows(text, mc.max_length, mc.stride);
 }
 
+// mx_encoder_cfg::precision of a configuration handed to SentenceEmbedder::spawn / load_pretrained_dir: "calibrate" -- open through
+// mx_encoder_open_calibrated (memex_hip.h), which measures on the loaded weights which mode holds the score bar.  Distinct
+// from the loaders' `precision < 0` = "the loader's choice by shape" (memex_pretrained.hpp), which is -1 everywhere.
+constexpr int kPrecisionCalibrated = -2;
+
 // The actor of embedding.rs:78-152: a dedicated thread owns the encoder; callers post
 // (text, segment?, reply) messages on a queue bounded at 100 (sync_channel(100), :87).
 class SentenceEmbedder {
   public:
     // `weights`: f32 blob in the order documented in memex_hip.h for `cfg`.
+    // `cfg.precision == kPrecisionCalibrated`: the calibrated open with the library's probe and MX_CALIBRATE_BAR; calibration() is its report.
     // `tok`: the model's tokenizer (Tokenizer::wordpiece / ::bpe); nullptr = the whitespace stand-in (tests, benchmarks).
     static std::pair<std::thread, std::shared_ptr<SentenceEmbedder>> spawn(const ModelConfig &mc, const mx_encoder_cfg &cfg,
                                                                            std::vector<float> weights, size_t max_seq_length,
@@ -1555,8 +1561,12 @@ class SentenceEmbedder {
         return r.back();
     }
     void shutdown() { post({"", false, nullptr, true}); }
+    // the report of the calibrated open; nullptr when the precision was named by the caller
+    const mx_encoder_calibration *calibration() const { return calibrated_ ? &calibration_ : nullptr; }
 
   private:
+    bool calibrated_ = false;  // (written by the runner before spawn() returns)
+    mx_encoder_calibration calibration_{};
     struct Msg {
         std::string text;
         bool segment;
@@ -1586,7 +1596,18 @@ class SentenceEmbedder {
             ready.set_value("mx_encoder_cfg size mismatch: header and libmemex_hip.so are different releases");
             return;
         }
-        int rc = mx_encoder_create(&cfg, w.data(), w.size() * sizeof(float), device, &enc);  // create_model(), :99-100
+        int rc;
+        if (cfg.precision == kPrecisionCalibrated) {
+            if (mx_encoder_calibration_size() != sizeof(mx_encoder_calibration)) {
+                ready.set_value("mx_encoder_calibration size mismatch: header and libmemex_hip.so are different releases");
+                return;
+            }
+            rc = mx_encoder_open_calibrated(nullptr, &cfg, w.data(), w.size() * sizeof(float), device, nullptr, nullptr, 0, 0, MX_CALIBRATE_BAR, 0,
+                                            &enc, &calibration_);
+            calibrated_ = rc == MX_OK;
+        } else {
+            rc = mx_encoder_create(&cfg, w.data(), w.size() * sizeof(float), device, &enc);  // create_model(), :99-100
+        }
         if (rc != MX_OK) {
             ready.set_value(mx_last_error());
             return;

@@ -292,6 +292,8 @@ inline PretrainedModel load_pretrained_dir_impl(const std::string &dir, int prec
 // -> configuration, f32 weight blob and tokenizer files of a sentence-transformers directory.  Throws EmbeddingError(SetupError)
 // and nothing else: whatever a damaged file provokes underneath (a bad number, an allocation the header asked for) is reported
 // as "Unable to load model", like the reference's create_model() failing (embedding.rs:99-100).
+// precision: MX_PREC_*, < 0 = the loader's choice by shape, or kPrecisionCalibrated (memex_hip.hpp), which is carried through in
+// the returned configuration: SentenceEmbedder::spawn then opens the encoder calibrated on these weights.
 inline PretrainedModel load_pretrained_dir(const std::string &dir, int precision = -1 /* the loader's choice */) {
     try {
         return load_pretrained_dir_impl(dir, precision);
@@ -357,7 +359,7 @@ inline PretrainedModel load_pretrained_dir_impl(const std::string &dir, int prec
     // precision < 0: the loader's choice -- the bf16 ingest mode, except for CLS-pooled hidden-768 models (bge-base-en), whose scores
     // move by 1e-2 ... 4e-2 on bf16 operands under checkpoint-like weights (north_star: 1e-3): MX_PREC_BF16X3 is the one mode that held
     // the bar on every draw of such weights tried (<= 6e-4; MX_PREC_MIXED reaches 1.1e-3 on two of eleven: profiles/r6_precision_modes_over_seeds.txt)
-    if (precision < 0) c.precision = (c.pooling == MX_POOL_CLS && c.hidden == 768) ? MX_PREC_BF16X3 : MX_PREC_BF16;
+    if (precision < 0 && precision != kPrecisionCalibrated) c.precision = (c.pooling == MX_POOL_CLS && c.hidden == 768) ? MX_PREC_BF16X3 : MX_PREC_BF16;
     pm.max_seq_length = (size_t)std::min(512, c.max_pos - c.pos_offset);
     if (file_exists(dir + "/sentence_bert_config.json")) {
         const Json sb = read_json(dir + "/sentence_bert_config.json");
@@ -437,7 +439,8 @@ inline std::shared_ptr<Tokenizer> pretrained_tokenizer(const PretrainedModel &pm
 }
 
 // SentenceEmbedder::spawn(&ModelConfig) with create_model() reading a LOCAL sentence-transformers directory
-// (embedding.rs:84-100): encoder + native tokenizer from the files the reference downloads
+// (embedding.rs:84-100): encoder + native tokenizer from the files the reference downloads.  precision = kPrecisionCalibrated:
+// the calibrated open; the embedder's calibration() is the report
 inline std::pair<std::thread, std::shared_ptr<SentenceEmbedder>> spawn_pretrained(const std::string &dir, const ModelConfig &mc = ModelConfig{},
                                                                                   int device = 0, int precision = -1 /* the loader's choice */) {
     PretrainedModel pm = load_pretrained_dir(dir, precision);

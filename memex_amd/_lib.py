@@ -25,6 +25,9 @@ MX_FILTER_AND, MX_FILTER_OR, MX_FILTER_ANDNOT, MX_FILTER_XOR = 0, 1, 2, 3
 MX_CORPUS_F32, MX_CORPUS_BF16 = 0, 1
 MX_POOL_MEAN, MX_POOL_CLS = 0, 1
 MX_PREC_BF16, MX_PREC_BF16X3, MX_PREC_MIXED, MX_PREC_MIXED1 = 0, 1, 2, 3
+PRECISION_NAMES = {MX_PREC_BF16: "bf16", MX_PREC_BF16X3: "bf16x3", MX_PREC_MIXED: "mixed", MX_PREC_MIXED1: "mixed1"}
+MX_CALIBRATE_BAR = 4e-4   # mx_encoder_open_calibrated's default bar (include/memex_hip.h)
+MX_CALIBRATE_ALL = 1
 
 # every symbol include/memex_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -50,7 +53,9 @@ EXPORTS = [
     "mx_index_set_profiling", "mx_index_get_stats", "mx_index_reset_stats", "mx_topk_merge_device", "mx_topk_merge_packed_device", "mx_topk_merge_packed_async",
     "mx_encoder_cfg_size", "mx_encoder_weight_bytes", "mx_encoder_create", "mx_encoder_open", "mx_encoder_wait_stream", "mx_encoder_destroy", "mx_encoder_encode",
     "mx_encoder_encode_device", "mx_encoder_set_profiling", "mx_encoder_get_stats",
-    "mx_encoder_reset_stats",
+    "mx_encoder_reset_stats", "mx_encoder_get_cfg",
+    "mx_encoder_calibration_size", "mx_encoder_default_probe", "mx_encoder_calibrate", "mx_encoder_open_calibrated",
+    "mx_encoder_weight_image", "mx_embeddings_deviation_device",
     "mx_tokenizer_create", "mx_tokenizer_create_from_memory", "mx_tokenizer_create_bpe", "mx_tokenizer_create_bpe_from_memory",
     "mx_tokenizer_create_from_json", "mx_tokenizer_create_from_json_memory",
     "mx_tokenizer_destroy", "mx_tokenizer_vocab_size",
@@ -86,6 +91,12 @@ class EncoderCfg(ctypes.Structure):
                 ("ffn", ctypes.c_int32), ("vocab", ctypes.c_int32), ("max_pos", ctypes.c_int32),
                 ("type_vocab", ctypes.c_int32), ("ln_eps", ctypes.c_float), ("pooling", ctypes.c_int32),
                 ("normalize", ctypes.c_int32), ("pos_offset", ctypes.c_int32), ("precision", ctypes.c_int32)]
+
+
+class EncoderCalibration(ctypes.Structure):
+    _fields_ = [("chosen", ctypes.c_int32), ("tried", ctypes.c_int32), ("probe_seqs", ctypes.c_int32),
+                ("probe_tokens", ctypes.c_int32), ("bar", ctypes.c_double), ("pair_dev", ctypes.c_double * 4),
+                ("row_dev", ctypes.c_double * 4), ("ms", ctypes.c_double)]
 
 
 class EncoderStats(ctypes.Structure):
@@ -203,6 +214,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "mx_encoder_set_profiling": [vp, i32],
         "mx_encoder_get_stats": [vp, P(EncoderStats)],
         "mx_encoder_reset_stats": [vp],
+        "mx_encoder_get_cfg": [vp, P(EncoderCfg)],
+        "mx_encoder_default_probe": [P(EncoderCfg), vp, vp, P(i32), P(i32)],
+        "mx_encoder_calibrate": [P(EncoderCfg), vp, ctypes.c_size_t, i32, vp, vp, i32, i32, ctypes.c_double, i32, P(EncoderCalibration)],
+        "mx_encoder_open_calibrated": [cp, P(EncoderCfg), vp, ctypes.c_size_t, i32, vp, vp, i32, i32, ctypes.c_double, i32, P(vp),
+                                       P(EncoderCalibration)],
+        "mx_encoder_weight_image": [vp, i32, i32, i32, i32, i32, vp],
+        "mx_embeddings_deviation_device": [vp, vp, i32, i32, P(ctypes.c_double), P(ctypes.c_double)],
         "mx_tokenizer_create": [cp, i32, P(vp)],
         "mx_tokenizer_create_from_memory": [cp, ctypes.c_size_t, i32, P(vp)],
         "mx_tokenizer_create_bpe": [cp, cp, P(vp)],
@@ -239,6 +257,8 @@ def _declare(L: ctypes.CDLL) -> None:
     L.mx_index_stats_size.argtypes = []
     L.mx_encoder_cfg_size.restype = ctypes.c_size_t
     L.mx_encoder_cfg_size.argtypes = []
+    L.mx_encoder_calibration_size.restype = ctypes.c_size_t
+    L.mx_encoder_calibration_size.argtypes = []
 
 
 def _load_torch_runtime_first() -> None:
@@ -296,6 +316,9 @@ def lib() -> ctypes.CDLL:
             if L.mx_encoder_cfg_size() != ctypes.sizeof(EncoderCfg):
                 raise MemexHipError(MX_EINVAL, f"{_path}: mx_encoder_cfg is {L.mx_encoder_cfg_size()} bytes, this binding "
                                                f"declares {ctypes.sizeof(EncoderCfg)} (library / binding version mismatch)")
+            if L.mx_encoder_calibration_size() != ctypes.sizeof(EncoderCalibration):
+                raise MemexHipError(MX_EINVAL, f"{_path}: mx_encoder_calibration is {L.mx_encoder_calibration_size()} bytes, this binding "
+                                               f"declares {ctypes.sizeof(EncoderCalibration)} (library / binding version mismatch)")
             _lib = L
         return _lib
 

@@ -12,7 +12,8 @@
 // with bf16 activations/weights, f32 accumulation and f32 LayerNorm/softmax/GELU.  Three kernel sets serve that layer:
 // large passes (pgemm_kernel / the fused tail_kernel), passes of <= 2048 rows of the hidden-384 models (encoder_small.hip:
 // query-time embedding, embedding.rs:146-151), and MX_PREC_BF16X3 (encoder_precise.hip: split bf16 operands, f32 hidden
-// state and attention) -- see include/memex_hip.h for what a caller can observe of the difference.
+// state and attention) -- see include/memex_hip.h for what a caller can observe of the difference.  Which of the four precision
+// modes a loaded model needs can be measured at load time: mx_encoder_open_calibrated (below; kernels in encoder_calibrate.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <cmath>
@@ -110,6 +111,8 @@ struct mx_encoder : RowWorkspace {
     mx_encoder_stats stats{};
     std::string key;  // registry key (mx_encoder_open); empty = private
     int refs = 1;
+    bool calibrated = false;         // opened by mx_encoder_open_calibrated: cfg.precision is what the calibration chose,
+    mx_encoder_calibration calib{};  // and this is its report
 };
 
 namespace {
@@ -125,26 +128,20 @@ hipError_t alloc_fixed(mx_encoder *e, T **dst, size_t bytes) {
     return hipSuccess;
 }
 
-int upload_f32(mx_encoder *e, const float *src, size_t n, float **dst) {
-    MX_HIP(alloc_fixed(e, dst, n * sizeof(float)));
-    MX_HIP(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
-    return MX_OK;
-}
-
+// The host routines of the four weight images (each returns the image; put_weight uploads it).  weight_image_kernel
+// (encoder_calibrate.hip) reproduces them bit for bit on the device.
 // Linear weight [rows, k] (nn.Linear layout) -> bf16, K-blocked [k/32][rows][32]: every 16-row x 64-byte
 // staging piece of the GEMM is then one contiguous KiB
-int upload_weight(mx_encoder *e, const float *src, size_t rows, size_t k, bf16_t **dst) {
+std::vector<uint16_t> upload_weight(const float *src, size_t rows, size_t k) {
     std::vector<uint16_t> tmp(rows * k);
     for (size_t r = 0; r < rows; ++r)
         for (size_t c = 0; c < k; ++c) tmp[((c >> 5) * rows + r) * 32 + (c & 31)] = f32_to_bf16(src[r * k + c]);
-    MX_HIP(alloc_fixed(e, dst, tmp.size() * sizeof(uint16_t)));
-    MX_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    return MX_OK;
+    return tmp;
 }
 
 // the bf16x3 form of a Linear weight: k tripled, [hi | hi | lo] against activations split as [hi | lo | hi]
 // (encoder_precise.hip), K-blocked like upload_weight's
-int upload_weight3(mx_encoder *e, const float *src, size_t rows, size_t k, bf16_t **dst) {
+std::vector<uint16_t> upload_weight3(const float *src, size_t rows, size_t k) {
     std::vector<uint16_t> tmp(rows * 3 * k);
     auto at = [&](size_t r, size_t c) -> uint16_t & { return tmp[((c >> 5) * rows + r) * 32 + (c & 31)]; };
     for (size_t r = 0; r < rows; ++r)
@@ -159,15 +156,13 @@ int upload_weight3(mx_encoder *e, const float *src, size_t rows, size_t k, bf16_
             at(r, k + c) = hi;
             at(r, 2 * k + c) = lo;
         }
-    MX_HIP(alloc_fixed(e, dst, tmp.size() * sizeof(uint16_t)));
-    MX_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    return MX_OK;
+    return tmp;
 }
 
 // the mixed modes' form of a Linear weight: ONE fp16 value per element (saturating).  copies = 2 (MX_PREC_MIXED): k doubled, [w | w]
 // against activations split as fp16 [hi | lo] -- two fp16 MFMA products per product, 11 + 22 significant bits; copies = 1
 // (MX_PREC_MIXED1): [w] against ONE fp16 value per activation
-int upload_weight2h(mx_encoder *e, const float *src, size_t rows, size_t k, bf16_t **dst, int copies = 2) {
+std::vector<uint16_t> upload_weight2h(const float *src, size_t rows, size_t k, int copies = 2) {
     std::vector<uint16_t> tmp(rows * (size_t)copies * k);
     auto at = [&](size_t r, size_t c) -> uint16_t & { return tmp[((c >> 5) * rows + r) * 32 + (c & 31)]; };
     for (size_t r = 0; r < rows; ++r)
@@ -179,8 +174,58 @@ int upload_weight2h(mx_encoder *e, const float *src, size_t rows, size_t k, bf16
             at(r, c) = bits;
             if (copies == 2) at(r, k + c) = bits;
         }
-    MX_HIP(alloc_fixed(e, dst, tmp.size() * sizeof(uint16_t)));
-    MX_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return tmp;
+}
+
+// the host routine of a form (MX_PREC_*: the four images a GEMM weight comes in) and the factor it widens k by
+std::vector<uint16_t> weight_image_host(const float *src, size_t rows, size_t k, int form) {
+    switch (form) {
+        case MX_PREC_BF16: return upload_weight(src, rows, k);
+        case MX_PREC_BF16X3: return upload_weight3(src, rows, k);
+        case MX_PREC_MIXED: return upload_weight2h(src, rows, k, 2);
+        default: return upload_weight2h(src, rows, k, 1);
+    }
+}
+constexpr size_t form_copies(int form) { return form == MX_PREC_BF16X3 ? 3 : form == MX_PREC_MIXED ? 2 : 1; }
+
+// Where an encoder's tensors come from: the caller's f32 blob (mx_encoder_create: every piece is converted on the host and
+// uploaded), or the same blob ALSO in HBM (the calibrated open builds several encoders from one upload: pieces are copied
+// device to device and the matrices re-laid by weight_image_kernel, on the encoder's stream).  Offsets are in floats.
+struct WeightBlob {
+    const float *host = nullptr;
+    const float *dev = nullptr;
+};
+
+int put_f32_at(mx_encoder *e, const WeightBlob &w, size_t off, size_t n, float *dst) {
+    if (w.dev) MX_HIP(hipMemcpyAsync(dst, w.dev + off, n * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    else MX_HIP(hipMemcpy(dst, w.host + off, n * sizeof(float), hipMemcpyHostToDevice));
+    return MX_OK;
+}
+
+int put_f32(mx_encoder *e, const WeightBlob &w, size_t off, size_t n, float **dst) {
+    MX_HIP(alloc_fixed(e, dst, n * sizeof(float)));
+    return put_f32_at(e, w, off, n, *dst);
+}
+
+// `parts` matrices [rows, k] at offs[0 .. parts) stacked into one [parts x rows, k] weight (Q, K and V are one GEMM) in `form`
+int put_weight(mx_encoder *e, const WeightBlob &w, const size_t *offs, int parts, size_t rows, size_t k, int form, bf16_t **dst) {
+    const size_t total = (size_t)parts * rows, bytes = total * form_copies(form) * k * sizeof(uint16_t);
+    if (w.dev) {
+        MX_HIP(alloc_fixed(e, dst, bytes));
+        for (int p = 0; p < parts; ++p)
+            MX_HIP(launch_weight_image(e->stream, w.dev + offs[p], rows, k, reinterpret_cast<uint16_t *>(*dst), total, (size_t)p * rows, form));
+        return MX_OK;
+    }
+    std::vector<float> cat;
+    const float *src = w.host + offs[0];
+    if (parts > 1) {
+        cat.resize(total * k);
+        for (int p = 0; p < parts; ++p) memcpy(cat.data() + (size_t)p * rows * k, w.host + offs[p], rows * k * sizeof(float));
+        src = cat.data();
+    }
+    const std::vector<uint16_t> tmp = weight_image_host(src, total, k, form);
+    MX_HIP(alloc_fixed(e, dst, bytes));
+    MX_HIP(hipMemcpy(*dst, tmp.data(), bytes, hipMemcpyHostToDevice));
     return MX_OK;
 }
 
@@ -494,31 +539,19 @@ int check_cfg(const mx_encoder_cfg *c) {
 
 static void destroy_impl(mx_encoder *e);
 
-extern "C" {
-
-size_t mx_encoder_cfg_size(void) { return sizeof(mx_encoder_cfg); }
-
-size_t mx_encoder_weight_bytes(const mx_encoder_cfg *c) {
-    if (!c) return 0;
-    const size_t H = (size_t)c->hidden, F = (size_t)c->ffn;
-    size_t n = ((size_t)c->vocab + c->max_pos + c->type_vocab) * H + 2 * H;
-    n += (size_t)c->layers * (3 * (H * H + H) + (H * H + H) + 2 * H + (F * H + F) + (H * F + H) + 2 * H);
-    return n * sizeof(float);
-}
-
-int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nbytes, int device, mx_encoder **out) try {
-    if (!out) return fail(MX_EINVAL, "out is null");
-    *out = nullptr;
-    int rc = check_cfg(cfg);
-    if (rc != MX_OK) return rc;
-    if (!weights) return fail(MX_EINVAL, "weights is null");
-    if (nbytes != mx_encoder_weight_bytes(cfg))
-        return fail(MX_EINVAL, "weight blob is %zu bytes, config needs %zu", nbytes, mx_encoder_weight_bytes(cfg));
+// the device exists (else MX_EDEVICE: nothing is ever computed on the host instead)
+static int check_device(int device) {
     int ndev = 0;
     hipError_t he = hipGetDeviceCount(&ndev);
     if (he != hipSuccess || ndev <= 0)
         return fail(MX_EDEVICE, "no HIP device available (%s)", he == hipSuccess ? "count 0" : hipGetErrorString(he));
     if (device < 0 || device >= ndev) return fail(MX_EDEVICE, "device %d out of range (have %d)", device, ndev);
+    return MX_OK;
+}
+
+// One encoder for a checked configuration on an existing device, from the host blob or from its copy in HBM (WeightBlob).
+// The device route leaves its copies and conversions finished on the encoder's stream: the caller may release the blob.
+static int build_encoder(const mx_encoder_cfg *cfg, const WeightBlob &w, int device, mx_encoder **out) {
     DeviceGuard g(device);
     if (!g.ok) return fail(MX_EDEVICE, "hipSetDevice(%d) failed", device);
     {
@@ -558,10 +591,10 @@ int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nby
         return bail(fail(MX_EDEVICE, "stream/event creation failed"));
 
     const size_t H = (size_t)cfg->hidden, F = (size_t)cfg->ffn;
-    const float *p = static_cast<const float *>(weights);
+    size_t pos = 0;  // in floats
     auto take = [&](size_t n) {
-        const float *r = p;
-        p += n;
+        const size_t r = pos;
+        pos += n;
         return r;
     };
 #define MX_TRY(x)                      \
@@ -569,47 +602,40 @@ int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nby
         int _rc = (x);                 \
         if (_rc != MX_OK) return bail(_rc); \
     } while (0)
-    MX_TRY(upload_f32(e, take((size_t)cfg->vocab * H), (size_t)cfg->vocab * H, &e->word));
-    MX_TRY(upload_f32(e, take((size_t)cfg->max_pos * H), (size_t)cfg->max_pos * H, &e->pos));
+    // the form of the attention block's matrices and of the MLP's (Layer)
+    const int form_a = e->precise ? MX_PREC_BF16X3 : MX_PREC_BF16;
+    const int form_m = e->mlp1 ? MX_PREC_MIXED1 : e->mixed ? MX_PREC_MIXED : form_a;
+    MX_TRY(put_f32(e, w, take((size_t)cfg->vocab * H), (size_t)cfg->vocab * H, &e->word));
+    MX_TRY(put_f32(e, w, take((size_t)cfg->max_pos * H), (size_t)cfg->max_pos * H, &e->pos));
     e->pos += (size_t)cfg->pos_offset * H;  // RoBERTa-style tables: token t of a sequence uses row pos_offset + t
-    {
-        const float *ty = take((size_t)cfg->type_vocab * H);
-        MX_TRY(upload_f32(e, ty, H, &e->type0));  // token_type 0 only (single-segment inputs)
-    }
-    MX_TRY(upload_f32(e, take(H), H, &e->eg));
-    MX_TRY(upload_f32(e, take(H), H, &e->eb));
+    MX_TRY(put_f32(e, w, take((size_t)cfg->type_vocab * H), H, &e->type0));  // token_type 0 only (single-segment inputs)
+    MX_TRY(put_f32(e, w, take(H), H, &e->eg));
+    MX_TRY(put_f32(e, w, take(H), H, &e->eb));
     e->layers.resize(cfg->layers);
     for (Layer &L : e->layers) {
-        std::vector<float> wqkv(3 * H * H), bqkv(3 * H);
+        size_t wq[3], bq[3];
         for (int part = 0; part < 3; ++part) {
-            memcpy(wqkv.data() + part * H * H, take(H * H), H * H * sizeof(float));
-            memcpy(bqkv.data() + part * H, take(H), H * sizeof(float));
+            wq[part] = take(H * H);
+            bq[part] = take(H);
         }
-        if (e->precise) MX_TRY(upload_weight3(e, wqkv.data(), 3 * H, H, &L.wqkv3));
-        else MX_TRY(upload_weight(e, wqkv.data(), 3 * H, H, &L.wqkv));
-        MX_TRY(upload_f32(e, bqkv.data(), 3 * H, &L.bqkv));
-        const float *wo_src = take(H * H);
-        if (e->precise) MX_TRY(upload_weight3(e, wo_src, H, H, &L.wo3));
-        else MX_TRY(upload_weight(e, wo_src, H, H, &L.wo));
-        const float *bo_src = take(H), *g1_src = take(H), *be1_src = take(H);
-        MX_TRY(upload_f32(e, bo_src, H, &L.bo));
-        MX_TRY(upload_f32(e, g1_src, H, &L.ln1g));
-        MX_TRY(upload_f32(e, be1_src, H, &L.ln1b));
-        const float *wi_src = take(F * H);
-        if (e->mixed) MX_TRY(upload_weight2h(e, wi_src, F, H, &L.wi2h, e->mlp1 ? 1 : 2));
-        else if (e->precise) MX_TRY(upload_weight3(e, wi_src, F, H, &L.wi3));
-        else MX_TRY(upload_weight(e, wi_src, F, H, &L.wi));
-        const float *b1_src = take(F);
-        MX_TRY(upload_f32(e, b1_src, F, &L.bi));
-        const float *wo2_src = take(H * F);
-        if (e->mixed) MX_TRY(upload_weight2h(e, wo2_src, H, F, &L.wo22h, e->mlp1 ? 1 : 2));
-        else if (e->precise) MX_TRY(upload_weight3(e, wo2_src, H, F, &L.wo23));
-        else MX_TRY(upload_weight(e, wo2_src, H, F, &L.wo2));
-        if (e->fused_tail) MX_TRY(upload_tail_stream(e, wo_src, wi_src, wo2_src, F, &L.wf));
-        const float *b2_src = take(H), *g2_src = take(H), *be2_src = take(H);
-        MX_TRY(upload_f32(e, b2_src, H, &L.bo2));
-        MX_TRY(upload_f32(e, g2_src, H, &L.ln2g));
-        MX_TRY(upload_f32(e, be2_src, H, &L.ln2b));
+        MX_TRY(put_weight(e, w, wq, 3, H, H, form_a, e->precise ? &L.wqkv3 : &L.wqkv));
+        if (alloc_fixed(e, &L.bqkv, 3 * H * sizeof(float)) != hipSuccess) return bail(fail(MX_ENOMEM, "hipMalloc(qkv bias) failed"));
+        for (int part = 0; part < 3; ++part) MX_TRY(put_f32_at(e, w, bq[part], H, L.bqkv + part * H));
+        const size_t wo_src = take(H * H);
+        MX_TRY(put_weight(e, w, &wo_src, 1, H, H, form_a, e->precise ? &L.wo3 : &L.wo));
+        MX_TRY(put_f32(e, w, take(H), H, &L.bo));
+        MX_TRY(put_f32(e, w, take(H), H, &L.ln1g));
+        MX_TRY(put_f32(e, w, take(H), H, &L.ln1b));
+        const size_t wi_src = take(F * H);
+        MX_TRY(put_weight(e, w, &wi_src, 1, F, H, form_m, e->mixed ? &L.wi2h : e->precise ? &L.wi3 : &L.wi));
+        MX_TRY(put_f32(e, w, take(F), F, &L.bi));
+        const size_t wo2_src = take(H * F);
+        MX_TRY(put_weight(e, w, &wo2_src, 1, H, F, form_m, e->mixed ? &L.wo22h : e->precise ? &L.wo23 : &L.wo2));
+        // (the fragment stream is laid out on the host on either route: bf16 at hidden 384 only)
+        if (e->fused_tail) MX_TRY(upload_tail_stream(e, w.host + wo_src, w.host + wi_src, w.host + wo2_src, F, &L.wf));
+        MX_TRY(put_f32(e, w, take(H), H, &L.bo2));
+        MX_TRY(put_f32(e, w, take(H), H, &L.ln2g));
+        MX_TRY(put_f32(e, w, take(H), H, &L.ln2b));
     }
     if (!e->fused_tail && !e->precise && H == 768) {
         e->split_small = debug_flag("splitk", 1) != 0 && debug_flag("small", 1) != 0;  // (small=0: one kernel set at every pass size)
@@ -629,9 +655,37 @@ int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nby
             alloc_fixed(e, &e->sp_part, (size_t)(F / 128) * e->small_rows * H * sizeof(float)) != hipSuccess)
             return bail(fail(MX_ENOMEM, "hipMalloc(small-pass workspace) failed"));
     }
+    if (w.dev && hipStreamSynchronize(e->stream) != hipSuccess) return bail(fail(MX_EDEVICE, "weight conversion on the device failed"));
 #undef MX_TRY
     *out = e;
     return MX_OK;
+}
+
+extern "C" {
+
+size_t mx_encoder_cfg_size(void) { return sizeof(mx_encoder_cfg); }
+
+size_t mx_encoder_weight_bytes(const mx_encoder_cfg *c) {
+    if (!c) return 0;
+    const size_t H = (size_t)c->hidden, F = (size_t)c->ffn;
+    size_t n = ((size_t)c->vocab + c->max_pos + c->type_vocab) * H + 2 * H;
+    n += (size_t)c->layers * (3 * (H * H + H) + (H * H + H) + 2 * H + (F * H + F) + (H * F + H) + 2 * H);
+    return n * sizeof(float);
+}
+
+int mx_encoder_create(const mx_encoder_cfg *cfg, const void *weights, size_t nbytes, int device, mx_encoder **out) try {
+    if (!out) return fail(MX_EINVAL, "out is null");
+    *out = nullptr;
+    int rc = check_cfg(cfg);
+    if (rc != MX_OK) return rc;
+    if (!weights) return fail(MX_EINVAL, "weights is null");
+    if (nbytes != mx_encoder_weight_bytes(cfg))
+        return fail(MX_EINVAL, "weight blob is %zu bytes, config needs %zu", nbytes, mx_encoder_weight_bytes(cfg));
+    rc = check_device(device);
+    if (rc != MX_OK) return rc;
+    WeightBlob w;
+    w.host = static_cast<const float *>(weights);
+    return build_encoder(cfg, w, device, out);
 } catch (...) {
     return guard_exception();
 }
@@ -688,6 +742,258 @@ int mx_encoder_open(const char *key, const mx_encoder_cfg *cfg, const void *weig
     e->key = k;
     g_enc_registry[k] = e;
     *out = e;
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+// ---- the calibrated open (include/memex_hip.h: the rule, the bar, the probe)
+
+size_t mx_encoder_calibration_size(void) { return sizeof(mx_encoder_calibration); }
+
+static uint64_t splitmix64(uint64_t x) {
+    x += 0x9e3779b97f4a7c15ULL;
+    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
+    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
+    return x ^ (x >> 31);
+}
+
+constexpr int kProbeSeqs = 16, kProbeLen = 200;
+
+int mx_encoder_default_probe(const mx_encoder_cfg *cfg, int32_t *ids, int32_t *lens, int *B, int *S) try {
+    if (!cfg || !B || !S) return fail(MX_EINVAL, "null argument");
+    if (cfg->vocab < 1 || cfg->pos_offset < 0 || cfg->pos_offset >= cfg->max_pos) return fail(MX_EINVAL, "vocab / max_pos / pos_offset out of range");
+    if (!ids != !lens) return fail(MX_EINVAL, "ids and lens: both or neither");
+    const int n = std::min(kProbeLen, cfg->max_pos - cfg->pos_offset);
+    *B = kProbeSeqs;
+    *S = n;
+    if (!ids) return MX_OK;
+    for (int b = 0; b < kProbeSeqs; ++b) lens[b] = std::max(1, n / 2 + b * (n - n / 2) / (kProbeSeqs - 1));
+    for (int i = 0; i < kProbeSeqs * n; ++i) ids[i] = (int32_t)(splitmix64((uint64_t)i) % (uint64_t)cfg->vocab);
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+namespace {
+struct EncoderOwner {  // a private encoder of the calibration in flight
+    mx_encoder *e = nullptr;
+    ~EncoderOwner() {
+        if (e) destroy_impl(e);
+    }
+};
+}  // namespace
+
+// the calibration; keep != null: *keep = the chosen encoder (the measured one), else nothing stays
+static int calibrate_impl(const mx_encoder_cfg *cfg_in, const void *weights, size_t nbytes, int device, const int32_t *ids,
+                          const int32_t *lens, int B, int S, double bar, int flags, mx_encoder **keep, mx_encoder_calibration *rep) {
+    if (!cfg_in) return fail(MX_EINVAL, "cfg is null");
+    mx_encoder_cfg cfg = *cfg_in;
+    cfg.precision = MX_PREC_BF16X3;  // (the caller's value is ignored; the reference mode's limits are every mode's)
+    int rc = check_cfg(&cfg);
+    if (rc != MX_OK) return rc;
+    if (!weights) return fail(MX_EINVAL, "weights is null");
+    if (nbytes != mx_encoder_weight_bytes(&cfg))
+        return fail(MX_EINVAL, "weight blob is %zu bytes, config needs %zu", nbytes, mx_encoder_weight_bytes(&cfg));
+    if (!(bar > 0.0) || !std::isfinite(bar)) return fail(MX_EINVAL, "bar must be finite and > 0");
+    if (flags & ~MX_CALIBRATE_ALL) return fail(MX_EINVAL, "flags %d", flags);
+    std::vector<int32_t> own_ids, own_lens;
+    if (!ids) {
+        rc = mx_encoder_default_probe(&cfg, nullptr, nullptr, &B, &S);
+        if (rc != MX_OK) return rc;
+        own_ids.resize((size_t)B * S);
+        own_lens.resize((size_t)B);
+        rc = mx_encoder_default_probe(&cfg, own_ids.data(), own_lens.data(), &B, &S);
+        if (rc != MX_OK) return rc;
+        ids = own_ids.data();
+        lens = own_lens.data();
+    } else {
+        if (!lens) return fail(MX_EINVAL, "lens is null");
+        if (B < 2 || B > 64) return fail(MX_EINVAL, "probe of %d sequences (need 2 ... 64)", B);
+        const int s_max = std::min(512, cfg.max_pos - cfg.pos_offset);
+        if (S < 1 || S > s_max) return fail(MX_EINVAL, "probe S=%d outside [1, %d]", S, s_max);
+        for (int b = 0; b < B; ++b)
+            if (lens[b] < 1 || lens[b] > S) return fail(MX_EINVAL, "lens[%d] = %d outside [1, %d]", b, lens[b], S);
+    }
+    rc = check_device(device);
+    if (rc != MX_OK) return rc;
+    DeviceGuard g(device);
+    if (!g.ok) return fail(MX_EDEVICE, "hipSetDevice(%d) failed", device);
+    const auto t0 = std::chrono::steady_clock::now();
+
+    const double nan = std::nan("");
+    mx_encoder_calibration r{};
+    r.chosen = MX_PREC_BF16X3;
+    r.probe_seqs = B;
+    for (int b = 0; b < B; ++b) r.probe_tokens += lens[b];
+    r.bar = bar;
+    for (int m = 0; m < 4; ++m) r.pair_dev[m] = r.row_dev[m] = nan;
+
+    const size_t H = (size_t)cfg.hidden;
+    Dev<float> blob, e_ref, e_cand;
+    Dev<int32_t> d_ids, d_lens;
+    Dev<double> d_dev;
+    MX_HIP(blob.alloc_bytes(nbytes));
+    MX_HIP(e_ref.alloc((size_t)B * H));
+    MX_HIP(e_cand.alloc((size_t)B * H));
+    MX_HIP(d_ids.alloc((size_t)B * S));
+    MX_HIP(d_lens.alloc((size_t)B));
+    MX_HIP(d_dev.alloc(2));
+    MX_HIP(hipMemcpy(blob, weights, nbytes, hipMemcpyHostToDevice));  // the one upload
+    MX_HIP(hipMemcpy(d_ids, ids, (size_t)B * S * sizeof(int32_t), hipMemcpyHostToDevice));
+    MX_HIP(hipMemcpy(d_lens, lens, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+    WeightBlob w;
+    w.host = static_cast<const float *>(weights);
+    w.dev = blob;
+    // encodes the probe on `e` and compares with the reference's embeddings (or `with` = the encoder's own: a finiteness check)
+    auto measure = [&](mx_encoder *e, float *emb, const float *with, double dev[2]) -> int {
+        int mrc = encode_all(e, d_ids, lens, d_lens, B, S, emb);
+        if (mrc != MX_OK) return mrc;
+        MX_HIP(launch_embeddings_deviation(e->stream, emb, with, B, (int)H, d_dev));
+        MX_HIP(hipMemcpyAsync(dev, d_dev, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        MX_HIP(hipStreamSynchronize(e->stream));
+        return MX_OK;
+    };
+    EncoderOwner ref, kept;
+    double dev[2];
+    rc = build_encoder(&cfg, w, device, &ref.e);
+    if (rc != MX_OK) return rc;
+    rc = measure(ref.e, e_ref, e_ref, dev);
+    if (rc != MX_OK) return rc;
+    if (!std::isfinite(dev[0]) || !std::isfinite(dev[1]))
+        return fail(MX_EINVAL, "calibration: the bf16x3 reference gives non-finite or zero embeddings on the probe (damaged weights?)");
+    r.tried |= 1 << MX_PREC_BF16X3;
+    r.pair_dev[MX_PREC_BF16X3] = r.row_dev[MX_PREC_BF16X3] = 0.0;
+    for (int mode : {MX_PREC_BF16, MX_PREC_MIXED1, MX_PREC_MIXED}) {  // in order of cost (README: chunks/s by mode)
+        EncoderOwner cand;
+        cfg.precision = mode;
+        rc = build_encoder(&cfg, w, device, &cand.e);
+        if (rc != MX_OK) return rc;
+        rc = measure(cand.e, e_cand, e_ref, dev);
+        if (rc != MX_OK) return rc;
+        r.tried |= 1 << mode;
+        r.pair_dev[mode] = dev[0];
+        r.row_dev[mode] = dev[1];
+        if (!kept.e && dev[0] <= bar) {
+            r.chosen = mode;
+            std::swap(kept.e, cand.e);
+            if (!(flags & MX_CALIBRATE_ALL)) break;
+        }
+    }
+    if (!kept.e) std::swap(kept.e, ref.e);
+    r.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *rep = r;
+    if (keep) {
+        kept.e->stats = mx_encoder_stats{};
+        kept.e->calibrated = true;
+        kept.e->calib = r;
+        *keep = kept.e;
+        kept.e = nullptr;
+    }
+    return MX_OK;  // (the blob, the probe buffers and every encoder still owned here go now)
+}
+
+int mx_encoder_calibrate(const mx_encoder_cfg *cfg, const void *weights, size_t nbytes, int device, const int32_t *ids,
+                         const int32_t *lens, int B, int S, double bar, int flags, mx_encoder_calibration *out) try {
+    if (!out) return fail(MX_EINVAL, "out is null");
+    return calibrate_impl(cfg, weights, nbytes, device, ids, lens, B, S, bar, flags, nullptr, out);
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_encoder_open_calibrated(const char *key, const mx_encoder_cfg *cfg, const void *weights, size_t nbytes, int device,
+                               const int32_t *ids, const int32_t *lens, int B, int S, double bar, int flags,
+                               mx_encoder **out, mx_encoder_calibration *report) try {
+    if (!out) return fail(MX_EINVAL, "out is null");
+    *out = nullptr;
+    mx_encoder_calibration rep{};
+    const std::string k = key ? key : "";
+    if (k.empty()) {
+        const int rc = calibrate_impl(cfg, weights, nbytes, device, ids, lens, B, S, bar, flags, out, &rep);
+        if (rc == MX_OK && report) *report = rep;
+        return rc;
+    }
+    std::lock_guard<std::mutex> lk(g_enc_reg_mu);
+    auto it = g_enc_registry.find(k);
+    if (it != g_enc_registry.end()) {
+        mx_encoder *e = it->second;
+        if (cfg) {  // every field but the precision: that one is the resident handle's to name
+            mx_encoder_cfg want = *cfg;
+            want.precision = e->cfg.precision;
+            if (memcmp(&want, &e->cfg, sizeof(want)) != 0) return fail(MX_EINVAL, "encoder '%s' is resident with another configuration", k.c_str());
+        }
+        if (e->device != device) return fail(MX_EINVAL, "encoder '%s' lives on device %d, not %d", k.c_str(), e->device, device);
+        if (report) {
+            if (e->calibrated) {
+                *report = e->calib;
+            } else {  // opened by mx_encoder_open: nothing was measured
+                rep.chosen = e->cfg.precision;
+                rep.bar = std::nan("");
+                for (int m = 0; m < 4; ++m) rep.pair_dev[m] = rep.row_dev[m] = std::nan("");
+                *report = rep;
+            }
+        }
+        e->refs += 1;
+        *out = e;
+        return MX_OK;
+    }
+    mx_encoder *e = nullptr;
+    const int rc = calibrate_impl(cfg, weights, nbytes, device, ids, lens, B, S, bar, flags, &e, &rep);
+    if (rc != MX_OK) return rc;
+    e->key = k;
+    g_enc_registry[k] = e;
+    if (report) *report = rep;
+    *out = e;
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_encoder_get_cfg(mx_encoder *e, mx_encoder_cfg *out) try {
+    if (!e || !out) return fail(MX_EINVAL, "null argument");
+    *out = e->cfg;
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_encoder_weight_image(const float *w, int rows, int k, int form, int via_device, int device, uint16_t *out) try {
+    if (!w || !out) return fail(MX_EINVAL, "null argument");
+    if (rows < 1 || k < 32 || k % 32) return fail(MX_EINVAL, "rows %d, k %d: k must be a multiple of 32", rows, k);
+    if (form < MX_PREC_BF16 || form > MX_PREC_MIXED1) return fail(MX_EINVAL, "form %d", form);
+    const size_t n_out = (size_t)rows * k * form_copies(form);
+    if (!via_device) {
+        const std::vector<uint16_t> img = weight_image_host(w, (size_t)rows, (size_t)k, form);
+        memcpy(out, img.data(), n_out * sizeof(uint16_t));
+        return MX_OK;
+    }
+    const int rc = check_device(device);
+    if (rc != MX_OK) return rc;
+    DeviceGuard g(device);
+    if (!g.ok) return fail(MX_EDEVICE, "hipSetDevice(%d) failed", device);
+    Dev<float> src;
+    Dev<uint16_t> dst;
+    MX_HIP(src.alloc((size_t)rows * k));
+    MX_HIP(dst.alloc(n_out));
+    MX_HIP(hipMemcpy(src, w, (size_t)rows * k * sizeof(float), hipMemcpyHostToDevice));
+    MX_HIP(launch_weight_image(nullptr, src, (size_t)rows, (size_t)k, dst, (size_t)rows, 0, form));
+    MX_HIP(hipMemcpy(out, dst, n_out * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return MX_OK;
+} catch (...) {
+    return guard_exception();
+}
+
+int mx_embeddings_deviation_device(const float *d_a, const float *d_b, int B, int H, double *pair, double *row) try {
+    if (!d_a || !d_b || !pair || !row) return fail(MX_EINVAL, "null argument");
+    if (B < 2 || B > 64) return fail(MX_EINVAL, "B=%d (need 2 ... 64)", B);
+    if (H != 384 && H != 768) return fail(MX_EINVAL, "H=%d (384 or 768)", H);
+    Dev<double> d_dev;
+    double dev[2];
+    MX_HIP(d_dev.alloc(2));
+    MX_HIP(launch_embeddings_deviation(nullptr, d_a, d_b, B, H, d_dev));
+    MX_HIP(hipMemcpy(dev, d_dev, sizeof(dev), hipMemcpyDeviceToHost));
+    *pair = dev[0];
+    *row = dev[1];
     return MX_OK;
 } catch (...) {
     return guard_exception();

@@ -170,4 +170,13 @@ hipError_t launch_add_ln_split(hipStream_t s, const float *a, float *xf, bf16_t 
 hipError_t launch_attention_f32(hipStream_t s, const float *qkv, const int32_t *cu, const int32_t *lens, int B, int S, int heads,
                                 int d_head, int hidden, bf16_t *ctxs, bool f32_mfma, bool p_single);
 
+// ---- the calibrated open (encoder_calibrate.hip)
+// src [rows, k] f32 in HBM (16-byte aligned, k a multiple of 32) -> rows row0 .. row0 + rows of the K-blocked image dst
+// [k' / 32][rows_total][32], k' = k x {1, 3, 2, 1} by form (MX_PREC_*): what upload_weight / upload_weight3 / upload_weight2h
+// (copies 2, 1) of encoder.hip lay out on the host, bit for bit
+hipError_t launch_weight_image(hipStream_t s, const float *src, size_t rows, size_t k, uint16_t *dst, size_t rows_total, size_t row0, int form);
+// a, b [B, H] f32, 2 <= B <= 64, H 384 / 768 -> out2[0] = max_{i<j} |cos(a_i, a_j) - cos(b_i, b_j)|, out2[1] = max_i 1 - cos(a_i, b_i)
+// in f64, fixed summation order; both +inf on a non-finite value or a zero row
+hipError_t launch_embeddings_deviation(hipStream_t s, const float *a, const float *b, int B, int H, double *out2);
+
 }  // namespace mx

@@ -203,19 +203,21 @@ class SentenceEmbedder:
     """embedding.rs:78-152.  ``spawn`` starts the dedicated model thread and returns
     ``(thread, embedder)``; messages are ``(text, segment?, reply)`` on a queue bounded at 100."""
 
-    def __init__(self, q: "queue.Queue"):
+    def __init__(self, q: "queue.Queue", calibration=None):
         self._q = q
+        # the report of the calibrated open (memex_amd.encoder.Calibration) when the encoder was opened with precision "auto"
+        self.calibration = calibration
 
     @classmethod
     def spawn(cls, model_config: ModelConfig = ModelConfig(), weights=None, tokenizer=None, device: int = 0,
               encoder_config: Optional[W.EncoderConfig] = None, seed: int = 0, allow_synthetic: bool = False,
-              encoder_key: Optional[str] = None):
+              encoder_key: Optional[str] = None, calibration_texts: Optional[Sequence[str]] = None):
         """``weights``: HF tensor mapping / packed blob of the checkpoint; ``tokenizer``: path to its
         ``vocab.txt`` (native WordPiece) or ``tokenizer.json``, or a tokenizer object.  Like the
         reference (``create_model()`` / ``Tokenizer::from_pretrained`` failing -> SetupError,
         embedding.rs:99-100,163-169) a missing checkpoint or vocabulary is an error; the seeded
         stand-ins (synthetic weights, whitespace-hash tokenizer) used by tests and benchmarks must be
-        asked for with ``allow_synthetic=True``."""
+        asked for with ``allow_synthetic=True``.  ``calibration_texts``: see :meth:`from_pretrained_dir`."""
         if (weights is None or tokenizer is None) and not allow_synthetic:
             what = "weights" if weights is None else "tokenizer"
             raise SetupError(f"Unable to load model <{model_config.model.value}>: no {what} given "
@@ -223,21 +225,28 @@ class SentenceEmbedder:
         q: "queue.Queue" = queue.Queue(maxsize=100)                              # sync_channel(100), :87
         ready: "queue.Queue" = queue.Queue(maxsize=1)
         th = threading.Thread(target=cls._runner, args=(q, ready, model_config, weights, tokenizer, device,
-                                                        encoder_config, seed, encoder_key), daemon=True)
+                                                        encoder_config, seed, encoder_key, calibration_texts), daemon=True)
         th.start()
         err = ready.get()
-        if err is not None:
+        if isinstance(err, BaseException):
             raise err
-        return th, cls(q)
+        return th, cls(q, calibration=err)
 
     @classmethod
     def from_pretrained_dir(cls, path: str, model_config: ModelConfig = ModelConfig(), device: int = 0,
-                            precision: Optional[str] = None, encoder_key: Optional[str] = None):
+                            precision: Optional[str] = None, encoder_key: Optional[str] = None,
+                            calibration_texts: Optional[Sequence[str]] = None):
         """``create_model()`` from a LOCAL sentence-transformers directory -- the files
         ``SentenceEmbeddingsBuilder::remote(..)`` downloads (embedding.rs:99-100): ``modules.json``, ``config.json``,
         ``sentence_bert_config.json``, ``1_Pooling/config.json``, ``model.safetensors`` / ``pytorch_model.bin``,
         ``vocab.txt`` (:mod:`memex_amd.pretrained`).  Returns ``(thread, embedder)`` like :meth:`spawn`; a model the HIP
-        encoder does not run (a ``2_Dense`` module, max pooling, ...) raises :class:`SetupError`."""
+        encoder does not run (a ``2_Dense`` module, max pooling, ...) raises :class:`SetupError`.
+
+        ``precision="auto"``: the calibrated open (:class:`memex_amd.encoder.Encoder`) -- the cheapest precision mode that holds
+        the score bar on THESE weights; the embedder's ``calibration`` is its report, and a failed calibration is a
+        :class:`SetupError` like every other load failure.  ``calibration_texts``: 2 to 64 texts (more are ignored) of the
+        caller's own kind, tokenised by the model's tokenizer and truncated to ``max_seq_length``, as the probe instead of the
+        library's."""
         from .pretrained import UnsupportedModel, load_pretrained_dir
         try:
             cfg, tensors, vocab, info = load_pretrained_dir(path, precision)
@@ -254,10 +263,10 @@ class SentenceEmbedder:
         except Exception as e:
             raise SetupError(f"Unable to load model <{path}>: {e}") from e
         return cls.spawn(model_config, weights=tensors, tokenizer=tok, device=device, encoder_config=cfg,
-                         encoder_key=encoder_key)
+                         encoder_key=encoder_key, calibration_texts=calibration_texts)
 
     @staticmethod
-    def _runner(q, ready, model_config, weights, tokenizer, device, encoder_config, seed, encoder_key=None):
+    def _runner(q, ready, model_config, weights, tokenizer, device, encoder_config, seed, encoder_key=None, calibration_texts=None):
         try:
             cfg = encoder_config or _ENCODER_CONFIGS.get(model_config.model)
             if cfg is None:
@@ -267,11 +276,18 @@ class SentenceEmbedder:
             tok = _as_tokenizer(tokenizer, cfg.vocab)
             # create_model(), :99-100 -- keyed: embedders spawned per request / per task (handlers.rs:61-63,
             # tasks.rs:17) share one resident copy of the weights instead of re-uploading them
-            enc = Encoder(cfg, weights, device, key=encoder_key)
+            probe = None
+            if cfg.precision == "auto" and calibration_texts is not None:
+                texts = list(calibration_texts)[:64]
+                if len(texts) < 2:
+                    raise SetupError("calibration_texts: at least 2 texts are needed")
+                probe = tok.encode_batch(texts, cfg.max_seq_length)
+            enc = Encoder(cfg, weights, device, key=encoder_key, probe=probe)
+            cfg = enc.cfg  # (precision "auto" resolved to the chosen mode)
         except Exception as e:  # surfaces like RustBertError from runner
             ready.put(e if isinstance(e, EmbeddingError) else SetupError(str(e)))
             return
-        ready.put(None)
+        ready.put(enc.calibration)
         # Two stages, one thread each, a slot of one batch between them: while the GPU embeds batch i (a C call, no GIL) this
         # thread segments and tokenises batch i+1 -- host work per document (segment + tokenise its windows) is about as long
         # as its encoder pass, so the stages hide each other.  The reference's runner does both in turn per message (:101-109).

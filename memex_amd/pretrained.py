@@ -87,8 +87,9 @@ def default_precision(hidden: int, pooling: str) -> str:
 
 
 def load_pretrained_dir(path: str, precision: Optional[str] = None) -> Tuple[EncoderConfig, Dict[str, np.ndarray], Optional[str], dict]:
-    """-> (EncoderConfig, tensors by HF name, path of vocab.txt or None, info).  ``precision``: "bf16" | "bf16x3" | "mixed" | "mixed1", or
-    None = :func:`default_precision` of the model.
+    """-> (EncoderConfig, tensors by HF name, path of vocab.txt or None, info).  ``precision``: "bf16" | "bf16x3" | "mixed" | "mixed1", "auto"
+    (carried through in the returned config: the encoder is then opened calibrated, the mode measured on the loaded weights --
+    :class:`memex_amd.encoder.Encoder`), or None = :func:`default_precision` of the model.
 
     ``info``: ``do_lower_case``, ``model_type``, ``modules`` (the pipeline's module types in order), ``bpe_files``
     (``(vocab.json, merges.txt)`` of a byte-level BPE tokenizer, or None), ``tokenizer_json`` (path of ``tokenizer.json``, or
