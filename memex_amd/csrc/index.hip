@@ -363,20 +363,28 @@ struct mx_filter {
     std::vector<FilterShard> sh;     // one per shard; a plain index: one
 };
 
-// A grouping: one u32 key per GLOBAL row (id - id_offset - 1) of the handle it was made for, 0 = ungrouped, in one
-// array on the device of the index that owns the stream (shards[0] of a composite: where the merged lists of a search end up).  No
-// host mirror.  Every call that reads or edits a grouping holds the handle's mutex.
-struct mx_grouping {
+// A per-row column: one 32-bit word per GLOBAL row (id - id_offset - 1) of the handle it was made for, 0 where nothing
+// was set, in one array on the device of the index that owns the stream (shards[0] of a composite: where the merged lists of a search
+// end up).  No host mirror.  A grouping's keys and a prior's values are each one column; every call that reads or edits one holds the
+// handle's mutex.
+struct RowColumn {
+    const char *noun;                // what the column is to its caller, for messages: "grouping" or "prior"
     mx_index *idx = nullptr;
-    uint64_t epoch = 0;              // idx->row_epoch when the grouping was made
-    int device = 0;                  // where the keys live
-    Dev<uint32_t> keys;              // device: [len]; a row at or past len has key 0
+    uint64_t epoch = 0;              // idx->row_epoch when the column was made
+    int device = 0;                  // where the words live
+    Dev<uint32_t> words;             // device: [len]; a row at or past len has the word 0
     uint64_t len = 0;
-    Dev<void> stage;                 // device: the ranges or ids of the call in progress and their keys
+    Dev<void> stage;                 // device: the ranges, ids or keys of the call in progress and its words
     size_t stage_bytes = 0;
-    Dev<uint64_t> part;              // device: [2 * kGroupCountBlocks] the partial sums of a count
-    Dev<uint64_t> dead;              // device: the removal mask by global row a sharded handle's count is taken against
+    Dev<uint64_t> dead;              // device: the removal mask by global row a sharded handle's reduction is taken against
     size_t dead_words = 0;
+    const float *floats() const { return reinterpret_cast<const float *>(words.get()); }  // a prior's view of its words
+};
+
+// A grouping: a column of u32 keys, 0 = ungrouped.
+struct mx_grouping {
+    RowColumn col{"grouping"};
+    Dev<uint64_t> part;              // device: [2 * kGroupCountBlocks] the partial sums of a count
     // outputs of the host-pointer search [kMaxBatch, out_cap] that the index's staging block has no room for
     Dev<uint32_t> out_keys;
     Dev<int32_t> out_rows;
@@ -388,21 +396,12 @@ struct mx_grouping {
     int members_cap = 0;
 };
 
-// A prior: one f32 per GLOBAL row of the handle it was made for, 0 where nothing was set, kept where a grouping's
-// keys are and under the same rules.  hi >= every value of the array at all times: edits raise it on the host, a refresh replaces it
-// by the exact maximum over the live rows and 0.
+// A prior: a column of f32 values.  hi >= every value of the column at all times: edits raise it on the host, a
+// refresh replaces it by the exact maximum over the live rows and 0.
 struct mx_prior {
-    mx_index *idx = nullptr;
-    uint64_t epoch = 0;              // idx->row_epoch when the prior was made
-    int device = 0;                  // where the values live
-    Dev<float> vals;                 // device: [len]; a row at or past len has prior 0
-    uint64_t len = 0;
+    RowColumn col{"prior"};
     float hi = 0.0f;
-    Dev<void> stage;                 // device: the ranges or ids of the call in progress and their values
-    size_t stage_bytes = 0;
     Dev<float> part;                 // device: [kBoostMaxBlocks] the partial maxima of a refresh
-    Dev<uint64_t> dead;              // device: the removal mask by global row a sharded handle's refresh is taken against
-    size_t dead_words = 0;
     Dev<float> weights;              // device: [kMaxBatch] the weights of the batch in progress
     // outputs of the host-pointer search [kMaxBatch, out_cap] that the index's staging block has no room for
     Dev<float> out_priors;
@@ -412,6 +411,40 @@ struct mx_prior {
 };
 
 namespace {
+
+// the device buffers of a handle, released with their device current (under idx->mu)
+void free_buffers(mx_filter *f) {
+    for (FilterShard &fs : f->sh) {
+        DeviceGuard dg(fs.device);
+        fs.bits.reset();
+        fs.stage.reset();
+        fs.list.reset();
+    }
+}
+void free_buffers(RowColumn &c) {
+    c.words.reset();
+    c.stage.reset();
+    c.dead.reset();
+}
+void free_buffers(mx_grouping *g) {
+    DeviceGuard dg(g->col.device);
+    free_buffers(g->col);
+    g->part.reset();
+    g->out_keys.reset();
+    g->out_rows.reset();
+    g->out_complete.reset();
+    g->out_members.reset();
+    g->out_members_complete.reset();
+}
+void free_buffers(mx_prior *p) {
+    DeviceGuard dg(p->col.device);
+    free_buffers(p->col);
+    p->part.reset();
+    p->weights.reset();
+    p->out_priors.reset();
+    p->out_combined.reset();
+    p->out_complete.reset();
+}
 
 std::mutex g_reg_mu;
 std::map<std::string, mx_index *> g_registry;
@@ -3961,6 +3994,70 @@ namespace {
 // the plain index or shard that holds shard g of a filter's rows
 mx_index *filter_target(mx_index *idx, size_t g) { return idx->composite() ? idx->shards[g] : idx; }
 
+// the index that owns the stream, the candidate lists and the per-row columns of a handle
+mx_index *group_owner(mx_index *idx) { return idx->composite() ? idx->shards[0] : idx; }
+
+// For the scope, inside a call that holds idx->mu: t (idx itself, or the shard of it named; the owner by default) locked unless it is
+// idx, and its device current.
+struct OwnerLock {
+    mx_index *t;
+    std::unique_lock<std::mutex> lk;
+    DeviceGuard dg;
+    OwnerLock(mx_index *idx, mx_index *target) : t(target), lk(take(idx, target)), dg(target->device) {}
+    explicit OwnerLock(mx_index *idx) : OwnerLock(idx, group_owner(idx)) {}
+
+  private:
+    static std::unique_lock<std::mutex> take(const mx_index *idx, mx_index *t) {
+        std::unique_lock<std::mutex> l(t->mu, std::defer_lock);
+        if (t != idx) l.lock();
+        return l;
+    }
+};
+
+extern "C++" {  // (templates: the file's functions are declared inside extern "C")
+// The frame of mx_filter_create, mx_grouping_create and mx_prior_create.  The handle takes a reference of its own (the rows stay while
+// it lives, whoever closes the index), build(h) allocates under idx->mu; a failure frees what it allocated, gives the reference back
+// and keeps the error text.
+template <class H, class Build>
+int create_handle(mx_index *idx, H **out, Build build) {
+    if (!out) return fail(MX_EINVAL, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(MX_EINVAL, "null index");
+    {
+        std::lock_guard<std::mutex> lk(g_reg_mu);
+        idx->refs += 1;
+    }
+    std::unique_ptr<H> h(new H());
+    int rc = MX_OK;
+    {
+        std::lock_guard<std::mutex> lk(idx->mu);
+        rc = usable(idx);
+        if (rc == MX_OK && (rc = build(h.get())) != MX_OK) free_buffers(h.get());
+    }
+    if (rc != MX_OK) {
+        const std::string keep = last_error_slot();
+        mx_index_close(idx);
+        last_error_slot() = keep;
+        return rc;
+    }
+    *out = h.release();
+    return MX_OK;
+}
+
+// mx_filter_destroy, mx_grouping_destroy, mx_prior_destroy (no search that names the handle is inside the library)
+template <class H>
+void destroy_handle(H *h, mx_index *idx) {
+    try {
+        std::lock_guard<std::mutex> lk(idx->mu);
+        free_buffers(h);
+    } catch (...) {
+    }
+    delete h;
+    mx_index_close(idx);
+}
+
+}  // extern "C++"
+
 // the bitmap of one shard covers the shard's capacity: new words hold no row of the set (t's device is current)
 int ensure_filter_bits(mx_index *t, FilterShard &fs) {
     const size_t words = (size_t)(t->cap / kTile8Rows);
@@ -3985,15 +4082,6 @@ int ensure_filter_stage(FilterShard &fs, size_t words) {
     return MX_OK;
 }
 
-void free_filter_buffers(mx_filter *f) {
-    for (FilterShard &fs : f->sh) {
-        DeviceGuard dg(fs.device);
-        fs.bits.reset();
-        fs.stage.reset();
-        fs.list.reset();
-    }
-}
-
 // set_ranges on the handle's global rows (normalised, clipped to the rows); under idx->mu
 int filter_edit_ranges(mx_filter *f, const Ranges &rows, bool allow) {
     mx_index *idx = f->idx;
@@ -4002,9 +4090,7 @@ int filter_edit_ranges(mx_filter *f, const Ranges &rows, bool allow) {
     // every allocation first: a call that fails leaves the set as it was
     for (size_t g = 0; g < G; ++g) {
         mx_index *t = filter_target(idx, g);
-        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
-        if (t != idx) lk.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         if (idx->composite()) {
             for (const auto &x : shard_ranges(rows, idx->block_rows, (uint64_t)G, (uint64_t)g))
                 if (x.first < std::min(x.second, t->n)) loc[g].emplace_back(x.first, std::min(x.second, t->n));
@@ -4022,9 +4108,7 @@ int filter_edit_ranges(mx_filter *f, const Ranges &rows, bool allow) {
         if (loc[g].empty()) continue;
         mx_index *t = filter_target(idx, g);
         FilterShard &fs = f->sh[g];
-        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
-        if (t != idx) lk.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         flat.clear();
         for (const auto &x : loc[g]) {
             flat.push_back(x.first);
@@ -4047,9 +4131,7 @@ int filter_edit_ids(mx_filter *f, const uint64_t *ids, uint64_t n_ids, bool allo
     const uint64_t total = rows_of(idx), off = idx->idmap.id_offset, R = idx->block_rows;
     for (size_t g = 0; g < G; ++g) {
         mx_index *t = filter_target(idx, g);
-        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
-        if (t != idx) lk.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         if (int rc = ensure_filter_bits(t, f->sh[g]); rc != MX_OK) return rc;
         if (int rc = ensure_filter_stage(f->sh[g], (size_t)n_ids); rc != MX_OK) return rc;
     }
@@ -4057,9 +4139,7 @@ int filter_edit_ids(mx_filter *f, const uint64_t *ids, uint64_t n_ids, bool allo
     for (size_t g = 0; g < G; ++g) {
         mx_index *t = filter_target(idx, g);
         FilterShard &fs = f->sh[g];
-        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
-        if (t != idx) lk.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         fs.cached = false;
         MX_HIP(hipMemcpyAsync(fs.stage, ids, (size_t)n_ids * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
         MX_HIP(launch_filter_id_edit(t->stream, fs.stage, n_ids, total, t->idmap, allow, fs.bits, fs.words));
@@ -4101,53 +4181,24 @@ void filter_rows(mx_filter *f, Ranges &out) {
 }  // namespace
 
 int mx_filter_create(mx_index *idx, mx_filter **out) try {
-    if (!out) return fail(MX_EINVAL, "out is null");
-    *out = nullptr;
-    if (!idx) return fail(MX_EINVAL, "null index");
-    {   // the filter's own reference: the rows stay while it lives, whoever closes the index
-        std::lock_guard<std::mutex> lk(g_reg_mu);
-        idx->refs += 1;
-    }
-    std::unique_ptr<mx_filter> f(new mx_filter());
-    int rc = MX_OK;
-    {
-        std::lock_guard<std::mutex> lk(idx->mu);
-        rc = usable(idx);
+    return create_handle(idx, out, [idx](mx_filter *f) {
         f->idx = idx;
         f->epoch = idx->row_epoch;
         f->sh.resize(idx->composite() ? idx->shards.size() : 1);
-        for (size_t g = 0; g < f->sh.size() && rc == MX_OK; ++g) {
+        for (size_t g = 0; g < f->sh.size(); ++g) {
             mx_index *t = filter_target(idx, g);
-            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-            if (t != idx) l2.lock();
-            DeviceGuard dg(t->device);
+            OwnerLock own(idx, t);
             f->sh[g].device = t->device;
-            rc = ensure_filter_bits(t, f->sh[g]);
+            if (int rc = ensure_filter_bits(t, f->sh[g]); rc != MX_OK) return rc;
         }
-        if (rc != MX_OK) free_filter_buffers(f.get());
-    }
-    if (rc != MX_OK) {
-        const std::string keep = last_error_slot();
-        mx_index_close(idx);
-        last_error_slot() = keep;
-        return rc;
-    }
-    *out = f.release();
-    return MX_OK;
+        return (int)MX_OK;
+    });
 } catch (...) {
     return guard_exception();
 }
 
 void mx_filter_destroy(mx_filter *f) {
-    if (!f) return;
-    mx_index *idx = f->idx;
-    try {
-        std::lock_guard<std::mutex> lk(idx->mu);  // (no search that names the filter is inside the library)
-        free_filter_buffers(f);
-    } catch (...) {
-    }
-    delete f;
-    mx_index_close(idx);
+    if (f) destroy_handle(f, f->idx);
 }
 
 int mx_filter_set_ranges(mx_filter *f, const uint64_t *ranges, uint64_t n_ranges, int allow) try {
@@ -4452,54 +4503,54 @@ int mx_index_search_fused_device(mx_index *idx, const float *d_q, int R, int m, 
     return guard_exception();
 }
 
-// ---- grouped search (mx_grouping, mx_index_search_grouped) ----------------------------------------------------------
+// ---- per-row columns and grouped search (RowColumn, mx_grouping, mx_index_search_grouped) ---------------------------
 namespace {
 
-// the index that owns the stream, the candidate lists and the keys of a grouping
-mx_index *group_owner(mx_index *idx) { return idx->composite() ? idx->shards[0] : idx; }
-
-// a grouping named in a call on idx (under idx->mu): made for this handle, and not older than its rows
-int check_grouping(const mx_index *idx, const mx_grouping *g) {
-    if (g->idx != idx) return fail(MX_EINVAL, "the grouping was made for another index");
-    if (g->epoch != idx->row_epoch)
-        return fail(MX_EINVAL, "the grouping is stale: the index was cleared, loaded or compacted after it was made (destroy it and make a new one)");
+// a column named in a call on idx (under idx->mu): made for this handle, and not older than its rows
+int check_column(const mx_index *idx, const RowColumn &c) {
+    if (c.idx != idx) return fail(MX_EINVAL, "the %s was made for another index", c.noun);
+    if (c.epoch != idx->row_epoch)
+        return fail(MX_EINVAL, "the %s is stale: the index was cleared, loaded or compacted after it was made (destroy it and make a new one)",
+                    c.noun);
     return MX_OK;
 }
 
-// the key array covers `rows` rows: a new block, the old keys copied, the rest zero (the owner's device is current)
-int ensure_group_keys(mx_grouping *g, mx_index *t, uint64_t rows) {
-    if (rows <= g->len) return MX_OK;
+// the head of every mx_grouping_* and mx_prior_* call but create and destroy; the caller holds idx->mu
+int column_ready(const RowColumn &c) {
+    if (int rc = usable(c.idx); rc != MX_OK) return rc;
+    return check_column(c.idx, c);
+}
+
+// the words cover `rows` rows: a new block, the old words copied, the rest zero (the owner's device is current)
+int ensure_column_rows(RowColumn &c, mx_index *t, uint64_t rows) {
+    if (rows <= c.len) return MX_OK;
     const uint64_t want = (rows + 1023) / 1024 * 1024;
     Dev<uint32_t> nb;
     MX_HIP(nb.alloc((size_t)want));
-    if (g->len) MX_HIP(hipMemcpyAsync(nb, g->keys, (size_t)g->len * sizeof(uint32_t), hipMemcpyDeviceToDevice, t->stream));
-    MX_HIP(hipMemsetAsync(nb.get() + g->len, 0, (size_t)(want - g->len) * sizeof(uint32_t), t->stream));
+    if (c.len) MX_HIP(hipMemcpyAsync(nb, c.words, (size_t)c.len * sizeof(uint32_t), hipMemcpyDeviceToDevice, t->stream));
+    MX_HIP(hipMemsetAsync(nb.get() + c.len, 0, (size_t)(want - c.len) * sizeof(uint32_t), t->stream));
     MX_HIP(hipStreamSynchronize(t->stream));
-    g->keys = std::move(nb);
-    g->len = want;
+    c.words = std::move(nb);
+    c.len = want;
     return MX_OK;
 }
 
-int ensure_group_stage(mx_grouping *g, size_t bytes) {
-    if (g->stage_bytes >= bytes) return MX_OK;
-    g->stage_bytes = 0;
+int ensure_column_stage(RowColumn &c, size_t bytes) {
+    if (c.stage_bytes >= bytes) return MX_OK;
+    c.stage_bytes = 0;
     const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-    MX_HIP(g->stage.alloc_bytes(want));  // (every call is host-synchronised before it returns)
-    g->stage_bytes = want;
+    MX_HIP(c.stage.alloc_bytes(want));  // (every call is host-synchronised before it returns)
+    c.stage_bytes = want;
     return MX_OK;
 }
 
-void free_grouping_buffers(mx_grouping *g) {
-    DeviceGuard dg(g->device);
-    g->keys.reset();
-    g->stage.reset();
-    g->part.reset();
-    g->dead.reset();
-    g->out_keys.reset();
-    g->out_rows.reset();
-    g->out_complete.reset();
-    g->out_members.reset();
-    g->out_members_complete.reset();
+// what mx_grouping_create and mx_prior_create build (under idx->mu): a column over the rows of the moment, all zero
+int make_column(RowColumn &c, mx_index *idx) {
+    OwnerLock own(idx);
+    c.idx = idx;
+    c.epoch = idx->row_epoch;
+    c.device = own.t->device;
+    return ensure_column_rows(c, own.t, rows_of(idx));
 }
 
 // ---- host checks of the per-row edits (a grouping's keys, a prior's values: 32-bit words either way) -----------------------------------
@@ -4601,11 +4652,187 @@ int dead_mask_on_device(mx_index *idx, mx_index *t, const std::vector<uint64_t> 
     return MX_OK;
 }
 
-// the head of every mx_grouping_* call but create and destroy; the caller holds idx->mu
-int grouping_ready(mx_grouping *g) {
-    if (int rc = usable(g->idx); rc != MX_OK) return rc;
-    return check_grouping(g->idx, g);
+extern "C++" {  // (templates: the file's functions are declared inside extern "C")
+// The edits and the read of a column, after the entry point's own checks of its arguments.  Each takes the handle's mutex, and the
+// owner's for the device work.  Every allocation comes first, the rows before the stage: a call that fails leaves the words as they
+// were.  commit() runs once in an edit that gets as far as storing (before the store is queued), or that has no row to store to.
+
+// set_ranges: the spans of read_word_spans
+template <class Commit>
+int column_set_ranges(RowColumn &c, const std::vector<WordSpan> &sp, Commit commit) {
+    mx_index *idx = c.idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = column_ready(c); rc != MX_OK) return rc;
+    std::vector<uint64_t> rows;
+    std::vector<uint32_t> rw;
+    spans_to_rows(sp, idx->idmap.id_offset, rows_of(idx), &rows, &rw);
+    if (rw.empty()) {
+        commit();
+        return MX_OK;
+    }
+    OwnerLock own(idx);
+    mx_index *t = own.t;
+    const size_t rb = rows.size() * sizeof(uint64_t), wb = rw.size() * sizeof(uint32_t);
+    if (int rc = ensure_column_rows(c, t, rows.back()); rc != MX_OK) return rc;
+    if (int rc = ensure_column_stage(c, rb + wb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(c.stage.get());
+    MX_HIP(hipMemcpyAsync(st, rows.data(), rb, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(hipMemcpyAsync(st + rb, rw.data(), wb, hipMemcpyHostToDevice, t->stream));
+    commit();
+    MX_HIP(launch_grouping_range_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + rb),
+                                      (uint32_t)rw.size(), rows.front(), rows.back(), c.words));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
 }
+
+// set_ids: words[i] for the row of ids[i]; an id that names no row is passed over
+template <class Commit>
+int column_set_ids(RowColumn &c, const uint64_t *ids, const uint32_t *words, uint64_t n_ids, Commit commit) {
+    mx_index *idx = c.idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = column_ready(c); rc != MX_OK) return rc;
+    const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
+    const uint64_t top = top_row_named(ids, n_ids, off, total);
+    if (top == 0) {
+        commit();
+        return MX_OK;
+    }
+    OwnerLock own(idx);
+    mx_index *t = own.t;
+    const size_t ib = (size_t)n_ids * sizeof(uint64_t), wb = (size_t)n_ids * sizeof(uint32_t);
+    if (int rc = ensure_column_rows(c, t, top); rc != MX_OK) return rc;
+    if (int rc = ensure_column_stage(c, ib + wb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(c.stage.get());
+    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(hipMemcpyAsync(st + ib, words, wb, hipMemcpyHostToDevice, t->stream));
+    commit();
+    MX_HIP(launch_grouping_id_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + ib), n_ids, off,
+                                   std::min(total, c.len), c.words));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+}
+
+// words[i] = the word of the row of ids[i]; 0 for an id that names no row (as a prior's value: +0.0f)
+int column_get(RowColumn &c, const uint64_t *ids, uint64_t n_ids, void *words) {
+    mx_index *idx = c.idx;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = column_ready(c); rc != MX_OK) return rc;
+    if (n_ids == 0) return MX_OK;
+    OwnerLock own(idx);
+    mx_index *t = own.t;
+    const size_t ib = (size_t)n_ids * sizeof(uint64_t), wb = (size_t)n_ids * sizeof(uint32_t);
+    if (int rc = ensure_column_stage(c, ib + wb); rc != MX_OK) return rc;
+    char *st = static_cast<char *>(c.stage.get());
+    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
+    MX_HIP(launch_grouping_get(t->stream, reinterpret_cast<const uint64_t *>(st), n_ids, idx->idmap.id_offset, std::min(rows_of(idx), c.len),
+                               c.words, reinterpret_cast<uint32_t *>(st + ib)));
+    MX_HIP(hipMemcpyAsync(words, st + ib, wb, hipMemcpyDeviceToHost, t->stream));
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+}
+
+// ---- the call path of the searches that re-rank the top-fetch rows by a column: grouped, group-rows, capped, boosted ------------------
+constexpr int kRerankExtras = 5;
+
+// one output of such a search beyond ids, scores, dists and n_found
+struct RerankOut {
+    void *dev;     // device: [kMaxBatch, per] the handle's buffer a host-pointer call stages the output in
+    void *user;    // the caller's array, host or device memory as the call's other arrays; null: not wanted
+    size_t elem;   // bytes per element
+    size_t per;    // elements per query
+};
+
+// where one batch leaves its results, all on the owner's device; x[i]: output i, null where the caller wants none
+struct RerankDst {
+    uint64_t *ids;
+    float *scores, *dists;
+    int32_t *nfound;
+    void *x[kRerankExtras];
+};
+
+// handles named in such a search (under idx->mu)
+int check_rerank_handles(mx_index *idx, const RowColumn &c, mx_filter *f) {
+    if (int rc = usable(idx); rc != MX_OK) return rc;
+    if (int rc = check_column(idx, c); rc != MX_OK) return rc;
+    return f ? check_filter(idx, f) : MX_OK;
+}
+
+// One batch (B <= kMaxBatch), queries and outputs on the device of the index that owns the stream, the caller holding idx->mu across
+// both stages: a plain (or resident-filtered) search pass at k = fetch into that index's lists (the diversified search's: a sharded
+// handle has them merged on devices[0] already, which is where the column is), then rank(t, b0, B, dst), which queues the feature's
+// one kernel; host-synchronised.
+template <class Rank>
+int rerank_batch(mx_index *idx, mx_filter *f, const float *d_q, int b0, int B, int fetch, const RerankDst &dst, Rank rank) {
+    mx_index *t = group_owner(idx);
+    int rc = ensure_mmr_lists(t, fetch);
+    if (rc != MX_OK) return rc;
+    const FilterArg fa{nullptr, f, 0};
+    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf, f ? &fa : nullptr)) != MX_OK) return rc;
+    if ((rc = rank(t, b0, B, dst)) != MX_OK) return rc;
+    MX_HIP(hipStreamSynchronize(t->stream));
+    return MX_OK;
+}
+
+// The host-pointer variants: queries staged per batch of kMaxBatch, ids, scores, dists (width per query) and n_found through the
+// owner's staging block, the nx outputs of x through the handle's buffers, which size_outputs() allocates and enters into x as dev.  Not
+// combined with other callers: the call holds the index across the candidate stage and the re-ranking, like a device-pointer call.
+template <class Size, class Rank>
+int rerank_host(mx_index *idx, const RowColumn &c, mx_filter *f, const float *q, int B, int width, int fetch, RerankOut *x, int nx,
+                Size size_outputs, Rank rank, uint64_t *ids, float *scores, float *dists, int32_t *n_found) {
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    const size_t dim = (size_t)idx->dim;
+    for (size_t i = 0; i < (size_t)B * dim; ++i)
+        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_rerank_handles(idx, c, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);  // owner of the staging buffers and the stream
+    DeviceGuard dg(t->device);
+    int rc = ensure_scratch(t);
+    if (rc != MX_OK) return rc;
+    if ((rc = ensure_out(t, width)) != MX_OK) return rc;
+    if ((rc = size_outputs()) != MX_OK) return rc;
+    Scratch &s = t->s;
+    RerankDst dst{s.out_ids, s.out_scores, s.out_dists, s.out_nfound, {}};
+    for (int i = 0; i < nx; ++i) dst.x[i] = x[i].dev;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * width;
+        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
+        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        if ((rc = rerank_batch(idx, f, s.qstage, b0, nb, fetch, dst, rank)) != MX_OK) return rc;
+        for (int i = 0; i < nx; ++i)
+            if (x[i].user)
+                MX_HIP(hipMemcpyAsync(static_cast<char *>(x[i].user) + (size_t)b0 * x[i].per * x[i].elem, x[i].dev,
+                                      (size_t)nb * x[i].per * x[i].elem, hipMemcpyDeviceToHost, t->stream));
+        if ((rc = copy_out_to_host(t, nb, width, false)) != MX_OK) return rc;
+        scatter_to_caller(s, 0, nb, width, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, nullptr);
+    }
+    return MX_OK;
+}
+
+// the device-pointer variants: every batch writes straight into the caller's arrays; prepare() allocates what rank needs besides
+template <class Prepare, class Rank>
+int rerank_device(mx_index *idx, const RowColumn &c, mx_filter *f, const float *d_q, int B, int width, int fetch, const RerankOut *x, int nx,
+                  Prepare prepare, Rank rank, uint64_t *d_ids, float *d_scores, float *d_dists, int32_t *d_nfound) {
+    if (!idx) return fail(MX_ESEARCH, "null index");
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (int rc = check_rerank_handles(idx, c, f); rc != MX_OK) return rc;
+    if (B == 0) return MX_OK;
+    mx_index *t = group_owner(idx);
+    DeviceGuard dg(t->device);
+    if (int rc = prepare(); rc != MX_OK) return rc;
+    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, B - b0);
+        const size_t o = (size_t)b0 * width;
+        RerankDst dst{d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr, d_nfound + b0, {}};
+        for (int i = 0; i < nx; ++i) dst.x[i] = x[i].user ? static_cast<char *>(x[i].user) + (size_t)b0 * x[i].per * x[i].elem : nullptr;
+        if (int rc = rerank_batch(idx, f, d_q + (size_t)b0 * idx->dim, b0, nb, fetch, dst, rank); rc != MX_OK) return rc;
+    }
+    return MX_OK;
+}
+
+}  // extern "C++"
 
 // arguments of the grouped-search entry points, checked before the index is looked at
 int read_grouped_args(int B, int k, int fetch, const mx_grouping *g, const void *q, const void *ids, const void *scores, const void *n_found) {
@@ -4618,80 +4845,55 @@ int read_grouped_args(int B, int k, int fetch, const mx_grouping *g, const void 
     return MX_OK;
 }
 
-// One batch (B <= kMaxBatch) of a grouped search, queries and outputs on the device of the index that owns the stream, the caller
-// holding idx->mu across both stages: a plain (or resident-filtered) search pass at k = fetch into that index's lists (the
-// diversified search's: a sharded handle has them merged on devices[0] already, which is where the keys are), one group_heads_kernel
-// launch; host-synchronised.
-int grouped_batch(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int fetch, uint64_t *d_ids, float *d_scores,
-                  float *d_dists, uint32_t *d_keys, int32_t *d_rows, int32_t *d_nfound, uint8_t *d_complete) {
-    mx_index *t = group_owner(idx);
-    int rc = ensure_mmr_lists(t, fetch);
-    if (rc != MX_OK) return rc;
-    const FilterArg fa{nullptr, f, 0};
-    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf, f ? &fa : nullptr)) != MX_OK) return rc;
-    GroupHeads p{B, k, fetch, idx->idmap.id_offset, g->len, g->keys, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf,
-                 d_ids, d_scores, d_dists, d_keys, d_rows, d_nfound, d_complete};
-    MX_HIP(launch_group_heads(t->stream, p));
-    MX_HIP(hipStreamSynchronize(t->stream));
+// the per-head staging of the host-pointer variants covers k heads per query (the owner's device is current); members: also the
+// group-rows form's
+int ensure_group_out(mx_grouping *g, int k, bool members) {
+    const size_t kc = (size_t)std::max(k, 16);
+    if (k > g->out_cap) {
+        g->out_cap = 0;
+        MX_HIP(g->out_keys.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_rows.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_complete.alloc(kMaxBatch));
+        g->out_cap = (int)kc;
+    }
+    if (members && k > g->members_cap) {
+        g->members_cap = 0;
+        MX_HIP(g->out_members.alloc((size_t)kMaxBatch * kc));
+        MX_HIP(g->out_members_complete.alloc((size_t)kMaxBatch * kc));
+        g->members_cap = (int)kc;
+    }
     return MX_OK;
 }
 
-// handles named in a grouped search (under idx->mu)
-int check_grouped_handles(mx_index *idx, mx_grouping *g, mx_filter *f) {
-    if (int rc = usable(idx); rc != MX_OK) return rc;
-    if (int rc = check_grouping(idx, g); rc != MX_OK) return rc;
-    return f ? check_filter(idx, f) : MX_OK;
+// both variants of the grouped search: one group_heads_kernel launch per batch
+int grouped_search(bool host, mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int fetch, uint64_t *ids, float *scores,
+                   float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_found, uint8_t *complete) {
+    RerankOut x[] = {{nullptr, keys, sizeof(uint32_t), (size_t)k}, {nullptr, group_rows, sizeof(int32_t), (size_t)k}, {nullptr, complete, 1, 1}};
+    auto rank = [&](mx_index *t, int, int nb, const RerankDst &d) {
+        GroupHeads p{nb, k, fetch, idx->idmap.id_offset, g->col.len, g->col.words, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf,
+                     d.ids, d.scores, d.dists, (uint32_t *)d.x[0], (int32_t *)d.x[1], d.nfound, (uint8_t *)d.x[2]};
+        MX_HIP(launch_group_heads(t->stream, p));
+        return (int)MX_OK;
+    };
+    auto size_outputs = [&] {
+        if (int rc = ensure_group_out(g, k, false); rc != MX_OK) return rc;
+        x[0].dev = g->out_keys, x[1].dev = g->out_rows, x[2].dev = g->out_complete;
+        return (int)MX_OK;
+    };
+    if (host) return rerank_host(idx, g->col, f, q, B, k, fetch, x, 3, size_outputs, rank, ids, scores, dists, n_found);
+    return rerank_device(idx, g->col, f, q, B, k, fetch, x, 3, [] { return (int)MX_OK; }, rank, ids, scores, dists, n_found);
 }
 
 }  // namespace
 
 int mx_grouping_create(mx_index *idx, mx_grouping **out) try {
-    if (!out) return fail(MX_EINVAL, "out is null");
-    *out = nullptr;
-    if (!idx) return fail(MX_EINVAL, "null index");
-    {   // the grouping's own reference: the rows stay while it lives, whoever closes the index
-        std::lock_guard<std::mutex> lk(g_reg_mu);
-        idx->refs += 1;
-    }
-    std::unique_ptr<mx_grouping> g(new mx_grouping());
-    int rc = MX_OK;
-    {
-        std::lock_guard<std::mutex> lk(idx->mu);
-        rc = usable(idx);
-        mx_index *t = group_owner(idx);
-        g->idx = idx;
-        g->epoch = idx->row_epoch;
-        g->device = t->device;
-        if (rc == MX_OK) {
-            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-            if (t != idx) l2.lock();
-            DeviceGuard dg(t->device);
-            rc = ensure_group_keys(g.get(), t, rows_of(idx));
-        }
-        if (rc != MX_OK) free_grouping_buffers(g.get());
-    }
-    if (rc != MX_OK) {
-        const std::string keep = last_error_slot();
-        mx_index_close(idx);
-        last_error_slot() = keep;
-        return rc;
-    }
-    *out = g.release();
-    return MX_OK;
+    return create_handle(idx, out, [idx](mx_grouping *g) { return make_column(g->col, idx); });
 } catch (...) {
     return guard_exception();
 }
 
 void mx_grouping_destroy(mx_grouping *g) {
-    if (!g) return;
-    mx_index *idx = g->idx;
-    try {
-        std::lock_guard<std::mutex> lk(idx->mu);  // (no search that names the grouping is inside the library)
-        free_grouping_buffers(g);
-    } catch (...) {
-    }
-    delete g;
-    mx_index_close(idx);
+    if (g) destroy_handle(g, g->col.idx);
 }
 
 int mx_grouping_set_ranges(mx_grouping *g, const uint64_t *ranges, const uint32_t *keys, uint64_t n_ranges) try {
@@ -4699,28 +4901,7 @@ int mx_grouping_set_ranges(mx_grouping *g, const uint64_t *ranges, const uint32_
     if ((!ranges || !keys) && n_ranges) return fail(MX_EINVAL, "null ranges or keys with n_ranges = %llu", (unsigned long long)n_ranges);
     std::vector<WordSpan> sp;
     if (int rc = read_word_spans(ranges, keys, n_ranges, &sp); rc != MX_OK) return rc;
-    mx_index *idx = g->idx;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
-    std::vector<uint64_t> rows;
-    std::vector<uint32_t> rk;
-    spans_to_rows(sp, idx->idmap.id_offset, rows_of(idx), &rows, &rk);
-    if (rk.empty()) return MX_OK;
-    mx_index *t = group_owner(idx);
-    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-    if (t != idx) l2.lock();
-    DeviceGuard dg(t->device);
-    // every allocation first: a call that fails leaves the keys as they were
-    const size_t rb = rows.size() * sizeof(uint64_t), kb = rk.size() * sizeof(uint32_t);
-    if (int rc = ensure_group_keys(g, t, rows.back()); rc != MX_OK) return rc;
-    if (int rc = ensure_group_stage(g, rb + kb); rc != MX_OK) return rc;
-    char *st = static_cast<char *>(g->stage.get());
-    MX_HIP(hipMemcpyAsync(st, rows.data(), rb, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(hipMemcpyAsync(st + rb, rk.data(), kb, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(launch_grouping_range_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + rb),
-                                      (uint32_t)rk.size(), rows.front(), rows.back(), g->keys));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
+    return column_set_ranges(g->col, sp, [] {});
 } catch (...) {
     return guard_exception();
 }
@@ -4729,26 +4910,7 @@ int mx_grouping_set_ids(mx_grouping *g, const uint64_t *ids, const uint32_t *key
     if (!g) return fail(MX_EINVAL, "null grouping");
     if ((!ids || !keys) && n_ids) return fail(MX_EINVAL, "null ids or keys with n_ids = %llu", (unsigned long long)n_ids);
     if (int rc = check_id_words(ids, keys, n_ids, "keys"); rc != MX_OK) return rc;
-    mx_index *idx = g->idx;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
-    const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
-    const uint64_t top = top_row_named(ids, n_ids, off, total);
-    if (top == 0) return MX_OK;
-    mx_index *t = group_owner(idx);
-    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-    if (t != idx) l2.lock();
-    DeviceGuard dg(t->device);
-    const size_t ib = (size_t)n_ids * sizeof(uint64_t), kb = (size_t)n_ids * sizeof(uint32_t);
-    if (int rc = ensure_group_keys(g, t, top); rc != MX_OK) return rc;
-    if (int rc = ensure_group_stage(g, ib + kb); rc != MX_OK) return rc;
-    char *st = static_cast<char *>(g->stage.get());
-    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(hipMemcpyAsync(st + ib, keys, kb, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(launch_grouping_id_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + ib), n_ids, off,
-                                   std::min(total, g->len), g->keys));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
+    return column_set_ids(g->col, ids, keys, n_ids, [] {});
 } catch (...) {
     return guard_exception();
 }
@@ -4756,46 +4918,29 @@ int mx_grouping_set_ids(mx_grouping *g, const uint64_t *ids, const uint32_t *key
 int mx_grouping_get_keys(mx_grouping *g, const uint64_t *ids, uint64_t n_ids, uint32_t *keys) try {
     if (!g) return fail(MX_EINVAL, "null grouping");
     if ((!ids || !keys) && n_ids) return fail(MX_EINVAL, "null ids or keys with n_ids = %llu", (unsigned long long)n_ids);
-    mx_index *idx = g->idx;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
-    if (n_ids == 0) return MX_OK;
-    mx_index *t = group_owner(idx);
-    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-    if (t != idx) l2.lock();
-    DeviceGuard dg(t->device);
-    const size_t ib = (size_t)n_ids * sizeof(uint64_t), kb = (size_t)n_ids * sizeof(uint32_t);
-    if (int rc = ensure_group_stage(g, ib + kb); rc != MX_OK) return rc;
-    char *st = static_cast<char *>(g->stage.get());
-    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(launch_grouping_get(t->stream, reinterpret_cast<const uint64_t *>(st), n_ids, idx->idmap.id_offset, std::min(rows_of(idx), g->len),
-                               g->keys, reinterpret_cast<uint32_t *>(st + ib)));
-    MX_HIP(hipMemcpyAsync(keys, st + ib, kb, hipMemcpyDeviceToHost, t->stream));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
+    return column_get(g->col, ids, n_ids, keys);
 } catch (...) {
     return guard_exception();
 }
 
 int mx_grouping_count(mx_grouping *g, uint64_t *n_keyed, uint64_t *n_live_keyed) try {
     if (!g) return fail(MX_EINVAL, "null grouping");
-    mx_index *idx = g->idx;
+    RowColumn &c = g->col;
+    mx_index *idx = c.idx;
     std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
-    const uint64_t n = std::min(rows_of(idx), g->len);
+    if (int rc = column_ready(c); rc != MX_OK) return rc;
+    const uint64_t n = std::min(rows_of(idx), c.len);
     uint64_t a = 0, l = 0;
     if (n) {
-        mx_index *t = group_owner(idx);
         std::vector<uint64_t> mask;
         composite_dead_mask(idx, n, &mask);
-        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-        if (t != idx) l2.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx);
+        mx_index *t = own.t;
         if (!g->part) MX_HIP(g->part.alloc(2 * kGroupCountBlocks));
         const uint64_t *d_dead = nullptr;
-        if (int rc = dead_mask_on_device(idx, t, mask, g->dead, g->dead_words, &d_dead); rc != MX_OK) return rc;
+        if (int rc = dead_mask_on_device(idx, t, mask, c.dead, c.dead_words, &d_dead); rc != MX_OK) return rc;
         uint64_t part[2 * kGroupCountBlocks];
-        MX_HIP(launch_grouping_count(t->stream, g->keys, n, d_dead, g->part));
+        MX_HIP(launch_grouping_count(t->stream, c.words, n, d_dead, g->part));
         MX_HIP(hipMemcpyAsync(part, g->part, sizeof(part), hipMemcpyDeviceToHost, t->stream));
         MX_HIP(hipStreamSynchronize(t->stream));
         for (int w = 0; w < kGroupCountBlocks; ++w) {
@@ -4813,43 +4958,7 @@ int mx_grouping_count(mx_grouping *g, uint64_t *n_keyed, uint64_t *n_live_keyed)
 int mx_index_search_grouped(mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int fetch, uint64_t *ids,
                             float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_found, uint8_t *complete) try {
     if (int rc = read_grouped_args(B, k, fetch, g, q, ids, scores, n_found); rc != MX_OK) return rc;
-    if (!idx) return fail(MX_ESEARCH, "null index");
-    const size_t dim = (size_t)idx->dim;
-    for (size_t i = 0; i < (size_t)B * dim; ++i)
-        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
-    // not combined with other callers: the call holds the index across the candidate stage and the grouping, like a device-pointer call
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
-    if (B == 0) return MX_OK;
-    mx_index *t = group_owner(idx);  // owner of the staging buffers and the stream
-    DeviceGuard dg(t->device);
-    int rc = ensure_scratch(t);
-    if (rc != MX_OK) return rc;
-    if ((rc = ensure_out(t, k)) != MX_OK) return rc;
-    if (k > g->out_cap) {
-        g->out_cap = 0;
-        const size_t kc = (size_t)std::max(k, 16);
-        MX_HIP(g->out_keys.alloc((size_t)kMaxBatch * kc));
-        MX_HIP(g->out_rows.alloc((size_t)kMaxBatch * kc));
-        MX_HIP(g->out_complete.alloc(kMaxBatch));
-        g->out_cap = (int)kc;
-    }
-    Scratch &s = t->s;
-    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
-        const int nb = std::min(kMaxBatch, B - b0);
-        const size_t o = (size_t)b0 * k;
-        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
-        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
-        if ((rc = grouped_batch(idx, g, f, s.qstage, nb, k, fetch, s.out_ids, s.out_scores, s.out_dists, g->out_keys, g->out_rows, s.out_nfound,
-                                g->out_complete)) != MX_OK)
-            return rc;
-        if (keys) MX_HIP(hipMemcpyAsync(keys + o, g->out_keys, (size_t)nb * k * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
-        if (group_rows) MX_HIP(hipMemcpyAsync(group_rows + o, g->out_rows, (size_t)nb * k * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        if (complete) MX_HIP(hipMemcpyAsync(complete + b0, g->out_complete, (size_t)nb, hipMemcpyDeviceToHost, t->stream));
-        if ((rc = copy_out_to_host(t, nb, k, false)) != MX_OK) return rc;
-        scatter_to_caller(s, 0, nb, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, nullptr);
-    }
-    return MX_OK;
+    return grouped_search(true, idx, g, f, q, B, k, fetch, ids, scores, dists, keys, group_rows, n_found, complete);
 } catch (...) {
     return guard_exception();
 }
@@ -4858,21 +4967,7 @@ int mx_index_search_grouped_device(mx_index *idx, mx_grouping *g, mx_filter *f, 
                                    float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows, int32_t *d_nfound,
                                    uint8_t *d_complete) try {
     if (int rc = read_grouped_args(B, k, fetch, g, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
-    if (!idx) return fail(MX_ESEARCH, "null index");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
-    if (B == 0) return MX_OK;
-    mx_index *t = group_owner(idx);
-    DeviceGuard dg(t->device);
-    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
-        const int nb = std::min(kMaxBatch, B - b0);
-        const size_t o = (size_t)b0 * k;
-        int rc = grouped_batch(idx, g, f, d_q + (size_t)b0 * idx->dim, nb, k, fetch, d_ids + o, d_scores + o, d_dists ? d_dists + o : nullptr,
-                               d_keys ? d_keys + o : nullptr, d_group_rows ? d_group_rows + o : nullptr, d_nfound + b0,
-                               d_complete ? d_complete + b0 : nullptr);
-        if (rc != MX_OK) return rc;
-    }
-    return MX_OK;
+    return grouped_search(false, idx, g, f, d_q, B, k, fetch, d_ids, d_scores, d_dists, d_keys, d_group_rows, d_nfound, d_complete);
 } catch (...) {
     return guard_exception();
 }
@@ -4896,101 +4991,29 @@ int read_group_rows_args(int B, int k, int per, const char *what, int per_cap, i
     return MX_OK;
 }
 
-// One batch (B <= kMaxBatch), as grouped_batch: the same candidate stage into the owner's lists, one group_rows_kernel launch;
-// host-synchronised.  per_key == 0: the group-rows form at n; otherwise the capped form (n = 1).
-int group_rows_batch(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int n, int per_key, int fetch,
-                     uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_rows, int32_t *d_members,
-                     uint8_t *d_mcomplete, int32_t *d_nfound, uint8_t *d_complete) {
-    mx_index *t = group_owner(idx);
-    int rc = ensure_mmr_lists(t, fetch);
-    if (rc != MX_OK) return rc;
-    const FilterArg fa{nullptr, f, 0};
-    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf, f ? &fa : nullptr)) != MX_OK) return rc;
-    GroupRows p{B, k, n, per_key, fetch, idx->idmap.id_offset, g->len, g->keys, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf,
-                d_ids, d_scores, d_dists, d_keys, d_rows, d_members, d_mcomplete, d_nfound, d_complete};
-    MX_HIP(launch_group_rows(t->stream, p));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
-}
-
-// the per-head staging of the host-pointer variants covers k heads per query (the owner's device is current)
-int ensure_group_rows_out(mx_grouping *g, int k) {
-    const size_t kc = (size_t)std::max(k, 16);
-    if (k > g->out_cap) {
-        g->out_cap = 0;
-        MX_HIP(g->out_keys.alloc((size_t)kMaxBatch * kc));
-        MX_HIP(g->out_rows.alloc((size_t)kMaxBatch * kc));
-        MX_HIP(g->out_complete.alloc(kMaxBatch));
-        g->out_cap = (int)kc;
-    }
-    if (k > g->members_cap) {
-        g->members_cap = 0;
-        MX_HIP(g->out_members.alloc((size_t)kMaxBatch * kc));
-        MX_HIP(g->out_members_complete.alloc((size_t)kMaxBatch * kc));
-        g->members_cap = (int)kc;
-    }
-    return MX_OK;
-}
-
-// the host-pointer variants: queries staged per batch of kMaxBatch, results through the owner's staging block (width k * n) and the
-// grouping's per-head arrays.  Not combined with other callers, like mx_index_search_grouped.
-int group_rows_host(mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int n, int per_key, int fetch, uint64_t *ids,
-                    float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_members, uint8_t *members_complete,
-                    int32_t *n_found, uint8_t *complete) {
-    if (!idx) return fail(MX_ESEARCH, "null index");
-    const size_t dim = (size_t)idx->dim;
-    for (size_t i = 0; i < (size_t)B * dim; ++i)
-        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
-    if (B == 0) return MX_OK;
-    mx_index *t = group_owner(idx);  // owner of the staging buffers and the stream
-    DeviceGuard dg(t->device);
-    const int width = k * n;
-    int rc = ensure_scratch(t);
-    if (rc != MX_OK) return rc;
-    if ((rc = ensure_out(t, width)) != MX_OK) return rc;
-    if ((rc = ensure_group_rows_out(g, k)) != MX_OK) return rc;
-    Scratch &s = t->s;
-    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
-        const int nb = std::min(kMaxBatch, B - b0);
-        const size_t o = (size_t)b0 * k;
-        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
-        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
-        if ((rc = group_rows_batch(idx, g, f, s.qstage, nb, k, n, per_key, fetch, s.out_ids, s.out_scores, s.out_dists, g->out_keys, g->out_rows,
-                                   g->out_members, g->out_members_complete, s.out_nfound, g->out_complete)) != MX_OK)
-            return rc;
-        if (keys) MX_HIP(hipMemcpyAsync(keys + o, g->out_keys, (size_t)nb * k * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
-        if (group_rows) MX_HIP(hipMemcpyAsync(group_rows + o, g->out_rows, (size_t)nb * k * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        if (n_members) MX_HIP(hipMemcpyAsync(n_members + o, g->out_members, (size_t)nb * k * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        if (members_complete)
-            MX_HIP(hipMemcpyAsync(members_complete + o, g->out_members_complete, (size_t)nb * k, hipMemcpyDeviceToHost, t->stream));
-        if (complete) MX_HIP(hipMemcpyAsync(complete + b0, g->out_complete, (size_t)nb, hipMemcpyDeviceToHost, t->stream));
-        if ((rc = copy_out_to_host(t, nb, width, false)) != MX_OK) return rc;
-        scatter_to_caller(s, 0, nb, width, ids + o * n, scores + o * n, dists ? dists + o * n : nullptr, n_found + b0, nullptr);
-    }
-    return MX_OK;
-}
-
-int group_rows_device(mx_index *idx, mx_grouping *g, mx_filter *f, const float *d_q, int B, int k, int n, int per_key, int fetch,
-                      uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows, int32_t *d_members,
-                      uint8_t *d_mcomplete, int32_t *d_nfound, uint8_t *d_complete) {
-    if (!idx) return fail(MX_ESEARCH, "null index");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = check_grouped_handles(idx, g, f); rc != MX_OK) return rc;
-    if (B == 0) return MX_OK;
-    mx_index *t = group_owner(idx);
-    DeviceGuard dg(t->device);
-    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
-        const int nb = std::min(kMaxBatch, B - b0);
-        const size_t o = (size_t)b0 * k, w = o * n;
-        int rc = group_rows_batch(idx, g, f, d_q + (size_t)b0 * idx->dim, nb, k, n, per_key, fetch, d_ids + w, d_scores + w,
-                                  d_dists ? d_dists + w : nullptr, d_keys ? d_keys + o : nullptr, d_group_rows ? d_group_rows + o : nullptr,
-                                  d_members ? d_members + o : nullptr, d_mcomplete ? d_mcomplete + o : nullptr, d_nfound + b0,
-                                  d_complete ? d_complete + b0 : nullptr);
-        if (rc != MX_OK) return rc;
-    }
-    return MX_OK;
+// both variants of the group-rows form at n (per_key == 0) and of the capped form (n = 1): results of width k * n, one
+// group_rows_kernel launch per batch
+int group_rows_search(bool host, mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int n, int per_key, int fetch,
+                      uint64_t *ids, float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_members,
+                      uint8_t *members_complete, int32_t *n_found, uint8_t *complete) {
+    const size_t kk = (size_t)k;
+    RerankOut x[] = {{nullptr, keys, sizeof(uint32_t), kk}, {nullptr, group_rows, sizeof(int32_t), kk}, {nullptr, n_members, sizeof(int32_t), kk},
+                     {nullptr, members_complete, 1, kk}, {nullptr, complete, 1, 1}};
+    auto rank = [&](mx_index *t, int, int nb, const RerankDst &d) {
+        GroupRows p{nb, k, n, per_key, fetch, idx->idmap.id_offset, g->col.len, g->col.words, t->mmr_ids, t->mmr_scores, t->mmr_dists,
+                    t->mmr_nf, d.ids, d.scores, d.dists, (uint32_t *)d.x[0], (int32_t *)d.x[1], (int32_t *)d.x[2], (uint8_t *)d.x[3],
+                    d.nfound, (uint8_t *)d.x[4]};
+        MX_HIP(launch_group_rows(t->stream, p));
+        return (int)MX_OK;
+    };
+    auto size_outputs = [&] {
+        if (int rc = ensure_group_out(g, k, true); rc != MX_OK) return rc;
+        x[0].dev = g->out_keys, x[1].dev = g->out_rows, x[2].dev = g->out_members, x[3].dev = g->out_members_complete;
+        x[4].dev = g->out_complete;
+        return (int)MX_OK;
+    };
+    if (host) return rerank_host(idx, g->col, f, q, B, k * n, fetch, x, 5, size_outputs, rank, ids, scores, dists, n_found);
+    return rerank_device(idx, g->col, f, q, B, k * n, fetch, x, 5, [] { return (int)MX_OK; }, rank, ids, scores, dists, n_found);
 }
 
 }  // namespace
@@ -4999,7 +5022,7 @@ int mx_index_search_group_rows(mx_index *idx, mx_grouping *g, mx_filter *f, cons
                                float *scores, float *dists, uint32_t *keys, int32_t *group_rows, int32_t *n_members,
                                uint8_t *members_complete, int32_t *n_found, uint8_t *complete) try {
     if (int rc = read_group_rows_args(B, k, n, "n", kGroupMaxMembers, fetch, g, q, ids, scores, n_found); rc != MX_OK) return rc;
-    return group_rows_host(idx, g, f, q, B, k, n, 0, fetch, ids, scores, dists, keys, group_rows, n_members, members_complete, n_found, complete);
+    return group_rows_search(true, idx, g, f, q, B, k, n, 0, fetch, ids, scores, dists, keys, group_rows, n_members, members_complete, n_found, complete);
 } catch (...) {
     return guard_exception();
 }
@@ -5008,7 +5031,7 @@ int mx_index_search_group_rows_device(mx_index *idx, mx_grouping *g, mx_filter *
                                       uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_group_rows,
                                       int32_t *d_n_members, uint8_t *d_members_complete, int32_t *d_nfound, uint8_t *d_complete) try {
     if (int rc = read_group_rows_args(B, k, n, "n", kGroupMaxMembers, fetch, g, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
-    return group_rows_device(idx, g, f, d_q, B, k, n, 0, fetch, d_ids, d_scores, d_dists, d_keys, d_group_rows, d_n_members,
+    return group_rows_search(false, idx, g, f, d_q, B, k, n, 0, fetch, d_ids, d_scores, d_dists, d_keys, d_group_rows, d_n_members,
                              d_members_complete, d_nfound, d_complete);
 } catch (...) {
     return guard_exception();
@@ -5017,7 +5040,7 @@ int mx_index_search_group_rows_device(mx_index *idx, mx_grouping *g, mx_filter *
 int mx_index_search_capped(mx_index *idx, mx_grouping *g, mx_filter *f, const float *q, int B, int k, int per_key, int fetch, uint64_t *ids,
                            float *scores, float *dists, uint32_t *keys, int32_t *n_found, uint8_t *complete) try {
     if (int rc = read_group_rows_args(B, k, per_key, "per_key", 0, fetch, g, q, ids, scores, n_found); rc != MX_OK) return rc;
-    return group_rows_host(idx, g, f, q, B, k, 1, per_key, fetch, ids, scores, dists, keys, nullptr, nullptr, nullptr, n_found, complete);
+    return group_rows_search(true, idx, g, f, q, B, k, 1, per_key, fetch, ids, scores, dists, keys, nullptr, nullptr, nullptr, n_found, complete);
 } catch (...) {
     return guard_exception();
 }
@@ -5026,7 +5049,7 @@ int mx_index_search_capped_device(mx_index *idx, mx_grouping *g, mx_filter *f, c
                                   uint64_t *d_ids, float *d_scores, float *d_dists, uint32_t *d_keys, int32_t *d_nfound,
                                   uint8_t *d_complete) try {
     if (int rc = read_group_rows_args(B, k, per_key, "per_key", 0, fetch, g, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
-    return group_rows_device(idx, g, f, d_q, B, k, 1, per_key, fetch, d_ids, d_scores, d_dists, d_keys, nullptr, nullptr, nullptr, d_nfound,
+    return group_rows_search(false, idx, g, f, d_q, B, k, 1, per_key, fetch, d_ids, d_scores, d_dists, d_keys, nullptr, nullptr, nullptr, d_nfound,
                              d_complete);
 } catch (...) {
     return guard_exception();
@@ -5040,27 +5063,26 @@ int mx_grouping_key_counts(mx_grouping *g, const uint32_t *keys, uint64_t n_keys
     std::vector<uint32_t> sorted(keys, keys + n_keys);
     std::sort(sorted.begin(), sorted.end());
     sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
-    mx_index *idx = g->idx;
+    RowColumn &c = g->col;
+    mx_index *idx = c.idx;
     std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = grouping_ready(g); rc != MX_OK) return rc;
+    if (int rc = column_ready(c); rc != MX_OK) return rc;
     if (n_keys == 0) return MX_OK;
     const uint64_t rows = rows_of(idx);
     std::vector<uint64_t> counts(2 * sorted.size(), 0);
     if (rows) {
-        mx_index *t = group_owner(idx);
         std::vector<uint64_t> mask;
         composite_dead_mask(idx, rows, &mask);
-        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-        if (t != idx) l2.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx);
+        mx_index *t = own.t;
         const uint64_t *d_dead = nullptr;
-        if (int rc = dead_mask_on_device(idx, t, mask, g->dead, g->dead_words, &d_dead); rc != MX_OK) return rc;
+        if (int rc = dead_mask_on_device(idx, t, mask, c.dead, c.dead_words, &d_dead); rc != MX_OK) return rc;
         const size_t cb = counts.size() * sizeof(uint64_t), kb = sorted.size() * sizeof(uint32_t);  // the counters first: 8-byte aligned
-        if (int rc = ensure_group_stage(g, cb + kb); rc != MX_OK) return rc;
-        char *st = static_cast<char *>(g->stage.get());
+        if (int rc = ensure_column_stage(c, cb + kb); rc != MX_OK) return rc;
+        char *st = static_cast<char *>(c.stage.get());
         MX_HIP(hipMemsetAsync(st, 0, cb, t->stream));
         MX_HIP(hipMemcpyAsync(st + cb, sorted.data(), kb, hipMemcpyHostToDevice, t->stream));
-        MX_HIP(launch_grouping_key_counts(t->stream, g->keys, g->len, rows, d_dead, reinterpret_cast<const uint32_t *>(st + cb),
+        MX_HIP(launch_grouping_key_counts(t->stream, c.words, c.len, rows, d_dead, reinterpret_cast<const uint32_t *>(st + cb),
                                           (uint32_t)sorted.size(), reinterpret_cast<uint64_t *>(st)));
         MX_HIP(hipMemcpyAsync(counts.data(), st, cb, hipMemcpyDeviceToHost, t->stream));
         MX_HIP(hipStreamSynchronize(t->stream));
@@ -5077,55 +5099,6 @@ int mx_grouping_key_counts(mx_grouping *g, const uint32_t *keys, uint64_t n_keys
 
 // ---- boosted search (mx_prior, mx_index_search_boosted) -------------------------------------------------------------
 namespace {
-
-// a prior named in a call on idx (under idx->mu): made for this handle, and not older than its rows
-int check_prior(const mx_index *idx, const mx_prior *p) {
-    if (p->idx != idx) return fail(MX_EINVAL, "the prior was made for another index");
-    if (p->epoch != idx->row_epoch)
-        return fail(MX_EINVAL, "the prior is stale: the index was cleared, loaded or compacted after it was made (destroy it and make a new one)");
-    return MX_OK;
-}
-
-// the value array covers `rows` rows: a new block, the old values copied, the rest zero (the owner's device is current)
-int ensure_prior_vals(mx_prior *p, mx_index *t, uint64_t rows) {
-    if (rows <= p->len) return MX_OK;
-    const uint64_t want = (rows + 1023) / 1024 * 1024;
-    Dev<float> nb;
-    MX_HIP(nb.alloc((size_t)want));
-    if (p->len) MX_HIP(hipMemcpyAsync(nb, p->vals, (size_t)p->len * sizeof(float), hipMemcpyDeviceToDevice, t->stream));
-    MX_HIP(hipMemsetAsync(nb.get() + p->len, 0, (size_t)(want - p->len) * sizeof(float), t->stream));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    p->vals = std::move(nb);
-    p->len = want;
-    return MX_OK;
-}
-
-int ensure_prior_stage(mx_prior *p, size_t bytes) {
-    if (p->stage_bytes >= bytes) return MX_OK;
-    p->stage_bytes = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-    MX_HIP(p->stage.alloc_bytes(want));  // (every call is host-synchronised before it returns)
-    p->stage_bytes = want;
-    return MX_OK;
-}
-
-void free_prior_buffers(mx_prior *p) {
-    DeviceGuard dg(p->device);
-    p->vals.reset();
-    p->stage.reset();
-    p->part.reset();
-    p->dead.reset();
-    p->weights.reset();
-    p->out_priors.reset();
-    p->out_combined.reset();
-    p->out_complete.reset();
-}
-
-// the head of every mx_prior_* call but create and destroy; the caller holds idx->mu
-int prior_ready(mx_prior *p) {
-    if (int rc = usable(p->idx); rc != MX_OK) return rc;
-    return check_prior(p->idx, p);
-}
 
 // the values of an edit as the words the edit kernels store; *top = the largest of them.  A value that is not finite: MX_EINVAL
 int read_prior_values(const float *values, uint64_t n, std::vector<uint32_t> *words, float *top) {
@@ -5154,80 +5127,49 @@ int read_boosted_args(int B, int k, int fetch, const mx_prior *p, const float *w
     return MX_OK;
 }
 
-// One batch (B <= kMaxBatch) of a boosted search, as grouped_batch: a plain (or resident-filtered) search pass at k = fetch into the
-// owner's lists, one boost_rank_kernel launch; host-synchronised.  weights: host memory [B] or null.
-int boosted_batch(mx_index *idx, mx_prior *p, mx_filter *f, const float *d_q, const float *weights, int B, int k, int fetch, uint64_t *d_ids,
-                  float *d_scores, float *d_dists, float *d_priors, double *d_combined, int32_t *d_nfound, uint8_t *d_complete) {
-    mx_index *t = group_owner(idx);
-    int rc = ensure_mmr_lists(t, fetch);
-    if (rc != MX_OK) return rc;
-    if (weights && !p->weights) MX_HIP(p->weights.alloc(kMaxBatch));
-    const FilterArg fa{nullptr, f, 0};
-    if ((rc = any_batch(idx, d_q, B, fetch, t->mmr_ids, t->mmr_scores, t->mmr_dists, t->mmr_nf, f ? &fa : nullptr)) != MX_OK) return rc;
-    if (weights) MX_HIP(hipMemcpyAsync(p->weights, weights, (size_t)B * sizeof(float), hipMemcpyHostToDevice, t->stream));
-    BoostRank a{B, k, fetch, idx->idmap.id_offset, p->len, p->vals, weights ? p->weights.get() : nullptr, p->hi, t->mmr_ids, t->mmr_scores,
-                t->mmr_dists, t->mmr_nf, d_ids, d_scores, d_dists, d_priors, d_combined, d_nfound, d_complete};
-    MX_HIP(launch_boost_rank(t->stream, a));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
-}
-
-// handles named in a boosted search (under idx->mu)
-int check_boosted_handles(mx_index *idx, mx_prior *p, mx_filter *f) {
-    if (int rc = usable(idx); rc != MX_OK) return rc;
-    if (int rc = check_prior(idx, p); rc != MX_OK) return rc;
-    return f ? check_filter(idx, f) : MX_OK;
+// both variants of the boosted search: one boost_rank_kernel launch per batch.  weights: host memory [B] or null.
+int boosted_search(bool host, mx_index *idx, mx_prior *p, mx_filter *f, const float *q, const float *weights, int B, int k, int fetch,
+                   uint64_t *ids, float *scores, float *dists, float *priors, double *combined, int32_t *n_found, uint8_t *complete) {
+    RerankOut x[] = {{nullptr, priors, sizeof(float), (size_t)k}, {nullptr, combined, sizeof(double), (size_t)k}, {nullptr, complete, 1, 1}};
+    auto rank = [&](mx_index *t, int b0, int nb, const RerankDst &d) {
+        if (weights) MX_HIP(hipMemcpyAsync(p->weights, weights + b0, (size_t)nb * sizeof(float), hipMemcpyHostToDevice, t->stream));
+        BoostRank a{nb, k, fetch, idx->idmap.id_offset, p->col.len, p->col.floats(), weights ? p->weights.get() : nullptr, p->hi, t->mmr_ids,
+                    t->mmr_scores, t->mmr_dists, t->mmr_nf, d.ids, d.scores, d.dists, (float *)d.x[0], (double *)d.x[1], d.nfound,
+                    (uint8_t *)d.x[2]};
+        MX_HIP(launch_boost_rank(t->stream, a));
+        return (int)MX_OK;
+    };
+    auto size_weights = [&] {
+        if (weights && !p->weights) MX_HIP(p->weights.alloc(kMaxBatch));
+        return (int)MX_OK;
+    };
+    auto size_outputs = [&] {
+        if (int rc = size_weights(); rc != MX_OK) return rc;
+        if (k > p->out_cap) {
+            p->out_cap = 0;
+            const size_t kc = (size_t)std::max(k, 16);
+            MX_HIP(p->out_priors.alloc((size_t)kMaxBatch * kc));
+            MX_HIP(p->out_combined.alloc((size_t)kMaxBatch * kc));
+            MX_HIP(p->out_complete.alloc(kMaxBatch));
+            p->out_cap = (int)kc;
+        }
+        x[0].dev = p->out_priors, x[1].dev = p->out_combined, x[2].dev = p->out_complete;
+        return (int)MX_OK;
+    };
+    if (host) return rerank_host(idx, p->col, f, q, B, k, fetch, x, 3, size_outputs, rank, ids, scores, dists, n_found);
+    return rerank_device(idx, p->col, f, q, B, k, fetch, x, 3, size_weights, rank, ids, scores, dists, n_found);
 }
 
 }  // namespace
 
 int mx_prior_create(mx_index *idx, mx_prior **out) try {
-    if (!out) return fail(MX_EINVAL, "out is null");
-    *out = nullptr;
-    if (!idx) return fail(MX_EINVAL, "null index");
-    {   // the prior's own reference: the rows stay while it lives, whoever closes the index
-        std::lock_guard<std::mutex> lk(g_reg_mu);
-        idx->refs += 1;
-    }
-    std::unique_ptr<mx_prior> p(new mx_prior());
-    int rc = MX_OK;
-    {
-        std::lock_guard<std::mutex> lk(idx->mu);
-        rc = usable(idx);
-        mx_index *t = group_owner(idx);
-        p->idx = idx;
-        p->epoch = idx->row_epoch;
-        p->device = t->device;
-        if (rc == MX_OK) {
-            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-            if (t != idx) l2.lock();
-            DeviceGuard dg(t->device);
-            rc = ensure_prior_vals(p.get(), t, rows_of(idx));
-        }
-        if (rc != MX_OK) free_prior_buffers(p.get());
-    }
-    if (rc != MX_OK) {
-        const std::string keep = last_error_slot();
-        mx_index_close(idx);
-        last_error_slot() = keep;
-        return rc;
-    }
-    *out = p.release();
-    return MX_OK;
+    return create_handle(idx, out, [idx](mx_prior *p) { return make_column(p->col, idx); });
 } catch (...) {
     return guard_exception();
 }
 
 void mx_prior_destroy(mx_prior *p) {
-    if (!p) return;
-    mx_index *idx = p->idx;
-    try {
-        std::lock_guard<std::mutex> lk(idx->mu);  // (no search that names the prior is inside the library)
-        free_prior_buffers(p);
-    } catch (...) {
-    }
-    delete p;
-    mx_index_close(idx);
+    if (p) destroy_handle(p, p->col.idx);
 }
 
 int mx_prior_set_ranges(mx_prior *p, const uint64_t *ranges, const float *values, uint64_t n_ranges) try {
@@ -5238,32 +5180,8 @@ int mx_prior_set_ranges(mx_prior *p, const uint64_t *ranges, const float *values
     if (int rc = read_prior_values(values, n_ranges, &words, &top); rc != MX_OK) return rc;
     std::vector<WordSpan> sp;
     if (int rc = read_word_spans(ranges, words.data(), n_ranges, &sp); rc != MX_OK) return rc;
-    mx_index *idx = p->idx;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = prior_ready(p); rc != MX_OK) return rc;
-    std::vector<uint64_t> rows;
-    std::vector<uint32_t> rw;
-    spans_to_rows(sp, idx->idmap.id_offset, rows_of(idx), &rows, &rw);
-    if (rw.empty()) {
-        p->hi = std::max(p->hi, top);  // (hi follows what the call was handed, whether or not a row took it)
-        return MX_OK;
-    }
-    mx_index *t = group_owner(idx);
-    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-    if (t != idx) l2.lock();
-    DeviceGuard dg(t->device);
-    // every allocation first: a call that fails leaves the values as they were
-    const size_t rb = rows.size() * sizeof(uint64_t), wb = rw.size() * sizeof(uint32_t);
-    if (int rc = ensure_prior_vals(p, t, rows.back()); rc != MX_OK) return rc;
-    if (int rc = ensure_prior_stage(p, rb + wb); rc != MX_OK) return rc;
-    char *st = static_cast<char *>(p->stage.get());
-    MX_HIP(hipMemcpyAsync(st, rows.data(), rb, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(hipMemcpyAsync(st + rb, rw.data(), wb, hipMemcpyHostToDevice, t->stream));
-    p->hi = std::max(p->hi, top);  // (before the store is queued: hi is never below a value of the array)
-    MX_HIP(launch_grouping_range_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + rb),
-                                      (uint32_t)rw.size(), rows.front(), rows.back(), reinterpret_cast<uint32_t *>(p->vals.get())));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
+    // (hi follows what the call was handed, whether or not a row took it, and is never below a value of the column)
+    return column_set_ranges(p->col, sp, [p, top] { p->hi = std::max(p->hi, top); });
 } catch (...) {
     return guard_exception();
 }
@@ -5275,30 +5193,7 @@ int mx_prior_set_ids(mx_prior *p, const uint64_t *ids, const float *values, uint
     float top = 0.0f;
     if (int rc = read_prior_values(values, n_ids, &words, &top); rc != MX_OK) return rc;
     if (int rc = check_id_words(ids, words.data(), n_ids, "value bits"); rc != MX_OK) return rc;
-    mx_index *idx = p->idx;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = prior_ready(p); rc != MX_OK) return rc;
-    const uint64_t off = idx->idmap.id_offset, total = rows_of(idx);
-    const uint64_t last = top_row_named(ids, n_ids, off, total);
-    if (last == 0) {
-        p->hi = std::max(p->hi, top);
-        return MX_OK;
-    }
-    mx_index *t = group_owner(idx);
-    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-    if (t != idx) l2.lock();
-    DeviceGuard dg(t->device);
-    const size_t ib = (size_t)n_ids * sizeof(uint64_t), wb = (size_t)n_ids * sizeof(uint32_t);
-    if (int rc = ensure_prior_vals(p, t, last); rc != MX_OK) return rc;
-    if (int rc = ensure_prior_stage(p, ib + wb); rc != MX_OK) return rc;
-    char *st = static_cast<char *>(p->stage.get());
-    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(hipMemcpyAsync(st + ib, words.data(), wb, hipMemcpyHostToDevice, t->stream));
-    p->hi = std::max(p->hi, top);
-    MX_HIP(launch_grouping_id_edit(t->stream, reinterpret_cast<const uint64_t *>(st), reinterpret_cast<const uint32_t *>(st + ib), n_ids, off,
-                                   std::min(total, p->len), reinterpret_cast<uint32_t *>(p->vals.get())));
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
+    return column_set_ids(p->col, ids, words.data(), n_ids, [p, top] { p->hi = std::max(p->hi, top); });
 } catch (...) {
     return guard_exception();
 }
@@ -5306,23 +5201,7 @@ int mx_prior_set_ids(mx_prior *p, const uint64_t *ids, const float *values, uint
 int mx_prior_get(mx_prior *p, const uint64_t *ids, uint64_t n_ids, float *values) try {
     if (!p) return fail(MX_EINVAL, "null prior");
     if ((!ids || !values) && n_ids) return fail(MX_EINVAL, "null ids or values with n_ids = %llu", (unsigned long long)n_ids);
-    mx_index *idx = p->idx;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = prior_ready(p); rc != MX_OK) return rc;
-    if (n_ids == 0) return MX_OK;
-    mx_index *t = group_owner(idx);
-    std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-    if (t != idx) l2.lock();
-    DeviceGuard dg(t->device);
-    const size_t ib = (size_t)n_ids * sizeof(uint64_t), wb = (size_t)n_ids * sizeof(uint32_t);
-    if (int rc = ensure_prior_stage(p, ib + wb); rc != MX_OK) return rc;
-    char *st = static_cast<char *>(p->stage.get());
-    MX_HIP(hipMemcpyAsync(st, ids, ib, hipMemcpyHostToDevice, t->stream));
-    MX_HIP(launch_grouping_get(t->stream, reinterpret_cast<const uint64_t *>(st), n_ids, idx->idmap.id_offset, std::min(rows_of(idx), p->len),
-                               reinterpret_cast<const uint32_t *>(p->vals.get()), reinterpret_cast<uint32_t *>(st + ib)));
-    MX_HIP(hipMemcpyAsync(values, st + ib, wb, hipMemcpyDeviceToHost, t->stream));  // (the word 0 of an id that names no row is +0.0f)
-    MX_HIP(hipStreamSynchronize(t->stream));
-    return MX_OK;
+    return column_get(p->col, ids, n_ids, values);
 } catch (...) {
     return guard_exception();
 }
@@ -5330,24 +5209,23 @@ int mx_prior_get(mx_prior *p, const uint64_t *ids, uint64_t n_ids, float *values
 int mx_prior_bound(mx_prior *p, int refresh, float *hi) try {
     if (!p) return fail(MX_EINVAL, "null prior");
     if (refresh != 0 && refresh != 1) return fail(MX_EINVAL, "refresh = %d is neither 0 nor 1", refresh);
-    mx_index *idx = p->idx;
+    RowColumn &c = p->col;
+    mx_index *idx = c.idx;
     std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = prior_ready(p); rc != MX_OK) return rc;
+    if (int rc = column_ready(c); rc != MX_OK) return rc;
     if (refresh) {
-        const uint64_t n = std::min(rows_of(idx), p->len);
+        const uint64_t n = std::min(rows_of(idx), c.len);
         float top = 0.0f;
         if (n) {
-            mx_index *t = group_owner(idx);
             std::vector<uint64_t> mask;
             composite_dead_mask(idx, n, &mask);
-            std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-            if (t != idx) l2.lock();
-            DeviceGuard dg(t->device);
+            OwnerLock own(idx);
+            mx_index *t = own.t;
             if (!p->part) MX_HIP(p->part.alloc(kBoostMaxBlocks));
             const uint64_t *d_dead = nullptr;
-            if (int rc = dead_mask_on_device(idx, t, mask, p->dead, p->dead_words, &d_dead); rc != MX_OK) return rc;
+            if (int rc = dead_mask_on_device(idx, t, mask, c.dead, c.dead_words, &d_dead); rc != MX_OK) return rc;
             float part[kBoostMaxBlocks];
-            MX_HIP(launch_prior_max(t->stream, p->vals, n, d_dead, p->part));
+            MX_HIP(launch_prior_max(t->stream, c.floats(), n, d_dead, p->part));
             MX_HIP(hipMemcpyAsync(part, p->part, sizeof(part), hipMemcpyDeviceToHost, t->stream));
             MX_HIP(hipStreamSynchronize(t->stream));
             for (int w = 0; w < kBoostMaxBlocks; ++w) top = std::max(top, part[w]);
@@ -5364,43 +5242,7 @@ int mx_index_search_boosted(mx_index *idx, mx_prior *p, mx_filter *f, const floa
                             uint64_t *ids, float *scores, float *dists, float *priors, double *combined, int32_t *n_found,
                             uint8_t *complete) try {
     if (int rc = read_boosted_args(B, k, fetch, p, weights, q, ids, scores, n_found); rc != MX_OK) return rc;
-    if (!idx) return fail(MX_ESEARCH, "null index");
-    const size_t dim = (size_t)idx->dim;
-    for (size_t i = 0; i < (size_t)B * dim; ++i)
-        if (!std::isfinite(q[i])) return fail(MX_EINVAL, "query %zu contains a non-finite value", i / dim);
-    // not combined with other callers: the call holds the index across the candidate stage and the re-ranking, like a device-pointer call
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = check_boosted_handles(idx, p, f); rc != MX_OK) return rc;
-    if (B == 0) return MX_OK;
-    mx_index *t = group_owner(idx);  // owner of the staging buffers and the stream
-    DeviceGuard dg(t->device);
-    int rc = ensure_scratch(t);
-    if (rc != MX_OK) return rc;
-    if ((rc = ensure_out(t, k)) != MX_OK) return rc;
-    if (k > p->out_cap) {
-        p->out_cap = 0;
-        const size_t kc = (size_t)std::max(k, 16);
-        MX_HIP(p->out_priors.alloc((size_t)kMaxBatch * kc));
-        MX_HIP(p->out_combined.alloc((size_t)kMaxBatch * kc));
-        MX_HIP(p->out_complete.alloc(kMaxBatch));
-        p->out_cap = (int)kc;
-    }
-    Scratch &s = t->s;
-    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
-        const int nb = std::min(kMaxBatch, B - b0);
-        const size_t o = (size_t)b0 * k;
-        memcpy(s.h_q, q + (size_t)b0 * dim, (size_t)nb * dim * sizeof(float));
-        MX_HIP(hipMemcpyAsync(s.qstage, s.h_q, (size_t)nb * dim * sizeof(float), hipMemcpyHostToDevice, t->stream));
-        if ((rc = boosted_batch(idx, p, f, s.qstage, weights ? weights + b0 : nullptr, nb, k, fetch, s.out_ids, s.out_scores, s.out_dists,
-                                p->out_priors, p->out_combined, s.out_nfound, p->out_complete)) != MX_OK)
-            return rc;
-        if (priors) MX_HIP(hipMemcpyAsync(priors + o, p->out_priors, (size_t)nb * k * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-        if (combined) MX_HIP(hipMemcpyAsync(combined + o, p->out_combined, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, t->stream));
-        if (complete) MX_HIP(hipMemcpyAsync(complete + b0, p->out_complete, (size_t)nb, hipMemcpyDeviceToHost, t->stream));
-        if ((rc = copy_out_to_host(t, nb, k, false)) != MX_OK) return rc;
-        scatter_to_caller(s, 0, nb, k, ids + o, scores + o, dists ? dists + o : nullptr, n_found + b0, nullptr);
-    }
-    return MX_OK;
+    return boosted_search(true, idx, p, f, q, weights, B, k, fetch, ids, scores, dists, priors, combined, n_found, complete);
 } catch (...) {
     return guard_exception();
 }
@@ -5409,21 +5251,7 @@ int mx_index_search_boosted_device(mx_index *idx, mx_prior *p, mx_filter *f, con
                                    uint64_t *d_ids, float *d_scores, float *d_dists, float *d_priors, double *d_combined,
                                    int32_t *d_nfound, uint8_t *d_complete) try {
     if (int rc = read_boosted_args(B, k, fetch, p, weights, d_q, d_ids, d_scores, d_nfound); rc != MX_OK) return rc;
-    if (!idx) return fail(MX_ESEARCH, "null index");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (int rc = check_boosted_handles(idx, p, f); rc != MX_OK) return rc;
-    if (B == 0) return MX_OK;
-    mx_index *t = group_owner(idx);
-    DeviceGuard dg(t->device);
-    for (int b0 = 0; b0 < B; b0 += kMaxBatch) {
-        const int nb = std::min(kMaxBatch, B - b0);
-        const size_t o = (size_t)b0 * k;
-        int rc = boosted_batch(idx, p, f, d_q + (size_t)b0 * idx->dim, weights ? weights + b0 : nullptr, nb, k, fetch, d_ids + o, d_scores + o,
-                               d_dists ? d_dists + o : nullptr, d_priors ? d_priors + o : nullptr, d_combined ? d_combined + o : nullptr,
-                               d_nfound + b0, d_complete ? d_complete + b0 : nullptr);
-        if (rc != MX_OK) return rc;
-    }
-    return MX_OK;
+    return boosted_search(false, idx, p, f, d_q, weights, B, k, fetch, d_ids, d_scores, d_dists, d_priors, d_combined, d_nfound, d_complete);
 } catch (...) {
     return guard_exception();
 }
@@ -5433,16 +5261,15 @@ namespace {
 
 constexpr uint64_t kWhereMaxKeys = 1ull << 20;
 
-// An edit by predicate, under idx->mu.  The predicate kernel (launch(stream, rows, d_sel, d_extra)) runs on the device of the column,
-// the owner's, and leaves a selection bitmap over the handle's GLOBAL rows at the head of the column's staging buffer, which
-// stage(bytes, &ptr) grows; `extra` (extra_bytes of host memory, the sorted keys) is uploaded behind it.  The selection comes to the
-// host, where it is counted and folded into the mirrors, and goes into every shard's words by filter_words_kernel: a plain index reads
+extern "C++" {  // (templates: the file's functions are declared inside extern "C")
+// An edit by predicate, under idx->mu.  The predicate kernel (launch(stream, rows, d_sel, d_extra)) runs on the device of the column
+// c it reads, the owner's, and leaves a selection bitmap over the handle's GLOBAL rows at the head of the column's staging buffer;
+// `extra` (extra_bytes of host memory, the sorted keys) is uploaded behind it.  The selection comes to the host, where it is
+// counted and folded into the mirrors, and goes into every shard's words by filter_words_kernel: a plain index reads
 // it where it lies (global rows are its local rows), a shard gets its own rows of it, dealt as filter_edit_ids deals ids (global block
 // b: local block b / G of shard b % G), through its stage.  Every allocation comes first: a call that fails leaves the set as it was.
-using WhereStage = std::function<int(size_t, char **)>;
-using WhereLaunch = std::function<hipError_t(hipStream_t, uint64_t, uint64_t *, const char *)>;
-int filter_edit_selected(mx_filter *f, const void *extra, size_t extra_bytes, const WhereStage &stage, const WhereLaunch &launch, bool allow,
-                         uint64_t *n_selected) {
+template <class Launch>
+int filter_edit_selected(mx_filter *f, RowColumn &c, const void *extra, size_t extra_bytes, Launch launch, bool allow, uint64_t *n_selected) {
     mx_index *idx = f->idx;
     const size_t G = f->sh.size();
     const uint64_t rows = rows_of(idx), R = idx->block_rows;
@@ -5450,9 +5277,7 @@ int filter_edit_selected(mx_filter *f, const void *extra, size_t extra_bytes, co
     std::vector<size_t> lw(G);  // the words of shard g that hold its rows
     for (size_t g = 0; g < G; ++g) {
         mx_index *t = filter_target(idx, g);
-        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
-        if (t != idx) lk.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         FilterShard &fs = f->sh[g];
         if (int rc = ensure_filter_bits(t, fs); rc != MX_OK) return rc;
         lw[g] = (size_t)((t->n + 63) >> 6);
@@ -5467,12 +5292,10 @@ int filter_edit_selected(mx_filter *f, const void *extra, size_t extra_bytes, co
     std::vector<uint64_t> sel_h(sw);
     const uint64_t *d_sel = nullptr;
     {
-        mx_index *t = group_owner(idx);
-        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
-        if (t != idx) lk.lock();
-        DeviceGuard dg(t->device);
-        char *st = nullptr;
-        if (int rc = stage(sb + extra_bytes, &st); rc != MX_OK) return rc;
+        OwnerLock own(idx);
+        mx_index *t = own.t;
+        if (int rc = ensure_column_stage(c, sb + extra_bytes); rc != MX_OK) return rc;
+        char *st = static_cast<char *>(c.stage.get());
         if (extra_bytes) MX_HIP(hipMemcpyAsync(st + sb, extra, extra_bytes, hipMemcpyHostToDevice, t->stream));
         MX_HIP(launch(t->stream, rows, reinterpret_cast<uint64_t *>(st), st + sb));
         MX_HIP(hipMemcpyAsync(sel_h.data(), st, sb, hipMemcpyDeviceToHost, t->stream));
@@ -5487,9 +5310,7 @@ int filter_edit_selected(mx_filter *f, const void *extra, size_t extra_bytes, co
         mx_index *t = filter_target(idx, g);
         FilterShard &fs = f->sh[g];
         if (lw[g] == 0) continue;
-        std::unique_lock<std::mutex> lk(t->mu, std::defer_lock);
-        if (t != idx) lk.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         const std::vector<uint64_t> *src = &sel_h;
         if (idx->composite()) {
             loc.assign(lw[g], 0);
@@ -5511,6 +5332,8 @@ int filter_edit_selected(mx_filter *f, const void *extra, size_t extra_bytes, co
     return MX_OK;
 }
 
+}  // extern "C++"
+
 // the handles of a predicate edit or a combination (under idx->mu, idx the filter's own index)
 int where_ready(mx_filter *f) {
     if (int rc = usable(f->idx); rc != MX_OK) return rc;
@@ -5527,15 +5350,11 @@ int mx_filter_set_where(mx_filter *f, mx_prior *p, float lo, float hi, int allow
     mx_index *idx = f->idx;
     std::lock_guard<std::mutex> lk(idx->mu);
     if (int rc = where_ready(f); rc != MX_OK) return rc;
-    if (int rc = check_prior(idx, p); rc != MX_OK) return rc;
+    RowColumn &c = p->col;
+    if (int rc = check_column(idx, c); rc != MX_OK) return rc;
     return filter_edit_selected(
-        f, nullptr, 0,
-        [&](size_t bytes, char **st) {
-            const int rc = ensure_prior_stage(p, bytes);
-            *st = static_cast<char *>(p->stage.get());
-            return rc;
-        },
-        [&](hipStream_t s, uint64_t rows, uint64_t *sel, const char *) { return launch_where_range(s, p->vals, p->len, rows, lo, hi, sel); },
+        f, c, nullptr, 0,
+        [&](hipStream_t s, uint64_t rows, uint64_t *sel, const char *) { return launch_where_range(s, c.floats(), c.len, rows, lo, hi, sel); },
         allow == 1, n_selected);
 } catch (...) {
     return guard_exception();
@@ -5554,20 +5373,16 @@ int mx_filter_set_keys(mx_filter *f, mx_grouping *g, const uint32_t *keys, uint6
     mx_index *idx = f->idx;
     std::lock_guard<std::mutex> lk(idx->mu);
     if (int rc = where_ready(f); rc != MX_OK) return rc;
-    if (int rc = check_grouping(idx, g); rc != MX_OK) return rc;
+    RowColumn &c = g->col;
+    if (int rc = check_column(idx, c); rc != MX_OK) return rc;
     if (sorted.empty()) {
         if (n_selected) *n_selected = 0;
         return MX_OK;
     }
     return filter_edit_selected(
-        f, sorted.data(), sorted.size() * sizeof(uint32_t),
-        [&](size_t bytes, char **st) {
-            const int rc = ensure_group_stage(g, bytes);
-            *st = static_cast<char *>(g->stage.get());
-            return rc;
-        },
+        f, c, sorted.data(), sorted.size() * sizeof(uint32_t),
         [&](hipStream_t s, uint64_t rows, uint64_t *sel, const char *extra) {
-            return launch_where_keys(s, g->keys, g->len, rows, reinterpret_cast<const uint32_t *>(extra), (uint32_t)sorted.size(), sel);
+            return launch_where_keys(s, c.words, c.len, rows, reinterpret_cast<const uint32_t *>(extra), (uint32_t)sorted.size(), sel);
         },
         allow == 1, n_selected);
 } catch (...) {
@@ -5586,9 +5401,7 @@ int mx_filter_combine(mx_filter *dst, mx_filter *a, mx_filter *b, int op) try {
     const size_t G = dst->sh.size();
     for (size_t g = 0; g < G; ++g) {  // every allocation first: the three bitmaps cover the shard's capacity, missing words are zeros
         mx_index *t = filter_target(idx, g);
-        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-        if (t != idx) l2.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         for (mx_filter *x : {dst, a, b})
             if (int rc = ensure_filter_bits(t, x->sh[g]); rc != MX_OK) return rc;
     }
@@ -5596,9 +5409,7 @@ int mx_filter_combine(mx_filter *dst, mx_filter *a, mx_filter *b, int op) try {
         mx_index *t = filter_target(idx, g);
         FilterShard &d = dst->sh[g];
         const FilterShard &x = a->sh[g], &y = b->sh[g];
-        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-        if (t != idx) l2.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         const size_t words = std::min(d.words, std::min(x.words, y.words));  // (equal: the capacity's)
         d.cached = false;
         d.list_ok = false;
@@ -5619,17 +5430,13 @@ int mx_filter_invert(mx_filter *f) try {
     const size_t G = f->sh.size();
     for (size_t g = 0; g < G; ++g) {
         mx_index *t = filter_target(idx, g);
-        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-        if (t != idx) l2.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         if (int rc = ensure_filter_bits(t, f->sh[g]); rc != MX_OK) return rc;
     }
     for (size_t g = 0; g < G; ++g) {  // a shard's rows are [0, n) of its own: the complement within the handle's rows, shard by shard
         mx_index *t = filter_target(idx, g);
         FilterShard &fs = f->sh[g];
-        std::unique_lock<std::mutex> l2(t->mu, std::defer_lock);
-        if (t != idx) l2.lock();
-        DeviceGuard dg(t->device);
+        OwnerLock own(idx, t);
         const size_t words = std::min(fs.words, (size_t)((t->n + 63) >> 6));
         fs.cached = false;
         fs.list_ok = false;

@@ -929,10 +929,50 @@ def ids_to_ranges(ids) -> np.ndarray:
     return np.ascontiguousarray(np.stack([starts, ends], axis=1), dtype=np.uint64)
 
 
-class IndexFilter:
+def _id_array(ids) -> np.ndarray:
+    """Ids (an array or any iterable) -> contiguous uint64 [n]."""
+    a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
+    return np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+
+
+def _per_item(x, n: int, dtype, noun: str) -> np.ndarray:
+    """One ``x`` per item, or one for all -> contiguous ``dtype`` [n]."""
+    v = np.asarray(x, dtype=dtype)
+    if v.ndim == 0:
+        v = np.full(n, v, dtype=dtype)
+    v = np.ascontiguousarray(v.reshape(-1))
+    if v.size != n:
+        raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {n} {noun}, got {v.size}")
+    return v
+
+
+class _Handle:
+    """A native handle ``_h`` that the library function named ``_destroy`` releases."""
+    _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class IndexFilter(_Handle):
     """A set of rows of one ``FlatIndex``, resident on the device(s) of the index (``mx_filter``).  It holds a
     reference on the index.  After the index's ``clear``, ``load`` or a ``compact`` that dropped rows every method but ``close``
     raises: make a new filter."""
+    _destroy = "mx_filter_destroy"
 
     def __init__(self, index: FlatIndex):
         h = ctypes.c_void_p()
@@ -947,8 +987,7 @@ class IndexFilter:
             r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
             check(lib().mx_filter_set_ranges(self._h, _ptr(r) if r.size else None, r.shape[0], allow))
         if ids is not None:
-            a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
-            a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+            a = _id_array(ids)
             check(lib().mx_filter_set_ids(self._h, _ptr(a) if a.size else None, a.size, allow))
 
     def allow(self, ranges=None, ids=None) -> None:
@@ -1021,64 +1060,36 @@ class IndexFilter:
             check(lib().mx_filter_get_ranges(self._h, _ptr(out), out.shape[0], ctypes.byref(n)))
         return out[: int(n.value)]
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().mx_filter_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class IndexGrouping:
+class IndexGrouping(_Handle):
     """Which rows of one ``FlatIndex`` belong together: one u32 key per row, resident on the index's first device (``mx_grouping``,
     DESIGN.md 3.16).  Key 0 means ungrouped; rows appended later have key 0 until a call names them.  It holds a reference on the
     index.  After the index's ``clear``, ``load`` or a ``compact`` that dropped rows every method but ``close`` raises: make a new
     grouping."""
+    _destroy = "mx_grouping_destroy"
 
     def __init__(self, index: FlatIndex):
         h = ctypes.c_void_p()
         check(lib().mx_grouping_create(index._h, ctypes.byref(h)))
         self._h = h
 
-    @staticmethod
-    def _keys(keys, n: int) -> np.ndarray:
-        k = np.asarray(keys, dtype=np.uint32)
-        if k.ndim == 0:
-            k = np.full(n, k, dtype=np.uint32)
-        k = np.ascontiguousarray(k.reshape(-1))
-        if k.size != n:
-            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {n} keys, got {k.size}")
-        return k
-
     def set_ranges(self, ranges, keys) -> None:
         """Every id of range ``i`` ([m, 2] half-open id ranges, pairwise disjoint, any order) gets ``keys[i]`` (one key per range,
         or one for all); key 0 un-groups.  Ids that name no row at this moment are ignored."""
         r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
-        k = self._keys(keys, r.shape[0])
+        k = _per_item(keys, r.shape[0], np.uint32, "keys")
         check(lib().mx_grouping_set_ranges(self._h, _ptr(r) if r.size else None, _ptr(k) if k.size else None, r.shape[0]))
 
     def set_ids(self, ids, keys) -> None:
         """``ids[i]`` gets ``keys[i]`` (one key per id, or one for all).  Ids may repeat and come in any order, but not with two
         different keys in one call."""
-        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
-        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
-        k = self._keys(keys, a.size)
+        a = _id_array(ids)
+        k = _per_item(keys, a.size, np.uint32, "keys")
         check(lib().mx_grouping_set_ids(self._h, _ptr(a) if a.size else None, _ptr(k) if k.size else None, a.size))
 
     def keys_of(self, ids) -> np.ndarray:
         """-> uint32 [n]: the key of the row each id names, 0 for an id that names no row."""
-        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
-        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        a = _id_array(ids)
         out = np.zeros(a.size, dtype=np.uint32)
         check(lib().mx_grouping_get_keys(self._h, _ptr(a) if a.size else None, a.size, _ptr(out) if out.size else None))
         return out
@@ -1099,64 +1110,36 @@ class IndexGrouping:
                                            _ptr(live) if k.size else None))
         return rows, live
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().mx_grouping_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class IndexPrior:
+class IndexPrior(_Handle):
     """What the vectors do not carry, per row of one ``FlatIndex``: one f32 per row, resident on the index's first device
     (``mx_prior``), added to the score by ``search_boosted``.  Rows nobody set, and rows appended later, read 0.  It
     holds a reference on the index.  After the index's ``clear``, ``load`` or a ``compact`` that dropped rows every method but
     ``close`` raises: make a new prior."""
+    _destroy = "mx_prior_destroy"
 
     def __init__(self, index: FlatIndex):
         h = ctypes.c_void_p()
         check(lib().mx_prior_create(index._h, ctypes.byref(h)))
         self._h = h
 
-    @staticmethod
-    def _values(values, n: int) -> np.ndarray:
-        v = np.asarray(values, dtype=np.float32)
-        if v.ndim == 0:
-            v = np.full(n, v, dtype=np.float32)
-        v = np.ascontiguousarray(v.reshape(-1))
-        if v.size != n:
-            raise _lib.MemexHipError(_lib.MX_EINVAL, f"expected {n} values, got {v.size}")
-        return v
-
     def set_ranges(self, ranges, values) -> None:
         """Every id of range ``i`` ([m, 2] half-open id ranges, pairwise disjoint, any order) gets ``values[i]`` (one value per
         range, or one for all).  Values are finite; a negative one is a penalty.  Ids that name no row at this moment are ignored."""
         r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
-        v = self._values(values, r.shape[0])
+        v = _per_item(values, r.shape[0], np.float32, "values")
         check(lib().mx_prior_set_ranges(self._h, _ptr(r) if r.size else None, _ptr(v) if v.size else None, r.shape[0]))
 
     def set_ids(self, ids, values) -> None:
         """``ids[i]`` gets ``values[i]`` (one value per id, or one for all).  Ids may repeat and come in any order, but not with two
         different values in one call."""
-        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
-        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
-        v = self._values(values, a.size)
+        a = _id_array(ids)
+        v = _per_item(values, a.size, np.float32, "values")
         check(lib().mx_prior_set_ids(self._h, _ptr(a) if a.size else None, _ptr(v) if v.size else None, a.size))
 
     def values_of(self, ids) -> np.ndarray:
         """-> float32 [n]: the value of the row each id names, 0 for an id that names no row."""
-        a = ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.uint64)
-        a = np.ascontiguousarray(a.astype(np.uint64, copy=False).reshape(-1))
+        a = _id_array(ids)
         out = np.zeros(a.size, dtype=np.float32)
         check(lib().mx_prior_get(self._h, _ptr(a) if a.size else None, a.size, _ptr(out) if out.size else None))
         return out
@@ -1167,23 +1150,6 @@ class IndexPrior:
         hi = ctypes.c_float(0.0)
         check(lib().mx_prior_bound(self._h, 1 if refresh else 0, ctypes.byref(hi)))
         return float(hi.value)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().mx_prior_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def _filter_ranges(ranges, ids) -> np.ndarray:

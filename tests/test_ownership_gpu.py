@@ -63,6 +63,39 @@ def cycle(make, plain, store):
     flt.allow(ranges=[[1000, 2500]])
     idx.search_with(flt, Q, K)
     flt.close()
+    grp, pri = idx.make_grouping(), idx.make_prior()
+    kept = [idx.make_grouping(), idx.make_prior()]       # these two stay open across idx.close()
+    for g in (grp, kept[0]):
+        g.set_ranges([[1, 700]], 7)                      # rows below 1,024, then rows above 2,048
+        g.set_ids([2500, 2600], [8, 9])
+    assert list(grp.keys_of([1, 699, 700, 2500, 2600, 4000])) == [7, 7, 0, 8, 9, 0]
+    assert grp.count() == (701, 701)
+    assert [list(c) for c in grp.key_counts([7, 9, 5])] == [[699, 1, 0], [699, 1, 0]]
+    for p in (pri, kept[1]):
+        p.set_ranges([[1, 700]], 0.5)
+        p.set_ids([2500, 2600], [0.25, -1.0])
+    assert list(pri.values_of([1, 700, 2500, 2600, 4000])) == [0.5, 0.0, 0.25, -1.0, 0.0]
+    assert pri.bound() == 0.5 and pri.bound(refresh=True) == 0.5
+    flt = idx.make_filter(ranges=[[1, 2000]])
+    for f in (None, flt):
+        assert (idx.search_grouped(grp, Q, K, flt=f)[5] == K).all()
+        assert (idx.search_group_rows(grp, Q, K, 3, flt=f)[7] == K).all()
+        assert (idx.search_capped(grp, Q, K, 2, flt=f)[4] == K).all()
+        assert (idx.search_boosted(pri, Q, K, flt=f)[5] == K).all()
+    assert flt.allow_where(pri, 0.2, 1.0) == 700 and flt.allow_keys(grp, [8, 9]) == 2
+    for h in (flt, grp, pri):
+        h.close()
+    grow = make()                                # a grouping and a prior made at 1,000 rows and edited at 3,000: their arrays grow
+    grow.add(X[:1000])
+    grp, pri = grow.make_grouping(), grow.make_prior()
+    grp.set_ids([10], 4)
+    pri.set_ids([10], 2.0)
+    grow.add(X[1000:])
+    grp.set_ids([2500], 5)
+    pri.set_ranges([[2400, 2600]], 3.0)
+    assert list(grp.keys_of([10, 2500])) == [4, 5] and list(pri.values_of([10, 2500])) == [2.0, 3.0]
+    for h in (grow, grp, pri):
+        h.close()
     assert idx.remove(np.arange(1, 600, 3)) == 200
     idx.search(Q, K)
     assert len(idx.compact()) == 2800
@@ -75,7 +108,10 @@ def cycle(make, plain, store):
     ids, _, _, nf = idx.search(Q, 300)           # k > 256: the EXACT path
     assert (nf == 300).all()
     idx.close()
-    assert live() == 0, live()                   # exact: every buffer of the index, its scratch and its filters is gone
+    assert live() > 0                            # the grouping and the prior left open keep the index
+    for h in kept:
+        h.close()
+    assert live() == 0, live()                   # exact: every buffer of the index, its scratch and its handles is gone
 
 assert live() == 0
 cycle(lambda: FlatIndex(128), True, os.path.join(sys.argv[1], "plain"))
@@ -128,6 +164,22 @@ with FlatIndex(128) as idx:                      # ... and nothing of the sweep 
     same_as_oracle(idx.search(Q, K))
     assert idx.stats().filter_kind != 0
 assert live() == 0
+# ---- mx_grouping_create, mx_prior_create on a populated index: allocation, memset and copy only
+idx = FlatIndex(128)
+idx.add(X)
+base = live()
+for make in (idx.make_grouping, idx.make_prior):
+    rc, n_make = armed(0, lambda: box.append(make()))
+    assert rc == _lib.MX_OK and n_make >= 1
+    box.pop().close()
+    assert live() == base
+    for n in range(1, n_make + 1):
+        rc, _ = armed(n, lambda: box.append(make()))
+        assert rc == _lib.MX_ENOMEM and not box, (n, rc)
+        assert live() == base, (n, live(), base)
+same_as_oracle(idx.search(Q, K))
+idx.close()
+assert live() == 0
 print("OWNERSHIP_OK")
 '''
 
@@ -139,18 +191,21 @@ def _child(code, *args):
 
 
 def test_every_buffer_is_released_with_its_owner(lib_built, tmp_path):
-    """One cycle through every feature that allocates -- open, add, each kind of search, a resident filter, remove, compact, both
-    filter-copy switches, save, load, the EXACT path, close -- on a plain index and on two logical shards, a second index opened
-    and closed meanwhile: after the last close the testing library counts exactly 0 live buffers.  The first search is compared
-    bit for bit with the oracle, so the scenario cannot pass by doing nothing."""
+    """One cycle through every feature that allocates -- open, add, each kind of search, a resident filter, a grouping and a prior
+    (edited, read, grown, named in the grouped, group-rows, capped and boosted searches and in filters by predicate), remove,
+    compact, both filter-copy switches, save, load, the EXACT path, close -- on a plain index and on two logical shards, a second
+    index opened and closed meanwhile, a grouping and a prior closed only after their index: after the last close the testing
+    library counts exactly 0 live buffers.  The first search is compared bit for bit with the oracle, so the scenario cannot pass
+    by doing nothing."""
     _child(_CYCLE, str(tmp_path))
 
 
 def test_failed_allocations_leak_nothing(lib_built):
-    """Every allocation of mx_index_open, and of reserve() on an empty index, fails in turn (the hook is armed across those two
-    calls only: neither launches a kernel).  The call returns MX_OK or MX_ENOMEM, and after closing whatever was opened nothing
-    is live.  A failed filter-copy allocation stays soft: reserve() returns MX_OK and the index answers like the oracle from
-    its f32 rows (filter_kind 0)."""
+    """Every allocation of mx_index_open, of reserve() on an empty index, and of mx_grouping_create and mx_prior_create on a
+    populated one fails in turn (the hook is armed across those calls only: none launches a kernel).  The call returns MX_OK or
+    MX_ENOMEM, and after closing whatever was opened nothing is live; a failed create leaves the live count where it was and the
+    index answering like the oracle.  A failed filter-copy allocation stays soft: reserve() returns MX_OK and the index answers
+    like the oracle from its f32 rows (filter_kind 0)."""
     _child(_FAILED_ALLOCS)
 
 
