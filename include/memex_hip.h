@@ -117,6 +117,9 @@ int mx_index_exchange(mx_index *idx, int *kind);
  * caller stream are NOT ordered against the index's stream by themselves: either synchronise that
  * stream first, or call mx_index_wait_stream(idx, stream) -- the next operation on the index then
  * starts after everything enqueued on `stream` (a hipStream_t; NULL = the default stream) so far.
+ * "Non-finite queries rejected" means, for a *_device variant, that the pipeline notices them where it reads the queries (MX_EINVAL,
+ * the outputs unspecified); a top-k form with nothing to find -- an empty index, a filter that allows no live row -- writes
+ * the blank lists without looking and returns MX_OK, on plain and sharded handles alike, while the range forms look on every path.
  */
 int mx_index_wait_stream(mx_index *idx, void *hip_stream);
 

@@ -2,7 +2,8 @@
 
 ``FlatIndex`` is the GPU-resident exact cosine index that stands in for memex's ``HnswStore``
 (reference lib/libmemex/src/storage/local.rs:21-166).  Host arrays are NumPy; the ``*_device``
-methods take anything exposing ``data_ptr()`` (torch tensors already in HBM).
+methods take torch tensors already in HBM and refuse one of the wrong device, dtype, shape or layout before
+the library sees its pointer (``FlatIndex._device_args``).
 """
 from __future__ import annotations
 
@@ -27,6 +28,11 @@ def _caller_stream(t) -> ctypes.c_void_p | None:
     except ImportError:
         pass
     return None
+
+
+# what a ``*_device`` tensor may be made of, by the kind the docstrings name
+_DEVICE_DTYPES = {"f32": ("float32",), "f64": ("float64",), "i32": ("int32",), "u8": ("uint8",),
+                  "id": ("int64", "uint64"), "key": ("int32", "uint32")}
 
 
 SEARCH_AUTO, SEARCH_EXACT = 0, 1   # mx_index_set_search_mode
@@ -70,6 +76,47 @@ class FlatIndex:
         hipStream_t as int / c_void_p, or None for the default stream).  See the stream contract in
         include/memex_hip.h; the ``*_device`` methods call this with torch's current stream."""
         check(lib().mx_index_wait_stream(self._h, stream))
+
+    def _device_args(self, *specs) -> None:
+        """The tensors of a ``*_device`` call, checked before any library call: ``(name, tensor, kind, shape)`` each, ``kind`` a key
+        of ``_DEVICE_DTYPES``; a tensor that is None (an optional output) and a ``shape`` that is None are not looked at.  The C ABI
+        takes raw pointers, so a tensor on another device, of another dtype, too small or strided would be read or written out of
+        bounds: each raises MX_EINVAL naming the argument."""
+        for name, t, kind, shape in specs:
+            if t is None:
+                continue
+            dev = getattr(t, "device", None)
+            if getattr(dev, "type", None) != "cuda" or dev.index != self.device:
+                raise _lib.MemexHipError(_lib.MX_EINVAL, f"{name}: expected a tensor on cuda:{self.device}, got one on {dev}")
+            dt = str(t.dtype).rsplit(".", 1)[-1]
+            if dt not in _DEVICE_DTYPES[kind]:
+                raise _lib.MemexHipError(_lib.MX_EINVAL, f"{name}: expected dtype {' or '.join(_DEVICE_DTYPES[kind])}, got {dt}")
+            if shape is not None and tuple(t.shape) != tuple(shape):
+                raise _lib.MemexHipError(_lib.MX_EINVAL, f"{name}: expected shape {list(shape)}, got {list(t.shape)}")
+            if not t.is_contiguous():
+                raise _lib.MemexHipError(_lib.MX_EINVAL, f"{name}: expected a contiguous tensor, got strides {tuple(t.stride())}")
+
+    def _device_queries(self, q, name: str = "q") -> int:
+        """-> B of a device block of vectors f32 [B, dim] (queries, or rows to add), checked like every other device tensor"""
+        if getattr(q, "ndim", None) != 2:
+            raise _lib.MemexHipError(_lib.MX_EINVAL, f"{name}: expected shape [B, {self.dim}], got {list(getattr(q, 'shape', ()))}")
+        B = int(q.shape[0])
+        self._device_args((name, q, "f32", (B, self.dim)))
+        return B
+
+    def _device_lists(self, B: int, width, ids, scores, dists, n_found, *extra) -> None:
+        """The outputs every search form has -- ids i64/u64, scores and dists f32 [B, *width], n_found i32 [B] -- and the form's own
+        ``(name, tensor, kind, shape)``, ``shape`` a tuple, "B" for [B] or "BW" for [B, *width]"""
+        w = tuple(max(int(x), 0) for x in width) if isinstance(width, tuple) else (max(int(width), 0),)
+        shapes = {"B": (B,), "BW": (B,) + w}
+        self._device_args(("ids", ids, "id", shapes["BW"]), ("scores", scores, "f32", shapes["BW"]), ("dists", dists, "f32", shapes["BW"]),
+                          ("n_found", n_found, "i32", shapes["B"]), *((n, t, kd, shapes.get(sh, sh)) for n, t, kd, sh in extra))
+
+    def _device_topk_args(self, q, width, ids, scores, dists, n_found, *extra) -> int:
+        """-> B of a form with a device query block [B, dim] and the outputs of ``_device_lists``"""
+        B = self._device_queries(q)
+        self._device_lists(B, width, ids, scores, dists, n_found, *extra)
+        return B
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self) -> None:
@@ -152,7 +199,7 @@ class FlatIndex:
 
     def add_device(self, t) -> int:
         """Append rows held in HBM (contiguous f32 [n, dim] tensor on this index's device)."""
-        n = int(t.shape[0])
+        n = self._device_queries(t, "rows")
         first = ctypes.c_uint64(0)
         st = _caller_stream(t)
         if st is not None:
@@ -207,7 +254,7 @@ class FlatIndex:
     def search_device(self, q, k: int, ids, scores, dists, n_found) -> None:
         """All arguments are device tensors: q f32 [B,dim]; ids i64/u64 [B,k]; scores, dists f32 [B,k];
         n_found i32 [B].  Blocks until the results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, k, ids, scores, dists, n_found)
         st = _caller_stream(q)
         if st is not None:  # q and the (possibly just zero-filled) outputs were produced on torch's stream
             self.wait_stream(st)
@@ -239,7 +286,7 @@ class FlatIndex:
         """``search_device`` restricted like ``search_filtered``: the queries and outputs are device tensors, the filter
         (``ranges`` or ``allow_ids``) stays on the host."""
         r = _filter_ranges(ranges, allow_ids)
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, k, ids, scores, dists, n_found)
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
@@ -296,7 +343,7 @@ class FlatIndex:
 
     def search_with_device(self, flt: "IndexFilter", q, k: int, ids, scores, dists, n_found) -> None:
         """``search_device`` restricted to the rows of a resident filter."""
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, k, ids, scores, dists, n_found)
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
@@ -339,7 +386,7 @@ class FlatIndex:
     def search_range_device(self, q, min_score, cap: int, ids, scores, dists, n_found, n_in_range) -> None:
         """``search_range`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,cap]; scores, dists f32 [B,cap] (dists may be
         None); n_found i32 [B]; n_in_range i64/u64 [B].  The thresholds stay on the host.  Blocks until the results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, max(int(cap), 0), ids, scores, dists, n_found, ("n_in_range", n_in_range, "id", "B"))
         t = self._min_scores(min_score, B)
         st = _caller_stream(q)
         if st is not None:
@@ -377,7 +424,7 @@ class FlatIndex:
     def search_mmr_device(self, q, k: int, ids, scores, dists, n_found, fetch=None, lam: float = 0.5) -> None:
         """``search_mmr`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,k]; scores, dists f32 [B,k] (dists may be None);
         n_found i32 [B].  Blocks until the results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, k, ids, scores, dists, n_found)
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
@@ -442,6 +489,8 @@ class FlatIndex:
         fused f64 [R,k] (dists, best_sub and fused may be None); n_found i32 [R].  The weights stay on the host.  Blocks until the
         results are in HBM."""
         R, m, code, w = self._fused_args(q.shape, mode, weights)
+        self._device_args(("q", q, "f32", None))
+        self._device_lists(R, k, ids, scores, dists, n_found, ("best_sub", best_sub, "i32", "BW"), ("fused", fused, "f64", "BW"))
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
@@ -494,7 +543,8 @@ class FlatIndex:
         """``search_grouped`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,k]; scores, dists f32 [B,k]; keys i32/u32 [B,k];
         group_rows i32 [B,k]; n_found i32 [B]; complete u8 [B] (dists, keys, group_rows and complete may be None).  Blocks until the
         results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, k, ids, scores, dists, n_found, ("keys", keys, "key", "BW"), ("group_rows", group_rows, "i32", "BW"),
+                                   ("complete", complete, "u8", "B"))
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
@@ -560,7 +610,11 @@ class FlatIndex:
         """``search_group_rows`` on device tensors: q f32 [B,dim]; ids i64/u64, scores, dists f32 [B,k,n]; keys i32/u32, group_rows
         i32, n_members i32, members_complete u8 [B,k]; n_found i32 [B]; complete u8 [B] (dists, keys, group_rows, n_members,
         members_complete and complete may be None).  Blocks until the results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_queries(q)
+        heads = (B, max(int(k), 0))
+        self._device_lists(B, (k, n), ids, scores, dists, n_found, ("keys", keys, "key", heads), ("group_rows", group_rows, "i32", heads),
+                           ("n_members", n_members, "i32", heads), ("members_complete", members_complete, "u8", heads),
+                           ("complete", complete, "u8", "B"))
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
@@ -593,7 +647,7 @@ class FlatIndex:
                              fetch=None, flt: "IndexFilter | None" = None) -> None:
         """``search_capped`` on device tensors: q f32 [B,dim]; ids i64/u64, scores, dists f32, keys i32/u32 [B,k]; n_found i32 [B];
         complete u8 [B] (dists, keys and complete may be None).  Blocks until the results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, k, ids, scores, dists, n_found, ("keys", keys, "key", "BW"), ("complete", complete, "u8", "B"))
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
@@ -655,7 +709,8 @@ class FlatIndex:
         """``search_boosted`` on device tensors: q f32 [B,dim]; ids i64/u64 [B,k]; scores, dists, priors f32 [B,k]; combined f64
         [B,k]; n_found i32 [B]; complete u8 [B] (dists, priors, combined and complete may be None).  ``weight`` stays on the host.
         Blocks until the results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_topk_args(q, k, ids, scores, dists, n_found, ("priors", priors, "f32", "BW"), ("combined", combined, "f64", "BW"),
+                                   ("complete", complete, "u8", "B"))
         w = self._boost_weights(weight, B)
         st = _caller_stream(q)
         if st is not None:
@@ -690,6 +745,7 @@ class FlatIndex:
         """``search_by_id`` with device tensors for the outputs: out_ids i64/u64 [B,k]; scores, dists f32 [B,k] (dists may be
         None); n_found i32 [B].  The query ids stay on the host.  Blocks until the results are in HBM."""
         a = self._query_ids(ids)
+        self._device_lists(a.size, k, out_ids, scores, dists, n_found)
         st = _caller_stream(out_ids)
         if st is not None:
             self.wait_stream(st)
@@ -722,6 +778,7 @@ class FlatIndex:
         thresholds stay on the host."""
         a = self._query_ids(ids)
         t = self._min_scores(min_score, a.size)
+        self._device_lists(a.size, cap, out_ids, scores, dists, n_found, ("n_in_range", n_in_range, "id", "B"))
         st = _caller_stream(out_ids)
         if st is not None:
             self.wait_stream(st)
@@ -795,6 +852,8 @@ class FlatIndex:
         host.  Blocks until the results are in HBM."""
         a, w, qw = self._like_args(example_ids, weights, None if queries is None else queries.shape, query_weights)
         R, m = a.shape
+        self._device_lists(R, k, ids, scores, dists, n_found, ("queries", queries, "f32", (R, self.dim)), ("n_used", n_used, "i32", "B"),
+                           ("combined", combined, "f32", (R, self.dim)))
         st = _caller_stream(queries if queries is not None else ids)
         if st is not None:
             self.wait_stream(st)
@@ -848,8 +907,11 @@ class FlatIndex:
     def score_ids_device(self, q, ids, scores, dists=None, order=None, n_found=None) -> None:
         """``score_ids`` on device tensors: q f32 [B,dim]; scores, dists f32 [B,m]; order i32 [B,m]; n_found i32 [B] (dists, order and
         n_found may be None).  The candidate ids stay on the host.  Blocks until the results are in HBM."""
-        B = int(q.shape[0])
+        B = self._device_queries(q)
         a = self._cand_ids(ids, B)
+        cand = (B, a.shape[1])
+        self._device_args(("scores", scores, "f32", cand), ("dists", dists, "f32", cand), ("order", order, "i32", cand),
+                          ("n_found", n_found, "i32", (B,)))
         st = _caller_stream(q)
         if st is not None:
             self.wait_stream(st)
